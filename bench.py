@@ -6,10 +6,16 @@ trim 15; no PBMC data ships with the reference), `clustering_bqm` model (BQM_clu
 gamma_factor 0.05, k 8) resident in HBM; ONE STEP = one anneal of 4096 replicas x 1000 sweeps per GPU
 (explicit geometric beta schedule, seed 1234).  The timed kernel is the one `MI355XSampler.sample_qubo`
 runs for this model: K2, the CSR form (sparse cut term + uniform pair term; dE = Q_i . x evaluated from
-the CSR rows).  The dense form (K1w, 27.8 MB fp32 Q) and the Potts kernel run beside it, untimed
-(`other_kernels`); `--kernel dense` makes the dense kernel the timed one.
+the CSR rows).  The dense form (K1w, 27.8 MB fp32 Q) and the Potts kernel run beside it under `--full`,
+untimed (`other_kernels`); `--kernel dense` makes the dense kernel the timed one.
 
-    python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N>1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds the side runs of rank 0
+on one GPU: `other_kernels` and `cpu_baseline` (the latter left out again by `--no-cpu-baseline`).
+`--dump-outputs DIR` writes what the last timed step returned (global best energy, replica id and state; the fp64
+energies, states and accept counts of that anneal) as DIR/<name>.npy in float32 / float64, for comparing two builds
+on the same seeded inputs.
 
 Multi-GPU: replicas shard (weak scaling: 4096 replicas per GPU, global ids rank*4096..), the model is
 replicated, and each step ends with the ONE exchange the path has: a 64-bit MIN all-reduce of the
@@ -422,6 +428,30 @@ def dense_xl_50k(rank_device, n=50000, replicas=1024, sweeps=4):
             "host_build_s": t_build, "upload_s": t_upload, "best_energy": float(en.min())}
 
 
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs writes at most this much (the .npy headers included)
+
+
+def dump_outputs(out_dir, best, states, energies, info):
+    """What the last timed step returned, as out_dir/<name>.npy: the global best of step() (fp64 energy, replica id,
+    state) and the anneal's per-replica fp64 energies, states and accept counts (this rank's replicas).  The states go
+    whole while they fit DUMP_BYTES; beyond that, a fixed seeded sample of replicas, their ids in states_replicas.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"best_energy": np.array([best[0]], dtype=np.float64),
+              "best_replica_global_id": np.array([best[1]], dtype=np.float64),
+              "best_state": np.asarray(best[3], dtype=np.float32),
+              "energies": np.asarray(energies, dtype=np.float64),
+              "accepted_proposals": np.array([info["accepted"], info["proposals"]], dtype=np.float64)}
+    R, n = states.shape
+    room = DUMP_BYTES - 1024 * (len(arrays) + 2) - sum(a.nbytes for a in arrays.values())
+    if R * n * 4 > room:
+        rows = np.sort(np.random.RandomState(0).choice(R, room // (n * 4 + 8), replace=False))
+        arrays["states_replicas"] = rows.astype(np.float64)
+        states = states[rows]
+    arrays["states"] = states.astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -431,8 +461,15 @@ def parse_args(argv=None):
     ap.add_argument("--sweeps", type=int, default=SWEEPS)
     ap.add_argument("--kernel", choices=("csr", "dense"), default="csr",
                     help="timed kernel: csr = K2 (what the sampler runs for this model), dense = K1w")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run other_kernels and cpu_baseline (rank 0, one GPU) after the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -540,8 +577,10 @@ def main():
     t_f0 = time.perf_counter()
     states, en, info = prob.fetch()
     fetch_ms = (time.perf_counter() - t_f0) * 1e3                  # R x n state bytes + R energies -> host
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, best, states, en, info)
     eq_states = eq_en = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the GPU side of cpu_baseline.equal_reads: replicas 0 .. EQUAL_READS - 1 of seed SEED over the full schedule,
         # whatever --steps / --warmup / --replicas were (a replica's chain depends on (seed, global id) only)
         prob.anneal(EQUAL_READS, betas, SEED)
@@ -601,7 +640,8 @@ def main():
                                "(gamma_factor 0.05, k 8), %s, resident in HBM, %d replicas/GPU x %d sweeps, "
                                "geometric beta, seed 1234" % (layout, R, len(betas)),
                    "kernel": args.kernel,
-                   "n": n, "device_slots": prob.n_dev // 64 if args.kernel == "csr" else None, "replicas_per_gpu": R, "sweeps": int(len(betas)), "parallelism": "replicas sharded x%d" % world},
+                   "n": n, "device_slots": prob.n_dev // 64 if args.kernel == "csr" else None, "replicas_per_gpu": R, "sweeps": int(len(betas)), "parallelism": "replicas sharded x%d" % world,
+                   "full": bool(args.full)},
         "roofline": roofline,
         "effective": {"algorithmic_bytes_per_update": bytes_per_update, "algorithmic_bytes_per_launch": alg_bytes,
                       "GBps": effective, "note": "SURVEY.md 8d byte model x updates / time: an effective-bandwidth figure "
@@ -616,9 +656,9 @@ def main():
         "energy_lower_bound": float(-m.info["gamma"] * n * n / 4),
     }
     if rank == 0:
-        if world == 1:
+        if args.full and world == 1:
             out["other_kernels"] = other_kernels(m, Qs, betas, graph, local, args.kernel)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the order the device sweeps the caller's variables in (holes of the padded layout take no proposal)
             perm = prob.perm if prob.perm is not None else (np.argsort(prob._inv) if prob._inv is not None else np.arange(n))
             out["cpu_baseline"] = cpu_baseline(m, Qs, betas, (eu, ev), eq_states, eq_en, float(np.min(en)), perm)
