@@ -147,6 +147,21 @@ int mi_sa_problem_set_absent(mi_sa_problem *p, const uint8_t *absent);
  * sparse couplings: MI_EINVAL otherwise.  Call before the first anneal of the problem. */
 int mi_sa_problem_set_pair_weights(mi_sa_problem *p, const int32_t *weights);
 
+/* Potts (k-way) models: integer NODE WEIGHTS of the pair term (chain specification 2d),
+ *     E(l) = offset + sum_{i<j, l_i == l_j} (S_ij + c_i w_j)      with the move test  dE = fmaf(cw_i, (float)(W_b - W_a + wq_i), hd)
+ * where W_q = sum_{l_j == q} wq_j is an exact integer cluster sum: the null-model term gamma / (2m) k_u k_v of weighted
+ * modularity at resolution gamma -- what Seurat's FindClusters(..., algorithm = 1, resolution = 0.5 ... 0.9) maximises on
+ * the SNN graph the reference's notebooks compare every annealed clustering with (R/pbmc3k/Pbmc3k_normalization_simulated_
+ * data.Rmd:234,252,1024, Pbmc3k_assess_QA_clusters.Rmd:93, Pbmc3k_data_subsampling_clusters.Rmd:53,64,156, R/kidney/
+ * Kidney_data.Rmd:148,154).  wq[i] >= 0 and sum_i wq[i] <= 2^30 (values at holes are ignored: weight 0); cw[i] is the
+ * fp32 coefficient of variable i in the move test; w64[i] (nullable: wq) its fp64 weight for the reported energies,
+ *     sum_{edges, same label} val64 + c64 / 2 sum_q (W64_q^2 - sum_{l_i == q} w64_i^2) + offset
+ * with c64 the c_pair of mi_sa_problem_set_energy_model_f64 (else the one given at creation).  wq = 1 and cw = c_pair
+ * reproduce the unweighted chain bit for bit.  MI_EINVAL: a negative weight, sum wq > 2^30, a problem that is not a
+ * Potts problem, a call after the first anneal.  MI_EUNSUPPORTED: together with the option "min_cluster_size" (either
+ * order).  Call before the first anneal of the problem; problems that never call it run as before. */
+int mi_sa_problem_set_node_weights(mi_sa_problem *p, const int32_t *wq, const float *cw, const double *w64);
+
 /* Diagnostic: copies the first `words` (<= 16) 64-bit statistics words of the last run ([0..2] as in
  * mi_sa_fetch; [8..12] per-phase cycle sums of builds compiled with -DMI_K2_PROFILE, otherwise 0; with words = 16,
  * [14] / [15] = chunks of the last scheduled dense run served by the workgroup kernel / the MFMA kernel). */

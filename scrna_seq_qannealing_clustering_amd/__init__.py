@@ -7,6 +7,7 @@ Public surface:
     build_bqm_qubo, build_bqm2_qubo, build_bqm3_cut_qubo, build_dqm_potts   model builders
     BinaryQuadraticModel, DiscreteQuadraticModel     stand-ins for the dimod classes
     clustering_bqm, clustering_bqm_2, clustering_bqm_3, clustering_dqm  reference-shaped drivers
+    clustering_modularity    weighted modularity at a resolution (Seurat's FindClusters objective)
 """
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
 from .models import (PottsModel, QuboModel, add_size_window_penalty, build_bqm2_qubo,
@@ -28,7 +29,7 @@ def __getattr__(name):
     if name == "MI355XSampler":
         from .sampler import MI355XSampler
         return MI355XSampler
-    if name in ("clustering_bqm", "clustering_bqm_2", "clustering_bqm_3", "clustering_dqm"):
+    if name in ("clustering_bqm", "clustering_bqm_2", "clustering_bqm_3", "clustering_dqm", "clustering_modularity"):
         from . import clustering
         return getattr(clustering, name)
     raise AttributeError(name)

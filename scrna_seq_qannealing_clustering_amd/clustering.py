@@ -252,6 +252,26 @@ def clustering_dqm(G, num_of_clusters, gamma, sampler=None, sampler_kwargs: Opti
     return sampleset
 
 
+def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sampler=None,
+                          sampler_kwargs: Optional[dict] = None, verbose=False):
+    """Weighted modularity at ``resolution`` -- the objective of Seurat's ``FindClusters(..., algorithm = 1)`` that the
+    reference's notebooks compare every annealed clustering with -- annealed on the Potts chain with node weights
+    (models.build_modularity_potts), at most ``max_clusters`` labels.  Returns the sampleset; ``info["modularity"]``
+    holds ``Q_gamma`` of every sample (record order), ``-energy / m``.  Default schedule: 16000 sweeps, geometric over
+    ``models.modularity_beta_range`` (``sampler_kwargs`` overrides either)."""
+    from .models import build_modularity_potts, modularity_beta_range
+    model = build_modularity_potts(G, resolution, max_clusters)
+    # default schedule: 16000 sweeps over modularity_beta_range -- single-site moves over more labels than communities
+    # need the time to merge a community split across two labels (DESIGN.md section 5); 256 reads as the sampler's default
+    kw = dict(num_sweeps=16000, beta_range=modularity_beta_range(model))
+    kw.update(sampler_kwargs or {})
+    sampleset = _sampler(sampler).sample_dqm(model, **kw)
+    sampleset.info["modularity"] = -np.asarray(sampleset.record["energy"], dtype=np.float64) / model.info["m"]
+    if verbose:
+        print("Modularity: {}\nSolution: {}".format(float(np.max(sampleset.info["modularity"])), sampleset.first.sample))
+    return sampleset
+
+
 def clustering_cqm(G, num_of_clusters, min_cluster_size: int = 20, sampler=None,
                    sampler_kwargs: Optional[dict] = None, verbose=False):
     """`clustering_cqm` (CQM_clustering.py:26-55): one-hot k-way model whose objective keeps heavy edges

@@ -194,6 +194,9 @@ struct mi_sa_problem {
     int k2_state_bytes = 0;                  // K2: byte-per-variable state (16 replicas x n bytes fit one CU's LDS)
     int32_t *d_wgt = nullptr;                // K2 family: the 64 pair-term weights of the weighted slot (mi_sa_problem_set_pair_weights)
     int wslot = -1;                          // ... its index; -1: every weight is 1
+    int32_t *d_nwq = nullptr;                // Potts: node weights of the pair term per position (mi_sa_problem_set_node_weights)
+    float *d_ncw = nullptr;                  // ... their fp32 coefficients
+    double *d_nw64 = nullptr;                // ... their fp64 weights (reported energies)
     int k2_free_block = 0;                   // K2s: widest block of seats (256 / 128 / 64; 0 = none) that holds no edge anywhere in the model
     int cus = 0;
     // run buffers
@@ -903,6 +906,41 @@ int mi_sa_problem_set_pair_weights(mi_sa_problem *p, const int32_t *weights)
     });
 }
 
+int mi_sa_problem_set_node_weights(mi_sa_problem *p, const int32_t *wq, const float *cw, const double *w64)
+{
+    if (!p || !wq || !cw) return fail(MI_EINVAL, "NULL argument");
+    if (const int rc_w = settle(p)) return rc_w;
+    if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_EINVAL, "node weights: Potts problems only");
+    if (p->has_run) return fail(MI_EINVAL, "node weights must be set before the first anneal");
+    if (p->opt_min_cluster_size > 0) return fail(MI_EUNSUPPORTED, "node weights together with min_cluster_size are not supported");
+    return guarded([&]() -> int {
+        const size_t seats = (size_t)p->slots * 64;
+        std::vector<int32_t> hq(seats, 0);
+        std::vector<float> hc(seats, 0.0f);
+        std::vector<double> hw(seats, 0.0);
+        int64_t total = 0;
+        for (int i = 0; i < p->n; ++i) {
+            if (p->h_meta[(size_t)i] >> 31) continue;                  // a hole: weight 0, in no cluster
+            if (wq[i] < 0 || (w64 && !(w64[i] >= 0.0)))
+                return fail(MI_EINVAL, "weight of variable %d is negative", i);
+            total += wq[i];
+            if (total > (int64_t)1 << 30) return fail(MI_EINVAL, "the node weights sum to more than 2^30");
+            hq[(size_t)i] = wq[i];
+            hc[(size_t)i] = cw[i];
+            hw[(size_t)i] = w64 ? w64[i] : (double)wq[i];
+        }
+        HIP_TRY(hipSetDevice(p->device));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        if (!p->d_nwq) HIP_TRY(hipMalloc((void **)&p->d_nwq, seats * sizeof(int32_t)));
+        if (!p->d_ncw) HIP_TRY(hipMalloc((void **)&p->d_ncw, seats * sizeof(float)));
+        if (!p->d_nw64) HIP_TRY(hipMalloc((void **)&p->d_nw64, seats * sizeof(double)));
+        HIP_TRY(hipMemcpy(p->d_nwq, hq.data(), seats * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->d_ncw, hc.data(), seats * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->d_nw64, hw.data(), seats * sizeof(double), hipMemcpyHostToDevice));
+        return MI_OK;
+    });
+}
+
 int mi_sa_problem_set_energy_model_f64(mi_sa_problem *p, const double *val, const double *lin, double c_pair)
 {
     return guarded([&]() -> int { return set_energy_model_impl(p, val, lin, c_pair); });
@@ -914,7 +952,7 @@ int mi_sa_problem_destroy(mi_sa_problem *p)
     (void)settle(p);
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    void *bufs[] = {p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
+    void *bufs[] = {p->d_nwq, p->d_ncw, p->d_nw64, p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
@@ -984,6 +1022,7 @@ int mi_sa_set_option(mi_sa_problem *p, const char *key, long value)
     if (!strcmp(key, "k3_fast") && value >= 0 && value <= 2) { p->opt_k3_fast = (int)value; return MI_OK; }
     if (!strcmp(key, "min_cluster_size") && value >= 0) {
         if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_EINVAL, "min_cluster_size applies to Potts problems");
+        if (value > 0 && p->d_nwq) return fail(MI_EUNSUPPORTED, "min_cluster_size together with node weights is not supported");
         p->opt_min_cluster_size = (int)value;
         return MI_OK;
     }
@@ -1139,6 +1178,7 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
         a.rows = p->d_rows; a.meta = p->d_meta; a.adj4 = p->d_adj4; a.slot_flags = p->d_slot_flags; a.state_bytes = p->k2_state_bytes; a.waves_override = p->opt_k2_waves; a.min_size = p->opt_min_cluster_size;
         a.ell_val64 = p->d_ell_val64; a.lin64 = p->d_lin64; a.c_pair64 = p->c_pair64;
         a.wgt = p->d_wgt; a.wslot = p->kind == MI_KIND_CSR_RANK1 ? p->wslot : -1;
+        a.nwq = p->d_nwq; a.ncw = p->d_ncw; a.nw64 = p->d_nw64;
         if (p->kind == MI_KIND_POTTS_CSR && init) {
             // labels must be < K: validated on the host copy (the device trusts them as cnt[] indices)
             const uint16_t *l = static_cast<const uint16_t *>(init);

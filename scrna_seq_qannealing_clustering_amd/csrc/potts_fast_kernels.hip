@@ -43,6 +43,18 @@ __device__ __forceinline__ uint32_t wave_scan32(uint32_t v)
     return v;
 }
 
+// OR over the 64 lanes (the same DPP pattern): the result sits in lane 63
+__device__ __forceinline__ uint32_t wave_or32(uint32_t v)
+{
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+    return v;
+}
+
 // per-lane select by a wave-uniform mask held in a scalar register pair
 __device__ __forceinline__ uint32_t select_by_mask(uint32_t if_clear, uint32_t if_set, uint64_t mask)
 {
@@ -58,9 +70,13 @@ __device__ __forceinline__ uint32_t select_by_mask(uint32_t if_clear, uint32_t i
 // target offset word mod (K - 1) of every proposal -- one group of four slots ahead and hands them over through a two-deep
 // ring in LDS (as k_anneal_csr_rank1_pair does): for runs of up to 1024 replicas (the sampler's default is 256 reads), where
 // every wavefront has a SIMD to itself and that work moves to an idle one.
-template <int D, int KM, bool UM, bool TW>
+// WT: node weights of the pair term (chain 2d, mi_sa_problem_set_node_weights): the LDS words of the cluster sizes hold
+// the integer cluster sums W_q, the lane's weight wq and coefficient cw ride with the slot's metadata, and the byte-packed
+// size scan (which cannot hold weights) gives way to one int32 DPP scan per label that this round's movers touch.
+template <int D, int KM, bool UM, bool TW, bool WT = false>
 __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k_anneal_potts_fast(EllArgs a)
 {
+    static_assert(!(UM && WT), "node weights with a minimum cluster size are not supported");
     extern __shared__ __attribute__((aligned(16))) char lds[];      // cell of seat i at byte 2 i, then the K cluster sizes
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x;
@@ -134,13 +150,22 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
         }
         cnt[lane] = cntv;                                           // (64 words reserved)
     }
+    if constexpr (WT) {
+        // the integer cluster sums (exact: integer atomics in any order; the wave's LDS operations run in order)
+        cnt[lane] = 0;
+        for (int t = 0; t < slots; ++t) {
+            const int i = t * 64 + lane;
+            if ((a.meta[i] >> 31) == 0u)
+                __hip_atomic_fetch_add(&cnt[dec_label<KM>(cell[i])], a.nwq[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+    }
 
     constexpr int G = D / 4;
     const __amdgpu_buffer_rsrc_t rs_adj = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint4 *>(a.adj4), 0, slots * G * 2048, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_meta = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint32_t *>(a.meta), 0, slots * 256, 0x00020000);
-    struct SlotAdj { u32x4 col[G]; u32x4 val[G]; uint32_t meta; };
+    struct SlotAdj { u32x4 col[G]; u32x4 val[G]; uint32_t meta; int wq; float cw; };
     const int lane16 = lane * 16;
 #ifdef MI_K3F_DBG_NOFETCH   /* timing only (wrong chain): slot 0's adjacency serves every slot, no vector-memory traffic in the sweep */
     auto fetch_real = [&](int t) {
@@ -157,6 +182,13 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
             p.val[g] = __builtin_amdgcn_raw_buffer_load_b128(rs_adj, lane16 + io + 1024, so, 0);
         }
         p.meta = __builtin_amdgcn_raw_buffer_load_b32(rs_meta, lane * 4, tt * 256, 0);
+        if constexpr (WT) {
+            p.wq = a.nwq[tt * 64 + lane];
+            p.cw = a.ncw[tt * 64 + lane];
+        } else {
+            p.wq = 1;
+            p.cw = 0.0f;
+        }
         return p;
     };
 
@@ -301,8 +333,10 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
         // byte selectors of the lane's two clusters inside a 64-bit scan (v_perm_b32: the byte lands in byte 0, zeros above)
         const uint32_t pa = 0x0c0c0c00u | (la & 7u), pb = 0x0c0c0c00u | (lb & 7u);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(na0), "+v"(nb0) :: "memory");
-        const int d0 = nb0 - na0 + 1;                               // cnt_b - (cnt_a - 1) before any move of this slot
-        uint64_t A0 = __ballot(__builtin_fmaf(c_eff, (float)d0, hd) < thr);
+        // WT: W_b - W_a + wq_i, and the lane's own coefficient (KM = 8: doubled, as the field sum)
+        const int d0 = nb0 - na0 + (WT ? cur.wq : 1);               // cnt_b - (cnt_a - 1) before any move of this slot
+        const float c_ln = WT ? (KM == 8 ? 2.0f * cur.cw : cur.cw) : c_eff;
+        uint64_t A0 = __ballot(__builtin_fmaf(c_ln, (float)d0, hd) < thr);
         if constexpr (UM) A0 &= __ballot(na0 - 1 >= a.min_size);
         if (A0 != 0ull) {                                           // wave-uniform
             // fixed-point rounds (ends by itself: a lane's decision depends on the movers below it only, so after k rounds
@@ -310,6 +344,29 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
             uint64_t A = A0;
 #pragma nounroll
             for (;;) {
+                if constexpr (WT) {
+                    // the net weight change of the lane's two clusters by the movers BELOW it: one exclusive int32 scan
+                    // per label that a mover of this round leaves or enters (the others do not change), picked by label
+                    const uint32_t mine = (1u << la) | (1u << lb);
+                    uint32_t touched = (uint32_t)__builtin_amdgcn_readlane((int)wave_or32(select_by_mask(0u, mine, A)), 63);
+                    int ea = 0, eb = 0;
+#pragma nounroll
+                    while (touched != 0u) {                          // wave-uniform
+                        const uint32_t q = (uint32_t)__builtin_ctz(touched);
+                        touched &= touched - 1u;
+                        const int cq = (lb == q ? cur.wq : 0) - (la == q ? cur.wq : 0);
+                        const int c = (int)select_by_mask(0u, (uint32_t)cq, A);
+                        const int ex = (int)wave_scan32((uint32_t)c) - c;
+                        ea = la == q ? ex : ea;
+                        eb = lb == q ? ex : eb;
+                    }
+                    const uint64_t A2 = __ballot(__builtin_fmaf(c_ln, (float)(d0 + eb - ea), hd) < thr);
+                    uint64_t df = A2 ^ A;
+                    asm("" : "+s"(df));
+                    A = A2;
+                    if (df == 0ull) break;
+                    continue;
+                }
                 const uint32_t own2 = select_by_mask(0u, 2u, A);    // the lane's own move inside the inclusive scan
                 uint32_t sa, sb;
                 if (KM == 8 && narrow) {
@@ -353,7 +410,7 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
                          "ds_add_u32 %1, %3\n\t"
                          "ds_sub_u32 %2, %3\n\t"
                          "s_mov_b64 exec, -1"
-                         :: "s"(A), "v"(cnt_base + lb * 4u), "v"(cnt_base + la * 4u), "v"(1u) : "memory");
+                         :: "s"(A), "v"(cnt_base + lb * 4u), "v"(cnt_base + la * 4u), "v"(WT ? (uint32_t)cur.wq : 1u) : "memory");
 #endif
         }
     };
@@ -406,8 +463,12 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
             if ((int)cc > i && dec_label<KM>(cell[cc]) == li) e += vv;
         }
     }
-    const int cntv = cnt[lane];
-    if (lane < K) e += (a.ell_val64 ? a.c_pair64 : (double)a.c_pair) * 0.5 * (double)cntv * (double)(cntv - 1);
+    if constexpr (WT) {
+        e += node_weight_energy(a, lane, [&](int j) { return dec_label<KM>(cell[j]); });
+    } else {
+        const int cntv = cnt[lane];
+        if (lane < K) e += (a.ell_val64 ? a.c_pair64 : (double)a.c_pair) * 0.5 * (double)cntv * (double)(cntv - 1);
+    }
     e = wave_sum_f64(e);
     if (lane == 0) {
         a.energy[r] = e + a.offset;
@@ -422,7 +483,8 @@ int launch_potts_fast(KernelT kernel, const EllArgs &a, int km, bool tw, hipStre
     if (lds > 160 * 1024) return fail(MI_EUNSUPPORTED, "potts fast kernel: n = %d exceeds the label LDS budget", a.n);
     if (lds > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    note_kernel(tw ? "k_anneal_potts_fast<%d, %d, tw>" : "k_anneal_potts_fast<%d, %d>", a.D, km);
+    if (a.nwq) note_kernel(tw ? "k_anneal_potts_fast<%d, %d, tw, weighted>" : "k_anneal_potts_fast<%d, %d, weighted>", a.D, km);
+    else note_kernel(tw ? "k_anneal_potts_fast<%d, %d, tw>" : "k_anneal_potts_fast<%d, %d>", a.D, km);
     hipLaunchKernelGGL(kernel, dim3(a.R), dim3(tw ? 128 : 64), lds, st, a);
     HIP_TRY(hipGetLastError());
     return MI_OK;
@@ -432,6 +494,11 @@ template <int D, int KM>
 int launch_potts_fast_dk(const EllArgs &a, bool tw, hipStream_t st)
 {
     const bool um = a.min_size > 0;
+    if (a.nwq) {                                                    // node weights (chain 2d; never with a minimum size)
+        if (um) return fail(MI_EUNSUPPORTED, "node weights with min_cluster_size are not supported");
+        return tw ? launch_potts_fast(k_anneal_potts_fast<D, KM, false, true, true>, a, KM, true, st)
+                  : launch_potts_fast(k_anneal_potts_fast<D, KM, false, false, true>, a, KM, false, st);
+    }
     if (tw) return um ? launch_potts_fast(k_anneal_potts_fast<D, KM, true, true>, a, KM, true, st)
                       : launch_potts_fast(k_anneal_potts_fast<D, KM, false, true>, a, KM, true, st);
     return um ? launch_potts_fast(k_anneal_potts_fast<D, KM, true, false>, a, KM, false, st)

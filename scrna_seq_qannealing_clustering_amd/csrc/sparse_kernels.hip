@@ -441,7 +441,10 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D <= 32 ? 4 : 2))) k
 // D = 16 / 32 / 64: the slot's adjacency is register resident (prefetched for D = 16).  D = 0: rows of ANY width
 // W = a.D (a multiple of 16; the untrimmed SNN graphs of the reference reach degrees of order k^2): the adjacency
 // is read entry by entry from L2 inside the field sum -- the same chain, slower.
-template <int D>
+// WT: node weights of the pair term (chain 2d, mi_sa_problem_set_node_weights): cnt[] holds the integer cluster sums
+// W_q, the lane's own weight wq and coefficient cw ride with the slot, and every slot takes the serial commit loop (the
+// mover's label and weight by readlane) -- the path that runs every weighted model K3f does not.
+template <int D, bool WT = false>
 __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs a)
 {
     const int W = D ? D : a.D;                               // adjacency entries per variable
@@ -482,6 +485,14 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
         if (lane == q) cntv = c;
     }
     cnt[lane] = cntv;
+    if constexpr (WT) {
+        // the integer cluster sums (exact: integer atomics in any order; the wave's LDS operations run in order)
+        cnt[lane] = 0;
+        for (int t = 0; t < slots; ++t) {
+            const int i = t * 64 + lane;
+            if ((a.meta[i] >> 31) == 0u) __hip_atomic_fetch_add(&cnt[lab[i]], a.nwq[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+    }
 
     constexpr bool PF = (D == 16);
     constexpr int DR = D ? D : 1;                            // register-resident entries (none for D = 0)
@@ -582,6 +593,13 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
             sum_h();
             K2_TICK(t_apply);
             int ia = cnt[la] - 1, ib = cnt[lb];              // sizes of this lane's two clusters
+            int wqi = 1;
+            float cwi = a.c_pair;
+            if constexpr (WT) {                              // W_a - wq_i and W_b: dE = fmaf(cw_i, (float)(W_b - W_a + wq_i), hd)
+                wqi = a.nwq[i];
+                cwi = a.ncw[i];
+                ia = cnt[la] - wqi;
+            }
             // one-hot images of this lane's two labels (K <= 32): a move a_s -> b_s then updates the sizes with
             // AND + bit-count on the vector unit alone, no compare results travelling through SGPRs
             const uint32_t oa = 1u << (la & 31), ob = 1u << (lb & 31);
@@ -594,7 +612,7 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
             while (true) {
                 // dE = (h_b + c n_b) - (h_a + c (n_a - 1)) as one fma of the integer size difference onto the
                 // field difference (oracle 2c evaluates the same expression)
-                const float dE = fmaf(a.c_pair, (float)(ib - ia), hd);
+                const float dE = fmaf(WT ? cwi : a.c_pair, (float)(ib - ia), hd);
                 // ia = (members of this lane's cluster) - 1: a move may not shrink a cluster below min_size
                 const uint64_t m = (UM ? __ballot(dE < thr && ia >= a.min_size) : __ballot(dE < thr)) & todo;
                 if (m == 0) break;
@@ -602,7 +620,13 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
                 todo = (~0ull << l) << 1;
                 flipped |= 1ull << l;
                 // integer sizes (the per-cluster table `cntv` is brought up to date once per slot, after the loop)
-                if constexpr (OH) {
+                if constexpr (WT) {                          // the mover's weight moves from its cluster a_s to b_s
+                    const int a_s = __builtin_amdgcn_readlane(la, l);
+                    const int b_s = __builtin_amdgcn_readlane(lb, l);
+                    const int w_s = __builtin_amdgcn_readlane(wqi, l);
+                    ia += w_s * ((int)(la == b_s) - (int)(la == a_s));
+                    ib += w_s * ((int)(lb == b_s) - (int)(lb == a_s));
+                } else if constexpr (OH) {
                     const uint32_t sa = (uint32_t)__builtin_amdgcn_readlane((int)oa, l);
                     const uint32_t sb = (uint32_t)__builtin_amdgcn_readlane((int)ob, l);
                     ia += (int)__builtin_popcount(oa & sb) - (int)__builtin_popcount(oa & sa);
@@ -627,7 +651,9 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
             };
             // the two wave-uniform switches select one of four straight-line copies of the loop (inside it they
             // would be a ladder of taken branches on the serial path)
-            if (has_in == 0ull && K <= 16 && a.waves_override != 99) {
+            if constexpr (WT) {
+                commit_loop(std::false_type{}, std::false_type{});
+            } else if (has_in == 0ull && K <= 16 && a.waves_override != 99) {
                 // ---- no variable of this slot has a neighbour inside it (every slot under the slot-independent
                 // order): a lane's decision depends on the movers below it only through the sizes of ITS two clusters.
                 // As in K2, the accept mask of the sequential sweep is the one fixed point of "evaluate every lane
@@ -763,8 +789,8 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
                 // cluster sizes: two LDS atomics per mover (the wave's LDS operations execute in order, so the
                 // next slot's reads of cnt[] see them)
                 if (moved) {
-                    __hip_atomic_fetch_add(&cnt[lb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    __hip_atomic_fetch_add(&cnt[la], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    __hip_atomic_fetch_add(&cnt[lb], WT ? wqi : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    __hip_atomic_fetch_add(&cnt[la], WT ? -wqi : -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 }
             }
             K2_TICK(t_loop);
@@ -791,8 +817,12 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
             if ((int)cc > i && lab[cc] == li) e += vv;
         }
     }
-    cntv = cnt[lane];
-    if (lane < K) e += (a.ell_val64 ? a.c_pair64 : (double)a.c_pair) * 0.5 * (double)cntv * (double)(cntv - 1);
+    if constexpr (WT) {
+        e += node_weight_energy(a, lane, [&](int j) { return (uint32_t)lab[j]; });
+    } else {
+        cntv = cnt[lane];
+        if (lane < K) e += (a.ell_val64 ? a.c_pair64 : (double)a.c_pair) * 0.5 * (double)cntv * (double)(cntv - 1);
+    }
     e = wave_sum_f64(e);
     if (lane == 0) {
         a.energy[r] = e + a.offset;
@@ -803,7 +833,7 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
 template <typename KernelT>
 int launch_sparse(KernelT kernel, const EllArgs &a, size_t lds_per_wave, hipStream_t st)
 {
-    note_kernel("k_anneal_potts<%d>", a.D <= 64 ? a.D : 0);
+    note_kernel(a.nwq ? "k_anneal_potts<%d, weighted>" : "k_anneal_potts<%d>", a.D <= 64 ? a.D : 0);
     int waves = kSparseWaves;                    // fewer replicas per workgroup when their LDS state is large
     while (waves > 1 && lds_per_wave * waves > 160 * 1024) --waves;
     const size_t lds = lds_per_wave * waves;
@@ -868,6 +898,13 @@ int mi_launch_csr_rank1(const EllArgs &a, hipStream_t st, bool tw)
 int mi_launch_potts(const EllArgs &a, hipStream_t st)
 {
     const size_t per_wave = (size_t)a.slots * 64 + 256;      // labels + cluster sizes
+    if (a.nwq) {                                             // node weights (chain 2d)
+        if (a.D == 16) return launch_sparse(k_anneal_potts<16, true>, a, per_wave, st);
+        if (a.D == 32) return launch_sparse(k_anneal_potts<32, true>, a, per_wave, st);
+        if (a.D == 64) return launch_sparse(k_anneal_potts<64, true>, a, per_wave, st);
+        if (a.D > 64 && a.D % 16 == 0) return launch_sparse(k_anneal_potts<0, true>, a, per_wave, st);
+        return fail(MI_EUNSUPPORTED, "slot-ELL width %d not built", a.D);
+    }
     if (a.D == 16) return launch_sparse(k_anneal_potts<16>, a, per_wave, st);
     if (a.D == 32) return launch_sparse(k_anneal_potts<32>, a, per_wave, st);
     if (a.D == 64) return launch_sparse(k_anneal_potts<64>, a, per_wave, st);

@@ -229,9 +229,10 @@ class Problem:
     @classmethod
     def potts_csr(cls, rowptr, col, val, c_pair: float, n: int, num_cases: int,
                   lin_offset: float = 0.0, device: int = 0, order: Optional[str] = None,
-                  energy_model=None) -> "Problem":
+                  energy_model=None, node_weights=None) -> "Problem":
         """``order="slots"`` / ``"padded"``: as in :meth:`csr_rank1` (labels go in and come out in the caller's order).
-        ``energy_model=(val64, c_pair64)``: fp64 coefficients for the reported energies."""
+        ``energy_model=(val64, c_pair64)``: fp64 coefficients for the reported energies.
+        ``node_weights=(wq, cw, w64)``: node weights of the pair term in the caller's order (:meth:`set_node_weights`)."""
         perm = None
         val64 = None if energy_model is None else np.asarray(energy_model[0], dtype=np.float64)
         if order == "slots":
@@ -248,7 +249,8 @@ class Problem:
             seats, nslots, _ = padded_slot_layout(rowptr, col)
             if nslots * 64 > _POTTS_MAX_N >= int(n):  # the holes would push the model over the kernel's size limit (its
                 # LDS budget is checked against the padded size): the packed order, clashing slots on the general path
-                return cls.potts_csr(rowptr, col, val, c_pair, n, num_cases, lin_offset, device, "slots", energy_model)
+                return cls.potts_csr(rowptr, col, val, c_pair, n, num_cases, lin_offset, device, "slots", energy_model,
+                                     node_weights)
             n_caller, n = int(n), nslots * 64
             if val64 is not None:
                 rowptr, col, val, val64 = pad_csr(rowptr, col, val, seats, n, also=val64)
@@ -276,7 +278,35 @@ class Problem:
             prob = cls(h, _lib.KIND_POTTS_CSR, int(n), int(num_cases), device, perm=perm)
         if val64 is not None:
             prob._set_energy_model(val64, None, float(energy_model[1]), len(val))
+        if node_weights is not None:
+            try:
+                prob.set_node_weights(*node_weights)
+            except Exception:
+                prob.close()
+                raise
         return prob
+
+    def set_node_weights(self, wq, cw, w64=None):
+        """Potts problems: integer node weights ``wq`` (>= 0, sum <= 2^30) of the pair term, their fp32 coefficients
+        ``cw`` and fp64 weights ``w64`` for the reported energies (default ``wq``), in the caller's variable order
+        (chain 2d, include/mi_sa.h mi_sa_problem_set_node_weights).  Holes of a padded layout get weight 0.  Call
+        before the first anneal."""
+        wq = np.asarray(wq)
+        cw = np.asarray(cw, dtype=np.float32)
+        w64 = None if w64 is None else np.asarray(w64, dtype=np.float64)
+        if wq.shape != (self.n,) or cw.shape != (self.n,) or (w64 is not None and w64.shape != (self.n,)):
+            raise ValueError("node weights need one entry per variable (%d)" % self.n)
+        if np.any(wq < 0) or np.any(wq > np.iinfo(np.int32).max):
+            raise ValueError("node weights must be non-negative int32 values")
+        cols = np.arange(self.n) if self._inv is None else self._inv
+        dq = np.zeros(self.n_dev, dtype=np.int32)
+        dc = np.zeros(self.n_dev, dtype=np.float32)
+        dw = np.zeros(self.n_dev, dtype=np.float64)
+        dq[cols] = wq.astype(np.int32)
+        dc[cols] = cw
+        dw[cols] = wq.astype(np.float64) if w64 is None else w64
+        _lib.check(_lib.load().mi_sa_problem_set_node_weights(self._h, _ptr(dq, C.c_int32), _ptr(dc, C.c_float),
+                                                               _ptr(dw, C.c_double)))
 
     def _set_energy_model(self, val64, lin64, c_pair64, nnz):
         if len(val64) != nnz or (lin64 is not None and len(lin64) != self.n_dev):

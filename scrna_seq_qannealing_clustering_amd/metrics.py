@@ -118,3 +118,31 @@ def cluster_stats(X: np.ndarray, labels, device: int = 0, return_distances: bool
     if return_distances:
         out["distances"] = r["distances"]
     return out
+
+
+def modularity(G, labels, resolution: float = 1.0) -> float:
+    """Weighted modularity ``Q_gamma`` of a labelling (host fp64), what ``networkx.community.modularity(G, communities,
+    weight="weight", resolution=gamma)`` returns: ``sum_c [L_c / m - gamma (K_c / 2m)^2]`` with L_c the weight inside
+    community c (a self-loop once) and K_c its degree sum (a self-loop twice).  ``labels``: a dict node -> label or a
+    sequence in ``G.nodes`` order."""
+    nodes = list(G.nodes)
+    index = {v: i for i, v in enumerate(nodes)}
+    lab = np.asarray([labels[v] for v in nodes] if isinstance(labels, dict) else labels).reshape(-1)
+    if len(lab) != len(nodes):
+        raise ValueError("labels must cover every node of G")
+    _, lab = np.unique(lab, return_inverse=True)
+    eu, ev, w = [], [], []
+    for u, v, d in G.edges(data="weight", default=1):
+        eu.append(index[u])
+        ev.append(index[v])
+        w.append(float(d))
+    eu, ev, w = np.asarray(eu, dtype=np.int64), np.asarray(ev, dtype=np.int64), np.asarray(w, dtype=np.float64)
+    k = np.zeros(len(nodes))
+    np.add.at(k, eu, w)
+    np.add.at(k, ev, w)
+    m = float(np.sum(k)) / 2.0
+    if m <= 0.0:
+        raise ValueError("modularity is undefined on a graph without edges")
+    inside = float(np.sum(w[lab[eu] == lab[ev]]))
+    Kc = np.bincount(lab, weights=k)
+    return inside / m - float(resolution) * float(np.sum((Kc / (2.0 * m)) ** 2))

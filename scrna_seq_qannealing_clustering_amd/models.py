@@ -339,6 +339,9 @@ class PottsModel:
     c_pair: float
     lin: np.ndarray                      # float64[n]    case-independent linear bias per variable
     info: Dict[str, Any] = field(default_factory=dict)
+    # node weights of the pair term (chain 2d): the pair u, v of one cluster carries c_pair w_u w_v instead of c_pair.
+    # None: every weight is 1 (the uniform term)
+    node_weight: Optional[np.ndarray] = None
 
     @property
     def num_variables(self) -> int:
@@ -354,6 +357,13 @@ class PottsModel:
         rows = np.repeat(np.arange(n), np.diff(self.rowptr))
         same = (L[:, rows] == L[:, self.col])
         e = 0.5 * (same * self.val[None, :]).sum(axis=1)
+        if self.node_weight is not None:
+            w = np.asarray(self.node_weight, dtype=np.float64)
+            sq = float(np.sum(w * w))
+            for r in range(R):
+                W = np.bincount(L[r], weights=w, minlength=self.num_cases)
+                e[r] += self.c_pair * 0.5 * (float(np.sum(W * W)) - sq)
+            return e + self.lin_offset
         for r in range(R):
             cnt = np.bincount(L[r], minlength=self.num_cases).astype(np.float64)
             e[r] += self.c_pair * 0.5 * float(np.sum(cnt * (cnt - 1.0)))
@@ -378,6 +388,92 @@ def build_dqm_potts(G, num_of_clusters: int, gamma: float) -> PottsModel:
     rowptr, col, val = _csr_from_edges(n, eu, ev, pair)
     return PottsModel(nodes, K, rowptr, col, val, c_pair=2.0 * gamma, lin=lin,
                       info={"gamma": gamma, "kind": "dqm"})
+
+
+def quantise_node_weights(w64, c: float):
+    """The integer weights and fp32 coefficients of chain 2d for the fp64 node weights ``w64`` of a pair term
+    ``c w_u w_v``: ``wq_i = round(w_i 2^e)`` with e the largest integer for which ``sum wq <= 2^30`` (exact integer
+    cluster sums on the device), ``cw_i = fp32(c 2^-2e wq_i)`` (one fp64 product, then fp32).  Returns ``(wq, cw, e)``."""
+    w = np.asarray(w64, dtype=np.float64)
+    if np.any(w < 0) or not np.all(np.isfinite(w)):
+        raise ValueError("node weights must be finite and non-negative")
+    total = float(np.sum(w))
+    if total <= 0.0:
+        raise ValueError("node weights sum to zero")
+    lim = 1 << 30
+
+    def qsum(e):
+        return int(np.sum(np.rint(np.ldexp(w, e))))
+
+    e = int(np.floor(np.log2(lim / total)))
+    while qsum(e + 1) <= lim:
+        e += 1
+    while qsum(e) > lim:
+        e -= 1
+    wq = np.rint(np.ldexp(w, e)).astype(np.int64)
+    cw = (np.ldexp(float(c), -2 * e) * wq.astype(np.float64)).astype(np.float32)
+    return wq.astype(np.int32), cw, e
+
+
+def potts_node_weights(model: PottsModel):
+    """``(wq int32, cw float32, w64 float64)`` of a model with node weights (mi_sa_problem_set_node_weights), or None."""
+    if model.node_weight is None:
+        return None
+    w64 = np.asarray(model.node_weight, dtype=np.float64)
+    wq, cw, _ = quantise_node_weights(w64, model.c_pair)
+    return wq, cw, w64
+
+
+def build_modularity_potts(G, resolution: float = 1.0, num_of_clusters: int = 16) -> PottsModel:
+    """Weighted modularity at resolution gamma -- the objective of Seurat's ``FindClusters(..., algorithm = 1,
+    resolution = gamma)`` (Louvain) on the SNN graph, which the reference's notebooks compare every annealed
+    clustering with -- as a Potts model with node weights:
+        E(l) = lin_offset + sum_{u<v, l_u == l_v} (-A_uv + c k_u k_v),   c = gamma / (2m),   k_u = sum_v A_uv,
+        lin_offset = c sum_u k_u^2 / 2 - sum_u A_uu
+    so that ``Q_gamma(l) = -E(l) / m`` is what ``networkx.community.modularity(G, communities, weight="weight",
+    resolution=gamma)`` returns (self-loops as networkx counts them).  ``num_of_clusters`` is an upper bound: empty
+    labels are allowed.  The exact degrees are the node weights (reported energies); the chain runs on their
+    quantised form (:func:`quantise_node_weights`)."""
+    K = int(num_of_clusters)
+    if K < 2:
+        raise ValueError("modularity clustering needs at least 2 labels (got %d)" % K)
+    nodes, eu, ev, w = graph_arrays(G)
+    n = len(nodes)
+    eu, ev, w = np.asarray(eu, dtype=np.int64), np.asarray(ev, dtype=np.int64), np.asarray(w, dtype=np.float64)
+    if len(w) and np.any(w < 0):
+        raise ValueError("modularity needs non-negative edge weights")
+    k = np.zeros(n, dtype=np.float64)
+    np.add.at(k, eu, w)
+    np.add.at(k, ev, w)                  # (a self-loop adds its weight twice, as networkx's degree counts it)
+    two_m = float(np.sum(k))
+    if len(w) == 0 or two_m <= 0.0:
+        raise ValueError("modularity is undefined on a graph without edges")
+    gamma = float(resolution)
+    c = gamma / two_m
+    loops = float(np.sum(w[eu == ev]))
+    rowptr, col, val = _csr_from_edges(n, eu, ev, -w)
+    lin = np.zeros(n, dtype=np.float64)
+    lin[0] = c * float(np.sum(k * k)) / 2.0 - loops
+    _, _, e = quantise_node_weights(k, c)
+    return PottsModel(nodes, K, rowptr, col, val, c_pair=c, lin=lin,
+                      info={"kind": "modularity", "resolution": gamma, "m": two_m / 2.0, "scale_exp": e},
+                      node_weight=k)
+
+
+def modularity_beta_range(model: PottsModel) -> Tuple[float, float]:
+    """Default inverse-temperature range of a modularity model (clustering_modularity): hot, a move that costs the
+    median degree is accepted with probability 1/100; cold, the smallest non-zero pair term with 1/10.  The neal rule
+    of ``default_potts_beta_range`` starts from the largest possible |dE| instead, about twice the largest degree, and
+    spends most of a run far above the temperatures at which the communities form."""
+    k = np.asarray(model.node_weight, dtype=np.float64)
+    n = model.num_variables
+    rows = np.repeat(np.arange(n), np.diff(model.rowptr))
+    full = np.abs(model.val + model.c_pair * k[rows] * k[model.col])
+    full = full[full != 0.0]
+    kpos = k[k > 0.0]
+    hot = float(np.log(100.0) / np.median(kpos)) if len(kpos) else 1.0
+    cold = float(np.log(10.0) / full.min()) if len(full) else 10.0 * hot
+    return hot, max(cold, hot)
 
 
 def build_cqm_potts(G, num_of_clusters: int, min_cluster_size: int = 20) -> PottsModel:

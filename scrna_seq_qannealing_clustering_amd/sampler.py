@@ -30,7 +30,7 @@ from . import _lib
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
 from .engine import Problem, energy_dense_f64, layout_block_for
 from .models import (PottsModel, QuboModel, _csr_from_edges, default_beta_range,
-                     make_beta_schedule, qubo_dict_to_model)
+                     make_beta_schedule, potts_node_weights, qubo_dict_to_model)
 from .sampleset import SampleSet
 
 # keyword arguments of the samplers the reference uses that have no meaning for an annealer on a GPU
@@ -324,12 +324,14 @@ class MI355XSampler:
         seed = self._seed(kw.get("seed"))
         num_reads, init = self._initial_states(kw, model.variables, kw.get("num_reads"), "DISCRETE")
         betas, beta_range, stype = self._schedule(kw, lambda: default_potts_beta_range(model))
+        # the CQM's "every cluster has at least m members" (CQM_clustering.py:46-48): a hard constraint on moves
+        min_size = int(kw.get("min_cluster_size", model.info.get("min_cluster_size", 0)) or 0)
+        if model.node_weight is not None and min_size > 0:
+            raise ValueError("node weights (a modularity model) together with min_cluster_size are not supported")
         prob = Problem.potts_csr(model.rowptr, model.col, model.val.astype(np.float32),
                                  float(np.float32(model.c_pair)), n, model.num_cases,
                                  lin_offset=model.lin_offset, device=self.device, order="padded",
-                                 energy_model=(model.val, model.c_pair))
-        # the CQM's "every cluster has at least m members" (CQM_clustering.py:46-48): a hard constraint on moves
-        min_size = int(kw.get("min_cluster_size", model.info.get("min_cluster_size", 0)) or 0)
+                                 energy_model=(model.val, model.c_pair), node_weights=potts_node_weights(model))
         if min_size * model.num_cases > n:
             raise ValueError("min_cluster_size %d x %d clusters exceeds the %d variables" % (min_size, model.num_cases, n))
         with prob:
@@ -388,6 +390,20 @@ def default_potts_beta_range(model: PottsModel) -> Tuple[float, float]:
     coupling gets acceptance 1/100 (the neal rule applied to the move set of the Potts chain)."""
     n = model.num_variables
     rows = np.repeat(np.arange(n), np.diff(model.rowptr))
+    if model.node_weight is not None:
+        # node weights: the pair u, v of one cluster carries c w_u w_v (w_u w_v on the stored pairs as well)
+        w = np.asarray(model.node_weight, dtype=np.float64)
+        cww = abs(model.c_pair) * w[rows] * w[model.col]
+        full = model.val + model.c_pair * w[rows] * w[model.col]
+        abs_sum = np.zeros(n)
+        np.add.at(abs_sum, rows, np.abs(full) - cww)
+        abs_sum += abs(model.c_pair) * w * (float(np.sum(w)) - w)
+        max_field = float(abs_sum.max()) if n else 1.0
+        cands = np.abs(full[full != 0.0])
+        min_bias = float(cands.min()) if len(cands) else 1.0
+        if max_field <= 0:
+            max_field = 1.0
+        return float(np.log(2.0) / max_field), float(np.log(100.0) / min_bias)
     full = model.val + model.c_pair
     abs_sum = np.zeros(n)
     np.add.at(abs_sum, rows, np.abs(full) - abs(model.c_pair))
