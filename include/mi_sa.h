@@ -162,6 +162,19 @@ int mi_sa_problem_set_pair_weights(mi_sa_problem *p, const int32_t *weights);
  * order).  Call before the first anneal of the problem; problems that never call it run as before. */
 int mi_sa_problem_set_node_weights(mi_sa_problem *p, const int32_t *wq, const float *cw, const double *w64);
 
+/* Potts problems with node weights: G >= 1 resolution groups (chain 2d per group).  cw: G x n fp32 coefficients in
+ * the caller's order, c64 / offset: G fp64 pair coefficients and energy offsets.  Call after
+ * mi_sa_problem_set_node_weights and before the first anneal.
+ * An anneal of R replicas then runs G groups of R / G consecutive replicas; replica r of group g = r / (R / G) anneals
+ * with row g of cw and reports sum_{edges, same label} val64 + c64[g] / 2 sum_q (W64_q^2 - sum_{l_i == q} w64_i^2) +
+ * offset[g], and its random stream is keyed by its index inside the group, replica_offset + r - g R / G: group g is the
+ * single-resolution run of (cw[g], c64[g], offset[g]) with the same seed, bit for bit.  The integer weights, the fp64
+ * weights and the couplings are shared.  MI_EINVAL: a NULL argument, G outside 1 .. 256, a problem without node weights,
+ * a call after the first anneal; at anneal time, an R that is not a multiple of G.  MI_EUNSUPPORTED with G > 1:
+ * MI_F_BETA_PER_REPLICA, MI_F_TEMPS_RESIDENT and tempering, mi_multi_gpu_*, mi_sa_best (one minimum across different
+ * objectives means nothing). */
+int mi_sa_problem_set_node_weight_groups(mi_sa_problem *p, int G, const float *cw, const double *c64, const double *offset);
+
 /* Diagnostic: copies the first `words` (<= 16) 64-bit statistics words of the last run ([0..2] as in
  * mi_sa_fetch; [8..12] per-phase cycle sums of builds compiled with -DMI_K2_PROFILE, otherwise 0; with words = 16,
  * [14] / [15] = chunks of the last scheduled dense run served by the workgroup kernel / the MFMA kernel). */
@@ -187,6 +200,8 @@ int mi_sa_anneal(mi_sa_problem *p, int R, uint32_t replica_offset, int num_sweep
 #define MI_F_BETA_PER_REPLICA 2u
 #define MI_F_TEMPS_RESIDENT   4u   /* betas ignored (may be NULL): every replica anneals at the temperature the
                                     * tempering state on the device holds for it (mi_sa_tempering_begin / _exchange) */
+#define MI_F_BETA_PER_GROUP   8u   /* mi_sa_anneal_ex: betas holds G x num_sweeps values, group-major (resolution groups,
+                                    * mi_sa_problem_set_node_weight_groups); without it every group uses the one schedule */
 int mi_sa_anneal_ex(mi_sa_problem *p, int R, uint32_t replica_offset, int num_sweeps,
                     const double *betas, uint64_t seed, const void *init, int resync_interval,
                     uint32_t sweep_offset, uint32_t flags);

@@ -8,6 +8,7 @@ Public surface:
     BinaryQuadraticModel, DiscreteQuadraticModel     stand-ins for the dimod classes
     clustering_bqm, clustering_bqm_2, clustering_bqm_3, clustering_dqm  reference-shaped drivers
     clustering_modularity    weighted modularity at a resolution (Seurat's FindClusters objective)
+    clustering_modularity_sweep  the same at several resolutions in one GPU launch
 """
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
 from .models import (PottsModel, QuboModel, add_size_window_penalty, build_bqm2_qubo,
@@ -29,7 +30,8 @@ def __getattr__(name):
     if name == "MI355XSampler":
         from .sampler import MI355XSampler
         return MI355XSampler
-    if name in ("clustering_bqm", "clustering_bqm_2", "clustering_bqm_3", "clustering_dqm", "clustering_modularity"):
+    if name in ("clustering_bqm", "clustering_bqm_2", "clustering_bqm_3", "clustering_dqm", "clustering_modularity",
+                "clustering_modularity_sweep"):
         from . import clustering
         return getattr(clustering, name)
     raise AttributeError(name)

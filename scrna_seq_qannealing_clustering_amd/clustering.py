@@ -272,6 +272,29 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
     return sampleset
 
 
+def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=None,
+                                sampler_kwargs: Optional[dict] = None, verbose=False):
+    """:func:`clustering_modularity` at several resolutions -- what Seurat users do with ``FindClusters(...,
+    resolution = c(...))`` -- in one upload and one launch (MI355XSampler.sample_dqm_many: one resolution group of
+    replicas per value).  Returns one sampleset per resolution, in the order given; each equals what
+    ``clustering_modularity(G, resolution, ...)`` returns with the same ``sampler_kwargs`` and has
+    ``info["resolution"]`` and ``info["modularity"]``.  Same defaults: 16000 sweeps, each resolution on its own
+    ``models.modularity_beta_range`` (a ``beta_range`` in ``sampler_kwargs`` applies to all).  An empty list, a
+    repeated value and a resolution <= 0 or not finite raise ValueError before any GPU work."""
+    from .models import build_modularity_sweep, check_resolutions, modularity_beta_range
+    res = check_resolutions(resolutions)
+    models = build_modularity_sweep(G, res, max_clusters)
+    kw = dict(num_sweeps=16000, beta_range=[modularity_beta_range(m) for m in models])
+    kw.update(sampler_kwargs or {})
+    samplesets = _sampler(sampler).sample_dqm_many(models, **kw)
+    for gamma, model, ss in zip(res, models, samplesets):
+        ss.info["resolution"] = gamma
+        ss.info["modularity"] = -np.asarray(ss.record["energy"], dtype=np.float64) / model.info["m"]
+        if verbose:
+            print("Resolution {}: modularity {}".format(gamma, float(np.max(ss.info["modularity"]))))
+    return samplesets
+
+
 def clustering_cqm(G, num_of_clusters, min_cluster_size: int = 20, sampler=None,
                    sampler_kwargs: Optional[dict] = None, verbose=False):
     """`clustering_cqm` (CQM_clustering.py:26-55): one-hot k-way model whose objective keeps heavy edges

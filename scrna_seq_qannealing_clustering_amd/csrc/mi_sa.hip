@@ -197,6 +197,8 @@ struct mi_sa_problem {
     int32_t *d_nwq = nullptr;                // Potts: node weights of the pair term per position (mi_sa_problem_set_node_weights)
     float *d_ncw = nullptr;                  // ... their fp32 coefficients
     double *d_nw64 = nullptr;                // ... their fp64 weights (reported energies)
+    int ngroups = 1;                         // ... resolution groups (mi_sa_problem_set_node_weight_groups): d_ncw holds ngroups x seats
+    double *d_gconst = nullptr;              // ... per group: fp64 pair coefficient, then energy offset [2 x ngroups] (null: c_pair64, offset)
     int k2_free_block = 0;                   // K2s: widest block of seats (256 / 128 / 64; 0 = none) that holds no edge anywhere in the model
     int cus = 0;
     // run buffers
@@ -941,6 +943,37 @@ int mi_sa_problem_set_node_weights(mi_sa_problem *p, const int32_t *wq, const fl
     });
 }
 
+int mi_sa_problem_set_node_weight_groups(mi_sa_problem *p, int G, const float *cw, const double *c64, const double *offset)
+{
+    if (!p || !cw || !c64 || !offset) return fail(MI_EINVAL, "NULL argument");
+    if (const int rc_w = settle(p)) return rc_w;
+    if (G < 1 || G > 256) return fail(MI_EINVAL, "resolution groups: 1 .. 256 (got %d)", G);
+    if (!p->d_nwq) return fail(MI_EINVAL, "resolution groups need node weights (mi_sa_problem_set_node_weights) first");
+    if (p->has_run) return fail(MI_EINVAL, "resolution groups must be set before the first anneal");
+    return guarded([&]() -> int {
+        const size_t seats = (size_t)p->slots * 64;
+        std::vector<float> hc((size_t)G * seats, 0.0f);
+        for (int g = 0; g < G; ++g) {
+            for (int i = 0; i < p->n; ++i)
+                if (!(p->h_meta[(size_t)i] >> 31)) hc[(size_t)g * seats + i] = cw[(size_t)g * p->n + i];   // (holes: 0)
+        }
+        HIP_TRY(hipSetDevice(p->device));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        if (G != p->ngroups) {
+            HIP_TRY(hipFree(p->d_ncw));
+            p->d_ncw = nullptr;
+            HIP_TRY(hipMalloc((void **)&p->d_ncw, (size_t)G * seats * sizeof(float)));
+            p->ngroups = G;
+        }
+        if (!p->d_gconst) HIP_TRY(hipMalloc((void **)&p->d_gconst, 2 * 256 * sizeof(double)));
+        std::vector<double> hk(c64, c64 + G);
+        hk.insert(hk.end(), offset, offset + G);
+        HIP_TRY(hipMemcpy(p->d_ncw, hc.data(), hc.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->d_gconst, hk.data(), hk.size() * sizeof(double), hipMemcpyHostToDevice));
+        return MI_OK;
+    });
+}
+
 int mi_sa_problem_set_energy_model_f64(mi_sa_problem *p, const double *val, const double *lin, double c_pair)
 {
     return guarded([&]() -> int { return set_energy_model_impl(p, val, lin, c_pair); });
@@ -952,7 +985,7 @@ int mi_sa_problem_destroy(mi_sa_problem *p)
     (void)settle(p);
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    void *bufs[] = {p->d_nwq, p->d_ncw, p->d_nw64, p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
+    void *bufs[] = {p->d_gconst, p->d_nwq, p->d_ncw, p->d_nw64, p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
@@ -1038,9 +1071,16 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
     if (const int rc_w = settle(p)) return rc_w;
     const bool cont = (flags & MI_F_CONTINUE) != 0, resident = (flags & MI_F_TEMPS_RESIDENT) != 0;
     const bool per_replica = (flags & MI_F_BETA_PER_REPLICA) != 0 || resident;
-    const int num_betas = per_replica ? R : num_sweeps;
-    if (flags & ~(uint32_t)(MI_F_CONTINUE | MI_F_BETA_PER_REPLICA | MI_F_TEMPS_RESIDENT)) return fail(MI_EINVAL, "unknown flags 0x%x", flags);
+    const bool per_group = (flags & MI_F_BETA_PER_GROUP) != 0;
+    if (flags & ~(uint32_t)(MI_F_CONTINUE | MI_F_BETA_PER_REPLICA | MI_F_TEMPS_RESIDENT | MI_F_BETA_PER_GROUP))
+        return fail(MI_EINVAL, "unknown flags 0x%x", flags);
     if (!p) return fail(MI_EINVAL, "NULL problem");
+    const int G = p->ngroups;                    // resolution groups (1 unless mi_sa_problem_set_node_weight_groups)
+    if (per_group && per_replica) return fail(MI_EINVAL, "MI_F_BETA_PER_GROUP together with per-replica temperatures");
+    if (G > 1 && per_replica)
+        return fail(MI_EUNSUPPORTED, "resolution groups together with per-replica or resident temperatures are not supported");
+    if (R % G != 0) return fail(MI_EINVAL, "R = %d is not a multiple of the %d resolution groups", R, G);
+    const int num_betas = per_replica ? R : (per_group ? G * num_sweeps : num_sweeps);
     if (resident && (p->pt_T == 0 || p->pt_R_local != R))
         return fail(MI_ESTATE, "MI_F_TEMPS_RESIDENT needs mi_sa_tempering_begin for %d replicas on this problem", R);
     if (R < 1) return fail(MI_EINVAL, "R must be >= 1 (got %d)", R);
@@ -1054,7 +1094,8 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
         if (!(betas[s] > 0.0) || !std::isfinite(betas[s]))
             return fail(MI_EINVAL, "betas[%d] = %g is not a positive finite number", s, betas[s]);
     HIP_TRY(hipSetDevice(p->device));
-    int rc = ensure_run_buffers(p, R, num_betas, init != nullptr);
+    // (the device buffer of the temperatures holds G x num_sweeps values: one schedule per group, or one shared)
+    int rc = ensure_run_buffers(p, R, G * num_sweeps > num_betas ? G * num_sweeps : num_betas, init != nullptr);
     if (rc) return rc;
     if (!resident) {                             // (tempering rounds: the exchange kernel keeps temps[] up to date)
         std::vector<float> temps((size_t)(num_betas > 0 ? num_betas : 1), 1.0f);
@@ -1179,6 +1220,7 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
         a.ell_val64 = p->d_ell_val64; a.lin64 = p->d_lin64; a.c_pair64 = p->c_pair64;
         a.wgt = p->d_wgt; a.wslot = p->kind == MI_KIND_CSR_RANK1 ? p->wslot : -1;
         a.nwq = p->d_nwq; a.ncw = p->d_ncw; a.nw64 = p->d_nw64;
+        a.groups = G; a.temps_group_stride = per_group ? num_sweeps : 0; a.gconst = p->d_gconst;
         if (p->kind == MI_KIND_POTTS_CSR && init) {
             // labels must be < K: validated on the host copy (the device trusts them as cnt[] indices)
             const uint16_t *l = static_cast<const uint16_t *>(init);
@@ -1266,6 +1308,7 @@ int mi_sa_tempering_begin(mi_sa_problem *p, const double *ladder_betas, int T, i
 {
     if (!p || !ladder_betas) return fail(MI_EINVAL, "NULL argument");
     if (const int rc_w = settle(p)) return rc_w;
+    if (p->ngroups > 1) return fail(MI_EUNSUPPORTED, "tempering with resolution groups is not supported");
     if (T < 2 || T > 1024) return fail(MI_EINVAL, "a tempering ladder has 2 .. 1024 temperatures (got %d)", T);
     if (chains < 1) return fail(MI_EINVAL, "chains must be >= 1");
     const long long total = (long long)T * chains;
@@ -1447,6 +1490,7 @@ int mi_sa_best(mi_sa_problem *p, int *out_index, double *out_energy, uint64_t *o
 {
     if (!p) return fail(MI_EINVAL, "NULL problem");
     if (const int rc_w = settle(p)) return rc_w;
+    if (p->ngroups > 1) return fail(MI_EUNSUPPORTED, "best of a run with resolution groups: one minimum across different objectives");
     if (!p->has_run) return fail(MI_ESTATE, "no anneal has been run on this problem");
     HIP_TRY(hipSetDevice(p->device));
     unsigned long long init_key = ~0ull, key = 0;
@@ -1483,6 +1527,7 @@ static int multi_check(mi_sa_problem *const *problems, int ndev)
     if (!problems || ndev < 1) return fail(MI_EINVAL, "need ndev >= 1 problem handles");
     for (int d = 0; d < ndev; ++d) {
         if (!problems[d]) return fail(MI_EINVAL, "problem %d is NULL", d);
+        if (problems[d]->ngroups > 1) return fail(MI_EUNSUPPORTED, "problem %d has resolution groups: not sharded over GPUs", d);
         if (problems[d]->kind != problems[0]->kind || problems[d]->n != problems[0]->n || problems[d]->K != problems[0]->K)
             return fail(MI_EINVAL, "problem %d is not the model of problem 0 (kind / size differ)", d);
     }

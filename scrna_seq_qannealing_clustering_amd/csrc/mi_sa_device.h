@@ -305,13 +305,31 @@ struct EllArgs {
     const int32_t *nwq = nullptr;  // integer weights: the cluster sums are exact int32
     const float *ncw = nullptr;    // fp32 coefficients of the move test
     const double *nw64 = nullptr;  // fp64 weights of the reported energy
+    // ... and resolution groups (mi_sa_problem_set_node_weight_groups): replicas [g R / groups, (g + 1) R / groups) form
+    // group g and draw the random stream of their index inside it; ncw holds groups x slots * 64 coefficients, temps
+    // groups x temps_group_stride values (0: one schedule for all); gconst (nullable: c_pair64 and offset) the fp64 pair
+    // coefficient of every group, then its energy offset: [2 x groups].  Read by the weighted kernels only.  (One pointer
+    // for both tables: a struct of 256 bytes leaves the unweighted kernels' code exactly as it was.)
+    int groups = 1;
+    int temps_group_stride = 0;
+    const double *gconst = nullptr;
 };
 
+// WT kernels: the resolution group of replica r and its index inside the group (wave-uniform; groups = 1: 0 and r)
+struct ReplicaGroup { int g; int rank; };
+__device__ __forceinline__ ReplicaGroup replica_group(const EllArgs &a, int r)
+{
+    if (a.groups <= 1) return {0, r};
+    const int rg = a.R / a.groups;
+    const int g = r / rg;
+    return {g, r - g * rg};
+}
+
 // fp64 weighted pair term of the reported energy (chain 2d): c64 / 2 sum_q (W_q^2 - sum_{i in q} w_i^2), returned as this
-// lane's share of a wave sum (lane 0 carries the cluster sums).  label(i): the label of position i (every lane of the wave
+// lane's share of a wave sum (lane 0 carries the cluster sums); c64 of resolution group grp.  label(i): the label of position i (every lane of the wave
 // calls it for the same t).
 template <typename LabelF>
-__device__ double node_weight_energy(const EllArgs &a, int lane, LabelF label)
+__device__ double node_weight_energy(const EllArgs &a, int lane, int grp, LabelF label)
 {
     double own = 0.0, tot = 0.0;
     for (int t = 0; t < a.slots; ++t) {
@@ -327,7 +345,7 @@ __device__ double node_weight_energy(const EllArgs &a, int lane, LabelF label)
         s = wave_sum_f64(s);
         tot += s * s;
     }
-    const double c64 = a.ell_val64 ? a.c_pair64 : (double)a.c_pair;
+    const double c64 = a.gconst ? a.gconst[grp] : (a.ell_val64 ? a.c_pair64 : (double)a.c_pair);
     return 0.5 * c64 * (own + (lane == 0 ? tot : 0.0));
 }
 

@@ -80,7 +80,11 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
     extern __shared__ __attribute__((aligned(16))) char lds[];      // cell of seat i at byte 2 i, then the K cluster sizes
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x;
-    const uint32_t gid = a.replica_offset + (uint32_t)r;
+    // WT: the replica's resolution group (its coefficients, schedule and energy constants) and its index inside the group,
+    // which keys its random stream: group g of a grouped run is the single-resolution run of its own tables
+    const ReplicaGroup rgp = WT ? replica_group(a, r) : ReplicaGroup{0, r};
+    const uint32_t gid = a.replica_offset + (uint32_t)rgp.rank;
+    const int tgo = WT ? rgp.g * a.temps_group_stride : 0;   // (the group's schedule: its first entry in temps)
     const int n = a.n, slots = a.slots, K = a.K;
     uint16_t *cell = reinterpret_cast<uint16_t *>(lds);
     const uint32_t cnt_base = (uint32_t)slots * 128u;
@@ -97,7 +101,7 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
             uint32_t pw0[4], pw2[4];
             uint32_t buf = 0;
             for (int s = 0; s < a.num_sweeps; ++s) {
-                float Tp = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a.temps[a.temps_per_replica ? r : s])));
+                float Tp = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a.temps[tgo + (a.temps_per_replica ? r : s)])));
                 if constexpr (KM == 8) Tp = 2.0f * Tp;
                 const uint32_t sw = (uint32_t)s + a.sweep_offset;
 #pragma unroll 1
@@ -184,7 +188,7 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
         p.meta = __builtin_amdgcn_raw_buffer_load_b32(rs_meta, lane * 4, tt * 256, 0);
         if constexpr (WT) {
             p.wq = a.nwq[tt * 64 + lane];
-            p.cw = a.ncw[tt * 64 + lane];
+            p.cw = a.ncw[(size_t)rgp.g * slots * 64 + tt * 64 + lane];   // (the group's coefficients)
         } else {
             p.wq = 1;
             p.cw = 0.0f;
@@ -416,7 +420,7 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
     };
 
     for (int s = 0; s < a.num_sweeps; ++s) {
-        T = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a.temps[a.temps_per_replica ? r : s])));
+        T = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a.temps[tgo + (a.temps_per_replica ? r : s)])));
         if constexpr (KM == 8) T = 2.0f * T;                        // (the doubled field sum against the doubled threshold)
         const uint32_t sw = (uint32_t)s + a.sweep_offset;
         SlotAdj P = fetch_adj(0), Q;
@@ -464,14 +468,14 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
         }
     }
     if constexpr (WT) {
-        e += node_weight_energy(a, lane, [&](int j) { return dec_label<KM>(cell[j]); });
+        e += node_weight_energy(a, lane, rgp.g, [&](int j) { return dec_label<KM>(cell[j]); });
     } else {
         const int cntv = cnt[lane];
         if (lane < K) e += (a.ell_val64 ? a.c_pair64 : (double)a.c_pair) * 0.5 * (double)cntv * (double)(cntv - 1);
     }
     e = wave_sum_f64(e);
     if (lane == 0) {
-        a.energy[r] = e + a.offset;
+        a.energy[r] = e + (WT && a.gconst ? a.gconst[a.groups + rgp.g] : a.offset);
         atomicAdd(&a.stats[1], accepted);
     }
 }

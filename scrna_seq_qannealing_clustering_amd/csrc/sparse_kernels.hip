@@ -453,8 +453,12 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int r = blockIdx.x * (int)(blockDim.x >> 6) + wave;
     if (r >= a.R) return;
-    const uint32_t gid = a.replica_offset + (uint32_t)r;
+    // WT: the replica's resolution group and its index inside the group (the key of its random stream), as in K3f
+    const ReplicaGroup rgp = WT ? replica_group(a, r) : ReplicaGroup{0, r};
+    const uint32_t gid = a.replica_offset + (uint32_t)rgp.rank;
+    const int tgo = WT ? rgp.g * a.temps_group_stride : 0;   // (the group's schedule: its first entry in temps)
     const int n = a.n, slots = a.slots, K = a.K;
+    const float *ncw = WT ? a.ncw + (size_t)rgp.g * slots * 64 : nullptr;    // (the group's coefficients)
     // LDS per wave: the labels (one byte per variable) and the K cluster sizes (one int each, 64 reserved)
     uint8_t *lab = reinterpret_cast<uint8_t *>(lds) + (size_t)wave * ((size_t)slots * 64 + 256);
     int *cnt = reinterpret_cast<int *>(lab + (size_t)slots * 64);
@@ -523,7 +527,7 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
     const uint32_t magic = dK == 1 ? 0xffffffffu : (uint32_t)(0x100000000ull / dK);   // (2^32 does not fit for d = 1)
     for (int s = 0; s < a.num_sweeps && K > 1; ++s) {
         const float T = __int_as_float(__builtin_amdgcn_readfirstlane(
-            __float_as_int(a.temps[a.temps_per_replica ? r : s])));
+            __float_as_int(a.temps[tgo + (a.temps_per_replica ? r : s)])));
         SlotAdj nxt;
         if constexpr (PF) nxt = fetch_adj(0);
         uint32_t w0[4] = {0u, 0u, 0u, 0u}, w2[4] = {0u, 0u, 0u, 0u};
@@ -597,7 +601,7 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
             float cwi = a.c_pair;
             if constexpr (WT) {                              // W_a - wq_i and W_b: dE = fmaf(cw_i, (float)(W_b - W_a + wq_i), hd)
                 wqi = a.nwq[i];
-                cwi = a.ncw[i];
+                cwi = ncw[i];
                 ia = cnt[la] - wqi;
             }
             // one-hot images of this lane's two labels (K <= 32): a move a_s -> b_s then updates the sizes with
@@ -818,14 +822,14 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
         }
     }
     if constexpr (WT) {
-        e += node_weight_energy(a, lane, [&](int j) { return (uint32_t)lab[j]; });
+        e += node_weight_energy(a, lane, rgp.g, [&](int j) { return (uint32_t)lab[j]; });
     } else {
         cntv = cnt[lane];
         if (lane < K) e += (a.ell_val64 ? a.c_pair64 : (double)a.c_pair) * 0.5 * (double)cntv * (double)(cntv - 1);
     }
     e = wave_sum_f64(e);
     if (lane == 0) {
-        a.energy[r] = e + a.offset;
+        a.energy[r] = e + (WT && a.gconst ? a.gconst[a.groups + rgp.g] : a.offset);
         atomicAdd(&a.stats[1], accepted);
     }
 }

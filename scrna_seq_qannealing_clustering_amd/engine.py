@@ -53,6 +53,7 @@ class Problem:
         if seats is not None:
             self._inv = np.asarray(seats, dtype=np.int64)
         self.n_dev = int(n if n_dev is None else n_dev)
+        self.groups = 1                  # resolution groups (set_node_weight_groups)
 
     # -- constructors ---------------------------------------------------------------------------
     @classmethod
@@ -308,6 +309,28 @@ class Problem:
         _lib.check(_lib.load().mi_sa_problem_set_node_weights(self._h, _ptr(dq, C.c_int32), _ptr(dc, C.c_float),
                                                                _ptr(dw, C.c_double)))
 
+    def set_node_weight_groups(self, cw, c64, offset):
+        """Resolution groups of a problem with node weights (include/mi_sa.h mi_sa_problem_set_node_weight_groups):
+        ``cw`` [G, n] fp32 coefficients in the caller's variable order, ``c64`` / ``offset`` [G] the fp64 pair coefficient
+        and energy offset of each group.  An anneal of R replicas then runs G groups of R / G consecutive replicas, each
+        keyed by its index inside the group (group g = the single-resolution run of its own tables, same seed); ``betas``
+        of shape [G, num_sweeps] give each group its own schedule.  Holes of a padded layout get 0.  Call after
+        :meth:`set_node_weights` and before the first anneal."""
+        cw = np.asarray(cw, dtype=np.float32)
+        c64 = np.ascontiguousarray(c64, dtype=np.float64)
+        offset = np.ascontiguousarray(offset, dtype=np.float64)
+        if cw.ndim != 2 or cw.shape[1] != self.n:
+            raise ValueError("cw must have shape [G, n] with n = %d" % self.n)
+        G = cw.shape[0]
+        if c64.shape != (G,) or offset.shape != (G,):
+            raise ValueError("c64 and offset need one entry per group (%d)" % G)
+        cols = np.arange(self.n) if self._inv is None else self._inv
+        dc = np.zeros((G, self.n_dev), dtype=np.float32)
+        dc[:, cols] = cw
+        _lib.check(_lib.load().mi_sa_problem_set_node_weight_groups(self._h, int(G), _ptr(dc, C.c_float),
+                                                                    _ptr(c64, C.c_double), _ptr(offset, C.c_double)))
+        self.groups = int(G)
+
     def _set_energy_model(self, val64, lin64, c_pair64, nnz):
         if len(val64) != nnz or (lin64 is not None and len(lin64) != self.n_dev):
             self.close()
@@ -364,16 +387,20 @@ class Problem:
         constant for ``num_sweeps`` sweeps (a tempering rung); ``betas=None`` with ``num_sweeps``: every replica
         at the temperature the device-side tempering state holds for it (``tempering_begin`` / ``_exchange``).
         ``continue_run`` starts from the states the previous call left on the device; ``sweep_offset`` continues
-        its random stream."""
+        its random stream.  With resolution groups (:meth:`set_node_weight_groups`) ``betas`` may have shape
+        [G, num_sweeps]: one schedule per group (else every group uses the one given)."""
         resident = betas is None
         if resident and num_sweeps is None:
             raise ValueError("betas=None (temperatures resident on the device) needs num_sweeps")
         betas = None if resident else np.ascontiguousarray(betas, dtype=np.float64)
         per_replica = num_sweeps is not None
+        per_group = not resident and betas.ndim == 2
+        if per_group and (per_replica or betas.shape[0] != self.groups):
+            raise ValueError("per-group betas need shape [G, num_sweeps] with G = %d groups" % self.groups)
         if per_replica and not resident and len(betas) != num_reads:
             raise ValueError("per-replica betas need one entry per replica")
-        flags = (1 if continue_run else 0) | (2 if per_replica else 0) | (4 if resident else 0)
-        sweeps = int(num_sweeps) if per_replica else len(betas)
+        flags = (1 if continue_run else 0) | (2 if per_replica else 0) | (4 if resident else 0) | (8 if per_group else 0)
+        sweeps = int(num_sweeps) if per_replica else (betas.shape[1] if per_group else len(betas))
         init = None
         if initial_states is not None:
             init = np.ascontiguousarray(initial_states, dtype=self.state_dtype)

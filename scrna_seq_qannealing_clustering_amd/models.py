@@ -460,6 +460,49 @@ def build_modularity_potts(G, resolution: float = 1.0, num_of_clusters: int = 16
                       node_weight=k)
 
 
+def check_resolutions(resolutions) -> List[float]:
+    """A list of resolutions for a sweep: non-empty, every value finite and > 0, no value twice (ValueError otherwise)."""
+    res = [float(g) for g in resolutions]
+    if not res:
+        raise ValueError("a resolution sweep needs at least one resolution")
+    if not all(np.isfinite(g) and g > 0.0 for g in res):
+        raise ValueError("resolutions must be finite and > 0 (got %r)" % (res,))
+    if len(set(res)) != len(res):
+        raise ValueError("resolutions must be distinct (got %r)" % (res,))
+    return res
+
+
+def build_modularity_sweep(G, resolutions, num_of_clusters: int = 16) -> List[PottsModel]:
+    """One modularity model per resolution (:func:`build_modularity_potts`, array for array): they share the graph,
+    the labels and the node weights and differ only in ``c_pair`` and ``lin_offset`` -- what one grouped launch
+    anneals at once (MI355XSampler.sample_dqm_many, :func:`potts_node_weight_groups`)."""
+    return [build_modularity_potts(G, g, num_of_clusters) for g in check_resolutions(resolutions)]
+
+
+def potts_node_weight_groups(models: Sequence[PottsModel]):
+    """``(wq int32, cw float32 [G, n], w64 float64, c64 float64 [G], offset float64 [G])`` of node-weighted Potts models
+    that differ only in their pair coefficient and energy offset (mi_sa_problem_set_node_weight_groups): row g of ``cw``
+    is ``potts_node_weights(models[g])[1]``.  ValueError unless every model has node weights and they all share
+    ``rowptr`` / ``col`` / ``val`` / ``node_weight`` / ``num_cases`` -- the quantised weights ``wq`` then agree too (the
+    exponent of :func:`quantise_node_weights` depends on the weights alone)."""
+    models = list(models)
+    if not models:
+        raise ValueError("no models")
+    m0 = models[0]
+    for m in models:
+        if m.node_weight is None:
+            raise ValueError("every model of a group run needs node weights")
+        if not (m.num_cases == m0.num_cases and np.array_equal(m.rowptr, m0.rowptr) and np.array_equal(m.col, m0.col)
+                and np.array_equal(m.val, m0.val) and np.array_equal(m.node_weight, m0.node_weight)):
+            raise ValueError("the models of a group run must share rowptr, col, val, node_weight and num_cases")
+    rows = [potts_node_weights(m) for m in models]
+    wq, _, w64 = rows[0]
+    cw = np.stack([r[1] for r in rows])
+    c64 = np.array([float(m.c_pair) for m in models], dtype=np.float64)
+    offset = np.array([m.lin_offset for m in models], dtype=np.float64)
+    return wq, cw, w64, c64, offset
+
+
 def modularity_beta_range(model: PottsModel) -> Tuple[float, float]:
     """Default inverse-temperature range of a modularity model (clustering_modularity): hot, a move that costs the
     median degree is accepted with probability 1/100; cold, the smallest non-zero pair term with 1/10.  The neal rule

@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import os
 import time
-from typing import Any, Dict, Hashable, Mapping, Optional, Sequence, Tuple
+from typing import Any, Dict, Hashable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -30,7 +30,7 @@ from . import _lib
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
 from .engine import Problem, energy_dense_f64, layout_block_for
 from .models import (PottsModel, QuboModel, _csr_from_edges, default_beta_range,
-                     make_beta_schedule, potts_node_weights, qubo_dict_to_model)
+                     make_beta_schedule, potts_node_weight_groups, potts_node_weights, qubo_dict_to_model)
 from .sampleset import SampleSet
 
 # keyword arguments of the samplers the reference uses that have no meaning for an annealer on a GPU
@@ -153,6 +153,74 @@ class MI355XSampler:
         (DQM_clustering.py:29-43): case-independent linear biases, equal-case quadratic biases."""
         model = dqm if isinstance(dqm, PottsModel) else dqm_to_potts(dqm)
         return self._sample_potts(model, kwargs)
+
+    def sample_dqm_many(self, models, **kwargs) -> List[SampleSet]:
+        """Several node-weighted Potts models that differ only in their pair coefficient and energy offset -- the
+        modularity models of one graph at several resolutions (models.build_modularity_sweep) -- in ONE upload and ONE
+        launch: model g runs as resolution group g (include/mi_sa.h mi_sa_problem_set_node_weight_groups), and its
+        SampleSet equals ``sample_dqm(models[g], **kwargs)``.  ``num_reads`` is per model; ``num_sweeps``, ``seed``,
+        ``initial_states`` (tiled to every group) and the sampler's ``replica_offset`` are shared.  The default schedule
+        is each model's own (``default_potts_beta_range``); a ``beta_range`` of shape [2] or a ``beta_schedule`` applies
+        to every model, one of shape [len(models), 2] gives each its own.  Every SampleSet's ``info`` has its own
+        ``beta_range`` and a ``batch`` entry with what the groups share: the kernel time and name, the group count, the
+        total proposals and accepted moves."""
+        models = list(models)
+        wq, cw, w64, c64, offsets = potts_node_weight_groups(models)
+        G = len(models)
+        kw, ignored = self._split_kwargs(dict(kwargs))
+        if kw.get("min_cluster_size"):
+            raise ValueError("node weights (a modularity model) together with min_cluster_size are not supported")
+        t0 = time.perf_counter()
+        m0 = models[0]
+        n = m0.num_variables
+        seed = self._seed(kw.get("seed"))
+        num_reads, init = self._initial_states(kw, m0.variables, kw.get("num_reads"), "DISCRETE")
+        if num_reads < 1:
+            raise ValueError("'num_reads' should be a positive integer")
+        ranges = kw.get("beta_range")
+        per_model = ranges is not None and np.ndim(ranges) == 2
+        if per_model and np.shape(ranges) != (G, 2):
+            raise ValueError("a per-model beta_range needs shape [%d, 2]" % G)
+        scheds = []
+        for g, model in enumerate(models):
+            kg = dict(kw, beta_range=ranges[g]) if per_model else kw
+            scheds.append(self._schedule(kg, lambda model=model: default_potts_beta_range(model)))
+        betas = np.stack([b for b, _, _ in scheds])
+        prob = Problem.potts_csr(m0.rowptr, m0.col, m0.val.astype(np.float32), float(np.float32(m0.c_pair)), n,
+                                 m0.num_cases, lin_offset=m0.lin_offset, device=self.device, order="padded",
+                                 energy_model=(m0.val, m0.c_pair), node_weights=(wq, cw[0], w64))
+        with prob:
+            prob.set_node_weight_groups(cw, c64, offsets)
+            init_arr = init
+            if isinstance(init, tuple):           # partial initial states + random remainder (group 0's random rows)
+                prob.anneal(num_reads * G, betas[0, :0], seed, self.replica_offset)
+                rnd, _, _ = prob.fetch(energies=False)
+                rnd = rnd[:num_reads]
+                rnd[: init[1].shape[0]] = init[1]
+                init_arr = rnd
+            if init_arr is not None:
+                init_arr = np.tile(np.asarray(init_arr, dtype=np.uint16), (G, 1))
+            t1 = time.perf_counter()
+            prob.anneal(num_reads * G, betas, seed, self.replica_offset, init_arr)
+            labels, dev_energy, stats = prob.fetch()
+            kernel_ms = prob.kernel_ms()
+            kernel = prob.kernel_name()
+            t2 = time.perf_counter()
+        batch = {"groups": G, "kernel_ms": kernel_ms, "kernel_name": kernel, "accepted": stats["accepted"],
+                 "proposals": stats["proposals"], "updates_per_s": (stats["proposals"] / (kernel_ms * 1e-3)) if kernel_ms > 0 else None,
+                 "timing": {"upload_s": t1 - t0, "anneal_s": t2 - t1}}
+        out = []
+        for g, model in enumerate(models):
+            rows = slice(g * num_reads, (g + 1) * num_reads)
+            info = {
+                "beta_range": scheds[g][1], "beta_schedule_type": scheds[g][2], "seed": seed,
+                "num_sweeps": int(betas.shape[1]), "num_reads": int(num_reads), "kernel": "potts_csr",
+                "device": self.device, "batch": batch,
+                "energy_evaluation": "device fp64 (caller's coefficients)",
+                "ignored_kwargs": ignored,
+            }
+            out.append(SampleSet(labels[rows].astype(np.int32), dev_energy[rows], model.variables, "DISCRETE", info=info))
+        return out
 
     # ------------------------------------------------------------------------------------------
     # internals
