@@ -96,6 +96,8 @@ int mi_sa_problem_info(const mi_sa_problem *p, int *kind, int *n, int *num_cases
  * sweeping a whole block per step (0 / 1, the default) and a workgroup of 2 / 4 wavefronts doing it (2)), "k2_tw" (0 / 1: the
  * random words and thresholds of a sweep come from a second "threshold" wavefront of the workgroup -- the pair kernel at 16
  * entries per variable and the one-wavefront few-replica kernel; 2: the sweeping wavefront computes them itself),
+ * "k2_trim" (that pair kernel with its threshold wavefront, on a model whose longest row has 13..15 entries at the
+ * 16-wide layout: 0 / 1 it neither fetches nor gathers the padding entries past that row length, 2 it does),
  * "k3_fast" (Potts: 0 the lean kernel csrc/potts_fast_kernels.hip when every slot is free of internal edges, K <= 16 and no
  * minimum size is set; 2 never), "xl_batched" (dense, n > 4096: 0 auto = all replicas together on the matrix cores from 256
  * replicas or n = 16384 up, 1 always, 2 a workgroup per replica), "xl_chain" (0 auto = the decisions and small passes of a group of eight blocks as one launch up to 512

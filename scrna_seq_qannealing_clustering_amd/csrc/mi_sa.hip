@@ -190,6 +190,9 @@ struct mi_sa_problem {
     std::vector<uint8_t> h_hole;             // structured binary: positions whose linear term is +inf (mi_sa_problem_set_pair_weights)
     uint4 *d_adj4 = nullptr;                 // K2: packed slot adjacency (see EllArgs::adj4)
     uint4 *d_adj4p = nullptr;                // K2p (two replicas per wavefront): the same with neighbour word = 4 * index; null = not eligible
+    uint4 *d_adj4r = nullptr;                // K2p at D = 16 with rows of at most k2p_rw < 16 entries: the trimmed packing (pack_pair_adjacency)
+    int k2p_rw = 0;
+    std::vector<uint32_t> h_adj4r;           // ... its host image until the linear terms are in it (RW = 15; mi_sa_problem_create_csr_rank1)
     uint32_t *d_slot_flags = nullptr;        // K2: slots with internal edges
     int k2_state_bytes = 0;                  // K2: byte-per-variable state (16 replicas x n bytes fit one CU's LDS)
     int32_t *d_wgt = nullptr;                // K2 family: the 64 pair-term weights of the weighted slot (mi_sa_problem_set_pair_weights)
@@ -229,6 +232,7 @@ struct mi_sa_problem {
     int opt_k2_wide = 0;                     // models laid out in blocks of 128 / 256 seats, few replicas: 0 / 1 one wavefront sweeps a block per step (K2w), 2 a workgroup of 2 / 4 wavefronts does (K2s)
     int opt_k3_fast = 0;                     // K3f (csrc/potts_fast_kernels.hip): 0 auto (when the model is eligible), 2 never
     int opt_k2_tw = 0;                       // K2p with a threshold wavefront per workgroup: 0 auto (when built for the width), 1 on, 2 off
+    int opt_k2_trim = 0;                     // ... and its trimmed rows (rows of 13..15 entries at D = 16): 0 auto / 1 on (when built), 2 off
     int opt_k2_split_max = 1024;             // ... auto: runs of up to this many replicas (a wavefront per SIMD at most)
     int opt_unit_rows = 0;                   // K1w ring unit (rows per rendezvous): 0 auto, 2 or 4
     int resident_waves = 0;                  // co-resident wavefronts of the anneal kernel on this device
@@ -448,6 +452,32 @@ int mi_sa_problem_create_dense_f32(const float *Qs, int n, double offset, int de
     return MI_OK;
 }
 
+// K2p's trimmed packing (csrc/sparse_pair_kernels.hip, RW < D): per slot, the groups of four entries that hold a real
+// neighbour somewhere -- [64 lanes][4] neighbour words, then [64][4] values -- with the last group cut to the LW = RW - 4 (G - 1)
+// entries a row can have: [64][LW] words, then [64][LW] values.  LW = 3 keeps every load 16 / 8 / 4-byte aligned instead:
+// [64][4] (three neighbour words, the lane's linear term -- filled in by the caller), [64][2] values, [64][1] value.
+// hc / hv: the slot-ELL ([slots][D][64], padding (self, +0)); the neighbour word of j is the LDS byte address of its cell, 4 j.
+static std::vector<uint32_t> pack_pair_adjacency(const std::vector<uint32_t> &hc, const std::vector<float> &hv, int slots, int D, int RW)
+{
+    const int G = D / 4, LW = RW - 4 * (G - 1);
+    const size_t slot_words = (size_t)(G - 1) * 512 + (LW == 3 ? 448 : (size_t)LW * 128);
+    std::vector<uint32_t> out((size_t)slots * slot_words, 0u);
+    for (int t = 0; t < slots; ++t)
+        for (int lane = 0; lane < 64; ++lane)
+            for (int k = 0; k < RW; ++k) {
+                const int g = k / 4, w = g < G - 1 ? 4 : LW;     // entries per lane in this group
+                const size_t grp = (size_t)t * slot_words + (size_t)g * 512;
+                size_t at_col = grp + (size_t)lane * w + (k & 3), at_val = at_col + (size_t)w * 64;
+                if (w == 3) {
+                    at_col = grp + (size_t)lane * 4 + (k & 3);
+                    at_val = (k & 3) < 2 ? grp + 256 + (size_t)lane * 2 + (k & 3) : grp + 384 + (size_t)lane;
+                }
+                out[at_col] = 4u * hc[((size_t)t * D + k) * 64 + lane];
+                memcpy(&out[at_val], &hv[((size_t)t * D + k) * 64 + lane], 4);
+            }
+    return out;
+}
+
 // CSR (both directions stored) -> slot-ELL device arrays (D = 16 / 32 / 64)
 static int upload_slot_ell(mi_sa_problem *p, const int32_t *rowptr, const int32_t *col, const float *val, int n)
 {
@@ -593,6 +623,16 @@ static int upload_slot_ell(mi_sa_problem *p, const int32_t *rowptr, const int32_
                                 4u * hc[((size_t)t * D + k) * 64 + lane];
                 HIP_TRY(hipMalloc((void **)&p->d_adj4p, ha.size() * sizeof(uint32_t)));
                 HIP_TRY(hipMemcpy(p->d_adj4p, ha.data(), ha.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+                if (D == 16 && maxdeg >= 13 && maxdeg < 16) {
+                    // entries maxdeg.. 15 are padding in every row: K2p's trimmed form neither fetches nor gathers them
+                    p->h_adj4r = pack_pair_adjacency(hc, hv, slots, D, maxdeg);
+                    p->k2p_rw = maxdeg;
+                    if (maxdeg != 15) {
+                        HIP_TRY(hipMalloc((void **)&p->d_adj4r, p->h_adj4r.size() * sizeof(uint32_t)));
+                        HIP_TRY(hipMemcpy(p->d_adj4r, p->h_adj4r.data(), p->h_adj4r.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+                        std::vector<uint32_t>().swap(p->h_adj4r);
+                    }
+                }
             }
         }
     }
@@ -792,6 +832,16 @@ int mi_sa_problem_create_csr_rank1_f32(const int32_t *rowptr, const int32_t *col
         for (int i = 0; i < n; ++i) p->h_hole[(size_t)i] = std::isinf(lin[i]) ? 1 : 0;
         HIP_TRY(hipMalloc((void **)&p->d_lin, hl.size() * sizeof(float)));
         HIP_TRY(hipMemcpy(p->d_lin, hl.data(), hl.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (!p->h_adj4r.empty()) {
+            // K2p's trimmed packing at RW = 15 carries the linear term beside the last three neighbour words (pack_pair_adjacency)
+            const size_t slot_words = p->h_adj4r.size() / (size_t)p->slots;
+            for (int t = 0; t < p->slots; ++t)
+                for (int lane = 0; lane < 64; ++lane)
+                    memcpy(&p->h_adj4r[(size_t)t * slot_words + 3 * 512 + (size_t)lane * 4 + 3], &hl[(size_t)t * 64 + lane], 4);
+            HIP_TRY(hipMalloc((void **)&p->d_adj4r, p->h_adj4r.size() * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpy(p->d_adj4r, p->h_adj4r.data(), p->h_adj4r.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            std::vector<uint32_t>().swap(p->h_adj4r);
+        }
         return MI_OK;
     });
     if (rc) { mi_sa_problem_destroy(p); return rc; }
@@ -985,7 +1035,7 @@ int mi_sa_problem_destroy(mi_sa_problem *p)
     (void)settle(p);
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    void *bufs[] = {p->d_gconst, p->d_nwq, p->d_ncw, p->d_nw64, p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
+    void *bufs[] = {p->d_gconst, p->d_nwq, p->d_ncw, p->d_nw64, p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_adj4r, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
@@ -1052,6 +1102,7 @@ int mi_sa_set_option(mi_sa_problem *p, const char *key, long value)
     if (!strcmp(key, "k2_split_max") && value >= 0) { p->opt_k2_split_max = (int)value; return MI_OK; }
     if (!strcmp(key, "k2_wide") && value >= 0 && value <= 2) { p->opt_k2_wide = (int)value; return MI_OK; }
     if (!strcmp(key, "k2_tw") && value >= 0 && value <= 2) { p->opt_k2_tw = (int)value; return MI_OK; }
+    if (!strcmp(key, "k2_trim") && value >= 0 && value <= 2) { p->opt_k2_trim = (int)value; return MI_OK; }
     if (!strcmp(key, "k3_fast") && value >= 0 && value <= 2) { p->opt_k3_fast = (int)value; return MI_OK; }
     if (!strcmp(key, "min_cluster_size") && value >= 0) {
         if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_EINVAL, "min_cluster_size applies to Potts problems");
@@ -1219,6 +1270,7 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
         a.rows = p->d_rows; a.meta = p->d_meta; a.adj4 = p->d_adj4; a.slot_flags = p->d_slot_flags; a.state_bytes = p->k2_state_bytes; a.waves_override = p->opt_k2_waves; a.min_size = p->opt_min_cluster_size;
         a.ell_val64 = p->d_ell_val64; a.lin64 = p->d_lin64; a.c_pair64 = p->c_pair64;
         a.wgt = p->d_wgt; a.wslot = p->kind == MI_KIND_CSR_RANK1 ? p->wslot : -1;
+        a.adj4_trim = p->opt_k2_trim != 2 ? p->d_adj4r : nullptr; a.trim_rw = p->k2p_rw;
         a.nwq = p->d_nwq; a.ncw = p->d_ncw; a.nw64 = p->d_nw64;
         a.groups = G; a.temps_group_stride = per_group ? num_sweeps : 0; a.gconst = p->d_gconst;
         if (p->kind == MI_KIND_POTTS_CSR && init) {

@@ -300,6 +300,10 @@ struct EllArgs {
     const int32_t *wgt = nullptr;
     int wslot = -1;
     int ring_off = 0;          // K2 with a threshold wavefront: byte offset of the ring of thresholds in LDS (set by its launcher)
+    // K2p with a threshold wavefront at D = 16: the pair packing without the entries past the model's longest row
+    // (trim_rw = 13..15 entries per lane, csrc/sparse_pair_kernels.hip); null = not built or switched off
+    const uint4 *adj4_trim = nullptr;
+    int trim_rw = 0;
     // K3 / K3f: node weights of the pair term (mi_sa_problem_set_node_weights, chain 2d), per position [slots * 64]
     // (0 at a hole and past n); null = the uniform term of chain 2c
     const int32_t *nwq = nullptr;  // integer weights: the cluster sums are exact int32

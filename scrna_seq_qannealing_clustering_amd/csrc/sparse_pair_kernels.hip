@@ -40,9 +40,16 @@ __device__ __forceinline__ float half_hi(uint32_t w) { return (float)__builtin_b
 // (scripts/probe_placement.hip).  Same chain: the thresholds are the same function of (variable, sweep, replica).
 // WGT: the model carries pair-term weights (mi_sa_problem_set_pair_weights; weighted_slot_sweep): a template switch, so
 // that the other models' code is what it was.
-template <int D, bool TW, bool WGT = false>
+// RW < D ("trimmed rows", the name's " r<RW>"): the model's longest row is RW < D entries, so entries RW.. D-1 of every
+// lane are padding (self, +0.0) in every slot.  They only ever add fma(+0, x, g) -- the oracle iterates CSR entries, and
+// the only effect is the sign of a zero field, which dE < thr cannot see -- so this form neither fetches nor gathers
+// them: a.adj4 then holds the trimmed packing (mi_sa.hip, pack_pair_adjacency), whose last group carries LW = RW - 4 (G - 1)
+// entries per lane ([64][LW] neighbours, then [64][LW] values; LW = 3: one dwordx4 of three neighbours and the linear
+// term, one dwordx2 and one dword of values -- 7936 bytes per slot and wavefront instead of 8448, nine loads as before).
+template <int D, bool TW, bool WGT = false, int RW = D>
 __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_pair(EllArgs a)
 {
+    static_assert(RW > D - 4 && RW <= D, "trimmed rows drop part of the last group of four only");
     extern __shared__ __attribute__((aligned(16))) char lds[];      // cell of variable i at byte 4 i
     const int lane = threadIdx.x & 63;
     const int pair = blockIdx.x;                                    // replicas 2 pair, 2 pair + 1
@@ -132,8 +139,10 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
     }
 
     constexpr int G = D / 4;                                        // groups of four (neighbour, value) per lane
+    constexpr int LW = RW - 4 * (G - 1);                            // entries of the last group (4 unless trimmed)
+    constexpr int SLOT_BYTES = (G - 1) * 2048 + (LW == 3 ? 1792 : LW * 512);   // one slot of the packing
     const __amdgpu_buffer_rsrc_t rs_adj = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint4 *>(a.adj4), 0, slots * G * 2048, 0x00020000);
+        const_cast<uint4 *>(a.adj4), 0, slots * SLOT_BYTES, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_lin = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(a.lin), 0, slots * 256, 0x00020000);
     struct SlotAdj { u32x4 col[G]; u32x4 val[G]; uint32_t lin; };
@@ -147,15 +156,32 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
 #endif
         SlotAdj p;
         const int tt = t < slots ? t : slots - 1;
-        const int soff = tt * (G * 2048);
+        const int soff = tt * SLOT_BYTES;
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             // (constant parts of the offset fold into the instruction's 12-bit immediate)
             const int so = soff + (g / 2) * 4096, io = (g & 1) * 2048;
-            p.col[g] = __builtin_amdgcn_raw_buffer_load_b128(rs_adj, lane16 + io, so, 0);
-            p.val[g] = __builtin_amdgcn_raw_buffer_load_b128(rs_adj, lane16 + io + 1024, so, 0);
+            if (LW == 4 || g < G - 1) {
+                p.col[g] = __builtin_amdgcn_raw_buffer_load_b128(rs_adj, lane16 + io, so, 0);
+                p.val[g] = __builtin_amdgcn_raw_buffer_load_b128(rs_adj, lane16 + io + 1024, so, 0);
+            } else if constexpr (LW == 3) {
+                // (aligned loads only: 12-byte lanes cost the L1 more accesses than 16-byte ones) three neighbour words and
+                // the lane's linear term, then two values and one
+                p.col[g] = __builtin_amdgcn_raw_buffer_load_b128(rs_adj, lane16 + io, so, 0);
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_adj, lane * 8 + io + 1024, so, 0);
+                p.val[g] = u32x4{v.x, v.y, __builtin_amdgcn_raw_buffer_load_b32(rs_adj, lane * 4 + io + 1536, so, 0), 0u};
+            } else if constexpr (LW == 2) {
+                const u32x2 c = __builtin_amdgcn_raw_buffer_load_b64(rs_adj, lane * 8 + io, so, 0);
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_adj, lane * 8 + io + 512, so, 0);
+                p.col[g] = __builtin_shufflevector(c, c, 0, 1, -1, -1);
+                p.val[g] = __builtin_shufflevector(v, v, 0, 1, -1, -1);
+            } else {
+                p.col[g][0] = __builtin_amdgcn_raw_buffer_load_b32(rs_adj, lane * 4 + io, so, 0);
+                p.val[g][0] = __builtin_amdgcn_raw_buffer_load_b32(rs_adj, lane * 4 + io + 256, so, 0);
+            }
         }
-        p.lin = __builtin_amdgcn_raw_buffer_load_b32(rs_lin, lane * 4, tt * 256, 0);
+        if constexpr (LW == 3) p.lin = p.col[G - 1][3];            // (the trimmed packing carries it)
+        else p.lin = __builtin_amdgcn_raw_buffer_load_b32(rs_lin, lane * 4, tt * 256, 0);
         return p;
     };
 #ifdef MI_K2P_NOFETCH
@@ -212,23 +238,26 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
         K2P_TICK(t_top);
 #pragma unroll
         for (int g0 = 0; g0 < G; g0 += 4) {
-            uint32_t word[16];
+            constexpr int NK0 = RW < 16 ? RW : 16;                  // gathers of the first block of four groups
+            const int NK = g0 == 0 ? NK0 : (RW - 4 * g0 < 16 ? RW - 4 * g0 : 16);
+            uint32_t word[16];                                      // (words past NK are never read nor written)
             // the packed neighbour word IS the LDS byte address of its cell (one wavefront per workgroup, no static LDS)
             if (g0 == 0) asm volatile("ds_read_b32 %0, %1" : "=v"(own) : "v"(i * 4));
             // (TW: the ring read second, so that "at most 15 reads outstanding" below means the own cell and the thresholds are back)
             if (g0 == 0 && TW) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(thr2) : "v"(ring_lane + ring_buf), "n"(C * 512));
 #pragma unroll
             for (int k = 0; k < 16; ++k)
+                if (k < NK)
 #ifdef MI_K2P_DBG_LINEAR   /* timing only: conflict-free addresses */
                 asm volatile("ds_read_b32 %0, %1" : "=v"(word[k]) : "v"((cur.col[g0 + k / 4][k & 3] & 0x3f00u) + lane * 4));
 #else
                 asm volatile("ds_read_b32 %0, %1" : "=v"(word[k]) : "v"(cur.col[g0 + k / 4][k & 3]));
 #endif
             if (g0 == 0 && TW) {
-                // 18 LDS reads are in flight and they return in order: with at most 15 outstanding the lane's own cell and
-                // the thresholds are here -- everything that depends only on them is computed UNDER the gathers (the
-                // second wait names its results, so it cannot sink below it)
-                asm volatile("s_waitcnt lgkmcnt(15)" : "+v"(own), "+v"(thr2) :: "memory");
+                // NK0 + 2 LDS reads are in flight and they return in order: with at most NK0 (15 at most: the counter's
+                // width) outstanding the lane's own cell and the thresholds are here -- everything that depends only on
+                // them is computed UNDER the gathers (the second wait names its results, so it cannot sink below it)
+                asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(own), "+v"(thr2) : "n"(NK0 < 15 ? NK0 : 15) : "memory");
 #ifndef MI_K2P_DBG_TERMS_AFTER   /* (timing only: the terms after the full wait, as before) */
                 own_terms();
 #endif
@@ -258,7 +287,7 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
             }
             K2P_TICK(t_gather);
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
+            for (int k = 0; k < NK; ++k) {
                 const float v = __uint_as_float(cur.val[g0 + k / 4][k & 3]);
                 gA = __builtin_fmaf(v, half_lo(word[k]), gA);       // fma(val, x, g): the oracle's conditional add
                 gB = __builtin_fmaf(v, half_hi(word[k]), gB);
@@ -415,14 +444,15 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
 }
 
 template <typename KernelT>
-int launch_pair(KernelT kernel, const EllArgs &a, bool tw, hipStream_t st)
+int launch_pair(KernelT kernel, const EllArgs &a, bool tw, hipStream_t st, int rw = 0)
 {
     // 4 bytes per variable; TW: the two-deep ring of thresholds behind them (2 x 4 slots x 64 lanes x 8 bytes)
     const size_t lds = (size_t)a.slots * 256 + (tw ? 4096 : 0);
     if (lds > 160 * 1024) return fail(MI_EUNSUPPORTED, "csr_rank1 pair kernel: n = %d exceeds the state LDS budget", a.n);
     if (lds > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    note_kernel(tw ? "k_anneal_csr_rank1_pair<%d, tw>" : "k_anneal_csr_rank1_pair<%d>", a.D);
+    if (rw) note_kernel("k_anneal_csr_rank1_pair<%d, tw> r%d", a.D, rw);
+    else note_kernel(tw ? "k_anneal_csr_rank1_pair<%d, tw>" : "k_anneal_csr_rank1_pair<%d>", a.D);
     hipLaunchKernelGGL(kernel, dim3((a.R + 1) / 2), dim3(tw ? 128 : 64), lds, st, a);
     HIP_TRY(hipGetLastError());
     return MI_OK;
@@ -441,6 +471,13 @@ int mi_launch_csr_rank1_pair(const EllArgs &a, bool tw, hipStream_t st)
         if (a.D != 16) return fail(MI_EUNSUPPORTED, "csr_rank1 pair kernel: pair-term weights at slot-ELL width %d not built", a.D);
         return tw ? launch_pair(k_anneal_csr_rank1_pair<16, true, true>, a, true, st)
                   : launch_pair(k_anneal_csr_rank1_pair<16, false, true>, a, false, st);
+    }
+    if (a.D == 16 && tw && a.adj4_trim) {     // rows of at most 15 entries: the trimmed packing (see the kernel)
+        EllArgs b = a;
+        b.adj4 = a.adj4_trim;
+        if (a.trim_rw == 15) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 15>, b, true, st, 15);
+        if (a.trim_rw == 14) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 14>, b, true, st, 14);
+        if (a.trim_rw == 13) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 13>, b, true, st, 13);
     }
     if (a.D == 16 && tw) return launch_pair(k_anneal_csr_rank1_pair<16, true>, a, true, st);
     if (a.D == 16) return launch_pair(k_anneal_csr_rank1_pair<16, false>, a, false, st);
