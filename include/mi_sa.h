@@ -177,8 +177,25 @@ int mi_sa_problem_set_node_weights(mi_sa_problem *p, const int32_t *wq, const fl
  * objectives means nothing). */
 int mi_sa_problem_set_node_weight_groups(mi_sa_problem *p, int G, const float *cw, const double *c64, const double *offset);
 
+/* Potts problems: MERGE MOVES (chain specification 2e).  With interval M > 0 every anneal of the
+ * problem runs a merge phase before each global sweep s = sweep_offset + local index with s > 0 and s % M == 0 (never at
+ * the end of a call: a run continued in pieces equals one call).  A phase makes `proposals` proposals "merge cluster b
+ * into cluster a" per replica, at that sweep's temperature, each accepted iff
+ *     dE = (double)Bq_ab 2^-f + cq_g (double)(W_a W_b)  <  (double)(neglog_u(word) T_s)
+ * where Bq_ab is the exact sum of the fixed-point couplings llrint(S_uv 2^f) between the two clusters (f the largest
+ * exponent with sum |S_uv| 2^f <= 2^62, over the couplings given at creation), W the integer cluster sums of the chain
+ * (member counts without node weights).  cq: G values (G = the resolution groups set so far, 1 without) -- for node
+ * weights the fp64 coefficient of the integer weight products, c_g 2^-2e; NULL (unweighted problems only) = c_pair.
+ * Merges have no reverse move: an optimiser, not a sampler.  Accepted merges are counted in mi_sa_debug_stats word [4];
+ * mi_sa_fetch's proposals and accepted moves are those of the single-site sweeps.  interval = 0 turns merges off (the
+ * chain is then exactly the one of a problem that never made this call).  MI_EINVAL: a problem that is not a Potts
+ * problem, interval < 0, proposals < 1, K < 2, node weights without cq (also at anneal time, or a cq count that no longer
+ * matches the resolution groups).  MI_EUNSUPPORTED: together with the option "min_cluster_size" (a merge empties a
+ * cluster; either order), with tempering (mi_sa_tempering_begin, MI_F_TEMPS_RESIDENT). */
+int mi_sa_problem_set_merge_moves(mi_sa_problem *p, int interval, int proposals, const double *cq);
+
 /* Diagnostic: copies the first `words` (<= 16) 64-bit statistics words of the last run ([0..2] as in
- * mi_sa_fetch; [8..12] per-phase cycle sums of builds compiled with -DMI_K2_PROFILE, otherwise 0; with words = 16,
+ * mi_sa_fetch; [4] merges accepted by the merge phases of the last anneal (mi_sa_problem_set_merge_moves); [8..12] per-phase cycle sums of builds compiled with -DMI_K2_PROFILE, otherwise 0; with words = 16,
  * [14] / [15] = chunks of the last scheduled dense run served by the workgroup kernel / the MFMA kernel). */
 int mi_sa_debug_stats(mi_sa_problem *p, uint64_t *out, int words);
 
@@ -240,7 +257,8 @@ int mi_sa_device_results(mi_sa_problem *p, void **out_d_states, double **out_d_e
 int mi_sa_last_kernel_ms(mi_sa_problem *p, float *out_ms);
 
 /* Number of anneal-kernel launches that served the last mi_sa_anneal (long schedules are cut into launches
- * of `chunk_sweeps` sweeps whose state persists in HBM; results do not depend on the cut).  The time of
+ * of `chunk_sweeps` sweeps whose state persists in HBM; results do not depend on the cut; with merge moves, the anneal
+ * launches between the merge phases plus one k_potts_merge launch per phase).  The time of
  * mi_sa_last_kernel_ms divided by this count is the average launch duration a profiler reports. */
 int mi_sa_last_launch_count(mi_sa_problem *p, int *out_launches);
 

@@ -253,17 +253,20 @@ def clustering_dqm(G, num_of_clusters, gamma, sampler=None, sampler_kwargs: Opti
 
 
 def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sampler=None,
-                          sampler_kwargs: Optional[dict] = None, verbose=False):
+                          sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None):
     """Weighted modularity at ``resolution`` -- the objective of Seurat's ``FindClusters(..., algorithm = 1)`` that the
     reference's notebooks compare every annealed clustering with -- annealed on the Potts chain with node weights
     (models.build_modularity_potts), at most ``max_clusters`` labels.  Returns the sampleset; ``info["modularity"]``
     holds ``Q_gamma`` of every sample (record order), ``-energy / m``.  Default schedule: 16000 sweeps, geometric over
-    ``models.modularity_beta_range`` (``sampler_kwargs`` overrides either)."""
+    ``models.modularity_beta_range`` (``sampler_kwargs`` overrides either).  ``merge_interval``: merge moves (chain 2e)
+    every that many sweeps, the sampler's ``merge_interval`` (off by default; ``sampler_kwargs`` may set it too)."""
     from .models import build_modularity_potts, modularity_beta_range
     model = build_modularity_potts(G, resolution, max_clusters)
     # default schedule: 16000 sweeps over modularity_beta_range -- single-site moves over more labels than communities
     # need the time to merge a community split across two labels (DESIGN.md section 5); 256 reads as the sampler's default
     kw = dict(num_sweeps=16000, beta_range=modularity_beta_range(model))
+    if merge_interval is not None:
+        kw["merge_interval"] = merge_interval
     kw.update(sampler_kwargs or {})
     sampleset = _sampler(sampler).sample_dqm(model, **kw)
     sampleset.info["modularity"] = -np.asarray(sampleset.record["energy"], dtype=np.float64) / model.info["m"]
@@ -273,18 +276,21 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
 
 
 def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=None,
-                                sampler_kwargs: Optional[dict] = None, verbose=False):
+                                sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None):
     """:func:`clustering_modularity` at several resolutions -- what Seurat users do with ``FindClusters(...,
     resolution = c(...))`` -- in one upload and one launch (MI355XSampler.sample_dqm_many: one resolution group of
     replicas per value).  Returns one sampleset per resolution, in the order given; each equals what
     ``clustering_modularity(G, resolution, ...)`` returns with the same ``sampler_kwargs`` and has
     ``info["resolution"]`` and ``info["modularity"]``.  Same defaults: 16000 sweeps, each resolution on its own
     ``models.modularity_beta_range`` (a ``beta_range`` in ``sampler_kwargs`` applies to all).  An empty list, a
-    repeated value and a resolution <= 0 or not finite raise ValueError before any GPU work."""
+    repeated value and a resolution <= 0 or not finite raise ValueError before any GPU work.  ``merge_interval`` as in
+    :func:`clustering_modularity`."""
     from .models import build_modularity_sweep, check_resolutions, modularity_beta_range
     res = check_resolutions(resolutions)
     models = build_modularity_sweep(G, res, max_clusters)
     kw = dict(num_sweeps=16000, beta_range=[modularity_beta_range(m) for m in models])
+    if merge_interval is not None:
+        kw["merge_interval"] = merge_interval
     kw.update(sampler_kwargs or {})
     samplesets = _sampler(sampler).sample_dqm_many(models, **kw)
     for gamma, model, ss in zip(res, models, samplesets):

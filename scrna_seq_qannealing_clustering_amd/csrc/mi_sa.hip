@@ -202,6 +202,11 @@ struct mi_sa_problem {
     double *d_nw64 = nullptr;                // ... their fp64 weights (reported energies)
     int ngroups = 1;                         // ... resolution groups (mi_sa_problem_set_node_weight_groups): d_ncw holds ngroups x seats
     double *d_gconst = nullptr;              // ... per group: fp64 pair coefficient, then energy offset [2 x ngroups] (null: c_pair64, offset)
+    // Potts: the merge phase of chain 2e (mi_sa_problem_set_merge_moves); interval 0 = off
+    int merge_interval = 0, merge_proposals = 0;
+    std::vector<double> merge_cq;            // ... coefficient of W_a W_b per resolution group (empty: c_pair, unweighted)
+    double *d_merge_cq = nullptr;            // ... its device copy (256 slots)
+    double merge_sumabs = 0.0;               // ... sum of |S_uv| over the stored couplings, in stored order (fixed-point exponent)
     int k2_free_block = 0;                   // K2s: widest block of seats (256 / 128 / 64; 0 = none) that holds no edge anywhere in the model
     int cus = 0;
     // run buffers
@@ -862,6 +867,7 @@ int mi_sa_problem_create_potts_csr_f32(const int32_t *rowptr, const int32_t *col
     mi_sa_problem *p = new (std::nothrow) mi_sa_problem();
     if (!p) return fail(MI_ENOMEM, "out of host memory");
     p->kind = MI_KIND_POTTS_CSR; p->n = n; p->K = K; p->offset = lin_offset; p->state_elem = 2; p->c_pair = c_pair;
+    for (int e = 0; e < rowptr[n]; ++e) p->merge_sumabs += std::fabs((double)val[e]);   // (sequential, in stored order)
     rc = problem_common_init(p, device);
     if (!rc) rc = guarded([&]() -> int { return upload_slot_ell(p, rowptr, col, val, n); });
     if (rc) { mi_sa_problem_destroy(p); return rc; }
@@ -1024,6 +1030,48 @@ int mi_sa_problem_set_node_weight_groups(mi_sa_problem *p, int G, const float *c
     });
 }
 
+// chain 2e: the exponent f of the fixed-point couplings vq = llrint(S_uv 2^f), the largest with sum |S_uv| 2^f <= 2^62
+// (clamped to [-1000, 1000]; 0 without couplings)
+static int merge_fixed_exponent(double sumabs)
+{
+    if (!(sumabs > 0.0)) return 0;
+    int E = 0;
+    const double m = std::frexp(sumabs, &E);              // sumabs = m 2^E, m in [1/2, 1)
+    const int f = 62 - E + (m == 0.5 ? 1 : 0);
+    return f < -1000 ? -1000 : (f > 1000 ? 1000 : f);
+}
+
+int mi_sa_problem_set_merge_moves(mi_sa_problem *p, int interval, int proposals, const double *cq)
+{
+    if (!p) return fail(MI_EINVAL, "NULL problem");
+    if (const int rc_w = settle(p)) return rc_w;
+    if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_EINVAL, "merge moves: Potts problems only");
+    if (interval < 0) return fail(MI_EINVAL, "merge interval must be >= 0 (got %d)", interval);
+    if (proposals < 1) return fail(MI_EINVAL, "merge proposals must be >= 1 (got %d)", proposals);
+    if (interval == 0) { p->merge_interval = 0; return MI_OK; }
+    if (p->K < 2) return fail(MI_EINVAL, "merge moves need K >= 2");
+    if (p->d_nwq && !cq) return fail(MI_EINVAL, "merge moves on a problem with node weights need the coefficients cq");
+    if (p->opt_min_cluster_size > 0) return fail(MI_EUNSUPPORTED, "merge moves together with min_cluster_size are not supported");
+    if (p->pt_T > 0) return fail(MI_EUNSUPPORTED, "merge moves under tempering are not supported");
+    return guarded([&]() -> int {
+        const int G = p->ngroups;
+        std::vector<double> h((size_t)G, (double)p->c_pair);
+        if (cq)
+            for (int g = 0; g < G; ++g) {
+                if (!std::isfinite(cq[g])) return fail(MI_EINVAL, "cq[%d] is not finite", g);
+                h[(size_t)g] = cq[g];
+            }
+        HIP_TRY(hipSetDevice(p->device));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        if (!p->d_merge_cq) HIP_TRY(hipMalloc((void **)&p->d_merge_cq, 256 * sizeof(double)));
+        HIP_TRY(hipMemcpy(p->d_merge_cq, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        p->merge_cq = cq ? h : std::vector<double>();
+        p->merge_interval = interval;
+        p->merge_proposals = proposals;
+        return MI_OK;
+    });
+}
+
 int mi_sa_problem_set_energy_model_f64(mi_sa_problem *p, const double *val, const double *lin, double c_pair)
 {
     return guarded([&]() -> int { return set_energy_model_impl(p, val, lin, c_pair); });
@@ -1035,7 +1083,7 @@ int mi_sa_problem_destroy(mi_sa_problem *p)
     (void)settle(p);
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    void *bufs[] = {p->d_gconst, p->d_nwq, p->d_ncw, p->d_nw64, p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_adj4r, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
+    void *bufs[] = {p->d_merge_cq, p->d_gconst, p->d_nwq, p->d_ncw, p->d_nw64, p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_adj4r, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
@@ -1107,6 +1155,7 @@ int mi_sa_set_option(mi_sa_problem *p, const char *key, long value)
     if (!strcmp(key, "min_cluster_size") && value >= 0) {
         if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_EINVAL, "min_cluster_size applies to Potts problems");
         if (value > 0 && p->d_nwq) return fail(MI_EUNSUPPORTED, "min_cluster_size together with node weights is not supported");
+        if (value > 0 && p->merge_interval > 0) return fail(MI_EUNSUPPORTED, "min_cluster_size together with merge moves is not supported");
         p->opt_min_cluster_size = (int)value;
         return MI_OK;
     }
@@ -1141,6 +1190,12 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
         return fail(MI_ESTATE, "MI_F_CONTINUE needs a previous run with the same number of replicas");
     if (cont && init) return fail(MI_EINVAL, "MI_F_CONTINUE and init are mutually exclusive");
     if (resync_interval < 0) return fail(MI_EINVAL, "resync_interval must be >= 0");
+    const bool merges = p->kind == MI_KIND_POTTS_CSR && p->merge_interval > 0 && num_sweeps > 0;
+    if (merges && resident) return fail(MI_EUNSUPPORTED, "merge moves with resident (tempering) temperatures are not supported");
+    if (merges && p->d_nwq && p->merge_cq.empty())
+        return fail(MI_EINVAL, "merge moves on a problem with node weights need the coefficients cq");
+    if (merges && !p->merge_cq.empty() && p->merge_cq.size() != (size_t)G)
+        return fail(MI_EINVAL, "merge moves: %zu coefficients for %d resolution groups", p->merge_cq.size(), G);
     for (int s = 0; s < (num_sweeps > 0 && !resident ? num_betas : 0); ++s)
         if (!(betas[s] > 0.0) || !std::isfinite(betas[s]))
             return fail(MI_EINVAL, "betas[%d] = %g is not a positive finite number", s, betas[s]);
@@ -1282,12 +1337,52 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
         p->last_launches = 1;
         HIP_TRY(hipEventRecord(p->ev0, p->stream));
         if (p->kind == MI_KIND_POTTS_CSR) {
-            if (p->d_adj4p && p->opt_k3_fast != 2 && mi_potts_fast_eligible(p->D, p->K, a.min_size)) {
-                a.adj4 = p->d_adj4p;                  // every slot free of internal edges: the lean kernel (same chain)
-                // (up to 1024 replicas every wavefront has a SIMD to itself: a threshold wavefront beside each)
-                rc = mi_launch_potts_fast(a, p->opt_k2_tw != 2 && R <= 1024, p->stream);
+            const bool fast = p->d_adj4p && p->opt_k3_fast != 2 && mi_potts_fast_eligible(p->D, p->K, a.min_size);
+            auto anneal_launch = [&](EllArgs &b) -> int {
+                if (fast) {
+                    b.adj4 = p->d_adj4p;              // every slot free of internal edges: the lean kernel (same chain)
+                    // (up to 1024 replicas every wavefront has a SIMD to itself: a threshold wavefront beside each)
+                    return mi_launch_potts_fast(b, p->opt_k2_tw != 2 && R <= 1024, p->stream);
+                }
+                return mi_launch_potts(b, p->stream);
+            };
+            if (!merges) {
+                rc = anneal_launch(a);
             } else {
-                rc = mi_launch_potts(a, p->stream);
+                // chain 2e: a merge phase before every global sweep s > 0 with s % M == 0 inside this call; the anneal
+                // launches between them continue from the labels in HBM, as MI_F_CONTINUE does
+                MergeArgs m;
+                m.ell_col = p->d_ell_col; m.ell_val = p->d_ell_val; m.meta = p->d_meta; m.nwq = p->d_nwq;
+                m.cq = p->d_merge_cq; m.temps = temps_buf; m.temps_per_replica = per_replica ? 1 : 0;
+                m.temps_group_stride = a.temps_group_stride; m.states = static_cast<uint16_t *>(p->d_states);
+                m.stats = p->d_stats;
+                const int f = merge_fixed_exponent(p->merge_sumabs);
+                m.scale = std::ldexp(1.0, f); m.inv_scale = std::ldexp(1.0, -f);
+                m.n = p->n; m.K = p->K; m.R = R; m.D = p->D; m.groups = G; m.proposals = p->merge_proposals;
+                m.replica_offset = replica_offset; m.seed_lo = a.seed_lo; m.seed_hi = a.seed_hi;
+                const uint32_t M = (uint32_t)p->merge_interval;
+                const void *labels = a.init;          // where the next launch finds the labels (null: tag-1 words)
+                int launches = 0, merge_launches = 0;
+                for (int s0 = 0; !rc && s0 < num_sweeps;) {
+                    const uint32_t s = sweep_offset + (uint32_t)s0;
+                    if (s > 0 && s % M == 0) {
+                        m.src = static_cast<const uint16_t *>(labels); m.sweep = s; m.sweep_local = s0;
+                        rc = mi_launch_potts_merge(m, p->stream);
+                        if (rc) break;
+                        labels = p->d_states;
+                        ++launches; ++merge_launches;
+                    }
+                    const int len = (int)std::min<uint32_t>((uint32_t)(num_sweeps - s0), M - s % M);
+                    EllArgs b = a;
+                    b.init = labels; b.num_sweeps = len; b.sweep_offset = s;
+                    if (!per_replica) b.temps = a.temps + s0;   // (per group: + g * temps_group_stride inside the kernel)
+                    rc = anneal_launch(b);
+                    labels = p->d_states;
+                    ++launches;
+                    s0 += len;
+                }
+                if (merge_launches) note_kernel("k_potts_merge");
+                p->last_launches = launches;
             }
         } else {
             // which of the kernels of the structured binary model (all run the same chain): an explicit option first;
@@ -1361,6 +1456,7 @@ int mi_sa_tempering_begin(mi_sa_problem *p, const double *ladder_betas, int T, i
     if (!p || !ladder_betas) return fail(MI_EINVAL, "NULL argument");
     if (const int rc_w = settle(p)) return rc_w;
     if (p->ngroups > 1) return fail(MI_EUNSUPPORTED, "tempering with resolution groups is not supported");
+    if (p->merge_interval > 0) return fail(MI_EUNSUPPORTED, "tempering with merge moves is not supported");
     if (T < 2 || T > 1024) return fail(MI_EINVAL, "a tempering ladder has 2 .. 1024 temperatures (got %d)", T);
     if (chains < 1) return fail(MI_EINVAL, "chains must be >= 1");
     const long long total = (long long)T * chains;

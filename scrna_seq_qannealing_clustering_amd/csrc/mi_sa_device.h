@@ -393,6 +393,25 @@ int mi_launch_potts(const EllArgs &, hipStream_t);
 // entries per variable, no size constraint); adj4 = packed adjacency with neighbour word = 2 * index
 bool mi_potts_fast_eligible(int D, int K, int min_size);
 int mi_launch_potts_fast(const EllArgs &, bool tw, hipStream_t);
+// potts_merge_kernels.hip: the merge phase of chain 2e (k_potts_merge), one workgroup per replica, between two launches of
+// K3 / K3f on the replica's labels in HBM
+struct MergeArgs {
+    const uint32_t *ell_col;   // the slot-ELL adjacency of the anneal kernels, [slots][D][64]
+    const float *ell_val;
+    const uint32_t *meta;      // per seat: degree << 8 | absent << 31
+    const int32_t *nwq;        // node weights (chain 2d); null: unit weights (chain 2c)
+    const double *cq;          // [groups] fp64 coefficient of W_a W_b
+    const float *temps;        // the call's temperatures (as EllArgs::temps of its first launch)
+    int temps_per_replica, temps_group_stride, sweep_local;
+    const uint16_t *src;       // labels to start from: states (in place), the caller's initial labels, or null (tag-1 words)
+    uint16_t *states;          // R x n labels
+    unsigned long long *stats; // [4] accepted merges
+    double scale, inv_scale;   // 2^f, 2^-f of the fixed-point couplings
+    int n, K, R, D, groups, proposals;
+    uint32_t sweep, replica_offset, seed_lo, seed_hi;   // sweep: the global index s of the sweep the phase precedes
+};
+size_t mi_potts_merge_lds_bytes(int K);
+int mi_launch_potts_merge(const MergeArgs &, hipStream_t);
 
 // K1x (dense_xl_kernels.hip): dense chain for 4096 < n <= 65536, one workgroup per replica
 struct DenseXlArgs {

@@ -331,6 +331,26 @@ class Problem:
                                                                     _ptr(c64, C.c_double), _ptr(offset, C.c_double)))
         self.groups = int(G)
 
+    def set_merge_moves(self, interval: int, proposals: Optional[int] = None, cq=None):
+        """Potts problems: merge moves (chain 2e, include/mi_sa.h mi_sa_problem_set_merge_moves).  Every anneal then runs
+        a merge phase of ``proposals`` proposals (default ``2 K``) before each global sweep ``s > 0`` with
+        ``s % interval == 0``; ``interval = 0`` turns merges off.  ``cq``: the coefficient of the cluster-sum product per
+        resolution group (``models.potts_merge_coefficients``; required with node weights), None = ``c_pair``.  Call
+        after :meth:`set_node_weight_groups`."""
+        if proposals is None:
+            proposals = 2 * int(self.num_cases)
+        cq_arr = None
+        if cq is not None:
+            cq_arr = np.ascontiguousarray(np.atleast_1d(np.asarray(cq, dtype=np.float64)))
+            if cq_arr.shape != (self.groups,):
+                raise ValueError("cq needs one value per resolution group (%d)" % self.groups)
+        _lib.check(_lib.load().mi_sa_problem_set_merge_moves(self._h, int(interval), int(proposals),
+                                                             _ptr(cq_arr, C.c_double)))
+
+    def merges_accepted(self) -> int:
+        """Merges the merge phases of the last anneal accepted (mi_sa_debug_stats word 4)."""
+        return int(self.debug_stats(5)[4])
+
     def _set_energy_model(self, val64, lin64, c_pair64, nnz):
         if len(val64) != nnz or (lin64 is not None and len(lin64) != self.n_dev):
             self.close()

@@ -12,6 +12,7 @@ Array convention (used everywhere): ``Qs`` is the symmetrised n x n matrix, ``Qs
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import Any, Dict, Hashable, List, Optional, Sequence, Tuple
 
@@ -501,6 +502,36 @@ def potts_node_weight_groups(models: Sequence[PottsModel]):
     c64 = np.array([float(m.c_pair) for m in models], dtype=np.float64)
     offset = np.array([m.lin_offset for m in models], dtype=np.float64)
     return wq, cw, w64, c64, offset
+
+
+def merge_fixed_exponent(val) -> int:
+    """The exponent f of the fixed-point couplings of chain 2e's merge phase, ``vq = llrint(S_uv 2^f)``: the largest
+    with ``sum |S_uv| 2^f <= 2^62`` (the sum in fp64, in stored order, over the fp32 couplings as the device holds them),
+    clamped to [-1000, 1000]; 0 without couplings.  The library computes the same from the couplings given at creation."""
+    v = np.abs(np.asarray(val, dtype=np.float32).astype(np.float64))
+    total = float(np.add.accumulate(v)[-1]) if len(v) else 0.0         # (sequential, not pairwise)
+    if not total > 0.0:
+        return 0
+    mant, E = math.frexp(total)
+    f = 62 - E + (1 if mant == 0.5 else 0)
+    return max(-1000, min(1000, f))
+
+
+def potts_merge_coefficients(model):
+    """``cq`` of the merge phase (mi_sa_problem_set_merge_moves) for a node-weighted Potts model, or a list of them (a
+    resolution sweep, one value per group): the fp64 coefficient of the integer weight products, ``c 2^-2e`` with e the
+    exponent of :func:`quantise_node_weights` -- so ``cq W_a W_b`` is the model's ``c sum_{u in a, v in b} k_u k_v`` on the
+    quantised weights.  None for a model without node weights (the library then uses its fp32 ``c_pair``)."""
+    models = list(model) if isinstance(model, (list, tuple)) else [model]
+    if all(m.node_weight is None for m in models):
+        return None
+    out = []
+    for m in models:
+        if m.node_weight is None:
+            raise ValueError("every model of a group run needs node weights")
+        _, _, e = quantise_node_weights(np.asarray(m.node_weight, dtype=np.float64), m.c_pair)
+        out.append(math.ldexp(float(m.c_pair), -2 * e))
+    return np.asarray(out, dtype=np.float64)
 
 
 def modularity_beta_range(model: PottsModel) -> Tuple[float, float]:

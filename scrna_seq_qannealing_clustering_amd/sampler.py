@@ -30,7 +30,8 @@ from . import _lib
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
 from .engine import Problem, energy_dense_f64, layout_block_for
 from .models import (PottsModel, QuboModel, _csr_from_edges, default_beta_range,
-                     make_beta_schedule, potts_node_weight_groups, potts_node_weights, qubo_dict_to_model)
+                     make_beta_schedule, potts_merge_coefficients, potts_node_weight_groups, potts_node_weights,
+                     qubo_dict_to_model)
 from .sampleset import SampleSet
 
 # keyword arguments of the samplers the reference uses that have no meaning for an annealer on a GPU
@@ -85,6 +86,7 @@ class MI355XSampler:
         "num_reads": [], "num_sweeps": [], "beta_range": [], "beta_schedule_type": [],
         "beta_schedule": [], "num_sweeps_per_beta": [], "seed": [], "initial_states": [],
         "initial_states_generator": [], "resync_interval": [], "kernel": [], "min_cluster_size": [],
+        "merge_interval": [], "merge_proposals": [],
         **{k: [] for k in _IGNORED_KWARGS},
     }
     properties = {"category": "software", "beta_schedule_options": ("linear", "geometric", "custom"),
@@ -170,6 +172,7 @@ class MI355XSampler:
         kw, ignored = self._split_kwargs(dict(kwargs))
         if kw.get("min_cluster_size"):
             raise ValueError("node weights (a modularity model) together with min_cluster_size are not supported")
+        merge_interval, merge_proposals = self._merge_kwargs(kw, 0)
         t0 = time.perf_counter()
         m0 = models[0]
         n = m0.num_variables
@@ -191,6 +194,8 @@ class MI355XSampler:
                                  energy_model=(m0.val, m0.c_pair), node_weights=(wq, cw[0], w64))
         with prob:
             prob.set_node_weight_groups(cw, c64, offsets)
+            if merge_interval:
+                prob.set_merge_moves(merge_interval, merge_proposals, potts_merge_coefficients(models))
             init_arr = init
             if isinstance(init, tuple):           # partial initial states + random remainder (group 0's random rows)
                 prob.anneal(num_reads * G, betas[0, :0], seed, self.replica_offset)
@@ -205,6 +210,7 @@ class MI355XSampler:
             labels, dev_energy, stats = prob.fetch()
             kernel_ms = prob.kernel_ms()
             kernel = prob.kernel_name()
+            merges = prob.merges_accepted() if merge_interval else None
             t2 = time.perf_counter()
         batch = {"groups": G, "kernel_ms": kernel_ms, "kernel_name": kernel, "accepted": stats["accepted"],
                  "proposals": stats["proposals"], "updates_per_s": (stats["proposals"] / (kernel_ms * 1e-3)) if kernel_ms > 0 else None,
@@ -219,6 +225,8 @@ class MI355XSampler:
                 "energy_evaluation": "device fp64 (caller's coefficients)",
                 "ignored_kwargs": ignored,
             }
+            if merge_interval:
+                info["merges_accepted"] = merges                  # (all groups together, like "batch")
             out.append(SampleSet(labels[rows].astype(np.int32), dev_energy[rows], model.variables, "DISCRETE", info=info))
         return out
 
@@ -232,6 +240,21 @@ class MI355XSampler:
         if unknown:
             raise TypeError("MI355XSampler got unexpected keyword argument(s): %s" % ", ".join(unknown))
         return {k: v for k, v in kwargs.items() if k not in _IGNORED_KWARGS}, ignored
+
+    @staticmethod
+    def _merge_kwargs(kw, min_size: int):
+        """``merge_interval`` (0 / None = off) and ``merge_proposals`` (None = 2 K) of the Potts samplers, checked before
+        any GPU work: merges empty clusters, so they do not combine with a minimum cluster size."""
+        interval = kw.get("merge_interval")
+        interval = 0 if interval is None else int(interval)
+        proposals = kw.get("merge_proposals")
+        if interval < 0:
+            raise ValueError("'merge_interval' should be a non-negative integer")
+        if proposals is not None and int(proposals) < 1:
+            raise ValueError("'merge_proposals' should be a positive integer")
+        if interval and (min_size or kw.get("min_cluster_size")):
+            raise ValueError("merge moves together with min_cluster_size are not supported")
+        return interval, (None if proposals is None else int(proposals))
 
     @staticmethod
     def _seed(seed) -> int:
@@ -396,6 +419,7 @@ class MI355XSampler:
         min_size = int(kw.get("min_cluster_size", model.info.get("min_cluster_size", 0)) or 0)
         if model.node_weight is not None and min_size > 0:
             raise ValueError("node weights (a modularity model) together with min_cluster_size are not supported")
+        merge_interval, merge_proposals = self._merge_kwargs(kw, min_size)
         prob = Problem.potts_csr(model.rowptr, model.col, model.val.astype(np.float32),
                                  float(np.float32(model.c_pair)), n, model.num_cases,
                                  lin_offset=model.lin_offset, device=self.device, order="padded",
@@ -403,6 +427,8 @@ class MI355XSampler:
         if min_size * model.num_cases > n:
             raise ValueError("min_cluster_size %d x %d clusters exceeds the %d variables" % (min_size, model.num_cases, n))
         with prob:
+            if merge_interval:
+                prob.set_merge_moves(merge_interval, merge_proposals, potts_merge_coefficients(model))
             init_arr = init
             if isinstance(init, tuple) or (min_size > 0 and init is None):
                 have = init[1] if isinstance(init, tuple) else np.zeros((0, n), dtype=np.uint16)
@@ -417,6 +443,7 @@ class MI355XSampler:
             prob.anneal(num_reads, betas, seed, self.replica_offset, init_arr)
             labels, dev_energy, stats = prob.fetch()
             kernel_ms = prob.kernel_ms()
+            merges = prob.merges_accepted() if merge_interval else None
             t2 = time.perf_counter()
         energies = dev_energy                    # evaluated on the device in the model's fp64 coefficients
         info = {
@@ -429,6 +456,8 @@ class MI355XSampler:
             "energy_evaluation": "device fp64 (caller's coefficients)",
             "ignored_kwargs": ignored,
         }
+        if merge_interval:
+            info["merges_accepted"] = merges
         return SampleSet(labels.astype(np.int32), energies, model.variables, "DISCRETE", info=info)
 
 
