@@ -12,6 +12,13 @@
  *
  * Distances: binary Jaccard d = 1 - |A & B| / |A | B| on the non-zero pattern of each cell's gene row,
  * evaluated in fp64 (two empty rows: 0).  Conventions as in mi_sa.h.
+ *
+ * mi_label_agreement_u16 answers "how much do two clusterings agree": the adjusted Rand index (Hubert-Arabie) and the
+ * normalised mutual information (arithmetic mean of the entropies) of every pair of labellings, the standard way to
+ * pick a resolution from replica stability (mean pairwise ARI of independent runs) or to compare against a reference
+ * clustering.  The contingency table of every pair is one integer product of one-hot matrices on the i8 matrix cores
+ * (exact: i32 accumulation); mi_sa_problem_label_agreement (mi_sa.h) runs the same on the states a Potts anneal left
+ * in HBM.  DESIGN.md section 5c.
  */
 #ifndef MI_METRICS_H
 #define MI_METRICS_H
@@ -35,6 +42,28 @@ extern "C" {
 int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, const int32_t *labels, int K, int device,
                              double *rowsum, double *rowsq_all, double *rowsq_within, double *diameter,
                              double *separation, float *out_D, float *out_kernel_ms);
+
+#define MI_AGREE_CROSS  0              /* all Ra x Rb pairs (A row i, B row j), pair index i * Rb + j */
+#define MI_AGREE_WITHIN 1              /* all r < s inside each of `groups` groups of Ra / groups consecutive rows of A */
+#define MI_AGREE_MAX_LABELLINGS 65536  /* Ra, Rb */
+#define MI_AGREE_MAX_TABLE_ENTRIES (1 << 28)   /* Ra * Rb * Ka * Kb when out_tables is given (1 GiB of int32) */
+
+/* A: Ra x n and B: Rb x n uint16 labellings, row-major host arrays, labels in [0, Ka) / [0, Kb), K <= 64 (unused labels
+ * allowed).  mode MI_AGREE_CROSS: every (A row, B row) pair, groups = 1.  MI_AGREE_WITHIN: B = NULL (Kb, Rb ignored),
+ * every pair r < s inside each group, row-major within a group, group after group (groups x C(Ra / groups, 2) pairs).
+ * Outputs (host, caller-allocated, each nullable), per pair:
+ *   out_ari       adjusted Rand index; 1.0 when no pair of cells is joined by one labelling and split by the other
+ *                 (identical up to renaming, both single-cluster, both all-singletons), as sklearn
+ *   out_nmi       normalised mutual information, arithmetic; 1.0 when both labellings have one cluster, 0.0 when exactly
+ *                 one does, mutual information clipped at 0 (sklearn's conventions)
+ *   out_pair_sum  S = sum over the table of C(n_ij, 2), exact in int64
+ *   out_tables    CROSS only: the Ka x Kb contingency table (rows: A's labels) per pair, int32; at most
+ *                 MI_AGREE_MAX_TABLE_ENTRIES entries in all (MI_EUNSUPPORTED beyond)
+ *   out_kernel_ms device time of the kernels
+ * MI_EINVAL for bad shapes, K outside [1, 64], a label >= K, n < 1. */
+int mi_label_agreement_u16(const uint16_t *A, int Ra, const uint16_t *B, int Rb, int n, int Ka, int Kb, int mode,
+                           int groups, int device, double *out_ari, double *out_nmi, int64_t *out_pair_sum,
+                           int32_t *out_tables, float *out_kernel_ms);
 
 #ifdef __cplusplus
 }

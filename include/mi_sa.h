@@ -272,6 +272,14 @@ int mi_sa_last_kernel_name(mi_sa_problem *p, char *out, int len);
  * stats[0] proposals, stats[1] accepted moves, stats[2] Q/CSR bytes read by accepted moves. */
 int mi_sa_fetch(mi_sa_problem *p, void *out_states, double *out_energy, uint64_t *out_stats);
 
+/* Label agreement of the last run's replicas (Potts problems), read in place from HBM: mi_label_agreement_u16 in
+ * WITHIN mode (include/mi_metrics.h) over the states of the last mi_sa_anneal, every pair r < s inside each of `groups`
+ * groups of consecutive replicas (groups <= 0: the problem's own resolution groups, 1 without them).  The hole seats of
+ * a padded layout (mi_sa_problem_set_absent) are not cells.  Read-only: states, energies and MI_F_CONTINUE are
+ * untouched.  Outputs as there (host, nullable); MI_ESTATE before a run and for binary kinds. */
+int mi_sa_problem_label_agreement(mi_sa_problem *p, int groups, double *out_ari, double *out_nmi, int64_t *out_pair_sum,
+                                  float *out_kernel_ms);
+
 /* Best replica of the last run (reduced on device): the replica with the lowest fp64 energy (ties: the lowest
  * index) -- its local index, energy, and an order-preserving packed key
  * (sortable(float(E)) << 32) | global_replica_id  suitable for an integer MIN all-reduce across GPUs (RCCL has

@@ -93,6 +93,9 @@ def _declare(lib):
         # include/mi_metrics.h
         "mi_jaccard_cluster_stats": (C.c_int, [u64p, C.c_int, C.c_int, i32p, C.c_int, C.c_int, f64p, f64p, f64p, f64p,
                                                f64p, f32p, f32p]),
+        "mi_label_agreement_u16": (C.c_int, [u16p, C.c_int, u16p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, f64p, f64p, C.POINTER(C.c_int64), i32p, f32p]),
+        "mi_sa_problem_label_agreement": (C.c_int, [vp, C.c_int, f64p, f64p, C.POINTER(C.c_int64), f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
@@ -108,7 +111,7 @@ EXPORTS = (
     "mi_sa_set_option", "mi_sa_plan_slot_order", "mi_sa_plan_slot_layout", "mi_sa_problem_set_absent", "mi_sa_problem_set_pair_weights", "mi_sa_problem_set_node_weights", "mi_sa_problem_set_node_weight_groups", "mi_sa_problem_set_merge_moves", "mi_sa_problem_set_energy_model_f64", "mi_sa_debug_pace", "mi_sa_debug_stats", "mi_sa_anneal", "mi_sa_anneal_ex", "mi_sa_tempering_begin", "mi_sa_tempering_exchange", "mi_sa_tempering_exchange_dev", "mi_sa_device_results", "mi_sa_tempering_state", "mi_sa_sync", "mi_sa_last_kernel_ms", "mi_sa_last_launch_count", "mi_sa_last_kernel_name", "mi_sa_fetch", "mi_sa_best",
     "mi_multi_gpu_anneal", "mi_multi_gpu_best", "mi_multi_gpu_fetch", "mi_sa_qubo_dense_f32", "mi_energy_dense_f32", "mi_energy_dense_f64", "mi_energy_dense_f32_ex",
     "mi_snn_build_f32", "mi_snn_build_ex_f32", "mi_snn_build_rounded_f32", "mi_snn_fetch_codes", "mi_snn_info", "mi_snn_fetch", "mi_snn_kernel_ms", "mi_snn_destroy",
-    "mi_jaccard_cluster_stats",
+    "mi_jaccard_cluster_stats", "mi_label_agreement_u16", "mi_sa_problem_label_agreement",
 )
 
 

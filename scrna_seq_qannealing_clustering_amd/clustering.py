@@ -253,13 +253,16 @@ def clustering_dqm(G, num_of_clusters, gamma, sampler=None, sampler_kwargs: Opti
 
 
 def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sampler=None,
-                          sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None):
+                          sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None,
+                          stability: bool = False):
     """Weighted modularity at ``resolution`` -- the objective of Seurat's ``FindClusters(..., algorithm = 1)`` that the
     reference's notebooks compare every annealed clustering with -- annealed on the Potts chain with node weights
     (models.build_modularity_potts), at most ``max_clusters`` labels.  Returns the sampleset; ``info["modularity"]``
     holds ``Q_gamma`` of every sample (record order), ``-energy / m``.  Default schedule: 16000 sweeps, geometric over
     ``models.modularity_beta_range`` (``sampler_kwargs`` overrides either).  ``merge_interval``: merge moves (chain 2e)
-    every that many sweeps, the sampler's ``merge_interval`` (off by default; ``sampler_kwargs`` may set it too)."""
+    every that many sweeps, the sampler's ``merge_interval`` (off by default; ``sampler_kwargs`` may set it too).
+    ``stability``: ``info["stability"]`` / ``info["stability_nmi"]``, the mean ARI / NMI over all pairs of reads, computed
+    on the device before the problem closes (metrics.replica_stability restates it on the host's records)."""
     from .models import build_modularity_potts, modularity_beta_range
     model = build_modularity_potts(G, resolution, max_clusters)
     # default schedule: 16000 sweeps over modularity_beta_range -- single-site moves over more labels than communities
@@ -267,6 +270,8 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
     kw = dict(num_sweeps=16000, beta_range=modularity_beta_range(model))
     if merge_interval is not None:
         kw["merge_interval"] = merge_interval
+    if stability:
+        kw["stability"] = True
     kw.update(sampler_kwargs or {})
     sampleset = _sampler(sampler).sample_dqm(model, **kw)
     sampleset.info["modularity"] = -np.asarray(sampleset.record["energy"], dtype=np.float64) / model.info["m"]
@@ -276,26 +281,37 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
 
 
 def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=None,
-                                sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None):
+                                sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None,
+                                stability: bool = False):
     """:func:`clustering_modularity` at several resolutions -- what Seurat users do with ``FindClusters(...,
     resolution = c(...))`` -- in one upload and one launch (MI355XSampler.sample_dqm_many: one resolution group of
     replicas per value).  Returns one sampleset per resolution, in the order given; each equals what
     ``clustering_modularity(G, resolution, ...)`` returns with the same ``sampler_kwargs`` and has
     ``info["resolution"]`` and ``info["modularity"]``.  Same defaults: 16000 sweeps, each resolution on its own
     ``models.modularity_beta_range`` (a ``beta_range`` in ``sampler_kwargs`` applies to all).  An empty list, a
-    repeated value and a resolution <= 0 or not finite raise ValueError before any GPU work.  ``merge_interval`` as in
-    :func:`clustering_modularity`."""
+    repeated value and a resolution <= 0 or not finite raise ValueError before any GPU work.  ``merge_interval`` and
+    ``stability`` as in :func:`clustering_modularity`; with ``stability`` every sampleset also gets
+    ``info["ari_to_previous"]``, the ARI between its best sample and the previous resolution's (None for the first):
+    the clustree view of how the clustering changes from one resolution to the next."""
     from .models import build_modularity_sweep, check_resolutions, modularity_beta_range
     res = check_resolutions(resolutions)
     models = build_modularity_sweep(G, res, max_clusters)
     kw = dict(num_sweeps=16000, beta_range=[modularity_beta_range(m) for m in models])
     if merge_interval is not None:
         kw["merge_interval"] = merge_interval
+    if stability:
+        kw["stability"] = True
     kw.update(sampler_kwargs or {})
     samplesets = _sampler(sampler).sample_dqm_many(models, **kw)
-    for gamma, model, ss in zip(res, models, samplesets):
+    if stability:
+        from .metrics import label_agreement
+        best = np.stack([np.asarray(ss.record["sample"][0]) for ss in samplesets])
+        ari = label_agreement(best[1:], best[:-1])["ari"] if len(best) > 1 else np.zeros((0, 0))
+    for g, (gamma, model, ss) in enumerate(zip(res, models, samplesets)):
         ss.info["resolution"] = gamma
         ss.info["modularity"] = -np.asarray(ss.record["energy"], dtype=np.float64) / model.info["m"]
+        if stability:
+            ss.info["ari_to_previous"] = None if g == 0 else float(ari[g - 1, g - 1])
         if verbose:
             print("Resolution {}: modularity {}".format(gamma, float(np.max(ss.info["modularity"]))))
     return samplesets

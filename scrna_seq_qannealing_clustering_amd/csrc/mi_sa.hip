@@ -1634,6 +1634,28 @@ int mi_sa_fetch(mi_sa_problem *p, void *out_states, double *out_energy, uint64_t
     return MI_OK;
 }
 
+int mi_sa_problem_label_agreement(mi_sa_problem *p, int groups, double *out_ari, double *out_nmi, int64_t *out_pair_sum,
+                                  float *out_kernel_ms)
+{
+    if (!p) return fail(MI_EINVAL, "NULL problem");
+    if (const int rc_w = settle(p)) return rc_w;
+    if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_ESTATE, "label agreement needs a Potts problem");
+    if (!p->has_run) return fail(MI_ESTATE, "no anneal has been run on this problem");
+    const int G = groups > 0 ? groups : p->ngroups;
+    if (p->last_R % G != 0) return fail(MI_EINVAL, "R = %d is not a multiple of groups = %d", p->last_R, G);
+    return guarded([&]() -> int {
+        int n_real = 0;
+        for (int i = 0; i < p->n; ++i) n_real += (p->h_meta[(size_t)i] >> 31) ? 0 : 1;
+        if (n_real < 1) return fail(MI_EINVAL, "every variable of the problem is a hole");
+        HIP_TRY(hipSetDevice(p->device));
+        AgreeArgs a;
+        a.A = static_cast<const uint16_t *>(p->d_states); a.lda = (size_t)p->n;
+        a.Ra = p->last_R; a.cols = p->n; a.Ka = a.Kb = p->K; a.groups = G;
+        a.meta = p->d_meta; a.n_real = n_real;
+        return mi_label_agreement_dev(a, p->stream, out_ari, out_nmi, out_pair_sum, nullptr, out_kernel_ms);
+    });
+}
+
 int mi_sa_best(mi_sa_problem *p, int *out_index, double *out_energy, uint64_t *out_key, void *out_state)
 {
     if (!p) return fail(MI_EINVAL, "NULL problem");

@@ -455,6 +455,20 @@ int mi_launch_energy_dense(const float *dQ, int n, int ldq, const uint8_t *dX, i
                            uint8_t *dXt, int path, hipStream_t st);
 int mi_launch_energy_dense_f64(const double *dQ, int n, const uint8_t *dX, int R, double offset, double *dE, hipStream_t st);
 
+// label agreement (agreement_kernels.hip): labellings as DEVICE uint16 rows of `cols` labels (row stride lda / ldb);
+// B == nullptr: WITHIN mode (all r < s inside each of `groups` groups of consecutive rows of A), else CROSS (Ra x Rb).
+// Column i is skipped when meta && meta[i] >> 31; n_real = the columns that count.  Outputs are HOST pointers (nullable);
+// the kernels run on `st` and the call returns when the results are copied.
+struct AgreeArgs {
+    const uint16_t *A = nullptr, *B = nullptr;
+    size_t lda = 0, ldb = 0;
+    int Ra = 0, Rb = 0, cols = 0, Ka = 0, Kb = 0, groups = 1;
+    const uint32_t *meta = nullptr;
+    int n_real = 0;
+};
+int mi_label_agreement_dev(const AgreeArgs &a, hipStream_t st, double *out_ari, double *out_nmi, int64_t *out_pair_sum,
+                           int32_t *out_tables, float *out_kernel_ms);
+
 // Energy of the final state, E = sum_i x_i diag_i + 1/2 sum_{i,j} x_i x_j Q2_ij, with every fp32 matrix
 // entry added EXACTLY once into fp64 accumulators (lane l sums its own columns over all set rows; one
 // wave reduction at the end).  Independent of the cached fp32 fields, so the reported energies carry

@@ -491,6 +491,25 @@ class Problem:
         _lib.check(_lib.load().mi_sa_last_kernel_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
+    def label_agreement(self, groups: Optional[int] = None) -> dict:
+        """ARI and NMI of every pair r < s of the last run's replicas inside each group of consecutive replicas (``groups``
+        None: the problem's own resolution groups), computed on the states in HBM without a host copy; hole seats are
+        not cells.  Potts problems only.  Returns ``ari``, ``nmi`` (fp64) and ``pair_sum`` (int64), each of shape
+        (groups, C(R / groups, 2)) in row-major pair order, and ``kernel_ms``.  Leaves the run untouched."""
+        if self._last is None:
+            raise RuntimeError("label_agreement() before anneal()")
+        R = self._last[0]
+        G = self.groups if groups is None else int(groups)
+        if G < 1 or R % G:
+            raise ValueError("%d replicas do not split into %d equal groups" % (R, G))
+        P = (R // G) * (R // G - 1) // 2
+        ari, nmi = np.empty((G, P)), np.empty((G, P))
+        S = np.empty((G, P), dtype=np.int64)
+        ms = C.c_float(0.0)
+        _lib.check(_lib.load().mi_sa_problem_label_agreement(self._h, G, _ptr(ari, C.c_double), _ptr(nmi, C.c_double),
+                                                             _ptr(S, C.c_int64), C.byref(ms)))
+        return {"ari": ari, "nmi": nmi, "pair_sum": S, "kernel_ms": float(ms.value)}
+
     def launch_count(self) -> int:
         """Kernel launches that served the last anneal (kernel_ms() / launch_count() = mean launch time)."""
         k = C.c_int(0)

@@ -146,3 +146,145 @@ def modularity(G, labels, resolution: float = 1.0) -> float:
     inside = float(np.sum(w[lab[eu] == lab[ev]]))
     Kc = np.bincount(lab, weights=k)
     return inside / m - float(resolution) * float(np.sum((Kc / (2.0 * m)) ** 2))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Label agreement: adjusted Rand index and normalised mutual information between labellings (include/mi_metrics.h
+# mi_label_agreement_u16, csrc/agreement_kernels.hip).  The contingency table of every pair is an exact integer product
+# on the i8 matrix cores; ARI (Hubert-Arabie) and NMI (arithmetic) are evaluated from it in fp64 on the device, with
+# sklearn's conventions for the degenerate cases.
+# ---------------------------------------------------------------------------------------------------------------------
+AGREE_CROSS, AGREE_WITHIN = 0, 1
+MAX_AGREE_LABELS = 64
+
+
+def _labellings(L, name: str):
+    """(n,) or (R, n) labels -> (R, n) uint16 in [0, K) and K.  A labelling with a label outside [0, 64) is compacted
+    (its distinct labels renumbered in sorted order); more than 64 distinct labels raise ValueError."""
+    A = np.asarray(L)
+    if A.ndim == 1:
+        A = A[None, :]
+    if A.ndim != 2:
+        raise ValueError("%s must be (n,) or (R, n) labels (got shape %s)" % (name, np.shape(L)))
+    if A.shape[0] < 1 or A.shape[1] < 1:
+        raise ValueError("%s needs at least one labelling of at least one cell (got shape %s)" % (name, A.shape))
+    if np.issubdtype(A.dtype, np.integer) and A.min() >= 0 and A.max() < MAX_AGREE_LABELS:
+        out = A.astype(np.uint16)
+    else:
+        out = np.empty(A.shape, dtype=np.uint16)
+        for r in range(A.shape[0]):
+            row = A[r]
+            if np.issubdtype(row.dtype, np.integer) and row.min() >= 0 and row.max() < MAX_AGREE_LABELS:
+                out[r] = row
+                continue
+            uniq, inv = np.unique(row, return_inverse=True)
+            if len(uniq) > MAX_AGREE_LABELS:
+                raise ValueError("%s: labelling %d has %d distinct labels (at most %d)" % (name, r, len(uniq), MAX_AGREE_LABELS))
+            out[r] = inv.reshape(-1)
+    return np.ascontiguousarray(out), int(out.max()) + 1
+
+
+def label_agreement(A, B=None, groups: int = 1, device: int = 0, tables: bool = False) -> dict:
+    """All pairs of labellings at once.  ``B`` given: every (row of A, row of B) pair, arrays of shape (Ra, Rb).  ``B``
+    None: every pair r < s inside each of ``groups`` groups of consecutive rows of A, flat in row-major order, group
+    after group.  Returns ``ari``, ``nmi``, ``pair_sum`` (sum of C(n_ij, 2), int64), ``tables`` (B given and
+    ``tables``: (Ra, Rb, Ka, Kb) int32 contingency tables; else None) and ``kernel_ms``."""
+    La, Ka = _labellings(A, "A")
+    Ra, n = La.shape
+    if B is not None:
+        Lb, Kb = _labellings(B, "B")
+        Rb = Lb.shape[0]
+        if Lb.shape[1] != n:
+            raise ValueError("A and B label different numbers of cells (%d, %d)" % (n, Lb.shape[1]))
+        if int(groups) != 1:
+            raise ValueError("groups apply to the pairs within A only")
+        shape, mode = (Ra, Rb), AGREE_CROSS
+    else:
+        Lb, Kb, Rb = None, Ka, 0
+        G = int(groups)
+        if G < 1 or Ra % G:
+            raise ValueError("%d labellings do not split into %d equal groups" % (Ra, G))
+        Rg = Ra // G
+        shape, mode = (G * Rg * (Rg - 1) // 2,), AGREE_WITHIN
+        if tables:
+            raise ValueError("contingency tables are returned for pairs across A and B only")
+    ari, nmi = np.empty(shape), np.empty(shape)
+    S = np.empty(shape, dtype=np.int64)
+    T = np.empty(shape + (Ka, Kb), dtype=np.int32) if tables else None
+    ms = C.c_float(0.0)
+    f64p, u16p = C.POINTER(C.c_double), C.POINTER(C.c_uint16)
+    _lib.check(_lib.load().mi_label_agreement_u16(
+        La.ctypes.data_as(u16p), Ra, Lb.ctypes.data_as(u16p) if Lb is not None else None, Rb, n, Ka, Kb, mode,
+        int(groups), int(device), ari.ctypes.data_as(f64p), nmi.ctypes.data_as(f64p),
+        S.ctypes.data_as(C.POINTER(C.c_int64)), T.ctypes.data_as(C.POINTER(C.c_int32)) if T is not None else None,
+        C.byref(ms)))
+    return {"ari": ari, "nmi": nmi, "pair_sum": S, "tables": T, "kernel_ms": float(ms.value)}
+
+
+def _against(a, b, key: str, device: int):
+    A = np.asarray(a)
+    if np.ndim(b) != 1:
+        raise ValueError("b must be one labelling of shape (n,)")
+    r = label_agreement(A, b, device=device)[key][:, 0]
+    return float(r[0]) if A.ndim == 1 else r
+
+
+def adjusted_rand_index(a, b, device: int = 0):
+    """ARI of labelling ``a`` (n,) against ``b`` (n,), a float; or of every row of ``a`` (R, n), an (R,) array."""
+    return _against(a, b, "ari", device)
+
+
+def normalized_mutual_info(a, b, device: int = 0):
+    """NMI (arithmetic normalisation) of ``a`` (n,) or every row of ``a`` (R, n) against ``b`` (n,)."""
+    return _against(a, b, "nmi", device)
+
+
+def contingency(a, b, device: int = 0) -> np.ndarray:
+    """The exact contingency table of two labellings (n,): entry (i, j) counts the cells labelled i by ``a`` and j by
+    ``b``; rows 0 .. max(a), columns 0 .. max(b) (after compaction of labels outside [0, 64))."""
+    if np.ndim(a) != 1 or np.ndim(b) != 1:
+        raise ValueError("contingency takes two labellings of shape (n,)")
+    return label_agreement(a, b, device=device, tables=True)["tables"][0, 0].astype(np.int64)
+
+
+def pairwise_agreement(L, other=None, groups: int = 1, device: int = 0):
+    """ARI and NMI matrices.  ``other`` given: (Ra, Rb) between the rows of ``L`` and of ``other``.  Else the rows of
+    ``L`` against each other: (R, R), symmetric with a diagonal of 1; with ``groups`` > 1 only pairs inside each group
+    of R / groups consecutive rows, as (groups, R / groups, R / groups)."""
+    if other is not None:
+        r = label_agreement(L, other, groups=groups, device=device)
+        return r["ari"], r["nmi"]
+    r = label_agreement(L, None, groups=groups, device=device)
+    R = np.asarray(L).shape[0] if np.ndim(L) == 2 else 1
+    G = int(groups)
+    Rg = R // G
+    iu = np.triu_indices(Rg, 1)
+    out = []
+    for key in ("ari", "nmi"):
+        M = np.zeros((G, Rg, Rg))
+        flat = r[key].reshape(G, -1)
+        for g in range(G):
+            M[g][iu] = flat[g]
+            M[g] = M[g] + M[g].T
+            np.fill_diagonal(M[g], 1.0)
+        out.append(M[0] if G == 1 else M)
+    return out[0], out[1]
+
+
+def mean_pair_agreement(ari, nmi):
+    """(mean ARI, mean NMI) over a flat array of pairs in a fixed-order fp64 sum (math.fsum); None with no pair."""
+    import math
+    if len(ari) == 0:
+        return None, None
+    return math.fsum(ari) / len(ari), math.fsum(nmi) / len(nmi)
+
+
+def replica_stability(sampleset, device: int = 0):
+    """Mean pairwise ARI over the READS of a sampleset: aggregated records are expanded by ``num_occurrences`` (two
+    reads of one record agree with ARI 1).  None with fewer than two reads."""
+    rec = sampleset.record
+    L = np.repeat(np.asarray(rec["sample"]), np.asarray(rec["num_occurrences"], dtype=np.int64), axis=0)
+    if L.shape[0] < 2:
+        return None
+    r = label_agreement(L, None, device=device)
+    return mean_pair_agreement(r["ari"], r["nmi"])[0]

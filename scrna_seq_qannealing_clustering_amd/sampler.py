@@ -32,6 +32,7 @@ from .engine import Problem, energy_dense_f64, layout_block_for
 from .models import (PottsModel, QuboModel, _csr_from_edges, default_beta_range,
                      make_beta_schedule, potts_merge_coefficients, potts_node_weight_groups, potts_node_weights,
                      qubo_dict_to_model)
+from .metrics import mean_pair_agreement
 from .sampleset import SampleSet
 
 # keyword arguments of the samplers the reference uses that have no meaning for an annealer on a GPU
@@ -86,7 +87,7 @@ class MI355XSampler:
         "num_reads": [], "num_sweeps": [], "beta_range": [], "beta_schedule_type": [],
         "beta_schedule": [], "num_sweeps_per_beta": [], "seed": [], "initial_states": [],
         "initial_states_generator": [], "resync_interval": [], "kernel": [], "min_cluster_size": [],
-        "merge_interval": [], "merge_proposals": [],
+        "merge_interval": [], "merge_proposals": [], "stability": [],
         **{k: [] for k in _IGNORED_KWARGS},
     }
     properties = {"category": "software", "beta_schedule_options": ("linear", "geometric", "custom"),
@@ -211,6 +212,7 @@ class MI355XSampler:
             kernel_ms = prob.kernel_ms()
             kernel = prob.kernel_name()
             merges = prob.merges_accepted() if merge_interval else None
+            agree = prob.label_agreement(G) if kw.get("stability") and num_reads >= 2 else None
             t2 = time.perf_counter()
         batch = {"groups": G, "kernel_ms": kernel_ms, "kernel_name": kernel, "accepted": stats["accepted"],
                  "proposals": stats["proposals"], "updates_per_s": (stats["proposals"] / (kernel_ms * 1e-3)) if kernel_ms > 0 else None,
@@ -227,6 +229,9 @@ class MI355XSampler:
             }
             if merge_interval:
                 info["merges_accepted"] = merges                  # (all groups together, like "batch")
+            if kw.get("stability"):
+                info["stability"], info["stability_nmi"] = (
+                    mean_pair_agreement(agree["ari"][g], agree["nmi"][g]) if agree is not None else (None, None))
             out.append(SampleSet(labels[rows].astype(np.int32), dev_energy[rows], model.variables, "DISCRETE", info=info))
         return out
 
@@ -339,6 +344,8 @@ class MI355XSampler:
     def _binary_steps(self, model: QuboModel, vartype: str, kwargs):
         """Generator: everything up to the enqueued anneal, ONE ``yield``, then the fetch and the SampleSet (its return value)."""
         kw, ignored = self._split_kwargs(dict(kwargs))
+        if kw.get("stability"):
+            raise ValueError("'stability' (label agreement of the reads) applies to the Potts samplers (sample_dqm)")
         t0 = time.perf_counter()
         n = model.num_variables
         if n == 0:
@@ -444,6 +451,7 @@ class MI355XSampler:
             labels, dev_energy, stats = prob.fetch()
             kernel_ms = prob.kernel_ms()
             merges = prob.merges_accepted() if merge_interval else None
+            agree = prob.label_agreement(1) if kw.get("stability") and num_reads >= 2 else None
             t2 = time.perf_counter()
         energies = dev_energy                    # evaluated on the device in the model's fp64 coefficients
         info = {
@@ -458,6 +466,9 @@ class MI355XSampler:
         }
         if merge_interval:
             info["merges_accepted"] = merges
+        if kw.get("stability"):
+            info["stability"], info["stability_nmi"] = (
+                mean_pair_agreement(agree["ari"][0], agree["nmi"][0]) if agree is not None else (None, None))
         return SampleSet(labels.astype(np.int32), energies, model.variables, "DISCRETE", info=info)
 
 
