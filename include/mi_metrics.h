@@ -19,6 +19,12 @@
  * clustering.  The contingency table of every pair is one integer product of one-hot matrices on the i8 matrix cores
  * (exact: i32 accumulation); mi_sa_problem_label_agreement (mi_sa.h) runs the same on the states a Potts anneal left
  * in HBM.  DESIGN.md section 5c.
+ *
+ * mi_coassociation_u16 answers "where do the labellings agree": the co-association (consensus) matrix C[i, j] = number of
+ * labellings that put cells i and j in one cluster (Monti et al.; Fred and Jain's evidence accumulation), again an exact
+ * integer product of one-hot matrices on the i8 matrix cores, now with the cells outside and (labelling, label) inside.
+ * The matrix is reduced tile by tile into its histogram (consensus CDF, PAC) and per-cell sums per reference cluster;
+ * the entries of a graph's edges come from a second kernel that needs nothing of size n x n.
  */
 #ifndef MI_METRICS_H
 #define MI_METRICS_H
@@ -65,6 +71,28 @@ int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, const int32
 int mi_label_agreement_u16(const uint16_t *A, int Ra, const uint16_t *B, int Rb, int n, int Ka, int Kb, int mode,
                            int groups, int device, double *out_ari, double *out_nmi, int64_t *out_pair_sum,
                            int32_t *out_tables, float *out_kernel_ms);
+
+#define MI_COASSOC_MAX_READS 8192                  /* R / groups: the workgroup's histogram bins live in LDS (4 B each) */
+#define MI_COASSOC_MAX_COUNT_ENTRIES (1 << 28)     /* groups * n * n when out_counts is given (1 GiB of int32) */
+
+/* L: R x n uint16 labellings ("reads"), row-major host array, labels in [0, K), K <= 64 (unused labels allowed); `groups`
+ * groups of Rg = R / groups consecutive rows.  C_g[i, j] = #{r in group g : L[r, i] == L[r, j]} (0 <= C <= Rg, C[i, i] = Rg).
+ * Outputs (host, caller-allocated, each nullable; the dense pass runs only if one of the first three is given, the edge
+ * pass only if out_edge is):
+ *   out_hist      groups x (Rg + 1) int64: hist[g][v] = number of pairs i < j with C_g[i, j] == v
+ *   out_rowsum    groups x n x Kref int64: sum of C_g[i, j] over j != i with ref[g][j] == c; needs `ref`, groups x n uint16
+ *                 reference labels in [0, Kref), Kref <= 64 (ref may be NULL without out_rowsum)
+ *   out_edge      groups x m int32: C_g[eu[e], ev[e]] for the m edges (eu, ev in [0, n); any order, repeats allowed),
+ *                 computed from the labels for any n (nothing n x n exists)
+ *   out_counts    groups x n x n int32, the full symmetric matrix; at most MI_COASSOC_MAX_COUNT_ENTRIES entries in all
+ *                 (MI_EUNSUPPORTED beyond).  Without it nothing of size n x n is allocated anywhere.
+ *   out_kernel_ms device time of the kernels
+ * MI_EINVAL for bad shapes, K or Kref outside [1, 64], R not a multiple of groups, a label >= K (ref: >= Kref), an edge
+ * index outside [0, n), out_rowsum without ref.  MI_EUNSUPPORTED, before anything is launched, for Rg >
+ * MI_COASSOC_MAX_READS and for out_counts beyond its cap. */
+int mi_coassociation_u16(const uint16_t *L, int R, int n, int K, int groups, const uint16_t *ref, int Kref,
+                         const int32_t *eu, const int32_t *ev, int64_t m, int device, int64_t *out_hist,
+                         int64_t *out_rowsum, int32_t *out_edge, int32_t *out_counts, float *out_kernel_ms);
 
 #ifdef __cplusplus
 }

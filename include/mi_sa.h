@@ -280,6 +280,18 @@ int mi_sa_fetch(mi_sa_problem *p, void *out_states, double *out_energy, uint64_t
 int mi_sa_problem_label_agreement(mi_sa_problem *p, int groups, double *out_ari, double *out_nmi, int64_t *out_pair_sum,
                                   float *out_kernel_ms);
 
+/* Co-association of the last run's replicas (Potts problems), read in place from HBM: mi_coassociation_u16
+ * (include/mi_metrics.h) over the states of the last mi_sa_anneal, `groups` groups of consecutive replicas (groups <= 0:
+ * the problem's own resolution groups).  Runs on the problem's stream after the run has settled.  Cells are the problem's
+ * variable indices, the columns mi_sa_fetch returns (n of mi_sa_problem_info): ref is groups x n, edges index [0, n),
+ * out_rowsum is groups x n x Kref, out_counts groups x n x n.  The hole seats of a padded layout are not cells: their rows
+ * and columns of out_counts are zero, they are in no pair of out_hist and no sum of out_rowsum, and an edge that touches
+ * one counts 0.  Read-only: states, energies and MI_F_CONTINUE are untouched.  Outputs and error codes as there;
+ * MI_ESTATE before a run and for binary kinds. */
+int mi_sa_problem_coassociation(mi_sa_problem *p, int groups, const uint16_t *ref, int Kref, const int32_t *eu,
+                                const int32_t *ev, int64_t m, int64_t *out_hist, int64_t *out_rowsum, int32_t *out_edge,
+                                int32_t *out_counts, float *out_kernel_ms);
+
 /* Best replica of the last run (reduced on device): the replica with the lowest fp64 energy (ties: the lowest
  * index) -- its local index, energy, and an order-preserving packed key
  * (sortable(float(E)) << 32) | global_replica_id  suitable for an integer MIN all-reduce across GPUs (RCCL has

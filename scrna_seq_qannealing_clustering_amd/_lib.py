@@ -96,6 +96,10 @@ def _declare(lib):
         "mi_label_agreement_u16": (C.c_int, [u16p, C.c_int, u16p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_int, f64p, f64p, C.POINTER(C.c_int64), i32p, f32p]),
         "mi_sa_problem_label_agreement": (C.c_int, [vp, C.c_int, f64p, f64p, C.POINTER(C.c_int64), f32p]),
+        "mi_coassociation_u16": (C.c_int, [u16p, C.c_int, C.c_int, C.c_int, C.c_int, u16p, C.c_int, i32p, i32p, C.c_int64,
+                                           C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32p, i32p, f32p]),
+        "mi_sa_problem_coassociation": (C.c_int, [vp, C.c_int, u16p, C.c_int, i32p, i32p, C.c_int64, C.POINTER(C.c_int64),
+                                                  C.POINTER(C.c_int64), i32p, i32p, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
@@ -112,6 +116,7 @@ EXPORTS = (
     "mi_multi_gpu_anneal", "mi_multi_gpu_best", "mi_multi_gpu_fetch", "mi_sa_qubo_dense_f32", "mi_energy_dense_f32", "mi_energy_dense_f64", "mi_energy_dense_f32_ex",
     "mi_snn_build_f32", "mi_snn_build_ex_f32", "mi_snn_build_rounded_f32", "mi_snn_fetch_codes", "mi_snn_info", "mi_snn_fetch", "mi_snn_kernel_ms", "mi_snn_destroy",
     "mi_jaccard_cluster_stats", "mi_label_agreement_u16", "mi_sa_problem_label_agreement",
+    "mi_coassociation_u16", "mi_sa_problem_coassociation",
 )
 
 

@@ -254,7 +254,7 @@ def clustering_dqm(G, num_of_clusters, gamma, sampler=None, sampler_kwargs: Opti
 
 def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sampler=None,
                           sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None,
-                          stability: bool = False):
+                          stability: bool = False, consensus: bool = False):
     """Weighted modularity at ``resolution`` -- the objective of Seurat's ``FindClusters(..., algorithm = 1)`` that the
     reference's notebooks compare every annealed clustering with -- annealed on the Potts chain with node weights
     (models.build_modularity_potts), at most ``max_clusters`` labels.  Returns the sampleset; ``info["modularity"]``
@@ -262,7 +262,11 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
     ``models.modularity_beta_range`` (``sampler_kwargs`` overrides either).  ``merge_interval``: merge moves (chain 2e)
     every that many sweeps, the sampler's ``merge_interval`` (off by default; ``sampler_kwargs`` may set it too).
     ``stability``: ``info["stability"]`` / ``info["stability_nmi"]``, the mean ARI / NMI over all pairs of reads, computed
-    on the device before the problem closes (metrics.replica_stability restates it on the host's records)."""
+    on the device before the problem closes (metrics.replica_stability restates it on the host's records).
+    ``consensus``: the sampler's ``consensus=True`` -- ``info["pac"]``, ``info["edge_cooccurrence"]`` (per edge of
+    ``info["consensus_edges"]``, the share of reads that keep it inside a cluster), ``info["consensus_labels"]`` (the
+    components of the edges kept by at least half of the reads, in ``sampleset.variables`` order) and
+    ``info["cell_confidence"]``, from the co-association of the reads on the device."""
     from .models import build_modularity_potts, modularity_beta_range
     model = build_modularity_potts(G, resolution, max_clusters)
     # default schedule: 16000 sweeps over modularity_beta_range -- single-site moves over more labels than communities
@@ -272,6 +276,8 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
         kw["merge_interval"] = merge_interval
     if stability:
         kw["stability"] = True
+    if consensus:
+        kw["consensus"] = True
     kw.update(sampler_kwargs or {})
     sampleset = _sampler(sampler).sample_dqm(model, **kw)
     sampleset.info["modularity"] = -np.asarray(sampleset.record["energy"], dtype=np.float64) / model.info["m"]
@@ -282,7 +288,7 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
 
 def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=None,
                                 sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None,
-                                stability: bool = False):
+                                stability: bool = False, consensus: bool = False):
     """:func:`clustering_modularity` at several resolutions -- what Seurat users do with ``FindClusters(...,
     resolution = c(...))`` -- in one upload and one launch (MI355XSampler.sample_dqm_many: one resolution group of
     replicas per value).  Returns one sampleset per resolution, in the order given; each equals what
@@ -292,7 +298,8 @@ def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=
     repeated value and a resolution <= 0 or not finite raise ValueError before any GPU work.  ``merge_interval`` and
     ``stability`` as in :func:`clustering_modularity`; with ``stability`` every sampleset also gets
     ``info["ari_to_previous"]``, the ARI between its best sample and the previous resolution's (None for the first):
-    the clustree view of how the clustering changes from one resolution to the next."""
+    the clustree view of how the clustering changes from one resolution to the next.  ``consensus`` as in
+    :func:`clustering_modularity`: ``info["pac"]`` per resolution then sits beside ``info["stability"]``."""
     from .models import build_modularity_sweep, check_resolutions, modularity_beta_range
     res = check_resolutions(resolutions)
     models = build_modularity_sweep(G, res, max_clusters)
@@ -301,6 +308,8 @@ def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=
         kw["merge_interval"] = merge_interval
     if stability:
         kw["stability"] = True
+    if consensus:
+        kw["consensus"] = True
     kw.update(sampler_kwargs or {})
     samplesets = _sampler(sampler).sample_dqm_many(models, **kw)
     if stability:
@@ -315,6 +324,74 @@ def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=
         if verbose:
             print("Resolution {}: modularity {}".format(gamma, float(np.max(ss.info["modularity"]))))
     return samplesets
+
+
+def consensus_round_seed(seed, t: int):
+    """Seed of round ``t`` of :func:`clustering_consensus`: the caller's seed for round 0 (so that round 0 is the plain
+    seeded call), ``seed + t * 0x9E3779B9`` modulo 2^63 afterwards; None (a fresh random seed per round) stays None."""
+    if seed is None or t == 0:
+        return seed
+    return (int(seed) + t * 0x9E3779B9) % (1 << 63)
+
+
+def consensus_reweight(nodes, eu, ev, share, tau: float):
+    """The next round's graph of :func:`clustering_consensus`: every node of ``nodes``, the edges (nodes[eu], nodes[ev])
+    with ``share >= tau``, weighted by their share; the kept edges' positions come back with it."""
+    from .graphs import EdgeListGraph
+    share = np.asarray(share, dtype=np.float64)
+    keep = np.flatnonzero(share >= tau)
+    return EdgeListGraph(list(nodes), np.asarray(eu)[keep], np.asarray(ev)[keep], share[keep]), keep
+
+
+def clustering_consensus(G, resolution: float = 1.0, max_clusters: int = 16, tau: float = 0.5, max_rounds: int = 5,
+                         sampler=None, sampler_kwargs: Optional[dict] = None, merge_interval: Optional[int] = None,
+                         verbose=False):
+    """Consensus clustering of Lancichinetti and Fortunato (2012) around :func:`clustering_modularity`.  Round 0 is
+    ``clustering_modularity(G, ..., stability=True, consensus=True)``; round t + 1 runs the same call on the graph whose
+    edges are those of round t with ``edge_cooccurrence >= tau``, weighted by that share (the nodes are always all of
+    G's).  The loop stops when every kept edge has share 1.0 and every dropped edge share 0.0 -- all reads agree -- or
+    after ``max_rounds`` rounds.  Returns the last round's sampleset with ``info["consensus_labels"]`` (the components of
+    its kept edges), ``info["consensus_rounds"]``, ``info["consensus_converged"]`` and ``info["consensus_history"]``:
+    per round ``edges`` (the round's graph), ``kept_edges`` (those with share >= tau), ``pac``, ``stability`` (mean
+    pairwise ARI of the reads) and ``modularity``, the modularity of that round's consensus labels on the ORIGINAL graph
+    at ``resolution`` (metrics.modularity).  A ``seed`` in ``sampler_kwargs`` makes the call reproducible: round t runs
+    with :func:`consensus_round_seed`."""
+    from .metrics import modularity
+    if max_rounds < 1:
+        raise ValueError("max_rounds must be at least 1")
+    if not 0.0 < tau <= 1.0:
+        raise ValueError("tau must lie in (0, 1]")
+    base_kw = dict(sampler_kwargs or {})
+    seed = base_kw.get("seed")
+    nodes = list(G.nodes)
+    Gt, history, converged, ss = G, [], False, None
+    for t in range(int(max_rounds)):
+        kw = dict(base_kw)
+        if seed is not None:
+            kw["seed"] = consensus_round_seed(seed, t)
+        ss = clustering_modularity(Gt, resolution, max_clusters, sampler=sampler, sampler_kwargs=kw, verbose=False,
+                                   merge_interval=merge_interval, stability=True, consensus=True)
+        if list(ss.variables) != nodes:
+            raise RuntimeError("the sampler returned the variables in another order than G.nodes")
+        eu, ev = ss.info["consensus_edges"]
+        share = np.asarray(ss.info["edge_cooccurrence"], dtype=np.float64)
+        nxt, keep = consensus_reweight(nodes, eu, ev, share, tau)
+        labels = np.asarray(ss.info["consensus_labels"])
+        history.append({"edges": int(len(share)), "kept_edges": int(len(keep)), "pac": ss.info["pac"],
+                        "stability": ss.info.get("stability"),
+                        "modularity": float(modularity(G, dict(zip(nodes, labels.tolist())), resolution))})
+        if verbose:
+            print("consensus round {}: {}".format(t, history[-1]))
+        dropped = np.ones(len(share), dtype=bool)
+        dropped[keep] = False
+        converged = bool(np.all(share[keep] == 1.0) and np.all(share[dropped] == 0.0))
+        if converged or len(keep) == 0:
+            break
+        Gt = nxt
+    ss.info["consensus_rounds"] = len(history)
+    ss.info["consensus_converged"] = converged
+    ss.info["consensus_history"] = history
+    return ss
 
 
 def clustering_cqm(G, num_of_clusters, min_cluster_size: int = 20, sampler=None,

@@ -1656,6 +1656,26 @@ int mi_sa_problem_label_agreement(mi_sa_problem *p, int groups, double *out_ari,
     });
 }
 
+int mi_sa_problem_coassociation(mi_sa_problem *p, int groups, const uint16_t *ref, int Kref, const int32_t *eu,
+                                const int32_t *ev, int64_t m, int64_t *out_hist, int64_t *out_rowsum, int32_t *out_edge,
+                                int32_t *out_counts, float *out_kernel_ms)
+{
+    if (!p) return fail(MI_EINVAL, "NULL problem");
+    if (const int rc_w = settle(p)) return rc_w;
+    if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_ESTATE, "co-association needs a Potts problem");
+    if (!p->has_run) return fail(MI_ESTATE, "no anneal has been run on this problem");
+    const int G = groups > 0 ? groups : p->ngroups;
+    if (const int rc = mi_coassociation_check(p->last_R, p->n, p->K, G, ref, Kref, eu, ev, m, out_rowsum, out_edge)) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        CoassocArgs a;
+        a.L = static_cast<const uint16_t *>(p->d_states); a.ld = (size_t)p->n;
+        a.R = p->last_R; a.cols = p->n; a.K = p->K; a.groups = G; a.meta = p->d_meta;
+        a.ref = ref; a.Kref = ref ? Kref : 1; a.eu = eu; a.ev = ev; a.m = out_edge ? m : 0;
+        return mi_coassociation_dev(a, p->stream, out_hist, out_rowsum, out_edge, out_counts, out_kernel_ms);
+    });
+}
+
 int mi_sa_best(mi_sa_problem *p, int *out_index, double *out_energy, uint64_t *out_key, void *out_state)
 {
     if (!p) return fail(MI_EINVAL, "NULL problem");

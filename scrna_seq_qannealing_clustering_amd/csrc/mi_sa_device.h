@@ -469,6 +469,24 @@ struct AgreeArgs {
 int mi_label_agreement_dev(const AgreeArgs &a, hipStream_t st, double *out_ari, double *out_nmi, int64_t *out_pair_sum,
                            int32_t *out_tables, float *out_kernel_ms);
 
+// co-association (coassoc_kernels.hip): R labellings as DEVICE uint16 rows of `cols` labels (row stride ld), `groups` groups of
+// consecutive rows; column i is skipped when meta && meta[i] >> 31.  ref (groups x cols), eu, ev (m edges) are HOST arrays,
+// checked by mi_coassociation_check; outputs are HOST pointers (nullable).  Runs on `st`, returns when the results are copied.
+struct CoassocArgs {
+    const uint16_t *L = nullptr;
+    size_t ld = 0;
+    int R = 0, cols = 0, K = 0, groups = 1;
+    const uint32_t *meta = nullptr;
+    const uint16_t *ref = nullptr;
+    int Kref = 1;
+    const int32_t *eu = nullptr, *ev = nullptr;
+    int64_t m = 0;
+};
+int mi_coassociation_check(int R, int n, int K, int groups, const uint16_t *ref, int Kref, const int32_t *eu, const int32_t *ev,
+                           int64_t m, const int64_t *out_rowsum, const int32_t *out_edge);
+int mi_coassociation_dev(const CoassocArgs &a, hipStream_t st, int64_t *out_hist, int64_t *out_rowsum, int32_t *out_edge,
+                         int32_t *out_counts, float *out_kernel_ms);
+
 // Energy of the final state, E = sum_i x_i diag_i + 1/2 sum_{i,j} x_i x_j Q2_ij, with every fp32 matrix
 // entry added EXACTLY once into fp64 accumulators (lane l sums its own columns over all set rows; one
 // wave reduction at the end).  Independent of the cached fp32 fields, so the reported energies carry

@@ -510,6 +510,46 @@ class Problem:
                                                              _ptr(S, C.c_int64), C.byref(ms)))
         return {"ari": ari, "nmi": nmi, "pair_sum": S, "kernel_ms": float(ms.value)}
 
+    def coassociation(self, groups: Optional[int] = None, ref=None, edges=None, matrix: bool = False,
+                      hist: bool = True) -> dict:
+        """Co-association of the last run's replicas inside each group of consecutive replicas (``groups`` None: the
+        problem's own resolution groups), computed on the states in HBM without a host copy: what
+        ``metrics.coassociation(fetch()[0], groups, ref, edges, matrix, hist=hist)`` returns, in the caller's variable order (hole
+        seats are not cells).  ``ref`` labels must lie in [0, 64).  Potts problems only.  Leaves the run untouched."""
+        from .metrics import _coassoc_outputs, _coassoc_result, _edge_arrays
+        if self._last is None:
+            raise RuntimeError("coassociation() before anneal()")
+        R = self._last[0]
+        G = self.groups if groups is None else int(groups)
+        if G < 1 or R % G:
+            raise ValueError("%d replicas do not split into %d equal groups" % (R, G))
+        Rg, n, nd = R // G, self.n, self.n_dev
+        cols = np.arange(n) if self._inv is None else np.asarray(self._inv)
+        dref, Kref = None, None
+        if ref is not None:
+            r = np.asarray(ref)
+            r = np.broadcast_to(r[None, :], (G, r.shape[0])) if r.ndim == 1 else r
+            if r.shape != (G, n) or not np.issubdtype(r.dtype, np.integer) or r.min() < 0 or r.max() >= 64:
+                raise ValueError("ref must be (n,) or (groups, n) integer labels in [0, 64)")
+            Kref = int(r.max()) + 1
+            dref = np.zeros((G, nd), dtype=np.uint16)
+            dref[:, cols] = r
+        eu = ev = None
+        if edges is not None:
+            eu, ev = _edge_arrays(edges, n)
+            eu = np.ascontiguousarray(cols[eu], dtype=np.int32)
+            ev = np.ascontiguousarray(cols[ev], dtype=np.int32)
+        hist, rowsum, edge, counts = _coassoc_outputs(G, Rg, nd, Kref, None if eu is None else len(eu), matrix, hist)
+        ms = C.c_float(0.0)
+        _lib.check(_lib.load().mi_sa_problem_coassociation(
+            self._h, G, _ptr(dref, C.c_uint16), int(Kref or 1), _ptr(eu, C.c_int32), _ptr(ev, C.c_int32),
+            0 if eu is None else len(eu), _ptr(hist, C.c_int64), _ptr(rowsum, C.c_int64), _ptr(edge, C.c_int32),
+            _ptr(counts, C.c_int32), C.byref(ms)))
+        if nd != n or self._inv is not None:             # device columns -> the caller's variables
+            rowsum = None if rowsum is None else np.ascontiguousarray(rowsum[:, cols])
+            counts = None if counts is None else np.ascontiguousarray(counts[:, cols][:, :, cols])
+        return _coassoc_result(G, Rg, hist, rowsum, edge, counts, ms.value)
+
     def launch_count(self) -> int:
         """Kernel launches that served the last anneal (kernel_ms() / launch_count() = mean launch time)."""
         k = C.c_int(0)

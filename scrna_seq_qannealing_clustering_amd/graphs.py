@@ -178,8 +178,11 @@ class EdgeListGraph:
     def number_of_edges(self):
         return len(self._w)
 
-    def edges(self, data=False):
+    def edges(self, data=False, default=None):
         nd = self._nodes
+        if isinstance(data, str):                      # networkx's edges(data="weight"): (u, v, value) triples
+            vals = self._w if data == "weight" else [default] * len(self._w)
+            return ((nd[int(a)], nd[int(b)], float(c) if c is not None else c) for a, b, c in zip(self._eu, self._ev, vals))
         if data:
             return ((nd[int(a)], nd[int(b)], {"weight": float(c)})
                     for a, b, c in zip(self._eu, self._ev, self._w))

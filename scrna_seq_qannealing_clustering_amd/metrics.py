@@ -288,3 +288,173 @@ def replica_stability(sampleset, device: int = 0):
         return None
     r = label_agreement(L, None, device=device)
     return mean_pair_agreement(r["ari"], r["nmi"])[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Consensus of a set of labellings ("reads"): the co-association matrix C[i, j] = number of reads that put cells i and j
+# in one cluster (Monti et al. 2003; Fred and Jain 2005), its distribution (consensus CDF, PAC of Senbabaoglu et al.
+# 2014), a per-cell confidence, and the consensus partition of Lancichinetti and Fortunato 2012 restricted to a graph's
+# edges.  include/mi_metrics.h mi_coassociation_u16, csrc/coassoc_kernels.hip: the matrix is an exact integer product on
+# the i8 matrix cores that is reduced tile by tile and never stored unless asked for.
+# ---------------------------------------------------------------------------------------------------------------------
+def _edge_arrays(edges, n: int):
+    """``edges``: (eu, ev) or an (m, 2) array of cell indices -> two contiguous int32 arrays, checked against [0, n)."""
+    if isinstance(edges, tuple) and len(edges) == 2:
+        eu, ev = np.asarray(edges[0]), np.asarray(edges[1])
+    else:
+        E = np.asarray(edges)
+        if E.ndim != 2 or E.shape[1] != 2:
+            raise ValueError("edges must be (eu, ev) or an (m, 2) array")
+        eu, ev = E[:, 0], E[:, 1]
+    if eu.shape != ev.shape or eu.ndim != 1:
+        raise ValueError("eu and ev must be two 1-D arrays of one length")
+    if len(eu) and (min(eu.min(), ev.min()) < 0 or max(eu.max(), ev.max()) >= n):
+        raise ValueError("edge index outside [0, %d)" % n)
+    return np.ascontiguousarray(eu, dtype=np.int32), np.ascontiguousarray(ev, dtype=np.int32)
+
+
+def _coassoc_outputs(G: int, Rg: int, n: int, Kref, m, matrix: bool, hist: bool = True):
+    hist = np.zeros((G, Rg + 1), dtype=np.int64) if hist else None
+    rowsum = np.zeros((G, n, Kref), dtype=np.int64) if Kref is not None else None
+    edge = np.zeros((G, m), dtype=np.int32) if m is not None else None
+    counts = np.zeros((G, n, n), dtype=np.int32) if matrix else None
+    return hist, rowsum, edge, counts
+
+
+def _coassoc_result(G, Rg, hist, rowsum, edge, counts, ms):
+    one = G == 1
+    pick = (lambda a: None if a is None else (a[0] if one else a))
+    return {"hist": pick(hist), "rowsum": pick(rowsum), "edge_counts": pick(edge), "counts": pick(counts),
+            "reads_per_group": Rg, "kernel_ms": float(ms)}
+
+
+def coassociation(L, groups: int = 1, ref=None, edges=None, matrix: bool = False, device: int = 0,
+                  hist: bool = True) -> dict:
+    """Co-association of the rows of ``L`` ((R, n) labels) inside each of ``groups`` groups of R / groups consecutive
+    rows: ``C[i, j]`` = number of rows of the group with ``L[r, i] == L[r, j]``.  Returns
+      ``hist``         (Rg + 1,) int64: number of pairs i < j with C[i, j] == v (None with ``hist=False``; with only
+                       ``edges`` besides, the dense pass is then skipped and nothing depends on n x n: any n)
+      ``rowsum``       (n, Kref) int64, only with ``ref`` ((n,) or (groups, n) reference labels): sum of C[i, j] over
+                       j != i with ref[j] == c
+      ``edge_counts``  (m,) int32, only with ``edges`` ((eu, ev) or (m, 2)): C[eu, ev]
+      ``counts``       (n, n) int32, only with ``matrix``
+      ``reads_per_group`` and ``kernel_ms``;
+    with ``groups`` > 1 every array has a leading axis of that length.  Labels outside [0, 64) are compacted per
+    labelling as in :func:`label_agreement`."""
+    La, K = _labellings(L, "L")
+    R, n = La.shape
+    G = int(groups)
+    if G < 1 or R % G:
+        raise ValueError("%d labellings do not split into %d equal groups" % (R, G))
+    Rg = R // G
+    Lr, Kref = None, None
+    if ref is not None:
+        Lr, Kref = _labellings(ref, "ref")
+        if Lr.shape[1] != n:
+            raise ValueError("ref labels %d cells, L labels %d" % (Lr.shape[1], n))
+        if Lr.shape[0] == 1 and G > 1:
+            Lr = np.ascontiguousarray(np.repeat(Lr, G, axis=0))
+        if Lr.shape[0] != G:
+            raise ValueError("ref must be (n,) or (groups, n)")
+    eu = ev = None
+    if edges is not None:
+        eu, ev = _edge_arrays(edges, n)
+    hist, rowsum, edge, counts = _coassoc_outputs(G, Rg, n, Kref, None if eu is None else len(eu), matrix, hist)
+    ms = C.c_float(0.0)
+    u16p, i32p, i64p = C.POINTER(C.c_uint16), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    ptr = (lambda a, t: None if a is None else a.ctypes.data_as(t))
+    _lib.check(_lib.load().mi_coassociation_u16(
+        La.ctypes.data_as(u16p), R, n, K, G, ptr(Lr, u16p), int(Kref or 1), ptr(eu, i32p), ptr(ev, i32p),
+        0 if eu is None else len(eu), int(device), ptr(hist, i64p), ptr(rowsum, i64p), ptr(edge, i32p),
+        ptr(counts, i32p), C.byref(ms)))
+    return _coassoc_result(G, Rg, hist, rowsum, edge, counts, ms.value)
+
+
+def consensus_cdf(hist) -> np.ndarray:
+    """Empirical CDF of the consensus index C / Rg over the pairs: entry v = share of pairs with C <= v (v = 0 .. Rg;
+    the last axis of ``hist``).  All zeros where there is no pair."""
+    h = np.asarray(hist, dtype=np.float64)
+    tot = h.sum(axis=-1, keepdims=True)
+    return np.cumsum(h, axis=-1) / np.where(tot > 0, tot, 1.0)
+
+
+def pac(hist, lo: float = 0.1, hi: float = 0.9):
+    """Proportion of ambiguous clustering: the share of pairs with ``lo < C / Rg < hi`` (strict on both sides, compared
+    as integers against ``lo * Rg`` and ``hi * Rg``).  0.0 where there is no pair.  A float, or an array over the
+    leading axes of ``hist``."""
+    h = np.asarray(hist, dtype=np.int64)
+    Rg = h.shape[-1] - 1
+    v = np.arange(Rg + 1, dtype=np.float64)
+    amb = (v > lo * Rg) & (v < hi * Rg)
+    tot = h.sum(axis=-1)
+    out = (h * amb).sum(axis=-1) / np.where(tot > 0, tot, 1)
+    return float(out) if np.ndim(out) == 0 else out
+
+
+def cell_confidence(rowsum, ref, reads: int) -> np.ndarray:
+    """Per cell i the mean consensus index with the other members of its own cluster of ``ref``:
+    ``rowsum[i, ref_i] / (reads * (|cluster(ref_i)| - 1))``; 1.0 for a singleton.  ``ref`` as given to
+    :func:`coassociation` (its labels compacted the same way when outside [0, 64))."""
+    lab = _labellings(ref, "ref")[0][0].astype(np.int64)
+    rs = np.asarray(rowsum)
+    if rs.ndim != 2 or rs.shape[0] != len(lab):
+        raise ValueError("rowsum must be (n, Kref) for the n cells of ref")
+    sizes = np.bincount(lab, minlength=rs.shape[1])
+    own = rs[np.arange(len(lab)), lab].astype(np.float64)
+    den = float(reads) * (sizes[lab] - 1)
+    return np.where(sizes[lab] > 1, own / np.where(den > 0, den, 1.0), 1.0)
+
+
+def consensus_labels(edge_counts, reads: int, eu, ev, n: int, tau: float = 0.5) -> np.ndarray:
+    """Connected components of the edges with ``edge_counts >= tau * reads`` over cells 0 .. n - 1 (host union-find),
+    numbered by their smallest cell in ascending order: the partition the Lancichinetti-Fortunato consensus loop ends in
+    when it converges; before that Fred and Jain's single-link cut at ``tau`` restricted to the graph."""
+    ec, eu, ev = np.asarray(edge_counts), np.asarray(eu), np.asarray(ev)
+    if not (ec.shape == eu.shape == ev.shape) or ec.ndim != 1:
+        raise ValueError("edge_counts, eu and ev must be three 1-D arrays of one length")
+    keep = ec >= tau * reads
+    parent = list(range(int(n)))
+    for a, b in zip(eu[keep].tolist(), ev[keep].tolist()):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        while parent[b] != b:
+            parent[b] = parent[parent[b]]
+            b = parent[b]
+        if a != b:                                   # the smaller cell is the root: a root is its component's minimum
+            if a < b:
+                parent[b] = a
+            else:
+                parent[a] = b
+    root = np.empty(int(n), dtype=np.int64)
+    for i in range(int(n)):
+        root[i] = i if parent[i] == i else root[parent[i]]          # parent[i] < i for every non-root
+    return np.unique(root, return_inverse=True)[1].reshape(-1).astype(np.int64)
+
+
+def confidence_passes(labels):
+    """The reference labellings :func:`cell_confidence_any` needs for ``labels``: per pass ``(ref, inside)``, 63 clusters in
+    order of decreasing size (ties: the smaller label first) under labels 0 .. 62 with every other cell under label 63;
+    ``inside`` marks the cells whose confidence the pass gives.  Singletons (confidence 1.0) need no pass."""
+    uniq, lab = np.unique(np.asarray(labels), return_inverse=True)
+    lab = lab.reshape(-1)
+    sizes = np.bincount(lab, minlength=len(uniq))
+    order = np.argsort(-sizes, kind="stable")
+    rank = np.empty(len(uniq), dtype=np.int64)
+    rank[order] = np.arange(len(uniq))
+    out = []
+    for lo in range(0, int((sizes > 1).sum()), 63):
+        rk = rank[lab] - lo
+        inside = (rk >= 0) & (rk < 63)
+        out.append((np.where(inside, rk, 63).astype(np.int64), inside))
+    return out
+
+
+def cell_confidence_any(rowsum_fn, labels, reads: int) -> np.ndarray:
+    """:func:`cell_confidence` for a labelling with any number of clusters.  ``rowsum_fn(ref)`` returns the (n, Kref) row
+    sums for reference labels in [0, 64); one call per pass of :func:`confidence_passes`."""
+    conf = np.ones(len(np.asarray(labels).reshape(-1)))
+    for ref, inside in confidence_passes(labels):
+        c = cell_confidence(np.asarray(rowsum_fn(ref)), ref, reads)
+        conf[inside] = c[inside]
+    return conf

@@ -32,7 +32,7 @@ from .engine import Problem, energy_dense_f64, layout_block_for
 from .models import (PottsModel, QuboModel, _csr_from_edges, default_beta_range,
                      make_beta_schedule, potts_merge_coefficients, potts_node_weight_groups, potts_node_weights,
                      qubo_dict_to_model)
-from .metrics import mean_pair_agreement
+from .metrics import cell_confidence, confidence_passes, consensus_labels, mean_pair_agreement, pac
 from .sampleset import SampleSet
 
 # keyword arguments of the samplers the reference uses that have no meaning for an annealer on a GPU
@@ -87,7 +87,7 @@ class MI355XSampler:
         "num_reads": [], "num_sweeps": [], "beta_range": [], "beta_schedule_type": [],
         "beta_schedule": [], "num_sweeps_per_beta": [], "seed": [], "initial_states": [],
         "initial_states_generator": [], "resync_interval": [], "kernel": [], "min_cluster_size": [],
-        "merge_interval": [], "merge_proposals": [], "stability": [],
+        "merge_interval": [], "merge_proposals": [], "stability": [], "consensus": [],
         **{k: [] for k in _IGNORED_KWARGS},
     }
     properties = {"category": "software", "beta_schedule_options": ("linear", "geometric", "custom"),
@@ -181,6 +181,7 @@ class MI355XSampler:
         num_reads, init = self._initial_states(kw, m0.variables, kw.get("num_reads"), "DISCRETE")
         if num_reads < 1:
             raise ValueError("'num_reads' should be a positive integer")
+        _check_consensus(kw, m0.num_cases, num_reads)
         ranges = kw.get("beta_range")
         per_model = ranges is not None and np.ndim(ranges) == 2
         if per_model and np.shape(ranges) != (G, 2):
@@ -213,6 +214,7 @@ class MI355XSampler:
             kernel = prob.kernel_name()
             merges = prob.merges_accepted() if merge_interval else None
             agree = prob.label_agreement(G) if kw.get("stability") and num_reads >= 2 else None
+            cons = _consensus_info(prob, G, m0, num_reads) if kw.get("consensus") else None
             t2 = time.perf_counter()
         batch = {"groups": G, "kernel_ms": kernel_ms, "kernel_name": kernel, "accepted": stats["accepted"],
                  "proposals": stats["proposals"], "updates_per_s": (stats["proposals"] / (kernel_ms * 1e-3)) if kernel_ms > 0 else None,
@@ -232,6 +234,8 @@ class MI355XSampler:
             if kw.get("stability"):
                 info["stability"], info["stability_nmi"] = (
                     mean_pair_agreement(agree["ari"][g], agree["nmi"][g]) if agree is not None else (None, None))
+            if cons is not None:
+                info.update(cons[g])
             out.append(SampleSet(labels[rows].astype(np.int32), dev_energy[rows], model.variables, "DISCRETE", info=info))
         return out
 
@@ -346,6 +350,8 @@ class MI355XSampler:
         kw, ignored = self._split_kwargs(dict(kwargs))
         if kw.get("stability"):
             raise ValueError("'stability' (label agreement of the reads) applies to the Potts samplers (sample_dqm)")
+        if kw.get("consensus"):
+            raise ValueError("'consensus' (co-association of the reads) applies to the Potts samplers (sample_dqm)")
         t0 = time.perf_counter()
         n = model.num_variables
         if n == 0:
@@ -422,6 +428,7 @@ class MI355XSampler:
         seed = self._seed(kw.get("seed"))
         num_reads, init = self._initial_states(kw, model.variables, kw.get("num_reads"), "DISCRETE")
         betas, beta_range, stype = self._schedule(kw, lambda: default_potts_beta_range(model))
+        _check_consensus(kw, model.num_cases, num_reads)
         # the CQM's "every cluster has at least m members" (CQM_clustering.py:46-48): a hard constraint on moves
         min_size = int(kw.get("min_cluster_size", model.info.get("min_cluster_size", 0)) or 0)
         if model.node_weight is not None and min_size > 0:
@@ -452,6 +459,7 @@ class MI355XSampler:
             kernel_ms = prob.kernel_ms()
             merges = prob.merges_accepted() if merge_interval else None
             agree = prob.label_agreement(1) if kw.get("stability") and num_reads >= 2 else None
+            cons = _consensus_info(prob, 1, model, num_reads) if kw.get("consensus") else None
             t2 = time.perf_counter()
         energies = dev_energy                    # evaluated on the device in the model's fp64 coefficients
         info = {
@@ -469,7 +477,60 @@ class MI355XSampler:
         if kw.get("stability"):
             info["stability"], info["stability_nmi"] = (
                 mean_pair_agreement(agree["ari"][0], agree["nmi"][0]) if agree is not None else (None, None))
+        if cons is not None:
+            info.update(cons[0])
         return SampleSet(labels.astype(np.int32), energies, model.variables, "DISCRETE", info=info)
+
+
+MAX_CONSENSUS_READS = 8192                 # MI_COASSOC_MAX_READS (include/mi_metrics.h)
+
+
+def model_edges(model):
+    """The model's edges as (eu, ev) index arrays into ``model.variables``: every stored pair once, eu < ev, sorted."""
+    n = model.num_variables
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(np.asarray(model.rowptr, dtype=np.int64)))
+    cols = np.asarray(model.col, dtype=np.int64)
+    keep = rows != cols
+    lo, hi = np.minimum(rows[keep], cols[keep]), np.maximum(rows[keep], cols[keep])
+    key = np.unique(lo * n + hi)
+    return (key // n).astype(np.int32), (key % n).astype(np.int32)
+
+
+def _consensus_info(prob, G: int, model, num_reads: int):
+    """Per resolution group the ``consensus=True`` entries of a sampleset's info, from the states in HBM: the model's own
+    edges, the share of reads that keep each inside a cluster, PAC, the components of the edges kept by at least half
+    of the reads, and every cell's confidence in its component."""
+    eu, ev = model_edges(model)
+    n = model.num_variables
+    first = prob.coassociation(G, edges=(eu, ev))
+    hist = first["hist"].reshape(G, -1)
+    edge = first["edge_counts"].reshape(G, -1)
+    labs = [consensus_labels(edge[g], num_reads, eu, ev, n, 0.5) for g in range(G)]
+    # confidence: one dense pass per 63 non-singleton components, the references of ALL groups in the same call
+    passes = [confidence_passes(labs[g]) for g in range(G)]
+    conf = [np.ones(n) for _ in range(G)]
+    for k in range(max(len(ps) for ps in passes)):
+        refs = np.zeros((G, n), dtype=np.int64)
+        for g in range(G):
+            if k < len(passes[g]):
+                refs[g] = passes[g][k][0]
+        rs = prob.coassociation(G, ref=refs, hist=False)["rowsum"].reshape(G, n, -1)
+        for g in range(G):
+            if k < len(passes[g]):
+                ref, inside = passes[g][k]
+                conf[g][inside] = cell_confidence(rs[g], ref, num_reads)[inside]
+    return [{"pac": pac(hist[g]), "edge_cooccurrence": edge[g].astype(np.float64) / float(num_reads),
+             "consensus_edges": (eu, ev), "consensus_labels": labs[g], "cell_confidence": conf[g]} for g in range(G)]
+
+
+def _check_consensus(kw, num_cases: int, num_reads: int):
+    """``consensus=True`` is refused before any GPU work where the co-association pass could not run after the anneal."""
+    if not kw.get("consensus"):
+        return
+    if num_cases > 64:
+        raise ValueError("'consensus' needs at most 64 cases per variable (got %d)" % num_cases)
+    if num_reads > MAX_CONSENSUS_READS:
+        raise ValueError("'consensus' needs at most %d reads per model (got %d)" % (MAX_CONSENSUS_READS, num_reads))
 
 
 def _make_feasible(labels: np.ndarray, K: int, min_size: int) -> np.ndarray:
