@@ -25,6 +25,12 @@
  * integer product of one-hot matrices on the i8 matrix cores, now with the cells outside and (labelling, label) inside.
  * The matrix is reduced tile by tile into its histogram (consensus CDF, PAC) and per-cell sums per reference cluster;
  * the entries of a graph's edges come from a second kernel that needs nothing of size n x n.
+ *
+ * mi_graph_components answers "which cells hang together": the connected components of one shared graph under a per-item
+ * edge filter, for many items at once -- a read's "same label" filter (the connected pieces of its clusters, the guarantee
+ * of Leiden's refinement step) or a group's "kept by at least half of the reads" mask (the consensus partition).
+ * Min-hooking with pointer jumping, the parent array in LDS; mi_sa_problem_components (mi_sa.h) runs the same on the
+ * states a Potts anneal left in HBM.  DESIGN.md section 5c.
  */
 #ifndef MI_METRICS_H
 #define MI_METRICS_H
@@ -93,6 +99,30 @@ int mi_label_agreement_u16(const uint16_t *A, int Ra, const uint16_t *B, int Rb,
 int mi_coassociation_u16(const uint16_t *L, int R, int n, int K, int groups, const uint16_t *ref, int Kref,
                          const int32_t *eu, const int32_t *ev, int64_t m, int device, int64_t *out_hist,
                          int64_t *out_rowsum, int32_t *out_edge, int32_t *out_counts, float *out_kernel_ms);
+
+#define MI_COMPONENTS_GLOBAL 1u                     /* flags bit 0: the global form (parent array in HBM) at any n */
+#define MI_COMPONENTS_LDS_MAX_CELLS 26624           /* n up to here runs with the parent array in LDS (see below) */
+#define MI_COMPONENTS_MAX_ENTRIES (1ll << 32)       /* B * n (16 GiB of int32 output) */
+
+/* Batched connected components of one undirected graph under a per-item edge filter.  rowptr (n + 1, rowptr[0] = 0,
+ * monotone) and col (rowptr[n] entries in [0, n)): host CSR over n cells; B items.  The stored entry e = (i, col[e]) is live
+ * in item b iff (L == NULL or L[b, i] == L[b, col[e]]) and (keep == NULL or keep[b, e] != 0); L is B x n uint16 (any
+ * values), keep B x rowptr[n] bytes.  An edge connects its ends when it is live in at least one stored direction (storing
+ * one direction only is enough); self loops connect nothing.  Outputs (host, caller-allocated):
+ *   out_labels    B x n int32: the component of every cell, numbered 0 .. C_b - 1 in ascending order of each component's
+ *                 smallest cell (the numbering of metrics.consensus_labels)
+ *   out_count     B int32: C_b
+ *   out_kernel_ms device time of the kernel, or NULL
+ * A pure function of the input: it does not depend on the order in which the atomics land.
+ * LDS plan of the primary form (one workgroup per item): the parent array, 4 B per cell, and the item's label row, 2 B
+ * per cell, read once, beside 320 B of static LDS (the 16 wavefront totals of the final scan, 64 B, and the scratch of the
+ * workgroup-wide "changed" vote); 6 n + 320 bytes <= 160 KB, rounded down to n <= MI_COMPONENTS_LDS_MAX_CELLS = 26 624 (one limit,
+ * with or without labels).  Beyond it, or with MI_COMPONENTS_GLOBAL, the parent array is the item's own row of the output
+ * in HBM (global atomics, one workgroup per item) and the labels are read from L2.
+ * MI_EINVAL for NULL outputs, n < 1, B < 1, unknown flags, rowptr[0] != 0, a non-monotone rowptr, a col outside [0, n);
+ * MI_EUNSUPPORTED for B * n > MI_COMPONENTS_MAX_ENTRIES; all before any device work. */
+int mi_graph_components(const int32_t *rowptr, const int32_t *col, int n, const uint16_t *L, const uint8_t *keep, int B,
+                        int device, uint32_t flags, int32_t *out_labels, int32_t *out_count, float *out_kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -292,6 +292,19 @@ int mi_sa_problem_coassociation(mi_sa_problem *p, int groups, const uint16_t *re
                                 const int32_t *ev, int64_t m, int64_t *out_hist, int64_t *out_rowsum, int32_t *out_edge,
                                 int32_t *out_counts, float *out_kernel_ms);
 
+/* Connected components of every replica's clusters (Potts problems), read in place from HBM: mi_graph_components
+ * (include/mi_metrics.h) over the states of the last mi_sa_anneal -- item r keeps the stored couplings whose two ends carry
+ * one label in replica r -- on the adjacency the problem already holds on the device.  Runs on the problem's stream after
+ * the run has settled.  Cells are the problem's variable indices, the columns mi_sa_fetch returns (n of
+ * mi_sa_problem_info): out_labels is R x n int32, out_count R.  The hole seats of a padded layout are not cells and connect
+ * nothing: their entry of out_labels is -1 and they are in no count.  Components are numbered by their smallest variable
+ * index; a caller that keeps the variables in another order than its own (Problem.components of the Python layer, whose
+ * padded layouts seat the caller's variable i in column seats[i]) renumbers them by the smallest cell of its own order
+ * after gathering the columns: the partition and out_count do not depend on the order, only which id a component gets
+ * does.  Read-only: states, energies and MI_F_CONTINUE are untouched.  MI_ESTATE before a run and
+ * for binary kinds. */
+int mi_sa_problem_components(mi_sa_problem *p, int32_t *out_labels, int32_t *out_count, float *out_kernel_ms);
+
 /* Best replica of the last run (reduced on device): the replica with the lowest fp64 energy (ties: the lowest
  * index) -- its local index, energy, and an order-preserving packed key
  * (sortable(float(E)) << 32) | global_replica_id  suitable for an integer MIN all-reduce across GPUs (RCCL has

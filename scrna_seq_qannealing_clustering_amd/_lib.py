@@ -100,6 +100,8 @@ def _declare(lib):
                                            C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32p, i32p, f32p]),
         "mi_sa_problem_coassociation": (C.c_int, [vp, C.c_int, u16p, C.c_int, i32p, i32p, C.c_int64, C.POINTER(C.c_int64),
                                                   C.POINTER(C.c_int64), i32p, i32p, f32p]),
+        "mi_graph_components": (C.c_int, [i32p, i32p, C.c_int, u16p, u8p, C.c_int, C.c_int, C.c_uint32, i32p, i32p, f32p]),
+        "mi_sa_problem_components": (C.c_int, [vp, i32p, i32p, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
@@ -117,6 +119,7 @@ EXPORTS = (
     "mi_snn_build_f32", "mi_snn_build_ex_f32", "mi_snn_build_rounded_f32", "mi_snn_fetch_codes", "mi_snn_info", "mi_snn_fetch", "mi_snn_kernel_ms", "mi_snn_destroy",
     "mi_jaccard_cluster_stats", "mi_label_agreement_u16", "mi_sa_problem_label_agreement",
     "mi_coassociation_u16", "mi_sa_problem_coassociation",
+    "mi_graph_components", "mi_sa_problem_components",
 )
 
 

@@ -241,10 +241,15 @@ def clustering_bqm_3(G, iteration, dirs, solver, gamma_factor, color, terminate_
 
 
 def clustering_dqm(G, num_of_clusters, gamma, sampler=None, sampler_kwargs: Optional[dict] = None,
-                   verbose=False):
-    """k-way clustering with the reference's DQM (DQM_clustering.py:24-47) solved in Potts form."""
+                   verbose=False, split_disconnected: bool = False):
+    """k-way clustering with the reference's DQM (DQM_clustering.py:24-47) solved in Potts form.
+    ``split_disconnected``: the sampler's ``split_disconnected=True`` (``info["split_labels"]``,
+    ``info["split_num_clusters"]``, ``info["split_energy"]``): a graph with more components than ``num_of_clusters``
+    otherwise gets clusters that are not connected."""
     model = build_dqm_potts(G, num_of_clusters, gamma)                # :29-43
     kw = dict(label='DQM - scRAN-seq')                                # :45
+    if split_disconnected:
+        kw["split_disconnected"] = True
     kw.update(sampler_kwargs or {})
     sampleset = _sampler(sampler).sample_dqm(model, **kw)
     if verbose:
@@ -254,7 +259,7 @@ def clustering_dqm(G, num_of_clusters, gamma, sampler=None, sampler_kwargs: Opti
 
 def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sampler=None,
                           sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None,
-                          stability: bool = False, consensus: bool = False):
+                          stability: bool = False, consensus: bool = False, split_disconnected: bool = False):
     """Weighted modularity at ``resolution`` -- the objective of Seurat's ``FindClusters(..., algorithm = 1)`` that the
     reference's notebooks compare every annealed clustering with -- annealed on the Potts chain with node weights
     (models.build_modularity_potts), at most ``max_clusters`` labels.  Returns the sampleset; ``info["modularity"]``
@@ -266,7 +271,11 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
     ``consensus``: the sampler's ``consensus=True`` -- ``info["pac"]``, ``info["edge_cooccurrence"]`` (per edge of
     ``info["consensus_edges"]``, the share of reads that keep it inside a cluster), ``info["consensus_labels"]`` (the
     components of the edges kept by at least half of the reads, in ``sampleset.variables`` order) and
-    ``info["cell_confidence"]``, from the co-association of the reads on the device."""
+    ``info["cell_confidence"]``, from the co-association of the reads on the device.
+    ``split_disconnected``: the sampler's ``split_disconnected=True`` -- every cluster of every record split into its
+    connected components on the device (``info["split_labels"]``, ``info["split_num_clusters"]``,
+    ``info["split_energy"]``; the records are unchanged), which lifts the ``max_clusters`` cap on the number of
+    communities and can only raise the modularity: ``info["split_modularity"] = -split_energy / m``."""
     from .models import build_modularity_potts, modularity_beta_range
     model = build_modularity_potts(G, resolution, max_clusters)
     # default schedule: 16000 sweeps over modularity_beta_range -- single-site moves over more labels than communities
@@ -278,9 +287,13 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
         kw["stability"] = True
     if consensus:
         kw["consensus"] = True
+    if split_disconnected:
+        kw["split_disconnected"] = True
     kw.update(sampler_kwargs or {})
     sampleset = _sampler(sampler).sample_dqm(model, **kw)
     sampleset.info["modularity"] = -np.asarray(sampleset.record["energy"], dtype=np.float64) / model.info["m"]
+    if "split_energy" in sampleset.info:
+        sampleset.info["split_modularity"] = -np.asarray(sampleset.info["split_energy"], dtype=np.float64) / model.info["m"]
     if verbose:
         print("Modularity: {}\nSolution: {}".format(float(np.max(sampleset.info["modularity"])), sampleset.first.sample))
     return sampleset
@@ -288,7 +301,7 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
 
 def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=None,
                                 sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None,
-                                stability: bool = False, consensus: bool = False):
+                                stability: bool = False, consensus: bool = False, split_disconnected: bool = False):
     """:func:`clustering_modularity` at several resolutions -- what Seurat users do with ``FindClusters(...,
     resolution = c(...))`` -- in one upload and one launch (MI355XSampler.sample_dqm_many: one resolution group of
     replicas per value).  Returns one sampleset per resolution, in the order given; each equals what
@@ -299,7 +312,8 @@ def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=
     ``stability`` as in :func:`clustering_modularity`; with ``stability`` every sampleset also gets
     ``info["ari_to_previous"]``, the ARI between its best sample and the previous resolution's (None for the first):
     the clustree view of how the clustering changes from one resolution to the next.  ``consensus`` as in
-    :func:`clustering_modularity`: ``info["pac"]`` per resolution then sits beside ``info["stability"]``."""
+    :func:`clustering_modularity`: ``info["pac"]`` per resolution then sits beside ``info["stability"]``.
+    ``split_disconnected`` as in :func:`clustering_modularity`, the components of all resolutions from one launch."""
     from .models import build_modularity_sweep, check_resolutions, modularity_beta_range
     res = check_resolutions(resolutions)
     models = build_modularity_sweep(G, res, max_clusters)
@@ -310,6 +324,8 @@ def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=
         kw["stability"] = True
     if consensus:
         kw["consensus"] = True
+    if split_disconnected:
+        kw["split_disconnected"] = True
     kw.update(sampler_kwargs or {})
     samplesets = _sampler(sampler).sample_dqm_many(models, **kw)
     if stability:
@@ -319,6 +335,8 @@ def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=
     for g, (gamma, model, ss) in enumerate(zip(res, models, samplesets)):
         ss.info["resolution"] = gamma
         ss.info["modularity"] = -np.asarray(ss.record["energy"], dtype=np.float64) / model.info["m"]
+        if "split_energy" in ss.info:
+            ss.info["split_modularity"] = -np.asarray(ss.info["split_energy"], dtype=np.float64) / model.info["m"]
         if stability:
             ss.info["ari_to_previous"] = None if g == 0 else float(ari[g - 1, g - 1])
         if verbose:

@@ -1676,6 +1676,22 @@ int mi_sa_problem_coassociation(mi_sa_problem *p, int groups, const uint16_t *re
     });
 }
 
+int mi_sa_problem_components(mi_sa_problem *p, int32_t *out_labels, int32_t *out_count, float *out_kernel_ms)
+{
+    if (!p) return fail(MI_EINVAL, "NULL problem");
+    if (!out_labels || !out_count) return fail(MI_EINVAL, "NULL argument");
+    if (const int rc_w = settle(p)) return rc_w;
+    if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_ESTATE, "components need a Potts problem");
+    if (!p->has_run) return fail(MI_ESTATE, "no anneal has been run on this problem");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        ComponentsArgs a;
+        a.rows = p->d_rows; a.meta = p->d_meta; a.D = p->D; a.n = p->n;
+        a.L = static_cast<const uint16_t *>(p->d_states); a.ldl = (size_t)p->n;
+        return mi_components_dev(a, p->last_R, false, p->stream, out_labels, out_count, out_kernel_ms);
+    });
+}
+
 int mi_sa_best(mi_sa_problem *p, int *out_index, double *out_energy, uint64_t *out_key, void *out_state)
 {
     if (!p) return fail(MI_EINVAL, "NULL problem");

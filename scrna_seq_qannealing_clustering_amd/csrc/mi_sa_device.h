@@ -487,6 +487,24 @@ int mi_coassociation_check(int R, int n, int K, int groups, const uint16_t *ref,
 int mi_coassociation_dev(const CoassocArgs &a, hipStream_t st, int64_t *out_hist, int64_t *out_rowsum, int32_t *out_edge,
                          int32_t *out_counts, float *out_kernel_ms);
 
+// connected components (components_kernels.hip): one graph, B items; all pointers are DEVICE pointers.  The graph is a CSR
+// (rowptr, col; nnz entries) or, when rows != nullptr, the row-major adjacency of a structured problem: row i holds its
+// neighbours in rows[i * D + k].x, k < (meta[i] >> 8) & 0x7fffff, and meta[i] >> 31 marks a hole seat (no cell: id -1, in no
+// count).  L: B rows of n uint16 labels (row stride ldl) or nullptr; keep: B x nnz bytes or nullptr (CSR only).  Outputs
+// are HOST pointers; the kernel runs on `st` and the call returns when the results are copied.
+struct ComponentsArgs {
+    const int32_t *rowptr = nullptr, *col = nullptr;
+    const uint2 *rows = nullptr;
+    const uint32_t *meta = nullptr;
+    int D = 0, n = 0;
+    long long nnz = 0;
+    const uint16_t *L = nullptr;
+    size_t ldl = 0;
+    const uint8_t *keep = nullptr;
+};
+int mi_components_dev(const ComponentsArgs &a, int B, bool force_global, hipStream_t st, int32_t *out_labels,
+                      int32_t *out_count, float *out_kernel_ms);
+
 // Energy of the final state, E = sum_i x_i diag_i + 1/2 sum_{i,j} x_i x_j Q2_ij, with every fp32 matrix
 // entry added EXACTLY once into fp64 accumulators (lane l sums its own columns over all set rows; one
 // wave reduction at the end).  Independent of the cached fp32 fields, so the reported energies carry

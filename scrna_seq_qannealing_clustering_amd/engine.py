@@ -550,6 +550,23 @@ class Problem:
             counts = None if counts is None else np.ascontiguousarray(counts[:, cols][:, :, cols])
         return _coassoc_result(G, Rg, hist, rowsum, edge, counts, ms.value)
 
+    def components(self):
+        """Every cluster of every replica of the last run split into its connected components in the model's graph (the
+        stored couplings), computed on the states and the adjacency in HBM without a host copy: what
+        ``metrics.split_disconnected((rowptr, col), n, fetch()[0])`` returns, ``(labels int32 (R, n), counts (R,))`` in
+        the caller's variable order, numbered by smallest cell (hole seats are not cells).  Potts problems only.  Leaves
+        the run untouched."""
+        from .metrics import renumber_by_first_cell
+        if self._last is None:
+            raise RuntimeError("components() before anneal()")
+        R = self._last[0]
+        out = np.empty((R, self.n_dev), dtype=np.int32)
+        cnt = np.empty(R, dtype=np.int32)
+        _lib.check(_lib.load().mi_sa_problem_components(self._h, _ptr(out, C.c_int32), _ptr(cnt, C.c_int32), None))
+        if self._inv is not None:                        # device columns -> the caller's variables, numbered in their order
+            out = renumber_by_first_cell(np.take(out, self._inv, axis=1))
+        return out, cnt
+
     def launch_count(self) -> int:
         """Kernel launches that served the last anneal (kernel_ms() / launch_count() = mean launch time)."""
         k = C.c_int(0)

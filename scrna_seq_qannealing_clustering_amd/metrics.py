@@ -432,6 +432,111 @@ def consensus_labels(edge_counts, reads: int, eu, ev, n: int, tau: float = 0.5) 
     return np.unique(root, return_inverse=True)[1].reshape(-1).astype(np.int64)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Connected components of one graph under a per-item edge filter, many items at once (include/mi_metrics.h
+# mi_graph_components, csrc/components_kernels.hip): a labelling's "same label" filter splits its clusters into their
+# connected pieces -- the guarantee of Leiden's refinement step (Traag et al. 2019), not Leiden itself -- and a mask over
+# the edges gives the consensus partition of :func:`consensus_labels` for every resolution group in one call.
+# ---------------------------------------------------------------------------------------------------------------------
+COMPONENTS_LDS_MAX_CELLS = 26624           # MI_COMPONENTS_LDS_MAX_CELLS (include/mi_metrics.h)
+
+
+def _graph_csr(edges_or_csr, n: int):
+    """``(rowptr, col)`` (len n + 1 with rowptr[-1] == len(col)) or edges ((eu, ev) / (m, 2)) -> ``(rowptr, col, order)``:
+    int32 CSR and, for edges, the position of every stored entry in the caller's edge list (each edge is stored once,
+    under its first end; None for a CSR)."""
+    n = int(n)
+    if isinstance(edges_or_csr, tuple) and len(edges_or_csr) == 2:
+        a, b = np.asarray(edges_or_csr[0]), np.asarray(edges_or_csr[1])
+        if a.ndim == 1 and b.ndim == 1 and len(a) == n + 1 and int(a[-1]) == len(b):      # (an edge index is < n <= len(b) - 1)
+            return np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(b, dtype=np.int32), None
+    eu, ev = _edge_arrays(edges_or_csr, n)
+    order = np.argsort(eu, kind="stable")
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(eu, minlength=n), out=rowptr[1:])
+    return rowptr.astype(np.int32), np.ascontiguousarray(ev[order]), order
+
+
+def _labels_u16(labels, n: int):
+    """(n,) or (B, n) labels -> (B, n) uint16.  Labels outside [0, 65536) are compacted per labelling (distinct labels
+    renumbered in sorted order), as :func:`_labellings` does for its narrower range."""
+    A = np.asarray(labels)
+    if A.ndim == 1:
+        A = A[None, :]
+    if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] != n:
+        raise ValueError("labels must be (n,) or (B, n) with n = %d (got shape %s)" % (n, np.shape(labels)))
+    if np.issubdtype(A.dtype, np.integer) and A.min() >= 0 and A.max() < 65536:
+        return np.ascontiguousarray(A, dtype=np.uint16)
+    out = np.empty(A.shape, dtype=np.uint16)
+    for r in range(A.shape[0]):
+        uniq, inv = np.unique(A[r], return_inverse=True)
+        if len(uniq) > 65536:
+            raise ValueError("labelling %d has %d distinct labels (at most 65536)" % (r, len(uniq)))
+        out[r] = inv.reshape(-1)
+    return out
+
+
+def connected_components(edges_or_csr, n: int, labels=None, keep=None, device: int = 0, force_global: bool = False):
+    """Connected components of the graph on cells 0 .. n - 1 for a batch of B items.  ``edges_or_csr``: ``(eu, ev)`` /
+    an (m, 2) array (every edge once is enough) or ``(rowptr, col)``.  ``labels`` ((n,) = one item, or (B, n)): item b
+    keeps the edges whose ends carry one label.  ``keep`` ((B, m) or (m,) over the edges, or over the CSR entries):
+    item b keeps the entries with ``keep[b, e] != 0``; an edge stored in both directions connects when either is kept.
+    With neither, B = 1.  Self loops connect nothing.  Returns ``(labels int32 (B, n), counts int32 (B,))``: components
+    numbered 0 .. C_b - 1 by their smallest cell, ascending (the numbering of :func:`consensus_labels`).
+    ``force_global``: the kernel's global form (parent array in HBM), which otherwise serves n >
+    ``COMPONENTS_LDS_MAX_CELLS``."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1 (got %d)" % n)
+    rowptr, col, order = _graph_csr(edges_or_csr, n)
+    nnz = len(col)
+    L = None if labels is None else _labels_u16(labels, n)
+    K = None
+    if keep is not None:
+        K = np.asarray(keep)
+        if K.ndim == 1:
+            K = K[None, :]
+        if K.ndim != 2 or K.shape[1] != nnz:
+            raise ValueError("keep must be (m,) or (B, m) over the %d edges (got shape %s)" % (nnz, np.shape(keep)))
+        K = K != 0
+        if order is not None:
+            K = K[:, order]
+        K = np.ascontiguousarray(K, dtype=np.uint8)
+    if L is not None and K is not None and L.shape[0] != K.shape[0]:
+        raise ValueError("labels give %d items, keep gives %d" % (L.shape[0], K.shape[0]))
+    B = L.shape[0] if L is not None else (K.shape[0] if K is not None else 1)
+    out = np.empty((B, n), dtype=np.int32)
+    cnt = np.empty(B, dtype=np.int32)
+    i32p = C.POINTER(C.c_int32)
+    ptr = (lambda a, t: None if a is None else a.ctypes.data_as(t))
+    _lib.check(_lib.load().mi_graph_components(
+        rowptr.ctypes.data_as(i32p), col.ctypes.data_as(i32p), n, ptr(L, C.POINTER(C.c_uint16)),
+        ptr(K, C.POINTER(C.c_uint8)), int(B), int(device), 1 if force_global else 0, out.ctypes.data_as(i32p),
+        cnt.ctypes.data_as(i32p), None))
+    return out, cnt
+
+
+def split_disconnected(edges_or_csr, n: int, labels, device: int = 0):
+    """Every cluster of every labelling split into its connected components in the graph: ``(refined labels int32 (B, n),
+    cluster counts (B,))``, numbered by smallest cell as :func:`connected_components`.  A refined cluster lies inside one
+    original cluster and is connected; a labelling whose clusters are all connected keeps its partition."""
+    return connected_components(edges_or_csr, n, labels=labels, device=device)
+
+
+def renumber_by_first_cell(labels) -> np.ndarray:
+    """(B, n) non-negative labels -> the same partitions numbered 0, 1, ... in the order their first cell appears."""
+    A = np.asarray(labels)
+    B, n = A.shape
+    width = int(A.max()) + 1
+    flat = (np.arange(B, dtype=np.int64)[:, None] * width + A).reshape(-1)
+    uniq, first, inv = np.unique(flat, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")              # (a flat position grows with the item, then with the cell)
+    rank = np.empty(len(uniq), dtype=np.int64)
+    rank[order] = np.arange(len(uniq))
+    start = np.searchsorted(first[order] // n, np.arange(B))         # rank of every item's first cluster
+    return (rank[inv.reshape(-1)].reshape(B, n) - start[:, None]).astype(np.int32)
+
+
 def confidence_passes(labels):
     """The reference labellings :func:`cell_confidence_any` needs for ``labels``: per pass ``(ref, inside)``, 63 clusters in
     order of decreasing size (ties: the smaller label first) under labels 0 .. 62 with every other cell under label 63;

@@ -371,6 +371,35 @@ class PottsModel:
         return e + self.lin_offset
 
 
+def potts_energies_any(model: PottsModel, L) -> np.ndarray:
+    """``model.energies`` for labellings with ANY integer labels -- more distinct ones than ``num_cases``, as the split of
+    disconnected clusters produces (metrics.split_disconnected) -- in fp64 from the model's own coefficients, one
+    labelling at a time (nothing of size labellings x couplings is built).  ``L``: (n,) or (R, n)."""
+    L = np.asarray(L)
+    if L.ndim == 1:
+        L = L[None, :]
+    n = model.num_variables
+    if L.ndim != 2 or L.shape[1] != n:
+        raise ValueError("L must be (n,) or (R, n) labels with n = %d" % n)
+    rows = np.repeat(np.arange(n), np.diff(model.rowptr))
+    col = np.asarray(model.col)
+    val = np.asarray(model.val, dtype=np.float64)
+    w = None if model.node_weight is None else np.asarray(model.node_weight, dtype=np.float64)
+    sq = 0.0 if w is None else float(np.sum(w * w))
+    out = np.empty(L.shape[0], dtype=np.float64)
+    for r in range(L.shape[0]):
+        lab = np.unique(L[r], return_inverse=True)[1].reshape(-1)
+        e = 0.5 * float(np.sum(val[lab[rows] == lab[col]]))
+        if w is not None:
+            W = np.bincount(lab, weights=w)
+            e += model.c_pair * 0.5 * (float(np.sum(W * W)) - sq)
+        else:
+            cnt = np.bincount(lab).astype(np.float64)
+            e += model.c_pair * 0.5 * float(np.sum(cnt * (cnt - 1.0)))
+        out[r] = e + model.lin_offset
+    return out
+
+
 def build_dqm_potts(G, num_of_clusters: int, gamma: float) -> PottsModel:
     """A4 -- `clustering_dqm` model, DQM_clustering.py:29-43, in Potts form.
 

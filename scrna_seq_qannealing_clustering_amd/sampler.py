@@ -30,10 +30,10 @@ from . import _lib
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
 from .engine import Problem, energy_dense_f64, layout_block_for
 from .models import (PottsModel, QuboModel, _csr_from_edges, default_beta_range,
-                     make_beta_schedule, potts_merge_coefficients, potts_node_weight_groups, potts_node_weights,
-                     qubo_dict_to_model)
-from .metrics import cell_confidence, confidence_passes, consensus_labels, mean_pair_agreement, pac
-from .sampleset import SampleSet
+                     make_beta_schedule, potts_energies_any, potts_merge_coefficients, potts_node_weight_groups,
+                     potts_node_weights, qubo_dict_to_model)
+from .metrics import cell_confidence, confidence_passes, connected_components, mean_pair_agreement, pac
+from .sampleset import SampleSet, _unique_rows
 
 # keyword arguments of the samplers the reference uses that have no meaning for an annealer on a GPU
 _IGNORED_KWARGS = frozenset((
@@ -87,7 +87,7 @@ class MI355XSampler:
         "num_reads": [], "num_sweeps": [], "beta_range": [], "beta_schedule_type": [],
         "beta_schedule": [], "num_sweeps_per_beta": [], "seed": [], "initial_states": [],
         "initial_states_generator": [], "resync_interval": [], "kernel": [], "min_cluster_size": [],
-        "merge_interval": [], "merge_proposals": [], "stability": [], "consensus": [],
+        "merge_interval": [], "merge_proposals": [], "stability": [], "consensus": [], "split_disconnected": [],
         **{k: [] for k in _IGNORED_KWARGS},
     }
     properties = {"category": "software", "beta_schedule_options": ("linear", "geometric", "custom"),
@@ -171,6 +171,7 @@ class MI355XSampler:
         wq, cw, w64, c64, offsets = potts_node_weight_groups(models)
         G = len(models)
         kw, ignored = self._split_kwargs(dict(kwargs))
+        _check_split(kw, int(kw.get("min_cluster_size") or 0), models)
         if kw.get("min_cluster_size"):
             raise ValueError("node weights (a modularity model) together with min_cluster_size are not supported")
         merge_interval, merge_proposals = self._merge_kwargs(kw, 0)
@@ -215,6 +216,7 @@ class MI355XSampler:
             merges = prob.merges_accepted() if merge_interval else None
             agree = prob.label_agreement(G) if kw.get("stability") and num_reads >= 2 else None
             cons = _consensus_info(prob, G, m0, num_reads) if kw.get("consensus") else None
+            comps = prob.components()[0] if kw.get("split_disconnected") else None    # (all groups in one call)
             t2 = time.perf_counter()
         batch = {"groups": G, "kernel_ms": kernel_ms, "kernel_name": kernel, "accepted": stats["accepted"],
                  "proposals": stats["proposals"], "updates_per_s": (stats["proposals"] / (kernel_ms * 1e-3)) if kernel_ms > 0 else None,
@@ -236,6 +238,8 @@ class MI355XSampler:
                     mean_pair_agreement(agree["ari"][g], agree["nmi"][g]) if agree is not None else (None, None))
             if cons is not None:
                 info.update(cons[g])
+            if comps is not None:
+                info.update(_split_info(model, labels[rows], dev_energy[rows], comps[rows]))
             out.append(SampleSet(labels[rows].astype(np.int32), dev_energy[rows], model.variables, "DISCRETE", info=info))
         return out
 
@@ -352,6 +356,8 @@ class MI355XSampler:
             raise ValueError("'stability' (label agreement of the reads) applies to the Potts samplers (sample_dqm)")
         if kw.get("consensus"):
             raise ValueError("'consensus' (co-association of the reads) applies to the Potts samplers (sample_dqm)")
+        if kw.get("split_disconnected"):
+            raise ValueError("'split_disconnected' (connected components of the clusters) applies to the Potts samplers (sample_dqm)")
         t0 = time.perf_counter()
         n = model.num_variables
         if n == 0:
@@ -431,6 +437,7 @@ class MI355XSampler:
         _check_consensus(kw, model.num_cases, num_reads)
         # the CQM's "every cluster has at least m members" (CQM_clustering.py:46-48): a hard constraint on moves
         min_size = int(kw.get("min_cluster_size", model.info.get("min_cluster_size", 0)) or 0)
+        _check_split(kw, min_size, [model])
         if model.node_weight is not None and min_size > 0:
             raise ValueError("node weights (a modularity model) together with min_cluster_size are not supported")
         merge_interval, merge_proposals = self._merge_kwargs(kw, min_size)
@@ -460,6 +467,7 @@ class MI355XSampler:
             merges = prob.merges_accepted() if merge_interval else None
             agree = prob.label_agreement(1) if kw.get("stability") and num_reads >= 2 else None
             cons = _consensus_info(prob, 1, model, num_reads) if kw.get("consensus") else None
+            comps = prob.components()[0] if kw.get("split_disconnected") else None
             t2 = time.perf_counter()
         energies = dev_energy                    # evaluated on the device in the model's fp64 coefficients
         info = {
@@ -479,6 +487,8 @@ class MI355XSampler:
                 mean_pair_agreement(agree["ari"][0], agree["nmi"][0]) if agree is not None else (None, None))
         if cons is not None:
             info.update(cons[0])
+        if comps is not None:
+            info.update(_split_info(model, labels, energies, comps))
         return SampleSet(labels.astype(np.int32), energies, model.variables, "DISCRETE", info=info)
 
 
@@ -505,7 +515,9 @@ def _consensus_info(prob, G: int, model, num_reads: int):
     first = prob.coassociation(G, edges=(eu, ev))
     hist = first["hist"].reshape(G, -1)
     edge = first["edge_counts"].reshape(G, -1)
-    labs = [consensus_labels(edge[g], num_reads, eu, ev, n, 0.5) for g in range(G)]
+    # the components of the edges kept by at least half of the reads, every group in one launch (what
+    # metrics.consensus_labels restates on the host)
+    labs = connected_components((eu, ev), n, keep=edge >= 0.5 * num_reads, device=prob.device)[0].astype(np.int64)
     # confidence: one dense pass per 63 non-singleton components, the references of ALL groups in the same call
     passes = [confidence_passes(labs[g]) for g in range(G)]
     conf = [np.ones(n) for _ in range(G)]
@@ -521,6 +533,33 @@ def _consensus_info(prob, G: int, model, num_reads: int):
                 conf[g][inside] = cell_confidence(rs[g], ref, num_reads)[inside]
     return [{"pac": pac(hist[g]), "edge_cooccurrence": edge[g].astype(np.float64) / float(num_reads),
              "consensus_edges": (eu, ev), "consensus_labels": labs[g], "cell_confidence": conf[g]} for g in range(G)]
+
+
+def _check_split(kw, min_size: int, models):
+    """``split_disconnected=True`` is refused before any GPU work where the split could break a constraint or raise the
+    energy: with a minimum cluster size, and with a negative pair coefficient (the pair terms a split removes must be
+    >= 0 for the refined labelling to be no worse)."""
+    if not kw.get("split_disconnected"):
+        return
+    if min_size > 0:
+        raise ValueError("'split_disconnected' together with min_cluster_size is not supported: a split can leave a "
+                         "cluster below the minimum size")
+    for m in models:
+        if m.c_pair < 0.0:
+            raise ValueError("'split_disconnected' needs a non-negative pair coefficient (got %r): the split of a "
+                             "disconnected cluster could raise the energy" % (m.c_pair,))
+
+
+def _split_info(model, labels, energies, comps):
+    """The ``split_disconnected=True`` entries of a sampleset's info: the reads' refined labellings ``comps`` brought into
+    record order (SampleSet keeps the first read of every distinct sample, sorted by energy, stable), their cluster
+    counts and their energies in the model's fp64 coefficients."""
+    labels, energies = np.asarray(labels), np.asarray(energies, dtype=np.float64)
+    first = _unique_rows(labels)[1] if len(energies) > 1 else np.arange(len(energies))
+    first = np.asarray(first)[np.argsort(energies[first], kind="stable")]
+    split = np.ascontiguousarray(comps[first], dtype=np.int32)
+    return {"split_labels": split, "split_num_clusters": (split.max(axis=1) + 1).astype(np.int64),
+            "split_energy": potts_energies_any(model, split)}
 
 
 def _check_consensus(kw, num_cases: int, num_reads: int):
