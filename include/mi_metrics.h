@@ -31,6 +31,13 @@
  * of Leiden's refinement step) or a group's "kept by at least half of the reads" mask (the consensus partition).
  * Min-hooking with pointer jumping, the parent array in LDS; mi_sa_problem_components (mi_sa.h) runs the same on the
  * states a Potts anneal left in HBM.  DESIGN.md section 5c.
+ *
+ * mi_rank_sum_markers_f32 answers "which genes mark a cluster": the sufficient statistics of the Wilcoxon rank-sum test of
+ * every cluster against all other cells, per gene, for many labellings at once (Seurat's FindAllMarkers with its default
+ * test, the step the reference's assessment notebook runs on the QA labels).  A gene's ranks do not depend on the
+ * labelling: every gene is sorted once (its non-zeros only; the zeros are one tie block of known rank) and scored against
+ * all labellings.  Rank sums, counts and the tie term are exact integers; the p-value, log fold change and AUC are closed
+ * forms of them (metrics.markers_from_stats).  DESIGN.md section 5c.
  */
 #ifndef MI_METRICS_H
 #define MI_METRICS_H
@@ -123,6 +130,42 @@ int mi_coassociation_u16(const uint16_t *L, int R, int n, int K, int groups, con
  * MI_EUNSUPPORTED for B * n > MI_COMPONENTS_MAX_ENTRIES; all before any device work. */
 int mi_graph_components(const int32_t *rowptr, const int32_t *col, int n, const uint16_t *L, const uint8_t *keep, int B,
                         int device, uint32_t flags, int32_t *out_labels, int32_t *out_count, float *out_kernel_ms);
+
+#define MI_MARKERS_SUM_PLAIN 1u                     /* flags bit 0: out_sum adds (double)x (scale.data, counts), not expm1 */
+#define MI_MARKERS_GLOBAL    2u                     /* flags bit 1: every gene is ranked in the HBM form */
+#define MI_MARKERS_LDS_MAX_NONZEROS 8192            /* a gene with at most this many non-zero cells is ranked in LDS */
+#define MI_MARKERS_LABELLING_CHUNK 16               /* labellings scored per pass over a sorted gene */
+#define MI_MARKERS_MAX_CELLS (1 << 20)              /* n: t^3 of a tie group of n cells must fit in int64 */
+#define MI_MARKERS_MAX_ENTRIES (1ll << 28)          /* B * g * K (2 GiB of int64 output) */
+
+/* Batched Wilcoxon rank-sum statistics.  X: n cells x g genes, row-major host array (the layout of cluster_stats), any
+ * finite values (negatives allowed; -0.0 and +0.0 are both zero; values compare as floats).  L: B x n uint16 labellings,
+ * labels in [0, K), K <= 64 (unused labels allowed).  The cells of a gene are ranked 1 .. n in ascending order of x, ties
+ * sharing the mean of their ranks (midranks).  Outputs (host, caller-allocated; all but out_rank2 nullable):
+ *   out_rank2     B x g x K int64: 2 * (sum of the midranks of the cells of cluster c), exact
+ *   out_npos      B x g x K int32: cells of cluster c with x > 0
+ *   out_sum       B x g x K double: sum over the cluster's cells, in ascending cell order, of expm1((double)x), or of
+ *                 (double)x with MI_MARKERS_SUM_PLAIN; one thread per (labelling, gene) adds in that order, so the result
+ *                 is a pure function of the input
+ *   out_tie       g int64: sum over the gene's tie groups (the zeros included) of t^3 - t
+ *   out_kernel_ms device time of the kernels
+ * Three kernels: a tiled transpose of X into gene-major order; the ranking pass, one workgroup per gene (grid-stride):
+ * the gene's non-zeros are compacted as (order-preserving key << 32 | cell) and sorted by a bitonic network, every sorted
+ * position finds its tie run by binary search and stores its doubled midrank (first + last rank of the run; positives lie
+ * behind the zero block, whose doubled midrank is 2 * negatives + zeros + 1), then MI_MARKERS_LABELLING_CHUNK labellings at a
+ * time add it to their clusters with integer LDS atomics (the zero block's share of a cluster is its size minus its
+ * non-zero cells); and the sums, one thread per (labelling, gene) walking the cells.
+ * LDS plan of the ranking pass: 8 B per sorted entry and 4 B per doubled midrank, for the next power of two of the largest
+ * non-zero count served in LDS, and 12 B per (labelling of the chunk, cluster): 12 * 8192 + 12 * 16 * 64 = 110 592 bytes of
+ * the 160 KB at the cap, MI_MARKERS_LDS_MAX_NONZEROS = 8192 (16 384 entries would need 208 896).  A gene with more
+ * non-zeros, or every gene with MI_MARKERS_GLOBAL, runs the same code on its workgroup's slab in HBM (the accumulators stay
+ * in LDS).
+ * MI_EINVAL for NULL X, L or out_rank2, n < 1, g < 1, B < 1, K outside [1, 64], unknown flags, a label >= K, a NaN or an
+ * infinity in X; MI_EUNSUPPORTED for n > MI_MARKERS_MAX_CELLS and for B * g * K > MI_MARKERS_MAX_ENTRIES; all before any
+ * device work. */
+int mi_rank_sum_markers_f32(const float *X, int n, int g, const uint16_t *L, int B, int K, int device, uint32_t flags,
+                            int64_t *out_rank2, int32_t *out_npos, double *out_sum, int64_t *out_tie,
+                            float *out_kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,8 @@ def _declare(lib):
                                                   C.POINTER(C.c_int64), i32p, i32p, f32p]),
         "mi_graph_components": (C.c_int, [i32p, i32p, C.c_int, u16p, u8p, C.c_int, C.c_int, C.c_uint32, i32p, i32p, f32p]),
         "mi_sa_problem_components": (C.c_int, [vp, i32p, i32p, f32p]),
+        "mi_rank_sum_markers_f32": (C.c_int, [f32p, C.c_int, C.c_int, u16p, C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                              C.POINTER(C.c_int64), i32p, f64p, C.POINTER(C.c_int64), f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
@@ -120,6 +122,7 @@ EXPORTS = (
     "mi_jaccard_cluster_stats", "mi_label_agreement_u16", "mi_sa_problem_label_agreement",
     "mi_coassociation_u16", "mi_sa_problem_coassociation",
     "mi_graph_components", "mi_sa_problem_components",
+    "mi_rank_sum_markers_f32",
 )
 
 

@@ -563,3 +563,146 @@ def cell_confidence_any(rowsum_fn, labels, reads: int) -> np.ndarray:
         c = cell_confidence(np.asarray(rowsum_fn(ref)), ref, reads)
         conf[inside] = c[inside]
     return conf
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Marker genes: the Wilcoxon rank-sum test of every cluster against all other cells, per gene (Seurat's FindAllMarkers with
+# its default test), for many labellings in one device call (include/mi_metrics.h mi_rank_sum_markers_f32,
+# csrc/markers_kernels.hip).  A gene's ranks do not depend on the labelling: the device sorts every gene once and returns
+# exact integer rank sums, counts and the tie term; everything reported is a closed form of those, evaluated here in fp64.
+# ---------------------------------------------------------------------------------------------------------------------
+MARKERS_LDS_MAX_NONZEROS = 8192            # MI_MARKERS_LDS_MAX_NONZEROS (include/mi_metrics.h)
+MARKERS_LABELLING_CHUNK = 16               # MI_MARKERS_LABELLING_CHUNK
+MARKERS_SUM_PLAIN, MARKERS_GLOBAL = 1, 2
+
+try:
+    from scipy.special import erfc as _erfc
+except ImportError:                        # the package does not need scipy
+    import math
+    _erfc = np.vectorize(math.erfc, otypes=[np.float64])
+
+
+def rank_sum_pass(X, L, K: int, device: int = 0, plain: bool = False, force_global: bool = False) -> dict:
+    """The device pass.  ``X``: cells x genes, finite; ``L``: (n,) or (B, n) labels in [0, K), K <= 64.  Returns, per
+    (labelling, gene, cluster), ``rank2`` (int64, twice the sum of the cluster's midranks among all n cells), ``npos``
+    (int32, its cells with x > 0) and ``sum`` (fp64, the sum of ``expm1(x)`` over its cells in cell order; of ``x`` with
+    ``plain``); ``tie`` (g,) int64, the sum of t^3 - t over each gene's tie groups; and ``kernel_ms``.
+    ``force_global``: the ranking kernel's HBM form, which otherwise serves genes with more than
+    ``MARKERS_LDS_MAX_NONZEROS`` non-zero cells."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    L = np.asarray(L)
+    if L.ndim == 1:
+        L = L[None, :]
+    if X.ndim != 2 or L.ndim != 2 or L.shape[1] != X.shape[0]:
+        raise ValueError("X must be (n, g) and L (n,) or (B, n) (got %s, %s)" % (X.shape, L.shape))
+    if L.size and (L.min() < 0 or L.max() > 65535):
+        raise ValueError("labels must lie in [0, K)")
+    L = np.ascontiguousarray(L, dtype=np.uint16)
+    (n, g), B, K = X.shape, L.shape[0], int(K)
+    shape = (B, g, max(K, 0))
+    rank2, npos = np.empty(shape, dtype=np.int64), np.empty(shape, dtype=np.int32)
+    sums, tie = np.empty(shape, dtype=np.float64), np.empty(g, dtype=np.int64)
+    ms = C.c_float(0.0)
+    i64p = C.POINTER(C.c_int64)
+    _lib.check(_lib.load().mi_rank_sum_markers_f32(
+        X.ctypes.data_as(C.POINTER(C.c_float)), n, g, L.ctypes.data_as(C.POINTER(C.c_uint16)), B, K, int(device),
+        (MARKERS_SUM_PLAIN if plain else 0) | (MARKERS_GLOBAL if force_global else 0), rank2.ctypes.data_as(i64p),
+        npos.ctypes.data_as(C.POINTER(C.c_int32)), sums.ctypes.data_as(C.POINTER(C.c_double)), tie.ctypes.data_as(i64p),
+        C.byref(ms)))
+    return {"rank2": rank2, "npos": npos, "sum": sums, "tie": tie, "kernel_ms": float(ms.value)}
+
+
+def markers_from_stats(rank2, npos, sums, tie, sizes, n: int, plain: bool = False) -> dict:
+    """Host fp64 closed forms of the rank-sum statistics.  ``rank2``, ``npos``, ``sums``: (..., g, K); ``tie``: (g,);
+    ``sizes``: (..., K) cluster sizes; ``n`` cells.  With n1 the cluster's size and n2 = n - n1, per (..., gene, cluster):
+      ``U``           rank2 / 2 - n1 (n1 + 1) / 2, the Mann-Whitney statistic of the cluster
+      ``p_val``       min(1, erfc(z / sqrt 2)), z = (|U - n1 n2 / 2| - 0.5) / sigma, sigma^2 = n1 n2 / 12 ((n + 1) - tie /
+                      (n (n - 1))): the two-sided normal approximation with tie and continuity corrections (R's
+                      ``wilcox.test(exact = FALSE, correct = TRUE)``, scipy's asymptotic ``mannwhitneyu``); NaN where n1 = 0,
+                      n2 = 0 or sigma = 0
+      ``p_val_adj``   min(1, p_val * g) (Bonferroni over all genes)
+      ``pct_1``, ``pct_2``  share of the cluster's / the other cells with x > 0
+      ``avg_log2FC``  log2(mean1 + 1) - log2(mean2 + 1), the means of ``sums`` inside and outside the cluster
+      ``auc``         U / (n1 n2)
+    and with ``plain`` (``sums`` of scaled data) also ``avg_diff`` = mean1 - mean2."""
+    rank2, npos, sums = np.asarray(rank2, dtype=np.float64), np.asarray(npos, dtype=np.float64), np.asarray(sums, dtype=np.float64)
+    g = rank2.shape[-2]
+    n = int(n)
+    n1 = np.asarray(sizes, dtype=np.float64)[..., None, :]
+    n2 = n - n1
+    tie = np.asarray(tie, dtype=np.float64).reshape(g, 1)
+    U = rank2 / 2.0 - n1 * (n1 + 1.0) / 2.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = n1 * n2 / 12.0 * ((n + 1.0) - tie / (n * (n - 1.0))) if n > 1 else np.zeros_like(U)
+        sigma = np.sqrt(np.maximum(var, 0.0))
+        ok = (n1 > 0) & (n2 > 0) & (sigma > 0)
+        z = (np.abs(U - n1 * n2 / 2.0) - 0.5) / np.where(ok, sigma, 1.0)
+        p = np.where(ok, np.minimum(1.0, _erfc(z / np.sqrt(2.0))), np.nan)
+        pct1 = np.where(n1 > 0, npos / n1, np.nan)
+        pct2 = np.where(n2 > 0, (npos.sum(axis=-1, keepdims=True) - npos) / n2, np.nan)
+        mean1 = np.where(n1 > 0, sums / n1, np.nan)
+        mean2 = np.where(n2 > 0, (sums.sum(axis=-1, keepdims=True) - sums) / n2, np.nan)
+        out = {"U": U, "p_val": p, "p_val_adj": np.minimum(1.0, p * g), "pct_1": pct1, "pct_2": pct2,
+               "avg_log2FC": np.log2(mean1 + 1.0) - np.log2(mean2 + 1.0),
+               "auc": np.where((n1 > 0) & (n2 > 0), U / np.where(n1 * n2 > 0, n1 * n2, 1.0), np.nan)}
+    if plain:
+        out["avg_diff"] = mean1 - mean2
+    return out
+
+
+def markers_passed(stats: dict, only_pos: bool = False, min_pct: float = 0.1, logfc_threshold: float = 0.25) -> np.ndarray:
+    """Seurat's filter on the fields of :func:`markers_from_stats`: ``max(round(pct_1, 3), round(pct_2, 3)) >= min_pct`` and
+    ``avg_log2FC >= logfc_threshold`` (``only_pos``) or ``|avg_log2FC| >= logfc_threshold``.  False where undefined."""
+    fc = stats["avg_log2FC"]
+    with np.errstate(invalid="ignore"):
+        pct = np.fmax(np.round(stats["pct_1"], 3), np.round(stats["pct_2"], 3)) >= min_pct
+        return pct & ((fc if only_pos else np.abs(fc)) >= logfc_threshold)
+
+
+def find_all_markers(X, labels, only_pos: bool = False, min_pct: float = 0.1, logfc_threshold: float = 0.25, genes=None,
+                     device: int = 0, plain: bool = False) -> dict:
+    """Seurat's ``FindAllMarkers`` (Wilcoxon rank-sum, every cluster against all other cells) for one labelling ((n,)) or
+    many ((B, n)) in one device call.  ``X``: cells x genes, log-normalised (``plain``: scaled data or counts, whose mean is
+    the plain mean).  Cluster ids are any values, at most 64 distinct over all labellings.  Returns the fields of
+    :func:`markers_from_stats`, shaped (g, K) or (B, g, K), ``passed`` (:func:`markers_passed`), ``cluster_ids`` (K,),
+    ``cluster_size`` ((K,) or (B, K); a labelling that does not use an id has size 0 and NaN statistics there),
+    ``genes`` (the names, default 0 .. g - 1) and ``kernel_ms``."""
+    X = np.asarray(X)
+    lab = np.asarray(labels)
+    one = lab.ndim == 1
+    if lab.ndim not in (1, 2) or X.ndim != 2 or lab.shape[-1] != X.shape[0]:
+        raise ValueError("labels must be (n,) or (B, n) for the n rows of X")
+    uniq, inv = np.unique(lab, return_inverse=True)
+    if len(uniq) > 64:
+        raise ValueError("%d distinct cluster ids (at most 64)" % len(uniq))
+    L = inv.reshape((1, -1) if one else lab.shape)
+    n, g = X.shape
+    K = len(uniq)
+    genes = np.arange(g) if genes is None else np.asarray(genes)
+    if genes.shape != (g,):
+        raise ValueError("genes must name the %d columns of X" % g)
+    sizes = np.stack([np.bincount(row, minlength=K) for row in L]).astype(np.int64)
+    r = rank_sum_pass(X, L, K, device=device, plain=plain)
+    out = markers_from_stats(r["rank2"], r["npos"], r["sum"], r["tie"], sizes, n, plain=plain)
+    out["passed"] = markers_passed(out, only_pos, min_pct, logfc_threshold)
+    out["cluster_size"] = sizes
+    if one:
+        out = {k: v[0] for k, v in out.items()}
+    out.update(cluster_ids=uniq, genes=genes, kernel_ms=r["kernel_ms"])
+    return out
+
+
+def top_markers(result: dict, n: int = 2, labelling: int = 0) -> dict:
+    """Per cluster id the names of the ``n`` passing genes with the largest ``avg_log2FC`` (ties: the earlier gene), the
+    notebook's ``slice_max(n = 2, order_by = avg_log2FC)``; ``labelling`` picks the row of a (B, n) call."""
+    fc, ok = np.asarray(result["avg_log2FC"]), np.asarray(result["passed"])
+    if fc.ndim == 3:
+        fc, ok = fc[labelling], ok[labelling]
+    elif labelling != 0:
+        raise ValueError("the result holds one labelling")
+    out = {}
+    for k, cid in enumerate(result["cluster_ids"]):
+        idx = np.flatnonzero(ok[:, k])
+        order = idx[np.argsort(-fc[idx, k], kind="stable")]
+        out[cid.item() if hasattr(cid, "item") else cid] = list(np.asarray(result["genes"])[order[:int(n)]])
+    return out
