@@ -1,0 +1,104 @@
+/*
+ * mi_prep.h -- C ABI of the preprocessing front end on MI355X (part of libmi_sa.so): counts -> log-normalised matrix ->
+ * variable-gene statistics -> scaled matrix -> Gram matrix and PCA projection.
+ *
+ * The step BEFORE mi_snn.h.  In the reference it is the first chunk of every data-preparation notebook, in R (Seurat):
+ *     R/pbmc3k/Pbmc3k_normalization_simulated_data.Rmd:81-82,184-185,488-492
+ *         NormalizeData(LogNormalize, 1e4) -> FindVariableFeatures("vst", nfeatures) -> ScaleData -> RunPCA
+ *     R/pbmc3k/Pbmc3k_prepare_data_for_QA_clustering.Rmd:51-52, R/kidney/Kidney_data.Rmd:47-48   the same RunPCA
+ * followed directly by FindNeighbors(dims = 1:dim), which is mi_snn_build_f32.  The passes over the n x g matrix and the
+ * O(n h^2) products run here; the loess curve of `vst` and the h x h eigen-solve stay on the host in fp64
+ * (scrna_seq_qannealing_clustering_amd/preprocess.py).  DESIGN.md section 5c.
+ *
+ * Conventions as in mi_sa.h / mi_snn.h: plain C types, an opaque handle uploaded once, caller-allocated host outputs,
+ * 0 / negative MI_E* return codes, mi_last_error() for the message, every argument check before any device work, and a
+ * nullable `float *out_kernel_ms` (HIP event time of the pass's kernels only) on each pass.
+ *
+ * Layouts and kernels (csrc/prep_kernels.hip):
+ *   X, Y     n cells x g genes, row-major f32 (the layout of mi_jaccard_cluster_stats and mi_rank_sum_markers_f32);
+ *            element index 64-bit everywhere.
+ *   k_prep_normalize    one wavefront per cell: the cell's total in fp64 (lane-strided, then a butterfly: a fixed order),
+ *                       then y = (float) log1p((double) x * scale_factor / total).  No LDS.
+ *   k_prep_col_partial  column reductions: a workgroup is 64 genes x 4 row lanes over a slice of MI_PREP_ROW_SLICE rows
+ *                       (reads coalesce along the genes); the 4 lanes meet in 2 KB + 1 KB of LDS in lane order; one fp64
+ *                       partial per (slice, gene).  k_prep_col_finish adds the slices in ascending order.  The slicing
+ *                       depends on n alone, so every result is a pure function of the input.
+ *   k_prep_select       one thread per element of Z: gathers the chosen columns of Y and scales them.  Z is n x ldz f32 with
+ *                       ldz = h rounded up to 128, the padding columns zero.
+ *   k_prep_gram         G = Z^T Z on v_mfma_f32_32x32x2_f32.  Work unit = (128 x 128 tile of the upper block triangle, chunk
+ *                       of MI_PREP_GRAM_CHUNK cells); workgroup = 2 x 2 wavefronts, 64 x 64 each as 2 x 2 accumulators.  The
+ *                       cells are the k index: 32 cells x 128 features of each of the two column blocks are staged in LDS as
+ *                       [cell][128] floats (2 x 16 KB; lane l reads [k + (l >> 5)][tile + (l & 31)], conflict-free, and
+ *                       Z's rows are already in that order, so no transpose is needed); a diagonal tile stages one block
+ *                       and skips its lower-left wavefront.  The next 32 cells are fetched into registers while the MFMAs
+ *                       of the current ones run.  A unit's f32 tile goes to a workspace;
+ *   k_prep_gram_reduce  adds the chunks' tiles in fp64 in ascending chunk order and writes each entry and its mirror.
+ *                       No floating-point atomics anywhere: two runs are bit-identical, G is exactly symmetric.
+ *   k_prep_project      out = Z V on the same MFMA.  Workgroup = 64 cells x 128 output columns, wavefront w owns columns
+ *                       32 w .. 32 w + 31 with two accumulators (cells 0-31, 32-63); 32 features per step: Z's tile, the
+ *                       transposed operand (lane l needs Z[cell l & 31][k + (l >> 5)]), sits in LDS as [cell][33] floats
+ *                       (odd stride: the 32 cells of a half-wave fall in 32 different banks), V's as [k][128]; 8.25 + 16 KB.
+ *                       f32 accumulation over all h in feature order.
+ */
+#ifndef MI_PREP_H
+#define MI_PREP_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct mi_prep_matrix mi_prep_matrix;
+
+#define MI_PREP_MAX_CELLS    (1 << 23)      /* n: the row slices of the column reductions are one grid dimension */
+#define MI_PREP_MAX_ENTRIES  (1ll << 32)    /* n * g (16 GiB of f32 per matrix; counts and normalised are both resident) */
+#define MI_PREP_MAX_FEATURES 4096           /* h of mi_prep_select (G: 128 MiB of fp64) */
+#define MI_PREP_MAX_PCS      128            /* p of mi_prep_project */
+#define MI_PREP_ROW_SLICE    256            /* rows per partial sum of the column reductions */
+#define MI_PREP_GRAM_CHUNK   512            /* cells whose products accumulate in f32 before the fp64 sum over chunks */
+
+/* X: n x g row-major counts (any non-negative finite values).  Uploads X to `device`.  MI_EINVAL for NULL arguments,
+ * n < 2, g < 1, a NaN, an infinity or a negative value; MI_EUNSUPPORTED for n > MI_PREP_MAX_CELLS or
+ * n * g > MI_PREP_MAX_ENTRIES. */
+int mi_prep_create_f32(const float *X, int n, int g, int device, mi_prep_matrix **out);
+int mi_prep_destroy(mi_prep_matrix *m);
+
+/* Seurat's LogNormalize: per-cell totals in fp64, y = (float) log1p((double) x * scale_factor / total), kept as a second
+ * device-resident matrix (a second call replaces it).  A cell whose total is 0 keeps all zeros (Seurat divides by the
+ * zero total and returns NaN for that cell).  MI_EINVAL unless scale_factor is finite and > 0. */
+int mi_prep_normalize(mi_prep_matrix *m, double scale_factor, float *out_kernel_ms);
+/* out: n x g.  MI_ESTATE before mi_prep_normalize. */
+int mi_prep_fetch_normalized(mi_prep_matrix *m, float *out);
+
+/* which: 0 = counts, 1 = normalised matrix (MI_ESTATE before mi_prep_normalize).  Per gene, in fp64, two passes: mean =
+ * (sum of x) / n, then var = (sum of (x - mean)^2) / (n - 1); nnz = cells with x != 0.  Outputs: g entries each, nullable. */
+int mi_prep_gene_stats(mi_prep_matrix *m, int which, double *mean, double *var, int32_t *nnz, float *out_kernel_ms);
+
+/* The second pass of Seurat's `vst`, on the counts: out[j] = sum_i min((x_ij - mean_j) / sd_j, clip)^2 / (n - 1) in fp64,
+ * 0 where sd_j == 0.  mean, sd, out: g entries.  MI_EINVAL for a non-finite mean, a negative or non-finite sd, a NaN clip. */
+int mi_prep_clipped_variance(mi_prep_matrix *m, const double *mean, const double *sd, double clip, double *out,
+                             float *out_kernel_ms);
+
+/* Gathers the h chosen columns of the normalised matrix (any order; MI_EINVAL for an index outside [0, g) or a repeated
+ * one, h < 1, a non-finite mu, a negative or non-finite sigma, clip NaN or <= 0) and materialises the scaled matrix once:
+ *     z = fminf((y - (float) mu) * (float) (1.0 / sigma), (float) clip),     z = 0 where sigma == 0
+ * (separate f32 subtract and multiply, no contraction).  mu, sigma: h entries, in the order of `genes`.  MI_EUNSUPPORTED
+ * for h > MI_PREP_MAX_FEATURES; MI_ESTATE before mi_prep_normalize.  mi_prep_fetch_scaled (out: n x h), mi_prep_gram and
+ * mi_prep_project all read this one Z: what the products consume is bit for bit what the caller can fetch. */
+int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double *mu, const double *sigma, double clip,
+                   float *out_kernel_ms);
+int mi_prep_fetch_scaled(mi_prep_matrix *m, float *out);
+
+/* out_G: h x h fp64, G = Z^T Z (not divided by n - 1).  Every entry is the fp64 sum, in chunk order, of the f32 fmaf chains
+ * over the cells of each chunk of MI_PREP_GRAM_CHUNK cells.  MI_ESTATE before mi_prep_select. */
+int mi_prep_gram(mi_prep_matrix *m, double *out_G, float *out_kernel_ms);
+
+/* out = Z V: V is h x p row-major f32 (finite), out n x p; every entry one f32 fmaf chain over the h features in order.
+ * MI_EINVAL for p < 1, MI_EUNSUPPORTED for p > MI_PREP_MAX_PCS, MI_ESTATE before mi_prep_select. */
+int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float *out_kernel_ms);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MI_PREP_H */

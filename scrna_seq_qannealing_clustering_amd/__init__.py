@@ -9,6 +9,7 @@ Public surface:
     clustering_bqm, clustering_bqm_2, clustering_bqm_3, clustering_dqm  reference-shaped drivers
     clustering_modularity    weighted modularity at a resolution (Seurat's FindClusters objective)
     clustering_modularity_sweep  the same at several resolutions in one GPU launch
+    preprocess               counts -> log-normalised matrix -> variable genes -> scaled matrix -> PCA coordinates (module)
 """
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
 from .models import (PottsModel, QuboModel, add_size_window_penalty, build_bqm2_qubo,
@@ -20,7 +21,7 @@ __all__ = [
     "MI355XSampler", "SampleSet", "QuboModel", "PottsModel", "BinaryQuadraticModel",
     "DiscreteQuadraticModel", "build_bqm_qubo", "build_bqm2_qubo", "build_bqm3_cut_qubo",
     "build_dqm_potts", "add_size_window_penalty", "default_beta_range", "make_beta_schedule",
-    "qubo_dict_to_model",
+    "qubo_dict_to_model", "preprocess",
 ]
 
 
@@ -34,4 +35,7 @@ def __getattr__(name):
                 "clustering_modularity_sweep"):
         from . import clustering
         return getattr(clustering, name)
+    if name == "preprocess":
+        import importlib
+        return importlib.import_module(".preprocess", __name__)
     raise AttributeError(name)

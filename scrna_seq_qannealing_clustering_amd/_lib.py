@@ -104,6 +104,17 @@ def _declare(lib):
         "mi_sa_problem_components": (C.c_int, [vp, i32p, i32p, f32p]),
         "mi_rank_sum_markers_f32": (C.c_int, [f32p, C.c_int, C.c_int, u16p, C.c_int, C.c_int, C.c_int, C.c_uint32,
                                               C.POINTER(C.c_int64), i32p, f64p, C.POINTER(C.c_int64), f32p]),
+        # include/mi_prep.h
+        "mi_prep_create_f32": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, pp]),
+        "mi_prep_destroy": (C.c_int, [vp]),
+        "mi_prep_normalize": (C.c_int, [vp, C.c_double, f32p]),
+        "mi_prep_fetch_normalized": (C.c_int, [vp, f32p]),
+        "mi_prep_gene_stats": (C.c_int, [vp, C.c_int, f64p, f64p, i32p, f32p]),
+        "mi_prep_clipped_variance": (C.c_int, [vp, f64p, f64p, C.c_double, f64p, f32p]),
+        "mi_prep_select": (C.c_int, [vp, i32p, C.c_int, f64p, f64p, C.c_double, f32p]),
+        "mi_prep_fetch_scaled": (C.c_int, [vp, f32p]),
+        "mi_prep_gram": (C.c_int, [vp, f64p, f32p]),
+        "mi_prep_project": (C.c_int, [vp, f32p, C.c_int, f32p, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
@@ -123,6 +134,8 @@ EXPORTS = (
     "mi_coassociation_u16", "mi_sa_problem_coassociation",
     "mi_graph_components", "mi_sa_problem_components",
     "mi_rank_sum_markers_f32",
+    "mi_prep_create_f32", "mi_prep_destroy", "mi_prep_normalize", "mi_prep_fetch_normalized", "mi_prep_gene_stats",
+    "mi_prep_clipped_variance", "mi_prep_select", "mi_prep_fetch_scaled", "mi_prep_gram", "mi_prep_project",
 )
 
 

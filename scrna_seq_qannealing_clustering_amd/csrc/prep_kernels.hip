@@ -1,0 +1,620 @@
+// prep_kernels.hip -- counts -> log-normalised matrix -> gene statistics -> scaled matrix -> Gram matrix / projection (gfx950).
+// C ABI, layouts and LDS plans: include/mi_prep.h; the loess curve and the eigen-solve are host fp64 in preprocess.py.
+//
+//   k_prep_normalize     one wavefront per cell: fp64 total, then y = (float) log1p((double) x * scale / total).
+//   k_prep_col_partial   per-gene reductions over a slice of kRowSlice rows, 64 genes x 4 row lanes per workgroup:
+//                        SUM (sum and non-zero count), CENTRED (squares about a given mean), CLIPPED (vst's clipped
+//                        standardised squares); k_prep_col_finish adds the slices in ascending order and divides.
+//   k_prep_select        z = fminf((y - mu) * inv, clip) for the chosen columns, into Z (n x ldz, zero padded columns).
+//   k_prep_gram          one (upper-triangle 128 x 128 tile, chunk of kChunk cells) per workgroup on the f32-input MFMA,
+//                        f32 tile out; k_prep_gram_reduce adds the chunks in fp64 in chunk order and mirrors.
+//   k_prep_project       out = Z V, 64 cells x 128 columns per workgroup on the same MFMA.
+// Operand maps of v_mfma_f32_32x32x2_f32 as in energy_kernels.hip: A: lane l holds A[i = l & 31][k = l >> 5]; B: lane l
+// holds B[k = l >> 5][j = l & 31]; C/D: register q of lane l is C[row = (q & 3) + 8 (q >> 2) + 4 (l >> 5)][col = l & 31].
+// No floating-point atomics; stores are ordinary vector stores.
+#include <vector>
+
+#include "../../include/mi_prep.h"
+#include "mi_sa_device.h"
+
+namespace mi_sa_impl {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kRowSlice = MI_PREP_ROW_SLICE;
+constexpr int kChunk = MI_PREP_GRAM_CHUNK;
+constexpr int kTile = 128, kKC = 32;
+constexpr int kProjCells = 64, kProjCols = MI_PREP_MAX_PCS;
+constexpr size_t kGramWorkspace = (size_t)256 << 20;                    // bytes of f32 tiles in flight between the two Gram kernels
+enum { kColSum = 0, kColCentred = 1, kColClipped = 2 };
+
+__global__ void __launch_bounds__(256) k_prep_normalize(const float *__restrict__ X, float *__restrict__ Y, int n, int g,
+                                                        double scale)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (size_t)n) return;
+    const float *x = X + row * g;
+    float *y = Y + row * g;
+    double t = 0.0;
+    for (int j = lane; j < g; j += 64) t += (double)x[j];
+    t = wave_sum_f64(t);
+    for (int j = lane; j < g; j += 64) y[j] = t > 0.0 ? (float)log1p((double)x[j] * scale / t) : 0.0f;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_prep_col_partial(const float *__restrict__ M, int n, int g,
+                                                          const double *__restrict__ mean, const double *__restrict__ sd,
+                                                          double clip, double *__restrict__ psum, int32_t *__restrict__ pnnz)
+{
+    __shared__ double s_sum[4][64];
+    __shared__ int32_t s_cnt[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int j = blockIdx.x * 64 + tx;
+    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
+    double acc = 0.0;
+    int32_t cnt = 0;
+    if (j < g) {
+        const double mj = MODE == kColSum ? 0.0 : mean[j], sj = MODE == kColClipped ? sd[j] : 1.0;
+        for (int r = r0 + ty; r < r1; r += 4) {
+            const float v = M[(size_t)r * g + j];
+            if (MODE == kColSum) {
+                acc += (double)v;
+                cnt += v != 0.0f;
+            } else if (MODE == kColCentred) {
+                const double d = (double)v - mj;
+                acc += d * d;
+            } else if (sj != 0.0) {
+                double d = ((double)v - mj) / sj;
+                d = d < clip ? d : clip;
+                acc += d * d;
+            }
+        }
+    }
+    s_sum[ty][tx] = acc;
+    s_cnt[ty][tx] = cnt;
+    __syncthreads();
+    if (ty == 0 && j < g) {
+        const size_t o = (size_t)blockIdx.y * g + j;
+        psum[o] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
+        if (MODE == kColSum) pnnz[o] = s_cnt[0][tx] + s_cnt[1][tx] + s_cnt[2][tx] + s_cnt[3][tx];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_prep_col_finish(const double *__restrict__ psum, const int32_t *__restrict__ pnnz,
+                                                         int slices, int g, double denom, double *__restrict__ out,
+                                                         int32_t *__restrict__ out_nnz)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= g) return;
+    double t = 0.0;
+    int32_t c = 0;
+    for (int s = 0; s < slices; ++s) {
+        t += psum[(size_t)s * g + j];
+        if (pnnz) c += pnnz[(size_t)s * g + j];
+    }
+    out[j] = t / denom;
+    if (pnnz) out_nnz[j] = c;
+}
+
+__global__ void __launch_bounds__(256) k_prep_select(const float *__restrict__ Y, int n, int g, const int32_t *__restrict__ genes,
+                                                     int h, int ldz, const float *__restrict__ mu, const float *__restrict__ inv,
+                                                     const uint8_t *__restrict__ flat, float clip, float *__restrict__ Z)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const size_t row = blockIdx.y;
+    if (c >= ldz) return;
+    float z = 0.0f;
+    if (c < h && !flat[c]) {
+        const float d = Y[row * g + genes[c]] - mu[c];
+        z = fminf(d * inv[c], clip);
+    }
+    Z[row * ldz + c] = z;
+}
+
+// tile s of the row-major list of the upper block triangle: row I holds the tiles J = I .. T - 1
+__device__ __forceinline__ void tile_of(int s, int T, int &I, int &J)
+{
+    I = 0;
+    while (s >= T - I) {
+        s -= T - I;
+        ++I;
+    }
+    J = I + s;
+}
+
+__global__ void __launch_bounds__(256, 2) k_prep_gram(const float *__restrict__ Z, int ldz, int n, int T, int chunk0,
+                                                      float *__restrict__ P)
+{
+    __shared__ __attribute__((aligned(16))) float As[kKC][kTile];
+    __shared__ __attribute__((aligned(16))) float Bs[kKC][kTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int I, J;
+    tile_of((int)blockIdx.x, T, I, J);
+    const bool diag = I == J;
+    const int c0 = (chunk0 + (int)blockIdx.y) * kChunk, c1 = c0 + kChunk < n ? c0 + kChunk : n;
+    const int steps = (c1 - c0 + kKC - 1) / kKC;
+    const int wi = (wave & 1) * 64, wj = (wave >> 1) * 64;         // this wavefront's 64 x 64 corner: rows (block I), columns (block J)
+    const bool idle = diag && wi > wj;                            // the lower-left corner of a diagonal tile is its mirror's
+    const int half = lane >> 5, col = lane & 31;
+    const int kk = tid >> 5, c4 = (tid & 31) * 4;
+    const float *za = Z + (size_t)I * kTile + c4, *zb = Z + (size_t)J * kTile + c4;
+
+    f32x4 ra[4], rb[4];
+    auto gload = [&](int step) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int cell = c0 + step * kKC + kk + 8 * q;
+            ra[q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            rb[q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            if (cell < c1) {
+                ra[q] = *reinterpret_cast<const f32x4 *>(za + (size_t)cell * ldz);
+                if (!diag) rb[q] = *reinterpret_cast<const f32x4 *>(zb + (size_t)cell * ldz);
+            }
+        }
+    };
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = f32x16{0};
+    const float(*Bp)[kTile] = diag ? As : Bs;
+
+    gload(0);
+    for (int step = 0; step < steps; ++step) {
+        __syncthreads();                                          // the MFMAs of the step before have read their operands
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            *reinterpret_cast<f32x4 *>(&As[kk + 8 * q][c4]) = ra[q];
+            if (!diag) *reinterpret_cast<f32x4 *>(&Bs[kk + 8 * q][c4]) = rb[q];
+        }
+        __syncthreads();
+        if (step + 1 < steps) gload(step + 1);                    // in flight under the MFMAs below
+        if (idle) continue;
+#pragma unroll
+        for (int j = 0; j < kKC / 2; ++j) {
+            const float a0 = As[2 * j + half][wi + col], a1 = As[2 * j + half][wi + 32 + col];
+            const float b0 = Bp[2 * j + half][wj + col], b1 = Bp[2 * j + half][wj + 32 + col];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    if (idle) return;
+    float *tile = P + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (kTile * kTile);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int row = wi + 32 * a + (q & 3) + 8 * (q >> 2) + 4 * half;
+                tile[row * kTile + wj + 32 * b + col] = acc[a][b][q];
+            }
+}
+
+// G (T * 128 square, fp64) += the `nb` chunk tiles of every upper-triangle tile, chunk after chunk; entry and mirror get one value
+__global__ void __launch_bounds__(256) k_prep_gram_reduce(const float *__restrict__ P, int tiles, int nb, int T,
+                                                          double *__restrict__ G)
+{
+    int I, J;
+    tile_of((int)blockIdx.x, T, I, J);
+    const size_t ldg = (size_t)T * kTile;
+    for (int e = threadIdx.x; e < kTile * kTile; e += 256) {
+        const int r = e >> 7, c = e & (kTile - 1);
+        if (I == J && r > c) continue;
+        const size_t gr = (size_t)I * kTile + r, gc = (size_t)J * kTile + c;
+        double t = G[gr * ldg + gc];
+        for (int b = 0; b < nb; ++b) t += (double)P[((size_t)b * tiles + blockIdx.x) * (kTile * kTile) + e];
+        G[gr * ldg + gc] = t;
+        G[gc * ldg + gr] = t;
+    }
+}
+
+// V: ldz x 128, zero padded both ways; hk = h rounded up to kKC (<= ldz)
+__global__ void __launch_bounds__(256) k_prep_project(const float *__restrict__ Z, int ldz, int n, int hk,
+                                                      const float *__restrict__ V, int p, float *__restrict__ out)
+{
+    __shared__ float Zs[kProjCells][kKC + 1];
+    __shared__ __attribute__((aligned(16))) float Vs[kKC][kProjCols];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int half = lane >> 5, col = lane & 31;
+    const int cell0 = (int)blockIdx.x * kProjCells;
+    const bool idle = wave * 32 >= p;                             // a column block past p
+    const int steps = hk / kKC;
+
+    f32x4 rz[2], rv[4];
+    auto gload = [&](int step) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int e = tid + 256 * q, cell = cell0 + (e >> 3);
+            rz[q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            if (cell < n) rz[q] = *reinterpret_cast<const f32x4 *>(Z + (size_t)cell * ldz + step * kKC + (e & 7) * 4);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + 256 * q;
+            rv[q] = *reinterpret_cast<const f32x4 *>(V + (size_t)(step * kKC + (e >> 5)) * kProjCols + (e & 31) * 4);
+        }
+    };
+    f32x16 acc[2] = {f32x16{0}, f32x16{0}};
+
+    gload(0);
+    for (int step = 0; step < steps; ++step) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int e = tid + 256 * q;
+            float *d = &Zs[e >> 3][(e & 7) * 4];
+            d[0] = rz[q].x; d[1] = rz[q].y; d[2] = rz[q].z; d[3] = rz[q].w;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + 256 * q;
+            *reinterpret_cast<f32x4 *>(&Vs[e >> 5][(e & 31) * 4]) = rv[q];
+        }
+        __syncthreads();
+        if (step + 1 < steps) gload(step + 1);
+        if (idle) continue;
+#pragma unroll
+        for (int j = 0; j < kKC / 2; ++j) {
+            const int k = 2 * j + half;
+            const float a0 = Zs[col][k], a1 = Zs[32 + col][k], b = Vs[k][wave * 32 + col];
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, acc[1], 0, 0, 0);
+        }
+    }
+    const int c = wave * 32 + col;
+    if (idle || c >= p) return;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int cell = cell0 + 32 * a + (q & 3) + 8 * (q >> 2) + 4 * half;
+            if (cell < n) out[(size_t)cell * p + c] = acc[a][q];
+        }
+}
+
+struct Timer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Timer()
+    {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    int start()
+    {
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, 0));
+        return MI_OK;
+    }
+    int stop(float *out_ms)
+    {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(e1, 0));
+        HIP_TRY(hipEventSynchronize(e1));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        if (out_ms) *out_ms = ms;
+        return MI_OK;
+    }
+};
+
+struct DevBufs {                                                  // scratch of one call, freed on every way out
+    std::vector<void *> p;
+    ~DevBufs()
+    {
+        for (void *b : p)
+            if (b) (void)hipFree(b);
+    }
+    template <typename T>
+    hipError_t alloc(T **out, size_t count)
+    {
+        void *b = nullptr;
+        const hipError_t e = hipMalloc(&b, (count ? count : 1) * sizeof(T));
+        if (e == hipSuccess) p.push_back(b);
+        *out = static_cast<T *>(b);
+        return e;
+    }
+};
+
+}  // namespace
+}  // namespace mi_sa_impl
+using namespace mi_sa_impl;
+
+struct mi_prep_matrix {
+    int n = 0, g = 0, device = 0, h = 0, ldz = 0;
+    bool normalized = false;
+    float *d_X = nullptr, *d_Y = nullptr, *d_Z = nullptr;
+};
+
+#define TRY(expr)                   \
+    do {                            \
+        const int rc_ = (expr);     \
+        if (rc_ != MI_OK) return rc_; \
+    } while (0)
+
+namespace {
+
+// one column reduction over M: partials per slice, then the ordered sum divided by denom (device pointers in and out)
+template <int MODE>
+int col_reduce(const mi_prep_matrix *m, const float *M, const double *d_mean, const double *d_sd, double clip, double denom,
+               double *d_psum, int32_t *d_pnnz, double *d_out, int32_t *d_out_nnz)
+{
+    const int slices = (m->n + kRowSlice - 1) / kRowSlice;
+    hipLaunchKernelGGL(k_prep_col_partial<MODE>, dim3((unsigned)((m->g + 63) / 64), (unsigned)slices), dim3(256), 0, 0, M, m->n,
+                       m->g, d_mean, d_sd, clip, d_psum, d_pnnz);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_prep_col_finish, dim3((unsigned)((m->g + 255) / 256)), dim3(256), 0, 0, d_psum,
+                       MODE == kColSum ? d_pnnz : nullptr, slices, m->g, denom, d_out, d_out_nnz);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_prep_destroy(mi_prep_matrix *m)
+{
+    if (!m) return MI_OK;
+    (void)hipSetDevice(m->device);
+    void *bufs[] = {m->d_X, m->d_Y, m->d_Z};
+    for (void *b : bufs)
+        if (b) (void)hipFree(b);
+    delete m;
+    return MI_OK;
+}
+
+int mi_prep_create_f32(const float *X, int n, int g, int device, mi_prep_matrix **out)
+{
+    if (out) *out = nullptr;
+    if (!X || !out) return fail(MI_EINVAL, "NULL argument");
+    if (n < 2) return fail(MI_EINVAL, "n must be >= 2 (got %d)", n);
+    if (g < 1) return fail(MI_EINVAL, "g must be >= 1 (got %d)", g);
+    if (n > MI_PREP_MAX_CELLS) return fail(MI_EUNSUPPORTED, "%d cells exceed %d", n, MI_PREP_MAX_CELLS);
+    if ((long long)n * g > MI_PREP_MAX_ENTRIES)
+        return fail(MI_EUNSUPPORTED, "%d x %d entries exceed %lld", n, g, (long long)MI_PREP_MAX_ENTRIES);
+    const size_t cells = (size_t)n * g;
+    for (size_t e = 0; e < cells; ++e)
+        if (!(X[e] >= 0.0f) || std::isinf(X[e]))
+            return fail(MI_EINVAL, "X[%lld, %lld] is NaN, infinite or negative", (long long)(e / g), (long long)(e % g));
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
+    if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
+    HIP_TRY(hipSetDevice(device));
+    mi_prep_matrix *m = new (std::nothrow) mi_prep_matrix();
+    if (!m) return fail(MI_ENOMEM, "out of host memory");
+    m->n = n; m->g = g; m->device = device;
+    const int rc = [&]() -> int {
+        HIP_TRY(hipMalloc((void **)&m->d_X, cells * sizeof(float)));
+        HIP_TRY(hipMemcpy(m->d_X, X, cells * sizeof(float), hipMemcpyHostToDevice));
+        return MI_OK;
+    }();
+    if (rc != MI_OK) {
+        mi_prep_destroy(m);
+        return rc;
+    }
+    *out = m;
+    return MI_OK;
+}
+
+int mi_prep_normalize(mi_prep_matrix *m, double scale_factor, float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m) return fail(MI_EINVAL, "NULL argument");
+    if (!(scale_factor > 0.0) || std::isinf(scale_factor)) return fail(MI_EINVAL, "scale_factor must be finite and > 0");
+    HIP_TRY(hipSetDevice(m->device));
+    if (!m->d_Y) HIP_TRY(hipMalloc((void **)&m->d_Y, (size_t)m->n * m->g * sizeof(float)));
+    m->normalized = false;
+    Timer t;
+    TRY(t.start());
+    hipLaunchKernelGGL(k_prep_normalize, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_X, m->d_Y, m->n, m->g,
+                       scale_factor);
+    TRY(t.stop(out_kernel_ms));
+    m->normalized = true;
+    return MI_OK;
+}
+
+int mi_prep_fetch_normalized(mi_prep_matrix *m, float *out)
+{
+    if (!m || !out) return fail(MI_EINVAL, "NULL argument");
+    if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemcpy(out, m->d_Y, (size_t)m->n * m->g * sizeof(float), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_prep_gene_stats(mi_prep_matrix *m, int which, double *mean, double *var, int32_t *nnz, float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m) return fail(MI_EINVAL, "NULL argument");
+    if (which != 0 && which != 1) return fail(MI_EINVAL, "which must be 0 (counts) or 1 (normalised), got %d", which);
+    if (which == 1 && !m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t g = (size_t)m->g, slices = (size_t)(m->n + kRowSlice - 1) / kRowSlice;
+    DevBufs bufs;
+    double *d_psum, *d_mean, *d_var;
+    int32_t *d_pnnz, *d_nnz;
+    HIP_TRY(bufs.alloc(&d_psum, slices * g));
+    HIP_TRY(bufs.alloc(&d_pnnz, slices * g));
+    HIP_TRY(bufs.alloc(&d_mean, g));
+    HIP_TRY(bufs.alloc(&d_var, g));
+    HIP_TRY(bufs.alloc(&d_nnz, g));
+    const float *M = which ? m->d_Y : m->d_X;
+    Timer t;
+    TRY(t.start());
+    TRY(col_reduce<kColSum>(m, M, nullptr, nullptr, 0.0, (double)m->n, d_psum, d_pnnz, d_mean, d_nnz));
+    TRY(col_reduce<kColCentred>(m, M, d_mean, nullptr, 0.0, (double)(m->n - 1), d_psum, nullptr, d_var, nullptr));
+    TRY(t.stop(out_kernel_ms));
+    if (mean) HIP_TRY(hipMemcpy(mean, d_mean, g * sizeof(double), hipMemcpyDeviceToHost));
+    if (var) HIP_TRY(hipMemcpy(var, d_var, g * sizeof(double), hipMemcpyDeviceToHost));
+    if (nnz) HIP_TRY(hipMemcpy(nnz, d_nnz, g * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_prep_clipped_variance(mi_prep_matrix *m, const double *mean, const double *sd, double clip, double *out,
+                             float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m || !mean || !sd || !out) return fail(MI_EINVAL, "NULL argument");
+    if (std::isnan(clip)) return fail(MI_EINVAL, "clip is NaN");
+    for (int j = 0; j < m->g; ++j) {
+        if (!std::isfinite(mean[j])) return fail(MI_EINVAL, "mean[%d] is not finite", j);
+        if (!(sd[j] >= 0.0) || std::isinf(sd[j])) return fail(MI_EINVAL, "sd[%d] must be finite and >= 0", j);
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t g = (size_t)m->g, slices = (size_t)(m->n + kRowSlice - 1) / kRowSlice;
+    DevBufs bufs;
+    double *d_psum, *d_mean, *d_sd, *d_out;
+    HIP_TRY(bufs.alloc(&d_psum, slices * g));
+    HIP_TRY(bufs.alloc(&d_mean, g));
+    HIP_TRY(bufs.alloc(&d_sd, g));
+    HIP_TRY(bufs.alloc(&d_out, g));
+    HIP_TRY(hipMemcpy(d_mean, mean, g * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_sd, sd, g * sizeof(double), hipMemcpyHostToDevice));
+    Timer t;
+    TRY(t.start());
+    TRY(col_reduce<kColClipped>(m, m->d_X, d_mean, d_sd, clip, (double)(m->n - 1), d_psum, nullptr, d_out, nullptr));
+    TRY(t.stop(out_kernel_ms));
+    HIP_TRY(hipMemcpy(out, d_out, g * sizeof(double), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double *mu, const double *sigma, double clip,
+                   float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m || !genes || !mu || !sigma) return fail(MI_EINVAL, "NULL argument");
+    if (h < 1) return fail(MI_EINVAL, "h must be >= 1 (got %d)", h);
+    if (h > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d features exceed %d", h, MI_PREP_MAX_FEATURES);
+    if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
+    return guarded([&]() -> int {
+        std::vector<uint8_t> seen((size_t)m->g, 0), flat((size_t)h, 0);
+        std::vector<float> muf((size_t)h), inv((size_t)h);
+        for (int c = 0; c < h; ++c) {
+            const int32_t j = genes[c];
+            if (j < 0 || j >= m->g) return fail(MI_EINVAL, "genes[%d] = %d is outside [0, %d)", c, (int)j, m->g);
+            if (seen[j]) return fail(MI_EINVAL, "gene %d is chosen twice", (int)j);
+            seen[j] = 1;
+            if (!std::isfinite(mu[c])) return fail(MI_EINVAL, "mu[%d] is not finite", c);
+            if (!(sigma[c] >= 0.0) || std::isinf(sigma[c])) return fail(MI_EINVAL, "sigma[%d] must be finite and >= 0", c);
+            flat[c] = sigma[c] == 0.0;
+            muf[c] = (float)mu[c];
+            inv[c] = flat[c] ? 0.0f : (float)(1.0 / sigma[c]);
+        }
+        if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
+        HIP_TRY(hipSetDevice(m->device));
+        const int ldz = (h + kTile - 1) / kTile * kTile;
+        m->h = 0;
+        if (m->d_Z && m->ldz != ldz) {
+            (void)hipFree(m->d_Z);
+            m->d_Z = nullptr;
+        }
+        if (!m->d_Z) HIP_TRY(hipMalloc((void **)&m->d_Z, (size_t)m->n * ldz * sizeof(float)));
+        m->ldz = ldz;
+        DevBufs bufs;
+        int32_t *d_genes;
+        float *d_mu, *d_inv;
+        uint8_t *d_flat;
+        HIP_TRY(bufs.alloc(&d_genes, (size_t)h));
+        HIP_TRY(bufs.alloc(&d_mu, (size_t)h));
+        HIP_TRY(bufs.alloc(&d_inv, (size_t)h));
+        HIP_TRY(bufs.alloc(&d_flat, (size_t)h));
+        HIP_TRY(hipMemcpy(d_genes, genes, (size_t)h * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_mu, muf.data(), (size_t)h * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_inv, inv.data(), (size_t)h * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_flat, flat.data(), (size_t)h, hipMemcpyHostToDevice));
+        Timer t;
+        TRY(t.start());
+        // (one cell per grid.y, whose limit is 65535: slabs of 32768 cells)
+        for (int r0 = 0; r0 < m->n; r0 += 32768) {
+            const int rows = m->n - r0 < 32768 ? m->n - r0 : 32768;
+            hipLaunchKernelGGL(k_prep_select, dim3((unsigned)(ldz / 256 + (ldz % 256 != 0)), (unsigned)rows), dim3(256), 0, 0,
+                               m->d_Y + (size_t)r0 * m->g, rows, m->g, d_genes, h, ldz, d_mu, d_inv, d_flat, (float)clip,
+                               m->d_Z + (size_t)r0 * ldz);
+            HIP_TRY(hipGetLastError());
+        }
+        TRY(t.stop(out_kernel_ms));
+        m->h = h;
+        return MI_OK;
+    });
+}
+
+int mi_prep_fetch_scaled(mi_prep_matrix *m, float *out)
+{
+    if (!m || !out) return fail(MI_EINVAL, "NULL argument");
+    if (m->h < 1) return fail(MI_ESTATE, "mi_prep_select has not run");
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemcpy2D(out, (size_t)m->h * sizeof(float), m->d_Z, (size_t)m->ldz * sizeof(float), (size_t)m->h * sizeof(float),
+                        (size_t)m->n, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_prep_gram(mi_prep_matrix *m, double *out_G, float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m || !out_G) return fail(MI_EINVAL, "NULL argument");
+    if (m->h < 1) return fail(MI_ESTATE, "mi_prep_select has not run");
+    HIP_TRY(hipSetDevice(m->device));
+    const int T = m->ldz / kTile, tiles = T * (T + 1) / 2;
+    const int chunks = (m->n + kChunk - 1) / kChunk;
+    const size_t tile_bytes = (size_t)kTile * kTile * sizeof(float), ldg = (size_t)T * kTile;
+    int batch = (int)(kGramWorkspace / (tile_bytes * tiles));
+    batch = batch < 1 ? 1 : (batch > chunks ? chunks : batch);
+    DevBufs bufs;
+    float *d_P;
+    double *d_G;
+    HIP_TRY(bufs.alloc(&d_P, (size_t)batch * tiles * kTile * kTile));
+    HIP_TRY(bufs.alloc(&d_G, ldg * ldg));
+    Timer t;
+    TRY(t.start());
+    HIP_TRY(hipMemsetAsync(d_G, 0, ldg * ldg * sizeof(double), 0));
+    for (int c0 = 0; c0 < chunks; c0 += batch) {
+        const int nb = chunks - c0 < batch ? chunks - c0 : batch;
+        hipLaunchKernelGGL(k_prep_gram, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, 0, m->d_Z, m->ldz, m->n, T, c0, d_P);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_prep_gram_reduce, dim3((unsigned)tiles), dim3(256), 0, 0, d_P, tiles, nb, T, d_G);
+        HIP_TRY(hipGetLastError());
+    }
+    TRY(t.stop(out_kernel_ms));
+    HIP_TRY(hipMemcpy2D(out_G, (size_t)m->h * sizeof(double), d_G, ldg * sizeof(double), (size_t)m->h * sizeof(double),
+                        (size_t)m->h, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m || !V || !out) return fail(MI_EINVAL, "NULL argument");
+    if (p < 1) return fail(MI_EINVAL, "p must be >= 1 (got %d)", p);
+    if (p > MI_PREP_MAX_PCS) return fail(MI_EUNSUPPORTED, "%d output columns exceed %d", p, MI_PREP_MAX_PCS);
+    if (m->h < 1) return fail(MI_ESTATE, "mi_prep_select has not run");
+    return guarded([&]() -> int {
+        std::vector<float> Vp((size_t)m->ldz * kProjCols, 0.0f);
+        for (int k = 0; k < m->h; ++k)
+            for (int c = 0; c < p; ++c) {
+                const float v = V[(size_t)k * p + c];
+                if (!std::isfinite(v)) return fail(MI_EINVAL, "V[%d, %d] is not finite", k, c);
+                Vp[(size_t)k * kProjCols + c] = v;
+            }
+        HIP_TRY(hipSetDevice(m->device));
+        DevBufs bufs;
+        float *d_V, *d_out;
+        HIP_TRY(bufs.alloc(&d_V, Vp.size()));
+        HIP_TRY(bufs.alloc(&d_out, (size_t)m->n * p));
+        HIP_TRY(hipMemcpy(d_V, Vp.data(), Vp.size() * sizeof(float), hipMemcpyHostToDevice));
+        Timer t;
+        TRY(t.start());
+        hipLaunchKernelGGL(k_prep_project, dim3((unsigned)((m->n + kProjCells - 1) / kProjCells)), dim3(256), 0, 0, m->d_Z, m->ldz,
+                           m->n, (m->h + kKC - 1) / kKC * kKC, d_V, p, d_out);
+        TRY(t.stop(out_kernel_ms));
+        HIP_TRY(hipMemcpy(out, d_out, (size_t)m->n * p * sizeof(float), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,346 @@
+"""Preprocessing on the GPU: counts -> log-normalised matrix -> variable genes -> scaled matrix -> PCA coordinates, the
+input of :func:`snn.build_snn`; the normalised matrix is the one :func:`metrics.find_all_markers` takes.
+
+This is the first chunk of every data-preparation notebook of the reference, in R
+(`R/pbmc3k/Pbmc3k_normalization_simulated_data.Rmd:81-82,184-185,488-492`: Seurat's ``NormalizeData(LogNormalize, 1e4)`` ->
+``FindVariableFeatures("vst")`` -> ``ScaleData`` -> ``RunPCA``; `Pbmc3k_prepare_data_for_QA_clustering.Rmd:51-52`,
+`Kidney_data.Rmd:47-48`).  The passes over the cells x genes matrix and the Gram and projection products run in libmi_sa.so
+(csrc/prep_kernels.hip, C ABI include/mi_prep.h); only the loess curve of ``vst`` and the h x h eigen-solve are host fp64.
+
+Out of scope: ``SCTransform``, ``vars.to.regress``, sparse (CSR / 10x) input, more than ``MAX_FEATURES`` = 4096 features.
+
+    emb = preprocess.embed(counts, nfeatures=2000, npcs=50)
+    g = snn.build_snn(emb.coords[:, :15], k=5, ord=15)
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import time
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+
+MAX_FEATURES = 4096        # MI_PREP_MAX_FEATURES (include/mi_prep.h)
+MAX_PCS = 128              # MI_PREP_MAX_PCS
+GRAM_CHUNK = 512           # MI_PREP_GRAM_CHUNK
+
+_f32p, _f64p, _i32p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)
+
+
+def _p(a, t):
+    return a.ctypes.data_as(t)
+
+
+class ExpressionMatrix:
+    """A cells x genes count matrix resident on the GPU (uploaded once), with one method per pass of include/mi_prep.h.
+    A context manager; ``timing`` collects the device milliseconds of every pass that has run."""
+
+    def __init__(self, X, device: int = 0):
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2:
+            raise ValueError("X must be (cells, genes) (got shape %s)" % (X.shape,))
+        self.n, self.g = (int(s) for s in X.shape)
+        self.device = int(device)
+        self.h = 0
+        self.timing = {}
+        self._stats = {}
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._lib.mi_prep_create_f32(_p(X, _f32p), self.n, self.g, self.device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            self._lib.mi_prep_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the ExpressionMatrix is closed")
+        return self._h
+
+    def normalize(self, scale_factor: float = 1e4):
+        """Seurat's ``LogNormalize``: ``log1p(x * scale_factor / total of the cell)``, kept on the device.  A cell without
+        counts keeps zeros (Seurat returns NaN there)."""
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_normalize(self._handle(), float(scale_factor), C.byref(ms)))
+        self._stats.pop(1, None)
+        self.timing["normalize_ms"] = float(ms.value)
+        return self
+
+    def fetch_normalized(self) -> np.ndarray:
+        out = np.empty((self.n, self.g), dtype=np.float32)
+        _lib.check(self._lib.mi_prep_fetch_normalized(self._handle(), _p(out, _f32p)))
+        return out
+
+    def gene_stats(self, which: str = "counts"):
+        """``(mean, variance, nnz)`` per gene of the ``"counts"`` or the ``"normalized"`` matrix: fp64 mean, sample
+        variance (ddof 1) about it, cells with a non-zero value."""
+        if which not in ("counts", "normalized"):
+            raise ValueError("which must be 'counts' or 'normalized'")
+        w = int(which == "normalized")
+        if w not in self._stats:
+            mean, var = np.empty(self.g), np.empty(self.g)
+            nnz = np.empty(self.g, dtype=np.int32)
+            ms = C.c_float(0.0)
+            _lib.check(self._lib.mi_prep_gene_stats(self._handle(), w, _p(mean, _f64p), _p(var, _f64p), _p(nnz, _i32p),
+                                                    C.byref(ms)))
+            self.timing["gene_stats_%s_ms" % which] = float(ms.value)
+            self._stats[w] = (mean, var, nnz)
+        return self._stats[w]
+
+    def clipped_variance(self, mean, sd, clip: float) -> np.ndarray:
+        """``sum_i min((x_ij - mean_j) / sd_j, clip)^2 / (n - 1)`` over the counts, 0 where ``sd_j == 0`` (the second pass
+        of ``vst``)."""
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        sd = np.ascontiguousarray(sd, dtype=np.float64)
+        if mean.shape != (self.g,) or sd.shape != (self.g,):
+            raise ValueError("mean and sd must have one entry per gene (%d)" % self.g)
+        out = np.empty(self.g)
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_clipped_variance(self._handle(), _p(mean, _f64p), _p(sd, _f64p), float(clip),
+                                                      _p(out, _f64p), C.byref(ms)))
+        self.timing["clipped_variance_ms"] = float(ms.value)
+        return out
+
+    def select(self, genes, mu, sigma, clip: float = 10.0):
+        """Materialises ``Z[:, c] = fminf((y[:, genes[c]] - f32(mu[c])) * f32(1 / sigma[c]), f32(clip))`` (0 where
+        ``sigma[c] == 0``) on the device; :meth:`fetch_scaled`, :meth:`gram` and :meth:`project` read it."""
+        genes = np.asarray(genes)
+        if genes.ndim != 1 or genes.dtype.kind not in "iu":
+            raise ValueError("genes must be a 1-d integer array")
+        if len(genes) and (genes.min() < -2 ** 31 or genes.max() >= 2 ** 31):
+            raise ValueError("gene index out of range")
+        genes = np.ascontiguousarray(genes, dtype=np.int32)
+        mu = np.ascontiguousarray(mu, dtype=np.float64)
+        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+        if mu.shape != genes.shape or sigma.shape != genes.shape:
+            raise ValueError("mu and sigma must have one entry per chosen gene")
+        ms = C.c_float(0.0)
+        self.h = 0
+        _lib.check(self._lib.mi_prep_select(self._handle(), _p(genes, _i32p), len(genes), _p(mu, _f64p), _p(sigma, _f64p),
+                                            float(clip), C.byref(ms)))
+        self.h = len(genes)
+        self.timing["select_ms"] = float(ms.value)
+        return self
+
+    def fetch_scaled(self) -> np.ndarray:
+        out = np.empty((self.n, max(self.h, 1)), dtype=np.float32)
+        _lib.check(self._lib.mi_prep_fetch_scaled(self._handle(), _p(out, _f32p)))
+        return out
+
+    def gram(self) -> np.ndarray:
+        """``Z^T Z`` (h x h, fp64; not divided by n - 1): exactly symmetric and identical between runs."""
+        out = np.empty((max(self.h, 1),) * 2)
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_gram(self._handle(), _p(out, _f64p), C.byref(ms)))
+        self.timing["gram_ms"] = float(ms.value)
+        return out
+
+    def project(self, V) -> np.ndarray:
+        """``Z @ V`` for ``V`` (h, p), p <= ``MAX_PCS``, accumulated in fp32."""
+        V = np.ascontiguousarray(V, dtype=np.float32)
+        if V.ndim != 2 or (self.h and V.shape[0] != self.h):
+            raise ValueError("V must be (h, p) with h = %d (got shape %s)" % (self.h, V.shape))
+        out = np.empty((self.n, V.shape[1]), dtype=np.float32)
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_project(self._handle(), _p(V, _f32p), V.shape[1], _p(out, _f32p), C.byref(ms)))
+        self.timing["project_ms"] = float(ms.value)
+        return out
+
+
+class Result(dict):
+    """A dict whose keys are also attributes (``emb.coords``)."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+def log_normalize(X, scale_factor: float = 1e4, device: int = 0) -> np.ndarray:
+    """The log-normalised fp32 matrix (cells x genes) :func:`metrics.find_all_markers` takes."""
+    with ExpressionMatrix(X, device=device) as m:
+        return m.normalize(scale_factor).fetch_normalized()
+
+
+def loess_fit(x, y, span: float = 0.3, degree: int = 2) -> np.ndarray:
+    """Local polynomial regression evaluated directly at every point, in fp64: for each ``x[i]`` the ``q = ceil(span * m)``
+    nearest points (ties in distance: the lower sorted position), tricube weights ``(1 - (|dx| / d)^3)^3`` with ``d`` the
+    largest of their distances, a weighted least-squares polynomial of ``degree`` in ``dx``, and its value at ``dx = 0``.
+    ``span >= 1`` uses all points.  A window whose points all share ``x[i]`` gives their mean.
+
+    R's ``loess`` (which Seurat's ``vst`` calls) evaluates the same local fits only at the vertices of a k-d tree and
+    interpolates between them; R is not available to compare against, so agreement with Seurat's curve is UNPINNED."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if x.ndim != 1 or x.shape != y.shape:
+        raise ValueError("x and y must be 1-d arrays of one length")
+    if not (np.isfinite(x).all() and np.isfinite(y).all()):
+        raise ValueError("x and y must be finite")
+    if degree not in (0, 1, 2):
+        raise ValueError("degree must be 0, 1 or 2")
+    if not span > 0:
+        raise ValueError("span must be > 0")
+    m = len(x)
+    q = min(m, int(math.ceil(span * m)))
+    if q < degree + 1:
+        raise ValueError("span * m = %d points cannot carry a polynomial of degree %d" % (q, degree))
+    order = np.argsort(x, kind="stable")
+    xs, ys = x[order], y[order]
+    fit = np.empty(m)
+    lo = 0
+    for i in range(m):
+        while lo + q < m and xs[lo + q] - xs[i] < xs[i] - xs[lo]:
+            lo += 1
+        dx = xs[lo:lo + q] - xs[i]
+        d = max(-dx[0], dx[-1])
+        if d == 0.0:
+            fit[i] = ys[lo:lo + q].mean()
+            continue
+        u = dx / d
+        sw = np.sqrt((1.0 - np.abs(u) ** 3) ** 3)
+        A = np.vander(u, degree + 1, increasing=True) * sw[:, None]
+        fit[i] = np.linalg.lstsq(A, ys[lo:lo + q] * sw, rcond=None)[0][0]
+    out = np.empty(m)
+    out[order] = fit
+    return out
+
+
+def top_features(variance_standardized, nfeatures: int) -> np.ndarray:
+    """Indices of the ``nfeatures`` largest values, descending, by a stable sort: the lower index wins a tie."""
+    v = np.asarray(variance_standardized, dtype=np.float64)
+    if v.ndim != 1 or np.isnan(v).any():
+        raise ValueError("variance_standardized must be a 1-d array without NaN")
+    nfeatures = int(nfeatures)
+    if nfeatures < 1 or nfeatures > len(v):
+        raise ValueError("nfeatures must lie in [1, %d] (got %d)" % (len(v), nfeatures))
+    return np.argsort(-v, kind="stable")[:nfeatures].astype(np.int32)
+
+
+def expected_sd_from_stats(mean, variance, span: float = 0.3) -> np.ndarray:
+    """``vst``'s expected standard deviation: ``sqrt(10 ^ loess(log10 variance ~ log10 mean))`` over the genes whose
+    variance is not 0, and 0 for those."""
+    mean, variance = np.asarray(mean, dtype=np.float64), np.asarray(variance, dtype=np.float64)
+    ok = variance > 0
+    sd = np.zeros(len(mean))
+    if ok.any():
+        sd[ok] = np.sqrt(10.0 ** loess_fit(np.log10(mean[ok]), np.log10(variance[ok]), span=span, degree=2))
+    return sd
+
+
+def find_variable_features(X_or_handle, nfeatures: int = 2000, span: float = 0.3, clip_max: Optional[float] = None,
+                           expected_sd=None, device: int = 0) -> Result:
+    """Seurat's ``FindVariableFeatures(selection.method = "vst")`` on the counts: per-gene mean and variance (device), the
+    loess curve of log10 variance on log10 mean over the non-constant genes (host, :func:`loess_fit`; see there what is
+    unpinned against R) unless ``expected_sd`` is given, the variance of the values standardised by it and clipped at
+    ``clip_max`` (default ``sqrt(n)``; device), and the top ``nfeatures`` by :func:`top_features`.  Returns ``mean``,
+    ``variance``, ``variance_expected``, ``variance_standardized`` and ``genes`` (in rank order)."""
+    if not isinstance(X_or_handle, ExpressionMatrix):
+        with ExpressionMatrix(X_or_handle, device=device) as m:
+            return find_variable_features(m, nfeatures, span, clip_max, expected_sd)
+    m = X_or_handle
+    nfeatures = int(nfeatures)
+    if nfeatures < 1 or nfeatures > m.g:
+        raise ValueError("nfeatures must lie in [1, %d] (got %d)" % (m.g, nfeatures))
+    mean, var, _ = m.gene_stats("counts")
+    t0 = time.perf_counter()
+    if expected_sd is None:
+        sd = expected_sd_from_stats(mean, var, span)
+    else:
+        sd = np.asarray(expected_sd, dtype=np.float64)
+        if sd.shape != (m.g,):
+            raise ValueError("expected_sd must have one entry per gene (%d)" % m.g)
+    m.timing["loess_s"] = time.perf_counter() - t0
+    clip = math.sqrt(m.n) if clip_max is None else float(clip_max)
+    vs = m.clipped_variance(mean, sd, clip)
+    return Result(mean=mean, variance=var, variance_expected=sd ** 2, variance_standardized=vs,
+                  genes=top_features(vs, nfeatures))
+
+
+def _select_scaled(m: ExpressionMatrix, genes, max_value: float):
+    genes = np.asarray(genes)
+    if genes.ndim != 1 or genes.dtype.kind not in "iu" or len(genes) < 1:
+        raise ValueError("genes must be a non-empty 1-d integer array")
+    if genes.min() < 0 or genes.max() >= m.g:
+        raise ValueError("gene indices must lie in [0, %d)" % m.g)
+    mean, var, _ = m.gene_stats("normalized")
+    m.select(genes, mean[genes], np.sqrt(var[genes]), max_value)
+
+
+def scale_data(handle: ExpressionMatrix, genes, max_value: float = 10.0) -> np.ndarray:
+    """Seurat's ``ScaleData`` on the chosen genes of the normalised matrix: centred by the gene's mean, divided by its
+    standard deviation (ddof 1), clipped above at ``max_value``; a constant gene gives zeros.  Returns ``Z`` (n x h, fp32).
+    ``vars.to.regress`` is not supported."""
+    _select_scaled(handle, genes, max_value)
+    return handle.fetch_scaled()
+
+
+def pca_from_gram(G, n: int, npcs: int) -> Result:
+    """The top ``npcs`` eigenpairs of ``G / (n - 1)`` (``scipy.linalg.eigh``, fp64), descending.  Each loading's sign makes
+    its largest-magnitude entry positive (the first such entry on ties) -- a convention of this package: irlba's signs, which
+    Seurat reports, are arbitrary and UNPINNED.  Returns ``loadings`` (h x npcs), ``eigenvalues``, ``stdev`` (their square
+    roots, Seurat's ``stdev``) and ``total_variance`` (trace / (n - 1))."""
+    from scipy.linalg import eigh
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim != 2 or G.shape[0] != G.shape[1]:
+        raise ValueError("G must be square")
+    h, n, npcs = G.shape[0], int(n), int(npcs)
+    if n < 2:
+        raise ValueError("n must be at least 2")
+    if npcs < 1 or npcs > h:
+        raise ValueError("npcs must lie in [1, %d] (got %d)" % (h, npcs))
+    Cm = G / (n - 1.0)
+    w, V = eigh(Cm, subset_by_index=[h - npcs, h - 1])
+    w, V = w[::-1].copy(), V[:, ::-1].copy()
+    top = np.argmax(np.abs(V), axis=0)                           # (argmax: the first of equal magnitudes)
+    V *= np.where(V[top, np.arange(npcs)] < 0, -1.0, 1.0)
+    return Result(loadings=V, eigenvalues=w, stdev=np.sqrt(np.maximum(w, 0.0)), total_variance=float(np.trace(Cm)))
+
+
+def pca(handle: ExpressionMatrix, genes, npcs: int = 50, max_value: float = 10.0) -> Result:
+    """Seurat's ``ScaleData`` + ``RunPCA(features = genes)``: the scaled matrix, its Gram matrix (device),
+    :func:`pca_from_gram` (host), and ``coords = Z @ f32(loadings)`` (device): Seurat's ``cell.embeddings``.  Returns the
+    fields of :func:`pca_from_gram`, ``coords`` (n x npcs, fp32) and ``timing`` (every kernel's ms, the eigen-solve's
+    seconds)."""
+    npcs = int(npcs)
+    if npcs < 1 or npcs > min(MAX_PCS, len(np.atleast_1d(genes))):
+        raise ValueError("npcs must lie in [1, min(%d, number of genes)] (got %d)" % (MAX_PCS, npcs))
+    _select_scaled(handle, genes, max_value)
+    G = handle.gram()
+    t0 = time.perf_counter()
+    r = pca_from_gram(G, handle.n, npcs)
+    handle.timing["eigh_s"] = time.perf_counter() - t0
+    r["coords"] = handle.project(r.loadings.astype(np.float32))
+    r["timing"] = dict(handle.timing)
+    return r
+
+
+def embed(X, nfeatures: int = 2000, npcs: int = 50, scale_factor: float = 1e4, max_value: float = 10.0, span: float = 0.3,
+          device: int = 0) -> Result:
+    """The whole chain on one upload: normalise, ``vst`` variable genes, scale, PCA.  Returns the fields of :func:`pca`
+    plus ``genes`` and ``features`` (the table of :func:`find_variable_features`).  ``coords[:, :dim]`` is what
+    :func:`snn.build_snn` takes.  ``SCTransform``, ``vars.to.regress`` and sparse input are not supported."""
+    with ExpressionMatrix(X, device=device) as m:
+        m.normalize(scale_factor)
+        feats = find_variable_features(m, nfeatures=nfeatures, span=span)
+        r = pca(m, feats.genes, npcs=npcs, max_value=max_value)
+    r["genes"] = feats.genes
+    r["features"] = feats
+    return r
