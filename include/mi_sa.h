@@ -98,6 +98,10 @@ int mi_sa_problem_info(const mi_sa_problem *p, int *kind, int *n, int *num_cases
  * entries per variable and the one-wavefront few-replica kernel; 2: the sweeping wavefront computes them itself),
  * "k2_trim" (that pair kernel with its threshold wavefront, on a model whose longest row has 13..15 entries at the
  * 16-wide layout: 0 / 1 it neither fetches nor gathers the padding entries past that row length, 2 it does),
+ * "k2_nbr16" (the pair kernel on models of at most 256 slots, with its threshold wavefront at 16 entries per variable or at 32
+ * entries: 0 / 1 the neighbour words of its packed adjacency are 16-bit LDS addresses, two per dword -- 6144 / 6400 bytes per
+ * slot and wavefront instead of 7936 / 8448 at 16 entries, 12544 instead of 16640 at 32; 2 the 32-bit packings, which models
+ * with pair-term weights and the 16-entry form without a threshold wavefront always keep),
  * "k3_fast" (Potts: 0 the lean kernel csrc/potts_fast_kernels.hip when every slot is free of internal edges, K <= 16 and no
  * minimum size is set; 2 never), "xl_batched" (dense, n > 4096: 0 auto = all replicas together on the matrix cores from 256
  * replicas or n = 16384 up, 1 always, 2 a workgroup per replica), "xl_chain" (0 auto = the decisions and small passes of a group of eight blocks as one launch up to 512
@@ -266,6 +270,12 @@ int mi_sa_last_launch_count(mi_sa_problem *p, int *out_launches);
  * several joined by " + " when a chunked dense run alternates kernels).  The library picks the kernel from the
  * model (kind, size, adjacency width, whether every slot is free of internal edges) and the number of replicas. */
 int mi_sa_last_kernel_name(mi_sa_problem *p, char *out, int len);
+
+/* Which adjacency packing that kernel read: the packed adjacency bytes ONE wavefront fetched per 64-variable slot in
+ * the last anneal -- the pair kernel's 8448 (16 entries per variable) / 7936 (trimmed rows of 15) / 16640 (32 entries),
+ * or 6400 / 6144 / 12544 with 16-bit neighbour words ("k2_nbr16"); 0 for a kernel without such a packing.  The kernel's
+ * name does not depend on the packing. */
+int mi_sa_last_adjacency_bytes_per_slot(mi_sa_problem *p, int *out_bytes);
 
 /* Copy results of the last run to host: states (R x n, uint8 or uint16 by kind; nullable),
  * energies (R doubles, recomputed from the final state on device; nullable), stats (nullable):

@@ -193,6 +193,9 @@ struct mi_sa_problem {
     uint4 *d_adj4r = nullptr;                // K2p at D = 16 with rows of at most k2p_rw < 16 entries: the trimmed packing (pack_pair_adjacency)
     int k2p_rw = 0;
     std::vector<uint32_t> h_adj4r;           // ... its host image until the linear terms are in it (RW = 15; mi_sa_problem_create_csr_rank1)
+    uint4 *d_adj16 = nullptr;                // K2p: the packing with 16-bit neighbour words (pack_pair_adjacency16); null = not built
+    uint4 *d_adj16r = nullptr;               // ... the same with the linear term in the sixteenth value (rows of 13..15 entries at D = 16)
+    std::vector<uint32_t> h_adj16;           // ... its host image until the linear terms are known (mi_sa_problem_create_csr_rank1)
     uint32_t *d_slot_flags = nullptr;        // K2: slots with internal edges
     int k2_state_bytes = 0;                  // K2: byte-per-variable state (16 replicas x n bytes fit one CU's LDS)
     int32_t *d_wgt = nullptr;                // K2 family: the 64 pair-term weights of the weighted slot (mi_sa_problem_set_pair_weights)
@@ -238,6 +241,8 @@ struct mi_sa_problem {
     int opt_k3_fast = 0;                     // K3f (csrc/potts_fast_kernels.hip): 0 auto (when the model is eligible), 2 never
     int opt_k2_tw = 0;                       // K2p with a threshold wavefront per workgroup: 0 auto (when built for the width), 1 on, 2 off
     int opt_k2_trim = 0;                     // ... and its trimmed rows (rows of 13..15 entries at D = 16): 0 auto / 1 on (when built), 2 off
+    int opt_k2_nbr16 = 0;                    // ... and its 16-bit neighbour words: 0 auto / 1 on (wherever built), 2 off (the 32-bit packings)
+    int last_adj_bytes = 0;                  // packed adjacency bytes a wavefront fetched per slot in the last anneal (0: a kernel without such a packing)
     int opt_k2_split_max = 1024;             // ... auto: runs of up to this many replicas (a wavefront per SIMD at most)
     int opt_unit_rows = 0;                   // K1w ring unit (rows per rendezvous): 0 auto, 2 or 4
     int resident_waves = 0;                  // co-resident wavefronts of the anneal kernel on this device
@@ -483,6 +488,27 @@ static std::vector<uint32_t> pack_pair_adjacency(const std::vector<uint32_t> &hc
     return out;
 }
 
+// K2p's packing with 16-bit neighbour words (csrc/sparse_pair_kernels.hip, N16): the neighbour word of j is still the LDS
+// byte address of its cell, 4 j -- below 65 536 for every model of at most 256 slots -- so two share a dword: per slot
+// [G / 2 + G][64 lanes][4 dwords], first G / 2 blocks of neighbours (entry k in half k & 1 of dword k / 2 of the lane),
+// then G blocks of values (entry k in dword k).  Padding: (self, +0.0).  A slot is 6144 bytes at D = 16 (8448 unpacked).
+static std::vector<uint32_t> pack_pair_adjacency16(const std::vector<uint32_t> &hc, const std::vector<float> &hv, int slots, int D)
+{
+    const int G = D / 4;
+    const size_t slot_words = (size_t)(G / 2 + G) * 256;
+    std::vector<uint32_t> out((size_t)slots * slot_words, 0u);
+    for (int t = 0; t < slots; ++t)
+        for (int lane = 0; lane < 64; ++lane)
+            for (int k = 0; k < D; ++k) {
+                const size_t src = ((size_t)t * D + k) * 64 + lane;
+                const size_t at_nbr = (size_t)t * slot_words + (size_t)(k / 8) * 256 + (size_t)lane * 4 + ((k / 2) & 3);
+                const size_t at_val = (size_t)t * slot_words + (size_t)(G / 2 + k / 4) * 256 + (size_t)lane * 4 + (k & 3);
+                out[at_nbr] |= (4u * hc[src]) << (16 * (k & 1));
+                memcpy(&out[at_val], &hv[src], 4);
+            }
+    return out;
+}
+
 // CSR (both directions stored) -> slot-ELL device arrays (D = 16 / 32 / 64)
 static int upload_slot_ell(mi_sa_problem *p, const int32_t *rowptr, const int32_t *col, const float *val, int n)
 {
@@ -628,6 +654,7 @@ static int upload_slot_ell(mi_sa_problem *p, const int32_t *rowptr, const int32_
                                 4u * hc[((size_t)t * D + k) * 64 + lane];
                 HIP_TRY(hipMalloc((void **)&p->d_adj4p, ha.size() * sizeof(uint32_t)));
                 HIP_TRY(hipMemcpy(p->d_adj4p, ha.data(), ha.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+                if (slots <= 256) p->h_adj16 = pack_pair_adjacency16(hc, hv, slots, D);   // (addresses of 16 bits)
                 if (D == 16 && maxdeg >= 13 && maxdeg < 16) {
                     // entries maxdeg.. 15 are padding in every row: K2p's trimmed form neither fetches nor gathers them
                     p->h_adj4r = pack_pair_adjacency(hc, hv, slots, D, maxdeg);
@@ -846,6 +873,19 @@ int mi_sa_problem_create_csr_rank1_f32(const int32_t *rowptr, const int32_t *col
             HIP_TRY(hipMalloc((void **)&p->d_adj4r, p->h_adj4r.size() * sizeof(uint32_t)));
             HIP_TRY(hipMemcpy(p->d_adj4r, p->h_adj4r.data(), p->h_adj4r.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
             std::vector<uint32_t>().swap(p->h_adj4r);
+        }
+        if (!p->h_adj16.empty()) {
+            HIP_TRY(hipMalloc((void **)&p->d_adj16, p->h_adj16.size() * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpy(p->d_adj16, p->h_adj16.data(), p->h_adj16.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            if (p->k2p_rw) {
+                // trimmed rows: the sixteenth value is padding in every row and carries the lane's linear term instead
+                for (int t = 0; t < p->slots; ++t)
+                    for (int lane = 0; lane < 64; ++lane)
+                        memcpy(&p->h_adj16[(size_t)t * 1536 + 5 * 256 + (size_t)lane * 4 + 3], &hl[(size_t)t * 64 + lane], 4);
+                HIP_TRY(hipMalloc((void **)&p->d_adj16r, p->h_adj16.size() * sizeof(uint32_t)));
+                HIP_TRY(hipMemcpy(p->d_adj16r, p->h_adj16.data(), p->h_adj16.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            }
+            std::vector<uint32_t>().swap(p->h_adj16);
         }
         return MI_OK;
     });
@@ -1083,7 +1123,7 @@ int mi_sa_problem_destroy(mi_sa_problem *p)
     (void)settle(p);
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    void *bufs[] = {p->d_merge_cq, p->d_gconst, p->d_nwq, p->d_ncw, p->d_nw64, p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_adj4r, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
+    void *bufs[] = {p->d_merge_cq, p->d_gconst, p->d_nwq, p->d_ncw, p->d_nw64, p->d_wgt, p->d_xg, p->d_pt_rung, p->d_pt_betas, p->d_pt_energy, p->d_pt_ladder, p->d_pt_temps, p->d_pt_stats, p->d_adj4p, p->d_adj4r, p->d_adj16, p->d_adj16r, p->d_ell_val64, p->d_lin64, p->d_Q2xl, p->d_diagxl, p->d_rows, p->d_meta, p->d_adj4, p->d_slot_flags, p->d_Qm, p->d_fields, p->d_ctrl, p->d_ell_col, p->d_ell_val, p->d_lin, p->d_pace, p->d_Qp, p->d_Qs, p->d_temps, p->d_init, p->d_states, p->d_energy, p->d_stats};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
@@ -1151,6 +1191,7 @@ int mi_sa_set_option(mi_sa_problem *p, const char *key, long value)
     if (!strcmp(key, "k2_wide") && value >= 0 && value <= 2) { p->opt_k2_wide = (int)value; return MI_OK; }
     if (!strcmp(key, "k2_tw") && value >= 0 && value <= 2) { p->opt_k2_tw = (int)value; return MI_OK; }
     if (!strcmp(key, "k2_trim") && value >= 0 && value <= 2) { p->opt_k2_trim = (int)value; return MI_OK; }
+    if (!strcmp(key, "k2_nbr16") && value >= 0 && value <= 2) { p->opt_k2_nbr16 = (int)value; return MI_OK; }
     if (!strcmp(key, "k3_fast") && value >= 0 && value <= 2) { p->opt_k3_fast = (int)value; return MI_OK; }
     if (!strcmp(key, "min_cluster_size") && value >= 0) {
         if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_EINVAL, "min_cluster_size applies to Potts problems");
@@ -1215,6 +1256,7 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
     if (!resident || init)
         HIP_TRY(hipStreamSynchronize(p->stream));   // inputs resident before the timed region
     g_kernel.clear();
+    p->last_adj_bytes = 0;
     const float *temps_buf = resident ? p->d_pt_temps : p->d_temps;
 
     if (p->kind == MI_KIND_DENSE && p->xl_chunks > 0) {
@@ -1436,7 +1478,10 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
                 rc = mi_launch_csr_rank1_split(a, p->k2_free_block / 64, p->stream);
             } else if (choice == 1) {
                 a.adj4 = p->d_adj4p;                  // two replicas per wavefront: half the adjacency traffic per update
-                rc = mi_launch_csr_rank1_pair(a, p->opt_k2_pair == 1 ? (tw && p->D == 16 && pair_wgs <= 8 * cus) : tw_pair, p->stream);
+                // (the 16-bit packings go to the launcher beside the arguments: EllArgs, and with it every other kernel's code, stays as it is)
+                const bool n16 = p->opt_k2_nbr16 != 2;
+                rc = mi_launch_csr_rank1_pair(a, p->opt_k2_pair == 1 ? (tw && p->D == 16 && pair_wgs <= 8 * cus) : tw_pair, p->stream,
+                                              n16 ? p->d_adj16 : nullptr, n16 && p->opt_k2_trim != 2 ? p->d_adj16r : nullptr, &p->last_adj_bytes);
             } else {
                 // K2: every wavefront alone on its SIMD (up to 1024 replicas) -> a threshold wavefront beside it
                 rc = mi_launch_csr_rank1(a, p->stream, tw && R <= 1024 && (p->D == 16 || p->D == 32) && p->k2_state_bytes <= 1);
@@ -1603,6 +1648,15 @@ int mi_sa_last_launch_count(mi_sa_problem *p, int *out_launches)
     if (const int rc_w = settle(p)) return rc_w;
     if (!p->has_run) return fail(MI_ESTATE, "no anneal has been run on this problem");
     *out_launches = p->last_launches;
+    return MI_OK;
+}
+
+int mi_sa_last_adjacency_bytes_per_slot(mi_sa_problem *p, int *out_bytes)
+{
+    if (!p || !out_bytes) return fail(MI_EINVAL, "NULL argument");
+    if (const int rc_w = settle(p)) return rc_w;
+    if (!p->has_run) return fail(MI_ESTATE, "no anneal has been run on this problem");
+    *out_bytes = p->last_adj_bytes;
     return MI_OK;
 }
 

@@ -385,7 +385,10 @@ __device__ __forceinline__ long long wave_sum_i64(long long v)
     return v;
 }
 int mi_launch_csr_rank1(const EllArgs &, hipStream_t, bool tw = false);   // tw: + a threshold wavefront (runs of up to 1024 replicas; bit / byte state, 16 / 32 entries)
-int mi_launch_csr_rank1_pair(const EllArgs &, bool tw, hipStream_t);   // sparse_pair_kernels.hip: two replicas per wavefront (tw: + a threshold wavefront)
+// sparse_pair_kernels.hip: two replicas per wavefront (tw: + a threshold wavefront).  adj16 / adj16_trim: the packings with
+// 16-bit neighbour words (full rows / linear term in the sixteenth value; null = not built or switched off);
+// adj_bytes (nullable): the packed adjacency bytes a wavefront fetches per slot in the kernel that was launched
+int mi_launch_csr_rank1_pair(const EllArgs &, bool tw, hipStream_t, const uint4 *adj16 = nullptr, const uint4 *adj16_trim = nullptr, int *adj_bytes = nullptr);
 int mi_launch_csr_rank1_split(const EllArgs &, int nw, hipStream_t);   // sparse_split_kernels.hip: nw wavefronts per replica
 int mi_launch_csr_rank1_wide(const EllArgs &, int spb, bool tw, hipStream_t);   // ... one wavefront per replica, spb slots per step (tw: + a threshold wavefront; spb = 1 only so)
 int mi_launch_potts(const EllArgs &, hipStream_t);

@@ -46,10 +46,22 @@ __device__ __forceinline__ float half_hi(uint32_t w) { return (float)__builtin_b
 // them: a.adj4 then holds the trimmed packing (mi_sa.hip, pack_pair_adjacency), whose last group carries LW = RW - 4 (G - 1)
 // entries per lane ([64][LW] neighbours, then [64][LW] values; LW = 3: one dwordx4 of three neighbours and the linear
 // term, one dwordx2 and one dword of values -- 7936 bytes per slot and wavefront instead of 8448, nine loads as before).
-template <int D, bool TW, bool WGT = false, int RW = D>
+// N16 ("16-bit neighbour words", round 5): a neighbour word is the LDS byte address of a cell, below 65 536 on every model
+// of at most 256 slots, so a.adj4 then holds two of them per dword (mi_sa.hip, pack_pair_adjacency16: per slot G / 2 blocks
+// of [64 lanes][4 dwords] neighbours, entry k in half k & 1 of dword k / 2, then G such blocks of values; RW < D: the last
+// value of a lane, padding in every row, is its linear term) -- six aligned dwordx4 loads and 6144 bytes per slot and
+// wavefront at D = 16.  Same chain: the same neighbours in the same order, the same values, the same fma sequence; an
+// address costs one v_and_b32 or v_lshrrev_b32 more.  N16 = 1 (D = 32, no threshold wavefront): unpacked at the top of the
+// slot from the slot's own registers.  N16 = 2 (TW): the neighbour dwords are fetched TWO slots ahead and the addresses of
+// slot t + 1 are unpacked under the gathers of slot t, next to the own-cell terms -- measured against N16 = 1 on the TW
+// form: 21.08 against 21.27 ms on the benchmark's model.  The D = 16 form WITHOUT a threshold wavefront keeps the 32-bit
+// packing: there the unpack at the top of the slot cost more than the bytes saved (profiles/r05_k2p_nbr16_ab.txt).
+template <int D, bool TW, bool WGT = false, int RW = D, int N16 = 0>
 __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_pair(EllArgs a)
 {
     static_assert(RW > D - 4 && RW <= D, "trimmed rows drop part of the last group of four only");
+    static_assert(N16 == 0 || !WGT, "the weighted form keeps the 32-bit packing");
+    static_assert(N16 != 2 || (TW && D == 16), "the pipelined unpack lives in the threshold-wavefront form's gather window");
     extern __shared__ __attribute__((aligned(16))) char lds[];      // cell of variable i at byte 4 i
     const int lane = threadIdx.x & 63;
     const int pair = blockIdx.x;                                    // replicas 2 pair, 2 pair + 1
@@ -140,13 +152,41 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
 
     constexpr int G = D / 4;                                        // groups of four (neighbour, value) per lane
     constexpr int LW = RW - 4 * (G - 1);                            // entries of the last group (4 unless trimmed)
-    constexpr int SLOT_BYTES = (G - 1) * 2048 + (LW == 3 ? 1792 : LW * 512);   // one slot of the packing
+    constexpr int GC = N16 ? G / 2 : G;                             // dwordx4 blocks of neighbour words per lane
+    constexpr int SLOT_BYTES = N16 ? (GC + G) * 1024 : (G - 1) * 2048 + (LW == 3 ? 1792 : LW * 512);   // one slot of the packing
     const __amdgpu_buffer_rsrc_t rs_adj = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint4 *>(a.adj4), 0, slots * SLOT_BYTES, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_lin = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(a.lin), 0, slots * 256, 0x00020000);
-    struct SlotAdj { u32x4 col[G]; u32x4 val[G]; uint32_t lin; };
+    struct SlotAdj { u32x4 col[GC]; u32x4 val[G]; uint32_t lin; };
+    struct NbrPack { u32x4 w[GC]; };                                // N16: the packed neighbour dwords of a slot
     const int lane16 = lane * 16;
+    // N16: block b of a slot's [GC + G][64][4] image (constant parts of the offset fold into the 12-bit immediate)
+    auto fetch_block16 = [&](int t, int b) {
+        const int tt = t < slots ? t : slots - 1;
+        return __builtin_amdgcn_raw_buffer_load_b128(rs_adj, lane16 + (b & 3) * 1024, tt * SLOT_BYTES + (b >> 2) * 4096, 0);
+    };
+    auto fetch_nbr16 = [&](int t) {
+        NbrPack q;
+#pragma unroll
+        for (int b = 0; b < GC; ++b) q.w[b] = fetch_block16(t, b);
+        return q;
+    };
+    auto fetch_val16 = [&](int t) {                                 // (.col stays unset: the pipelined form keeps it in a NbrPack)
+        SlotAdj p;
+#pragma unroll
+        for (int g = 0; g < G; ++g) p.val[g] = fetch_block16(t, GC + g);
+        if constexpr (RW < D) p.lin = p.val[G - 1][3];
+        else p.lin = __builtin_amdgcn_raw_buffer_load_b32(rs_lin, lane * 4, (t < slots ? t : slots - 1) * 256, 0);
+        return p;
+    };
+    uint32_t m16 = 0xffffu;
+    asm("" : "+s"(m16));                                            // (the mask in a scalar register, not a literal per instruction)
+    auto unpack16 = [&](const u32x4 *w, int e) -> uint32_t {       // LDS address of entry e
+        const uint32_t pw = w[e / 8][(e / 2) & 3];
+        return (e & 1) ? pw >> 16 : (pw & m16);
+    };
+    uint32_t addr[16];                                              // N16 = 2: the addresses of the slot swept next
 #ifdef MI_K2P_NOFETCH
     // TIMING-ONLY build (`make dbg`, never the shipped library; wrong chain): the adjacency of slot 0 serves every slot, so
     // the sweep loop issues no vector-memory instruction -- what the kernel would cost without its L2 traffic
@@ -154,6 +194,13 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
 #else
     auto fetch_adj = [&](int t) {
 #endif
+        if constexpr (N16 != 0) {
+            SlotAdj p = fetch_val16(t);
+            const NbrPack q = fetch_nbr16(t);
+#pragma unroll
+            for (int b = 0; b < GC; ++b) p.col[b] = q.w[b];
+            return p;
+        }
         SlotAdj p;
         const int tt = t < slots ? t : slots - 1;
         const int soff = tt * SLOT_BYTES;
@@ -211,7 +258,8 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
     // data dependence, not a scheduling accident -- and the wait is lgkmcnt(0), so whatever LDS or scalar-memory
     // operation the compiler may place before it is waited for as well (scripts/check_asm_lds.py checks the emitted
     // code for a read of such a register ahead of its wait at build time).
-    auto slot_body = [&](auto c_in_group, int t, const SlotAdj &cur, uint32_t wordA, uint32_t wordB) {
+    // N16 = 2: `nxt` = the packed neighbour dwords of slot t + 1 (fetched a slot ago); addr[] holds slot t's on entry, slot t + 1's on exit
+    auto slot_body = [&](auto c_in_group, int t, const SlotAdj &cur, NbrPack &nxt, uint32_t wordA, uint32_t wordB) {
         constexpr int C = decltype(c_in_group)::value;
         const int i = t * 64 + lane;
         uint32_t own;                                               // [x_A | x_B] of this lane's variable
@@ -251,16 +299,34 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
 #ifdef MI_K2P_DBG_LINEAR   /* timing only: conflict-free addresses */
                 asm volatile("ds_read_b32 %0, %1" : "=v"(word[k]) : "v"((cur.col[g0 + k / 4][k & 3] & 0x3f00u) + lane * 4));
 #else
+                {
+                    if constexpr (N16 == 2) asm volatile("ds_read_b32 %0, %1" : "=v"(word[k]) : "v"(addr[k]));
+                    else if constexpr (N16 == 1) asm volatile("ds_read_b32 %0, %1" : "=v"(word[k]) : "v"(unpack16(cur.col, 4 * g0 + k)));
+                    else
                 asm volatile("ds_read_b32 %0, %1" : "=v"(word[k]) : "v"(cur.col[g0 + k / 4][k & 3]));
+                }
 #endif
             if (g0 == 0 && TW) {
                 // NK0 + 2 LDS reads are in flight and they return in order: with at most NK0 (15 at most: the counter's
                 // width) outstanding the lane's own cell and the thresholds are here -- everything that depends only on
                 // them is computed UNDER the gathers (the second wait names its results, so it cannot sink below it)
+                // (N16 = 2: the next slot's neighbour dwords pass through this wait, so their unpack cannot rise above the gathers)
+                if constexpr (N16 == 2)
+                    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(own), "+v"(thr2), "+v"(nxt.w[0]), "+v"(nxt.w[1]) : "n"(NK0 < 15 ? NK0 : 15) : "memory");
+                else
                 asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(own), "+v"(thr2) : "n"(NK0 < 15 ? NK0 : 15) : "memory");
 #ifndef MI_K2P_DBG_TERMS_AFTER   /* (timing only: the terms after the full wait, as before) */
                 own_terms();
 #endif
+                if constexpr (N16 == 2) {
+                    // ... and into the registers the gathers above have consumed; the empty statements tie each result to
+                    // this side of the full wait (volatile statements keep their order)
+#pragma unroll
+                    for (int k = 0; k < NK0; ++k) {
+                        addr[k] = unpack16(nxt.w, k);
+                        asm volatile("" : "+v"(addr[k]));
+                    }
+                }
                 asm volatile("s_waitcnt lgkmcnt(0)"
                              : "+v"(word[0]), "+v"(word[1]), "+v"(word[2]), "+v"(word[3]), "+v"(word[4]), "+v"(word[5]),
                                "+v"(word[6]), "+v"(word[7]), "+v"(word[8]), "+v"(word[9]), "+v"(word[10]), "+v"(word[11]),
@@ -367,31 +433,64 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
             }
         }
         const uint32_t sw = (uint32_t)s + a.sweep_offset;
-        // four slots per trip (one Philox block per replica), the adjacency one slot ahead in two register sets
-        SlotAdj P = fetch_adj(0), Q;
+        if constexpr (N16 == 2) {
+            // the values one slot ahead as below, the neighbour dwords TWO (NA / NB), the unpacked addresses of one slot
+            SlotAdj P = fetch_val16(0), Q;
+            NbrPack NA = fetch_nbr16(0), NB;
+#pragma unroll
+            for (int k = 0; k < (RW < 16 ? RW : 16); ++k) addr[k] = unpack16(NA.w, k);
+            NA = fetch_nbr16(1);
 #pragma unroll 1
-        for (int t = 0; t < slots; t += 4) {
-            if constexpr (TW) {
+            for (int t = 0; t < slots; t += 4) {
                 K2P_TICK(t_top);
                 __builtin_amdgcn_s_barrier();                       // this group's thresholds are in the ring
                 K2P_TICK(t_barrier);
-            } else {
-                philox4x32_10((uint32_t)((t >> 2) * 64 + lane), sw, gidA, 0u, a.seed_lo, a.seed_hi, wa);
-                philox4x32_10((uint32_t)((t >> 2) * 64 + lane), sw, gidB, 0u, a.seed_lo, a.seed_hi, wb);
-            }
-            Q = fetch_adj(t + 1);
-            slot_body(integral_constant<int, 0>{}, t, P, wa[0], wb[0]);
-            if (t + 1 < slots) {                                    // wave-uniform
-                P = fetch_adj(t + 2);
-                slot_body(integral_constant<int, 1>{}, t + 1, Q, wa[1], wb[1]);
-                if (t + 2 < slots) {
-                    Q = fetch_adj(t + 3);
-                    slot_body(integral_constant<int, 2>{}, t + 2, P, wa[2], wb[2]);
-                    P = fetch_adj(t + 4);
-                    if (t + 3 < slots) slot_body(integral_constant<int, 3>{}, t + 3, Q, wa[3], wb[3]);
+                Q = fetch_val16(t + 1);
+                NB = fetch_nbr16(t + 2);
+                slot_body(integral_constant<int, 0>{}, t, P, NA, wa[0], wb[0]);
+                if (t + 1 < slots) {                                // wave-uniform
+                    P = fetch_val16(t + 2);
+                    NA = fetch_nbr16(t + 3);
+                    slot_body(integral_constant<int, 1>{}, t + 1, Q, NB, wa[1], wb[1]);
+                    if (t + 2 < slots) {
+                        Q = fetch_val16(t + 3);
+                        NB = fetch_nbr16(t + 4);
+                        slot_body(integral_constant<int, 2>{}, t + 2, P, NA, wa[2], wb[2]);
+                        P = fetch_val16(t + 4);
+                        NA = fetch_nbr16(t + 5);
+                        if (t + 3 < slots) slot_body(integral_constant<int, 3>{}, t + 3, Q, NB, wa[3], wb[3]);
+                    }
                 }
+                ring_buf ^= 2048u;
             }
-            if constexpr (TW) ring_buf ^= 2048u;
+        } else {
+            NbrPack none;
+            // four slots per trip (one Philox block per replica), the adjacency one slot ahead in two register sets
+            SlotAdj P = fetch_adj(0), Q;
+    #pragma unroll 1
+            for (int t = 0; t < slots; t += 4) {
+                if constexpr (TW) {
+                    K2P_TICK(t_top);
+                    __builtin_amdgcn_s_barrier();                       // this group's thresholds are in the ring
+                    K2P_TICK(t_barrier);
+                } else {
+                    philox4x32_10((uint32_t)((t >> 2) * 64 + lane), sw, gidA, 0u, a.seed_lo, a.seed_hi, wa);
+                    philox4x32_10((uint32_t)((t >> 2) * 64 + lane), sw, gidB, 0u, a.seed_lo, a.seed_hi, wb);
+                }
+                Q = fetch_adj(t + 1);
+                slot_body(integral_constant<int, 0>{}, t, P, none, wa[0], wb[0]);
+                if (t + 1 < slots) {                                    // wave-uniform
+                    P = fetch_adj(t + 2);
+                    slot_body(integral_constant<int, 1>{}, t + 1, Q, none, wa[1], wb[1]);
+                    if (t + 2 < slots) {
+                        Q = fetch_adj(t + 3);
+                        slot_body(integral_constant<int, 2>{}, t + 2, P, none, wa[2], wb[2]);
+                        P = fetch_adj(t + 4);
+                        if (t + 3 < slots) slot_body(integral_constant<int, 3>{}, t + 3, Q, none, wa[3], wb[3]);
+                    }
+                }
+                if constexpr (TW) ring_buf ^= 2048u;
+            }
         }
         accepted += (unsigned long long)accA + (liveB ? (unsigned long long)accB : 0ull);
         accA = accB = 0;
@@ -461,24 +560,45 @@ int launch_pair(KernelT kernel, const EllArgs &a, bool tw, hipStream_t st, int r
 }  // namespace
 
 // a.adj4 must hold the pair packing (neighbour word = 4 * index)
-int mi_launch_csr_rank1_pair(const EllArgs &a, bool tw, hipStream_t st)
+int mi_launch_csr_rank1_pair(const EllArgs &a, bool tw, hipStream_t st, const uint4 *adj16, const uint4 *adj16_trim, int *adj_bytes)
 {
     if (!a.adj4) return fail(MI_EHIP, "csr_rank1 pair kernel: packed adjacency missing");
+#ifdef MI_K2P_NOFETCH
+    adj16 = adj16_trim = nullptr;             // (the timing builds are arms of the 32-bit packing)
+#endif
     // the ring costs LDS: beyond 64 slots only seven workgroups (14 replicas) fit a CU, and a run that fills the chip
     // (16 replicas per CU) would take two rounds -- such models keep the kernel without a threshold wavefront
     if (tw && ((size_t)a.slots * 256 + 4096) * 8 > 160 * 1024 && a.R > 2 * 7 * 256) tw = false;
+    // (which packing the launched kernel reads, in bytes per slot and wavefront: mi_sa_last_adjacency_bytes_per_slot)
+    auto fetches = [&](int bytes) { if (adj_bytes) *adj_bytes = bytes; };
     if (a.wslot >= 0) {                       // pair-term weights (16 entries per variable)
         if (a.D != 16) return fail(MI_EUNSUPPORTED, "csr_rank1 pair kernel: pair-term weights at slot-ELL width %d not built", a.D);
+        fetches(8448);
         return tw ? launch_pair(k_anneal_csr_rank1_pair<16, true, true>, a, true, st)
                   : launch_pair(k_anneal_csr_rank1_pair<16, false, true>, a, false, st);
     }
+    EllArgs b = a;
+    if (a.D == 16 && tw && a.adj4_trim && adj16_trim) {   // rows of at most 15 entries, 16-bit neighbour words
+        b.adj4 = adj16_trim;
+        fetches(6144);
+        if (a.trim_rw == 15) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 15, 2>, b, true, st, 15);
+        if (a.trim_rw == 14) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 14, 2>, b, true, st, 14);
+        if (a.trim_rw == 13) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 13, 2>, b, true, st, 13);
+    }
     if (a.D == 16 && tw && a.adj4_trim) {     // rows of at most 15 entries: the trimmed packing (see the kernel)
-        EllArgs b = a;
         b.adj4 = a.adj4_trim;
+        fetches(a.trim_rw == 15 ? 7936 : (a.trim_rw == 14 ? 7424 : 6912));
         if (a.trim_rw == 15) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 15>, b, true, st, 15);
         if (a.trim_rw == 14) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 14>, b, true, st, 14);
         if (a.trim_rw == 13) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 13>, b, true, st, 13);
     }
+    if (adj16 && ((a.D == 16 && tw) || a.D == 32)) {   // full rows, 16-bit neighbour words (+ the dword of linear terms)
+        b.adj4 = adj16;
+        fetches(a.D == 16 ? 6400 : 12544);
+        if (a.D == 16) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 16, 2>, b, true, st);
+        return launch_pair(k_anneal_csr_rank1_pair<32, false, false, 32, 1>, b, false, st);
+    }
+    fetches(a.D == 16 ? 8448 : 16640);
     if (a.D == 16 && tw) return launch_pair(k_anneal_csr_rank1_pair<16, true>, a, true, st);
     if (a.D == 16) return launch_pair(k_anneal_csr_rank1_pair<16, false>, a, false, st);
     if (a.D == 32) return launch_pair(k_anneal_csr_rank1_pair<32, false>, a, false, st);

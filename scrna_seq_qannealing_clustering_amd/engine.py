@@ -579,6 +579,13 @@ class Problem:
         _lib.check(_lib.load().mi_sa_last_kernel_name(self._h, buf, 256))
         return buf.value.decode()
 
+    def adjacency_bytes_per_slot(self) -> int:
+        """Packed adjacency bytes one wavefront fetched per 64-variable slot in the last anneal (which packing the pair
+        kernel read: 6144 / 6400 / 12544 with 16-bit neighbour words, 7936 / 8448 / 16640 without); 0 for other kernels."""
+        k = C.c_int(0)
+        _lib.check(_lib.load().mi_sa_last_adjacency_bytes_per_slot(self._h, C.byref(k)))
+        return int(k.value)
+
     def fetch(self, states: bool = True, energies: bool = True):
         if self._last is None:
             raise RuntimeError("fetch() before anneal()")
