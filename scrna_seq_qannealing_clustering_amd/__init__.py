@@ -10,6 +10,7 @@ Public surface:
     clustering_modularity    weighted modularity at a resolution (Seurat's FindClusters objective)
     clustering_modularity_sweep  the same at several resolutions in one GPU launch
     preprocess               counts -> log-normalised matrix -> variable genes -> scaled matrix -> PCA coordinates (module)
+    umap, run_umap           Seurat's RunUMAP: kNN -> fuzzy graph -> deterministic layout (module and its driver)
 """
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
 from .models import (PottsModel, QuboModel, add_size_window_penalty, build_bqm2_qubo,
@@ -21,7 +22,7 @@ __all__ = [
     "MI355XSampler", "SampleSet", "QuboModel", "PottsModel", "BinaryQuadraticModel",
     "DiscreteQuadraticModel", "build_bqm_qubo", "build_bqm2_qubo", "build_bqm3_cut_qubo",
     "build_dqm_potts", "add_size_window_penalty", "default_beta_range", "make_beta_schedule",
-    "qubo_dict_to_model", "preprocess",
+    "qubo_dict_to_model", "preprocess", "umap", "run_umap",
 ]
 
 
@@ -35,7 +36,10 @@ def __getattr__(name):
                 "clustering_modularity_sweep"):
         from . import clustering
         return getattr(clustering, name)
-    if name == "preprocess":
+    if name in ("preprocess", "umap"):
         import importlib
-        return importlib.import_module(".preprocess", __name__)
+        return importlib.import_module("." + name, __name__)
+    if name == "run_umap":
+        from .umap import run_umap
+        return run_umap
     raise AttributeError(name)

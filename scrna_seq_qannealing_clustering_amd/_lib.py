@@ -116,6 +116,17 @@ def _declare(lib):
         "mi_prep_fetch_scaled": (C.c_int, [vp, f32p]),
         "mi_prep_gram": (C.c_int, [vp, f64p, f32p]),
         "mi_prep_project": (C.c_int, [vp, f32p, C.c_int, f32p, f32p]),
+        # include/mi_umap.h
+        "mi_umap_knn_f32": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, pp, f32p]),
+        "mi_umap_destroy": (C.c_int, [vp]),
+        "mi_umap_fetch_knn": (C.c_int, [vp, i32p, f32p]),
+        "mi_umap_smooth": (C.c_int, [vp, f32p]),
+        "mi_umap_fetch_smooth": (C.c_int, [vp, f64p, f64p]),
+        "mi_umap_union": (C.c_int, [vp, f32p]),
+        "mi_umap_info": (C.c_int, [vp, ip, ip, C.POINTER(C.c_int64), ip, f32p]),
+        "mi_umap_fetch_graph": (C.c_int, [vp, C.POINTER(C.c_int64), i32p, f32p]),
+        "mi_umap_layout_f32": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), i32p, f32p, f32p, C.c_float, C.c_float,
+                                         C.c_float, C.c_int, C.c_int, C.c_uint64, C.c_int, f32p, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
@@ -137,6 +148,8 @@ EXPORTS = (
     "mi_rank_sum_markers_f32",
     "mi_prep_create_f32", "mi_prep_destroy", "mi_prep_normalize", "mi_prep_fetch_normalized", "mi_prep_gene_stats",
     "mi_prep_clipped_variance", "mi_prep_select", "mi_prep_fetch_scaled", "mi_prep_gram", "mi_prep_project",
+    "mi_umap_knn_f32", "mi_umap_destroy", "mi_umap_fetch_knn", "mi_umap_smooth", "mi_umap_fetch_smooth", "mi_umap_union",
+    "mi_umap_info", "mi_umap_fetch_graph", "mi_umap_layout_f32",
 )
 
 

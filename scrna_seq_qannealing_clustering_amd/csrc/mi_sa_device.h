@@ -508,6 +508,13 @@ struct ComponentsArgs {
 int mi_components_dev(const ComponentsArgs &a, int B, bool force_global, hipStream_t st, int32_t *out_labels,
                       int32_t *out_count, float *out_kernel_ms);
 
+// snn_kernels.hip: the exact kNN (k_knn), the single-workgroup exclusive scan and the reverse-neighbour lists on DEVICE
+// pointers, for umap_kernels.hip
+int mi_snn_knn_dev(const float *dX, int n, int dim, int k, int32_t *d_nn, hipStream_t st);
+int mi_scan_exclusive_dev(const int *d_in, int *d_out, int n, hipStream_t st);
+int mi_snn_reverse_lists_dev(const int32_t *d_nn, int n, int k, int *d_cnt, int *d_rn_ptr, int *d_cursor, int32_t *d_rn_idx,
+                             hipStream_t st);
+
 // Energy of the final state, E = sum_i x_i diag_i + 1/2 sum_{i,j} x_i x_j Q2_ij, with every fp32 matrix
 // entry added EXACTLY once into fp64 accumulators (lane l sums its own columns over all set rows; one
 // wave reduction at the end).  Independent of the cached fp32 fields, so the reported energies carry

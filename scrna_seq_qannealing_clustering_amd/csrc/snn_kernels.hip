@@ -494,6 +494,35 @@ int launch_knn(const float *dX, int n, int dim, int k, int32_t *d_nn, hipStream_
 }
 
 }  // namespace
+
+// S1 and S2 for other translation units (umap_kernels.hip): the same kernels on device pointers, enqueued on `st`
+int mi_snn_knn_dev(const float *dX, int n, int dim, int k, int32_t *d_nn, hipStream_t st)
+{
+    return dim <= 16 ? launch_knn<16>(dX, n, dim, k, d_nn, st)
+                     : (dim <= 32 ? launch_knn<32>(dX, n, dim, k, d_nn, st) : launch_knn<64>(dX, n, dim, k, d_nn, st));
+}
+
+int mi_scan_exclusive_dev(const int *d_in, int *d_out, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, st, d_in, d_out, n);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+// d_cnt, d_cursor: n + 1 ints, zeroed by the caller; d_rn_ptr: n + 1; d_rn_idx: n * k.  RN(m) = rn_idx[rn_ptr[m] .. rn_ptr[m + 1]),
+// in the order the fill's atomics arrived (not a function of the input: sort before use)
+int mi_snn_reverse_lists_dev(const int32_t *d_nn, int n, int k, int *d_cnt, int *d_rn_ptr, int *d_cursor, int32_t *d_rn_idx,
+                             hipStream_t st)
+{
+    const long long total = (long long)n * k;
+    const int gblocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_rn_count, dim3(gblocks), dim3(256), 0, st, d_nn, total, d_cnt);
+    hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, st, d_cnt, d_rn_ptr, n);
+    hipLaunchKernelGGL(k_rn_fill, dim3(gblocks), dim3(256), 0, st, d_nn, n, k, d_rn_ptr, d_cursor, d_rn_idx);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
 

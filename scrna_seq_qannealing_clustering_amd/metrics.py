@@ -706,3 +706,23 @@ def top_markers(result: dict, n: int = 2, labelling: int = 0) -> dict:
         order = idx[np.argsort(-fc[idx, k], kind="stable")]
         out[cid.item() if hasattr(cid, "item") else cid] = list(np.asarray(result["genes"])[order[:int(n)]])
     return out
+
+
+def knn_preservation(nn_high, Y, k=None, device: int = 0) -> float:
+    """Mean fraction of each point's high-dimensional neighbours (``nn_high``: n x k_high indices, column 0 the point
+    itself, as :func:`umap.knn` and :func:`snn.build_snn` return them; the point itself does not count) found among its
+    ``k`` nearest neighbours in the embedding ``Y`` (n x 2 or n x 3; ``k`` counts the point, default ``k_high``).  The
+    neighbours in ``Y`` come from the same exact kNN kernel, euclidean."""
+    from . import umap
+    nn_high = np.asarray(nn_high)
+    Y = np.asarray(Y)
+    if nn_high.ndim != 2 or nn_high.dtype.kind not in "iu" or nn_high.shape[1] < 2:
+        raise ValueError("nn_high must be an (n, k) integer array with k >= 2")
+    if Y.ndim != 2 or Y.shape[0] != nn_high.shape[0]:
+        raise ValueError("Y must be (n, c) with n = %d" % nn_high.shape[0])
+    k = nn_high.shape[1] if k is None else int(k)
+    if not 2 <= k <= nn_high.shape[1]:
+        raise ValueError("k must lie in [2, %d] (got %d)" % (nn_high.shape[1], k))
+    nn_low, _ = umap.knn(Y, k, "euclidean", device)
+    hit = (nn_high[:, 1:k, None] == nn_low[:, None, 1:]).any(axis=2)
+    return float(hit.mean())

@@ -260,3 +260,32 @@ def disconnected_components(G, min_valid: int = 15, verbose: bool = False):
             for node in s.nodes():
                 G.nodes[node]["valid"] = 0
     return G, S, lengths
+
+
+def plot_and_save_embedding(coords, labels, path, title=None):
+    """Seurat's ``DimPlot(reduction = "umap", group.by = ...)`` (`R/pbmc3k/Pbmc3k_assess_QA_clusters.Rmd:96-108`): the first two
+    columns of ``coords`` (n x 2 or n x 3, e.g. :func:`umap.run_umap`'s), one colour and one legend entry per distinct
+    label (``labels=None``: one colour).  Returns the labels in legend order, or None when matplotlib is missing."""
+    import numpy as np
+    coords = np.asarray(coords, dtype=np.float64)
+    if coords.ndim != 2 or coords.shape[1] < 2:
+        raise ValueError("coords must be (n, 2) or (n, 3)")
+    labels = np.zeros(len(coords), dtype=np.int64) if labels is None else np.asarray(labels)
+    if labels.shape != (len(coords),):
+        raise ValueError("labels must have one entry per point (%d)" % len(coords))
+    plt = _canvas(coords)
+    if plt is None:
+        return None
+    groups = sorted(set(labels.tolist()))
+    cmap = plt.get_cmap("tab20")
+    for q, lab in enumerate(groups):
+        sel = labels == lab
+        plt.scatter(coords[sel, 0], coords[sel, 1], s=4, color=cmap(q % 20), label=str(lab), linewidths=0)
+    plt.xlabel("UMAP_1")
+    plt.ylabel("UMAP_2")
+    if title:
+        plt.title(title)
+    if 1 < len(groups) <= 40:
+        plt.legend(markerscale=3, fontsize="small", loc="center left", bbox_to_anchor=(1.0, 0.5), frameon=False)
+    _save(plt, path)
+    return groups

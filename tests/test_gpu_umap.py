@@ -1,0 +1,317 @@
+"""UMAP on the device (csrc/umap_kernels.hip, include/mi_umap.h, scrna_seq_qannealing_clustering_amd/umap.py) against the numpy
+restatement of chain U in tests/umap_reference.py.
+
+U1 - U3: the neighbour table is `build_snn`'s; the distances are the specification's f32 chain evaluated by the reference
+from the device's own indices (2 f32 steps: the reference rounds an fp64 fmaf to f32, the device fuses; then sqrtf); rho is
+exact; sigma and the weights hold the project's fp64 tolerance (the weights one f32 step after their store); the structure
+is equal and w is symmetric bit for bit.  U4: D32, the largest difference between the reference's float32 and fp64
+evaluations of the same input, is the scale; the device may differ from the fp64 evaluation by 4 D32 (another summation
+order, v_log_f32 / v_exp_f32).  The small hand checks (n = 2, coincident points) have no D32 to speak of and use a bound from
+the formats instead: see SMALL_TOL."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import prep_reference as prep_ref
+import umap_reference as ref
+from scrna_seq_qannealing_clustering_amd import _lib, metrics, preprocess, snn, umap
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-9                                   # the project's fp64 tolerance (tests/test_gpu_prep.py)
+EINVAL, EUNSUPPORTED, ESTATE = -1, -5, -6
+A32, B32 = (float(np.float32(v)) for v in umap.find_ab_params(1.0, 0.1))
+T8 = 8
+# v_log_f32 and v_exp_f32 are good to one f32 step; the exponent b log2(s) (|.| <= 32 for the s of these tests) turns that
+# into a relative error of at most 2^-18 in s^b.  Every term is clamped to 4 and alpha <= 1, so T epochs of 1 + neg terms
+# are off by at most T (1 + neg) 4 2^-18.
+SMALL_TOL = T8 * 6 * 4.0 * 2.0 ** -18
+
+
+def ulps(a, b):
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    assert (a >= 0).all() and (b >= 0).all()
+    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
+
+
+def check_graph(X, k, metric):
+    """U1 - U3 of the device against the reference -> the device's result"""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    n = len(X)
+    g = umap.fuzzy_graph(X, k, metric)
+    Xs = ref.normalize_rows(X) if metric == "cosine" else X
+    assert np.array_equal(g.nn, snn.build_snn(Xs, k).nn)
+    assert g.dist.dtype == np.float32 and not g.dist[:, 0].any()
+    want = ref.distances(Xs, g.nn, metric)
+    assert ulps(g.dist, want).max() <= 2
+    rho, sigma, _, _ = ref.smooth(g.dist)
+    assert np.array_equal(g.rho, rho)
+    np.testing.assert_allclose(g.sigma, sigma, rtol=RTOL, atol=0.0)
+    rowptr, col, w64, w32 = ref.union(g.nn, g.dist, g.rho, g.sigma)
+    assert np.array_equal(g.rowptr, rowptr) and np.array_equal(g.col, col)
+    assert g.weights.dtype == np.float32 and ulps(g.weights, w32).max(initial=0) <= 1
+    M = np.zeros((n, n), dtype=np.float32)
+    M[np.repeat(np.arange(n), np.diff(g.rowptr)), g.col] = g.weights
+    assert np.array_equal(M, M.T) and not M.diagonal().any()
+    assert g.max_degree == int(np.diff(rowptr).max()) and g.w_max == float(g.weights.max(initial=0))
+    assert all(g.timing[s] >= 0.0 for s in ("knn_ms", "smooth_ms", "union_ms"))
+    return g
+
+
+# ---- 1. U1 - U3 at the edges of the kernels ---------------------------------------------------------------------------------
+
+SHAPES = [(n, k, dim) for n in (2, 63, 65, 257) for k in (2, 15, 64) for dim in (1, 3, 50) if k <= n]
+
+
+@pytest.mark.parametrize("metric", ["euclidean", "cosine"])
+@pytest.mark.parametrize("n,k,dim", SHAPES)
+def test_graph_stages(n, k, dim, metric):
+    rng = np.random.default_rng(1000 * n + 10 * k + dim)
+    check_graph(rng.normal(size=(n, dim)) + 0.5, k, metric)
+
+
+# ---- 2. special inputs ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("metric", ["euclidean", "cosine"])
+def test_duplicated_points(metric):
+    rng = np.random.default_rng(7)
+    X = rng.normal(size=(70, 4)).astype(np.float32)
+    X[10:15] = X[10]                                              # five copies: with k = 4 all three neighbours are duplicates
+    X[30:32] = X[30]                                              # two copies: one duplicate neighbour, rho > 0
+    g = check_graph(X, 4, metric)
+    assert not g.rho[10:15].any() and not g.dist[10:15].any()
+    _, _, binds, mean_i = ref.smooth(g.dist)
+    assert binds[10:15].all()                                     # psum is the constant 3 > log2(4): the floor is all there is
+    np.testing.assert_allclose(g.sigma[10:15], 1e-3 * np.cumsum(mean_i)[-1] / 70, rtol=RTOL)
+    assert g.dist[30, 1] == 0.0 and g.rho[30] > 0.0
+
+
+def test_zero_row_under_cosine():
+    rng = np.random.default_rng(8)
+    X = rng.normal(size=(66, 5)).astype(np.float32)
+    X[20] = 0.0
+    g = check_graph(X, 6, "cosine")
+    assert np.isfinite(g.dist).all() and np.isfinite(g.sigma).all() and np.isfinite(g.weights).all()
+    np.testing.assert_allclose(g.dist[20, 1:], 0.5, rtol=1e-6)    # |0 - u|^2 / 2
+
+
+def test_hub_row_crosses_the_wavefront():
+    X = np.zeros((129, 64), dtype=np.float32)
+    others = np.delete(np.arange(129), 64)                        # the hub sits in the middle of the index range
+    X[others[:64], np.arange(64)] = 1.5
+    X[others[64:], np.arange(64)] = -1.5
+    g = check_graph(X, 2, "euclidean")
+    assert np.all(g.nn[others, 1] == 64)
+    assert np.diff(g.rowptr)[64] == 128 and g.max_degree == 128
+
+
+# ---- 3. the layout against the reference -----------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def handmade():
+    rowptr, col, w = ref.handmade_graph(T=T8)
+    n = len(rowptr) - 1
+    deg = np.diff(rowptr)
+    assert n % 64 and deg[7] == 130 and deg[50] == 0 and deg[n - 1] == 1 and w.max() == 1.0
+    assert (w < 1.0 / T8).sum() == 4 and 0.3 < w.mean() < 0.7
+    return rowptr, col, w
+
+
+def start(n, c, seed=3):
+    return (np.random.default_rng(seed).normal(size=(n, c)) * 4.0).astype(np.float32)
+
+
+@pytest.mark.parametrize("neg", [0, 5])
+@pytest.mark.parametrize("c", [2, 3])
+def test_layout_against_reference(handmade, c, neg):
+    """Observed on an MI355X (c, neg: D32, device - fp64): (2, 0): 1.450e-06, 1.450e-06; (2, 5): 1.385e-02, 3.237e-03;
+    (3, 0): 1.091e-06, 1.091e-06; (3, 5): 3.344e-04, 3.853e-05."""
+    rowptr, col, w = handmade
+    n = len(rowptr) - 1
+    Y0 = start(n, c)
+    y64 = ref.layout(rowptr, col, w, Y0, A32, B32, 1.0, T8, neg, 42, np.float64)
+    y32 = ref.layout(rowptr, col, w, Y0, A32, B32, 1.0, T8, neg, 42, np.float32)
+    Y = umap.layout(rowptr, col, w, Y0, A32, B32, T8, 1.0, neg, 42)
+    d32, dev = float(np.abs(y32 - y64).max()), float(np.abs(Y - y64).max())
+    print("layout c=%d neg=%d: D32 = %.3e, device = %.3e, moved = %.3f" % (c, neg, d32, dev, np.abs(y64 - Y0).max()))
+    assert Y.dtype == np.float32 and Y.shape == (n, c)
+    assert np.abs(y64 - Y0).max() > 0.5 and d32 > 0.0
+    assert dev <= 4.0 * d32
+    assert np.array_equal(Y[50], Y0[50])                          # the empty row, bit for bit
+    assert np.array_equal(Y[n - 1], Y0[n - 1])                    # its only edge never fires
+    # without the edge {n - 2, n - 1} (below 1 / T; the last entry of the CSR both ways: no other entry is renumbered)
+    assert np.array_equal(Y, umap.layout(*ref.drop_edge(rowptr, col, w, n - 2, n - 1), Y0, A32, B32, T8, 1.0, neg, 42))
+    if neg == 0:                                                  # ... and without the one inside the ring
+        assert np.array_equal(Y, umap.layout(*ref.drop_edge(rowptr, col, w, 3, 4), Y0, A32, B32, T8, 1.0, 0, 42))
+
+
+@pytest.mark.parametrize("neg", [0, 5])
+@pytest.mark.parametrize("n,density,lanes", [(70, 0.35, 32), (150, 0.5, 64)])
+def test_layout_wider_lane_groups(n, density, lanes, neg):
+    """the kernel gives a vertex 16, 32 or 64 lanes by the mean row length (the hand-made graph: 16); at 64 some rows loop.
+    With negatives the float32 trajectory itself wanders (D32 is large): neg = 0 is the sharp case.  Observed (D32, device):
+    n = 70: 6.566e-06, 1.003e-05 (neg 0), 2.324e-02, 5.654e-02 (neg 5); n = 150: 7.223e-05, 1.282e-04 and 3.802, 1.502."""
+    rowptr, col, w = ref.random_graph(n, density, n)
+    mean = rowptr[-1] / n
+    assert (16 < mean <= 32) if lanes == 32 else (mean > 32 and np.diff(rowptr).max() > 64)
+    Y0 = start(n, 2, seed=n)
+    y64 = ref.layout(rowptr, col, w, Y0, A32, B32, 1.0, T8, neg, 42, np.float64)
+    y32 = ref.layout(rowptr, col, w, Y0, A32, B32, 1.0, T8, neg, 42, np.float32)
+    Y = umap.layout(rowptr, col, w, Y0, A32, B32, T8, 1.0, neg, 42)
+    d32, dev = float(np.abs(y32 - y64).max()), float(np.abs(Y - y64).max())
+    print("layout n=%d lanes=%d neg=%d: D32 = %.3e, device = %.3e" % (n, lanes, neg, d32, dev))
+    assert np.abs(y64 - Y0).max() > 0.5 and d32 > 0.0 and dev <= 4.0 * d32
+
+
+@pytest.mark.parametrize("c", [2, 3])
+def test_layout_two_points(c):
+    rowptr, col, w = np.array([0, 1, 2]), np.array([1, 0], dtype=np.int32), np.array([0.7, 0.7], dtype=np.float32)
+    Y0 = start(2, c, seed=5) / 4.0
+    y64 = ref.layout(rowptr, col, w, Y0, A32, B32, 1.0, T8, 5, 42)
+    Y = umap.layout(rowptr, col, w, Y0, A32, B32, T8, 1.0, 5, 42)
+    assert np.abs(y64 - Y0).max() > 0.1 and np.abs(Y - y64).max() <= SMALL_TOL
+
+
+def test_layout_coincident_points_take_the_plus_four_rule():
+    rowptr = np.array([0, 2, 4, 6])
+    col = np.array([1, 2, 0, 2, 0, 1], dtype=np.int32)
+    w = np.ones(6, dtype=np.float32)
+    Y0 = np.array([[1.0, 2.0], [1.0, 2.0], [3.0, -1.0]], dtype=np.float32)
+    first = ref.layout(rowptr, col, w, Y0, A32, B32, 1.0, 1, 5, 42)
+    assert (first[1] - Y0[1]).min() >= 8.0                        # vertex 1 drew its twin more than once: +4 on every component each time
+    y64 = ref.layout(rowptr, col, w, Y0, A32, B32, 1.0, T8, 5, 42)
+    Y = umap.layout(rowptr, col, w, Y0, A32, B32, T8, 1.0, 5, 42)
+    assert np.abs(Y - y64).max() <= SMALL_TOL
+    assert np.abs(umap.layout(rowptr, col, w, Y0, A32, B32, 1, 1.0, 5, 42) - first).max() <= SMALL_TOL
+
+
+# ---- 4. determinism --------------------------------------------------------------------------------------------------------
+
+def test_determinism(handmade):
+    rowptr, col, w = handmade
+    Y0 = start(len(rowptr) - 1, 2)
+    runs = {(neg, seed): umap.layout(rowptr, col, w, Y0, A32, B32, T8, 1.0, neg, seed)
+            for neg in (0, 5) for seed in (42, 43, 2 ** 40 + 42)}
+    assert np.array_equal(runs[5, 42], umap.layout(rowptr, col, w, Y0, A32, B32, T8, 1.0, 5, 42))
+    assert not np.array_equal(runs[5, 42], runs[5, 43])
+    assert not np.array_equal(runs[5, 42], runs[5, 2 ** 40 + 42])       # the high word of the seed is part of the key
+    assert np.array_equal(runs[0, 42], runs[0, 43])
+    X = np.random.default_rng(9).normal(size=(100, 5)).astype(np.float32)
+    r1, r2 = (umap.run_umap(X, n_neighbors=10, n_epochs=20) for _ in range(2))
+    assert np.array_equal(r1.coords, r2.coords) and np.array_equal(r1.weights, r2.weights)
+
+
+# ---- 5. quality on planted data --------------------------------------------------------------------------------------------
+
+def test_planted_blobs_quality():
+    """Three blobs, n = 600, dim 10, centres 10 sd apart, k = 15, T = 200, euclidean.  Both runs must put >= 0.95 of a point's 15
+    nearest embedding neighbours into its blob.  knn_preservation of the device run >= the reference run's (seed 42) minus
+    three times the spread (max - min) of the reference's value over seeds 0 .. 7: the two are different rounding trajectories of
+    one process, and seed spread is the scale of honest disagreement.  Observed: device 0.3255, reference 0.3161, spread 0.0098
+    (margin 0.029)."""
+    X, labels = ref.blobs(0)
+    a, b = (float(np.float32(v)) for v in umap.find_ab_params(1.0, 0.3))
+    Y0 = umap.pca_init(X, 2)
+    nn_ref, rowptr, col, w = ref.reference_graph(X, 15)
+    kps = []
+    for seed in list(range(8)) + [42]:
+        Yr = ref.layout(rowptr, col, w, Y0, a, b, 1.0, 200, 5, seed)
+        kps.append(ref.knn_preservation(nn_ref, Yr))
+    assert ref.label_purity(Yr, labels, 16) >= 0.95                # the reference alone satisfies the condition
+    margin = 3.0 * (max(kps[:8]) - min(kps[:8]))
+    r = umap.run_umap(X, n_neighbors=15, metric="euclidean", n_epochs=200, seed=42)
+    kp = metrics.knn_preservation(r.nn, r.coords)
+    print("knn_preservation: device %.4f, reference %.4f, seed spread %.4f" % (kp, kps[8], margin / 3.0))
+    assert (r.a, r.b, r.n_epochs) == (a, b, 200)
+    assert ref.label_purity(r.coords, labels, 16) >= 0.95
+    # the device metric is the reference's (a near-tie at the k-th neighbour, ranked in f32 there and fp64 here, moves one of
+    # the 600 * 14 entries)
+    assert abs(kp - ref.knn_preservation(r.nn, r.coords)) <= 1e-3
+    assert kp >= kps[8] - margin
+
+
+# ---- 6. the chain, and the error codes -------------------------------------------------------------------------------------
+
+def test_chain_from_counts():
+    X, _ = prep_ref.planted_counts(0)
+    emb = preprocess.embed(X, nfeatures=prep_ref.PLANTED_FEATURES, npcs=20)
+    for c in (2, 3):
+        r = umap.run_umap(emb.coords[:, :15], n_components=c, n_epochs=30)
+        assert r.coords.shape == (len(X), c) and r.coords.dtype == np.float32 and np.isfinite(r.coords).all()
+        assert r.nn.shape == (len(X), 30) and r.n_epochs == 30 and len(r.col) == r.rowptr[-1] == len(r.weights)
+        for key in ("knn_ms", "smooth_ms", "union_ms", "layout_ms", "epoch_ms", "host_ms", "total_ms"):
+            assert r.timing[key] >= 0.0, key
+    assert umap.run_umap(emb.coords[:60, :15], n_neighbors=5, init=np.zeros((60, 2)), n_epochs=3).coords.shape == (60, 2)
+
+
+def raw_layout(n=3, c=2, rowptr=(0, 1, 2, 2), col=(1, 0), w=(1.0, 1.0), Y0=None, a=1.0, b=1.0, alpha=1.0, T=2, neg=1):
+    """mi_umap_layout_f32 itself: the Python layer would refuse most of these first"""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    col, w = np.asarray(col, dtype=np.int32), np.asarray(w, dtype=np.float32)
+    Y0 = np.ones((n, max(c, 1)), dtype=np.float32) * np.arange(n)[:, None] if Y0 is None else np.asarray(Y0, dtype=np.float32)
+    out = np.zeros_like(Y0)
+    p = lambda arr, t: arr.ctypes.data_as(C.POINTER(t))
+    return _lib.load().mi_umap_layout_f32(n, c, p(rowptr, C.c_int64), p(col, C.c_int32), p(w, C.c_float), p(Y0, C.c_float),
+                                          a, b, alpha, T, neg, C.c_uint64(1), 0, p(out, C.c_float), None)
+
+
+def test_layout_error_codes():
+    assert raw_layout() == 0
+    bad_y = np.zeros((3, 2), dtype=np.float32)
+    bad_y[2, 1] = np.nan
+    for kw in (dict(col=(0, 1), rowptr=(0, 1, 2, 2)),                       # diagonal entries
+               dict(rowptr=(0, 2, 3, 4), col=(2, 1, 0, 0), w=(1, 1, 1, 1)),  # unsorted row
+               dict(rowptr=(0, 2, 3, 4), col=(1, 1, 0, 0), w=(1, 1, 1, 1)),  # repeated column
+               dict(col=(3, 0)), dict(col=(-1, 0)),                         # out of range
+               dict(w=(np.nan, 1.0)), dict(w=(np.inf, 1.0)), dict(w=(0.0, 1.0)), dict(w=(-1.0, 1.0)),
+               dict(rowptr=(1, 1, 2, 2)), dict(rowptr=(0, 2, 1, 2)),
+               dict(T=0), dict(T=10001), dict(neg=-1), dict(neg=17),
+               dict(Y0=bad_y), dict(a=np.nan), dict(b=np.inf), dict(alpha=np.nan), dict(n=0)):
+        assert raw_layout(**kw) == EINVAL, kw
+    for kw in (dict(c=1), dict(c=4)):
+        assert raw_layout(**kw) == EUNSUPPORTED, kw
+    # nnz >= 2^32 is refused from rowptr alone (col and w are never read)
+    assert raw_layout(rowptr=(0, 2 ** 32, 2 ** 32, 2 ** 32)) == EUNSUPPORTED
+    lib = _lib.load()
+    assert lib.mi_umap_layout_f32(3, 2, None, None, None, None, 1.0, 1.0, 1.0, 2, 1, C.c_uint64(1), 0, None, None) == EINVAL
+    # through the Python layer a bad graph is the package's usual exception
+    with pytest.raises(_lib.MiSaError) as ei:
+        umap.layout([0, 1, 2], [0, 1], [1.0, 1.0], np.zeros((2, 2)), 1.0, 1.0)
+    assert ei.value.code == EINVAL and "diagonal" in ei.value.message
+
+
+def test_graph_error_codes_and_state():
+    lib = _lib.load()
+    X = np.random.default_rng(11).normal(size=(12, 3)).astype(np.float32)
+    xp = X.ctypes.data_as(C.POINTER(C.c_float))
+    h = C.c_void_p()
+    for args in ((None, 12, 3, 4, 0), (xp, 1, 3, 2, 0), (xp, 12, 0, 4, 0), (xp, 4, 65, 2, 0), (xp, 12, 3, 1, 0),
+                 (xp, 12, 3, 13, 0), (xp, 12, 3, 4, 2), (xp, 12, 3, 4, -1)):
+        assert lib.mi_umap_knn_f32(*args, 0, C.byref(h), None) == EINVAL, args[1:]
+    assert lib.mi_umap_knn_f32(xp, 12, 3, 4, 0, 99, C.byref(h), None) == EINVAL
+    B = X.copy()
+    B[5, 1] = np.inf
+    assert lib.mi_umap_knn_f32(B.ctypes.data_as(C.POINTER(C.c_float)), 12, 3, 4, 0, 0, C.byref(h), None) == EINVAL
+    assert lib.mi_umap_knn_f32(xp, 2 ** 23 + 1, 3, 4, 0, 0, C.byref(h), None) == EUNSUPPORTED
+    assert lib.mi_umap_smooth(None, None) == EINVAL and lib.mi_umap_info(None, None, None, None, None, None) == EINVAL
+
+    def code_of(fn, *a):
+        with pytest.raises(_lib.MiSaError) as ei:
+            fn(*a)
+        return ei.value.code
+    with umap.FuzzyGraph(X, 4, "euclidean") as g:
+        assert code_of(g.fetch_smooth) == ESTATE
+        assert code_of(g.union) == ESTATE
+        assert code_of(g.fetch_graph) == ESTATE
+        assert g.info() == {"nnz": 0, "max_degree": 0, "w_max": 0.0}
+        g.smooth()
+        assert code_of(g.fetch_graph) == ESTATE
+        rho, _ = g.fetch_smooth()
+        g.union()
+        rowptr, col, w = g.fetch_graph()
+        assert g.info()["nnz"] == len(col) == rowptr[-1] and np.array_equal(g.smooth().fetch_smooth()[0], rho)
+        assert code_of(g.fetch_graph) == ESTATE                   # a new smoothing invalidates the graph
+        assert np.array_equal(g.union().fetch_graph()[2], w)
+    with pytest.raises(ValueError):
+        g.fetch_knn()
