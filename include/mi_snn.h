@@ -31,7 +31,11 @@ extern "C" {
 
 typedef struct mi_snn_graph mi_snn_graph;
 
-/* X: n x dim row-major fp32 (e.g. PCA coordinates), 1 <= dim <= 64; k = k.param (the point itself counts,
+/* X: n x dim row-major fp32 (e.g. PCA coordinates), 1 <= dim <= 64.  Every cell must be finite, and the coordinate
+ * ranges r_c = max_i x_ic - min_i x_ic must satisfy sum_c r_c^2 <= FLT_MAX / 2, so that no fp32 squared distance can
+ * overflow: otherwise MI_EINVAL ("X[i, c] is not finite" resp. a message naming the widest range), decided on the
+ * host before any device work.  A distance of +inf or NaN would never enter a neighbour list and the table would hold
+ * no valid index there.  k = k.param (the point itself counts,
  * 2 <= k <= 64, k <= n); prune = prune.SNN (weights below it are dropped; 0 keeps everything);
  * ord = degree cap of the trim (<= 0: no trim).  Builds the graph on `device` and keeps it in HBM. */
 int mi_snn_build_f32(const float *X, int n, int dim, int k, double prune, int ord, int device,

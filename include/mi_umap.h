@@ -49,7 +49,10 @@ typedef struct mi_umap_graph mi_umap_graph;
  * metric MI_UMAP_EUCLIDEAN: d = sqrtf(d2).  MI_UMAP_COSINE: every row is first divided by its norm on the host (fp64 sum of
  * squares in coordinate order, sqrt, fp64 quotient rounded to f32; an all-zero row stays zero), the search is euclidean
  * on those rows and d = d2 / 2 (= 1 - cos up to rounding, and the same ordering).  MI_EINVAL for NULL arguments, the ranges
- * above, an unknown metric, a non-finite coordinate; MI_EUNSUPPORTED for n > MI_UMAP_MAX_POINTS or n * k >= 2^30. */
+ * above, an unknown metric, a non-finite coordinate, or coordinate ranges r_c = max_i x_ic - min_i x_ic with sum_c r_c^2 >
+ * FLT_MAX / 2 (an fp32 squared distance could overflow and the point would get no neighbour; the same rule as mi_snn.h,
+ * applied to the rows the search sees, so the cosine metric always passes it); MI_EUNSUPPORTED for n > MI_UMAP_MAX_POINTS or
+ * n * k >= 2^30. */
 int mi_umap_knn_f32(const float *X, int n, int dim, int k, int metric, int device, mi_umap_graph **out,
                     float *out_kernel_ms);
 int mi_umap_destroy(mi_umap_graph *g);

@@ -514,6 +514,9 @@ int mi_snn_knn_dev(const float *dX, int n, int dim, int k, int32_t *d_nn, hipStr
 int mi_scan_exclusive_dev(const int *d_in, int *d_out, int n, hipStream_t st);
 int mi_snn_reverse_lists_dev(const int32_t *d_nn, int n, int k, int *d_cnt, int *d_rn_ptr, int *d_cursor, int32_t *d_rn_idx,
                              hipStream_t st);
+// the input domain of k_knn (host pointer, no device work): MI_EINVAL for a non-finite cell or coordinate ranges wide enough for
+// an fp32 squared distance to overflow -- either would leave INT_MAX in the neighbour table
+int mi_snn_check_points(const float *X, int n, int dim);
 
 // Energy of the final state, E = sum_i x_i diag_i + 1/2 sum_{i,j} x_i x_j Q2_ij, with every fp32 matrix
 // entry added EXACTLY once into fp64 accumulators (lane l sums its own columns over all set rows; one

@@ -19,6 +19,7 @@
 //                      what columns < i deleted); column i only depends on its smaller NEIGHBOURS, so many
 //                      columns are in flight, each waiting for those (k_trim = the one-workgroup fallback).
 //   S5 k_compact_*     drops the deleted entries.
+#include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -523,6 +524,41 @@ int mi_snn_reverse_lists_dev(const int32_t *d_nn, int n, int k, int *d_cnt, int 
     return MI_OK;
 }
 
+// The input domain of k_knn, checked on the host before any device work (snn_build_impl, mi_umap_knn_f32).  k_knn starts
+// every neighbour slot as (INFINITY, INT_MAX) and inserts a candidate only when d < bd[KM - 1]: a distance that is +inf or
+// NaN is never inserted, INT_MAX would reach nn[] and the kernels after it (k_rn_count, k_umap_dist) index with it.  So:
+//   1. every cell of X is finite;
+//   2. no squared distance can overflow.  With r_c = max_i x_ic - min_i x_ic and S = sum_c r_c^2 (fp64; at most
+//      64 * (2 FLT_MAX)^2, far inside fp64), every pair's exact squared distance is at most S.  The fp32 chain
+//      d = fmaf(x_ic - x_jc, x_ic - x_jc, d) rounds the difference once (so its square carries (1 + 2^-24)^2) and the
+//      running sum once per step, dim steps in all: its result exceeds the exact value by at most a factor
+//      (1 + 2^-24)^(2 dim + dim) < 1 + 2e-5 at dim = 64 (roundings in the subnormal range add at most 2^-149 each).
+//      S <= FLT_MAX / 2 therefore keeps every d finite (and every difference too: |x_ic - x_jc| <= sqrt(S) < 1.31e19).
+// With both, each point has n - 1 >= k - 1 finite candidates and every slot the kernel writes out holds a real index.
+int mi_snn_check_points(const float *X, int n, int dim)
+{
+    const size_t cells = (size_t)n * dim;
+    for (size_t e = 0; e < cells; ++e)
+        if (!std::isfinite(X[e])) return fail(MI_EINVAL, "X[%lld, %lld] is not finite", (long long)(e / dim), (long long)(e % dim));
+    double S = 0.0, worst = -1.0, worst_lo = 0.0, worst_hi = 0.0;
+    int worst_c = 0;
+    for (int c = 0; c < dim; ++c) {
+        float lo = X[c], hi = X[c];
+        for (int i = 1; i < n; ++i) {
+            const float v = X[(size_t)i * dim + c];
+            lo = v < lo ? v : lo;
+            hi = v > hi ? v : hi;
+        }
+        const double r = (double)hi - (double)lo;
+        S += r * r;
+        if (r > worst) { worst = r; worst_c = c; worst_lo = lo; worst_hi = hi; }
+    }
+    if (!(S <= (double)FLT_MAX / 2.0))
+        return fail(MI_EINVAL, "the coordinate ranges are too wide: their squares sum to %.6g > FLT_MAX / 2 = %.6g (widest: coordinate %d "
+                    "spans [%.6g, %.6g]), fp32 squared distances would overflow", S, (double)FLT_MAX / 2.0, worst_c, worst_lo, worst_hi);
+    return MI_OK;
+}
+
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
 
@@ -589,6 +625,7 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
     if (!(prune >= 0.0)) return fail(MI_EINVAL, "prune must be >= 0");
     if ((size_t)n + kRowCap * 8 + 64 > 160 * 1024)
         return fail(MI_EUNSUPPORTED, "SNN kernel keeps one byte per point in LDS: n <= %d (got %d)", 160 * 1024 - kRowCap * 8 - 64, n);
+    if (const int rc0 = mi_snn_check_points(X, n, dim)) return rc0;
     int cnt = 0;
     if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
     if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);

@@ -383,13 +383,13 @@ int mi_umap_knn_f32(const float *X, int n, int dim, int k, int metric, int devic
     if (n > MI_UMAP_MAX_POINTS) return fail(MI_EUNSUPPORTED, "n = %d exceeds %d", n, MI_UMAP_MAX_POINTS);
     if ((long long)n * k >= (1ll << 30)) return fail(MI_EUNSUPPORTED, "n * k = %lld reaches 2^30", (long long)n * k);
     const size_t cells = (size_t)n * dim;
-    for (size_t e = 0; e < cells; ++e)
-        if (!std::isfinite(X[e])) return fail(MI_EINVAL, "X[%lld, %lld] is not finite", (long long)(e / dim), (long long)(e % dim));
-    TRY(pick_device(device));
-    mi_umap_graph *g = nullptr;
-    const int rc = guarded([&]() -> int {
-        std::vector<float> unit;
-        const float *src = X;
+    // the domain of k_knn (mi_snn_check_points: finite cells, no fp32 overflow of a squared distance), on the rows the search
+    // sees -- the normalised ones for the cosine metric, which always pass the range check -- and before any device work
+    std::vector<float> unit;
+    const float *src = X;
+    const int rc0 = guarded([&]() -> int {
+        for (size_t e = 0; e < cells; ++e)
+            if (!std::isfinite(X[e])) return fail(MI_EINVAL, "X[%lld, %lld] is not finite", (long long)(e / dim), (long long)(e % dim));
         if (metric == MI_UMAP_COSINE) {
             unit.resize(cells);
             for (int i = 0; i < n; ++i) {
@@ -401,6 +401,12 @@ int mi_umap_knn_f32(const float *X, int n, int dim, int k, int metric, int devic
             }
             src = unit.data();
         }
+        return mi_snn_check_points(src, n, dim);
+    });
+    if (rc0) return rc0;
+    TRY(pick_device(device));
+    mi_umap_graph *g = nullptr;
+    const int rc = guarded([&]() -> int {
         g = new mi_umap_graph();
         g->n = n; g->dim = dim; g->k = k; g->metric = metric; g->device = device;
         DevBufs tmp;

@@ -85,6 +85,11 @@ def build_snn(X: np.ndarray, k: int, prune: float = 0.0, ord: Optional[int] = No
     """``X``: (n, dim) coordinates (fp32 on the device), ``k`` = Seurat's ``k.param`` (self included),
     ``prune`` = ``prune.SNN``, ``ord`` = degree cap of the trim loop (None: no trim).
 
+    Accepted ``X``: every cell finite AFTER the cast to fp32, and coordinate ranges ``r_c = max_i x_ic - min_i x_ic`` with
+    ``sum_c r_c**2 <= FLT_MAX / 2`` (about 1.7e38), so that no fp32 squared distance overflows.  Anything else raises
+    ``MiSaError`` (code -1, MI_EINVAL) before the device is touched: a point at infinite distance from everything has no
+    neighbours to list.
+
     The notebooks' optional chunks (`Pbmc3k_general_data_preparation.Rmd:77-123`, `Kidney_data.Rmd:235-266` -- the
     reference's ``..._trimmed_15enh.gexf`` inputs, `main.py:105-110`): ``symmetric=False`` = the UNSYMMETRIC first
     trim (columns only), ``enhance="mutual"`` adds ``mutual_bonus`` (2 in the PBMC notebook, 1 in the kidney one) to
