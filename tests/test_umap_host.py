@@ -2,11 +2,13 @@
 (tests/umap_reference.py), without a GPU: the reference's Philox against the oracle's, the curve constants against the
 published umap-learn / Seurat values, the PCA initialisation's edges, the firing schedule, the smooth-kNN normalisation
 of the reference, every argument error of the Python layer (raised before any ctypes call), and the embedding plot."""
+import hashlib
 import os
 
 import numpy as np
 import pytest
 
+import umap_layout_cases as uc
 import umap_reference as ref
 from oracle import sa_oracle as so
 from scrna_seq_qannealing_clustering_amd import metrics, outputs, umap
@@ -87,6 +89,81 @@ def test_reference_layout_float32_tracks_fp64():
     assert np.isfinite(n5[0]).all() and not np.array_equal(n5[0], n5[1]) and not np.array_equal(n5[0], y64)
     assert np.abs(y64 - Y0).max() > 0.5                            # the points did move
     assert np.array_equal(y64[50], Y0[50].astype(np.float64))      # the empty row
+
+
+def test_reference_layout_default_path_is_unchanged():
+    """`mutate=None` is the function as it was before `mutate` existed: the stored hashes are the old function's results.
+    a = b = 1: pow(s, 1) and pow(s, 0) are exact in every libm, so the bits depend on numpy's +, -, *, / alone, while the run
+    still passes every line a mutation touches (schedule, alpha, Philox addressing, self-draws, 0.001, clamp)."""
+    rowptr, col, w = ref.handmade_graph()
+    Y0 = (np.random.default_rng(3).normal(size=(203, 3)) * 4.0).astype(np.float32)
+    want = {np.float64: "957183b472ef93c61ca18b907bc714c0189af1e9fc8f0996999ed5677da21557",
+            np.float32: "f837e6289e83855ea08f0bbb386761044cf2d8d7913fd470d867118ba65454ec"}
+    for dt, digest in want.items():
+        y = ref.layout(rowptr, col, w, Y0, 1.0, 1.0, 1.0, 8, 5, 2 ** 40 + 42, dt)
+        assert hashlib.sha256(np.ascontiguousarray(y).tobytes()).hexdigest() == digest
+    with pytest.raises(AssertionError):
+        ref.layout(rowptr, col, w, Y0, 1.0, 1.0, 1.0, 8, 5, 42, mutate="no such line")
+
+
+def test_graph_builders():
+    for name, (_, lanes, mean) in uc.GRAPHS.items():
+        rowptr, col, w = uc.graph(name)                            # (asserts the mean, the empty row, the long row, max w = 1)
+        n = len(rowptr) - 1
+        rows = np.repeat(np.arange(n), np.diff(rowptr))
+        M = np.zeros((n, n), dtype=np.float32)
+        M[rows, col] = w
+        assert not M.diagonal().any() and (np.diff(col)[np.diff(rows) == 0] > 0).all()
+        odd = int(rowptr[-1]) & 1                                  # an odd number of entries: exactly one has no mirror
+        assert ((M > 0) != (M.T > 0)).sum() == 2 * odd and np.array_equal(M[(M > 0) & (M.T > 0)], M.T[(M > 0) & (M.T > 0)])
+    assert uc.graph("mean16")[0][-1] == 16 * 67 and uc.graph("mean32+")[0][-1] == 32 * 67 + 1
+    for T in (8, 10000):
+        rowptr, col, w, edges = ref.schedule_graph(T)
+        assert w.max() == 1.0 and np.diff(rowptr)[7] == 1 and col[-1] == 6 and col[rowptr[7] - 1] == 7
+        assert ref.fire_counts(edges[6, 7], T) == 0 and ref.fire_counts(edges[4, 5], T) == 1
+        assert ref.fire_counts(edges[0, 1], T) == T and ref.fire_counts(edges[1, 2], T) == T - 1
+
+
+# which deviations a case can show at all: without negatives nothing is drawn
+NEEDS_NEG = ("philox_t_q", "philox_local_E", "keep_self", "no_eps")
+
+
+@pytest.mark.parametrize("group", ["g16", "g32", "g64", "mean"])
+def test_small_step_criterion_sees_errors(group):
+    """The conditions tests/test_gpu_umap_layout.py relies on, shown on the reference alone for every one of its cases:
+    D32 is storage rounding (<= 8 f32 steps of the largest coordinate; observed: at most 2.65 steps on the x4 starts, at most
+    6.87 on the x0.5 starts -- above 3 only at neg = 16, where a vertex moves up to 1.0), the largest move is >= 1000 D32
+    (observed: >= 3978), and every deviation of ref.MUTATIONS that changes the fp64 result at all changes it by more than
+    the 4 D32 the device is allowed.  Smallest observed (change / D32) over the cases where the deviation acts, x4 / x0.5 start:
+        philox_t_q 484 / 64931      philox_local_E 485 / 47848     fire_next 1112 / 49370      alpha_next 983 / 20230
+        keep_self 1539 / 15141      clamp_coef 5.4 / 501           no_eps 0.28 / 880
+    no_eps is asserted on the x0.5 starts only.  Leaving 0.001 out changes a repulsive term by the factor 0.001 / s; on the
+    x4 starts a drawn pair has s of the order 2 * c * 16 >= 64, the term itself is below 2 b / s^1.5, and 8 epochs of
+    2^-10 of that are below the rounding of a coordinate near 10: there the criterion cannot see it, which is why the cases
+    have a second start with s of the order 1.  clamp_coef acts without negatives too (an attraction at s < 1, b < 1)."""
+    seen = {}                                                     # mutation -> smallest change / D32
+    for case in uc.CASES:
+        g, c, neg, scale, seed, ab = case
+        if not g.startswith(group):
+            continue
+        rowptr, col, w, Y0, y64, d32, moved = uc.reference(case)
+        top = np.abs(Y0).max() if scale == 0.5 else np.abs(y64).max()
+        assert 0.0 < d32 <= 8.0 * np.spacing(np.float32(top)), uc.case_id(case)
+        assert moved >= 1000.0 * d32, uc.case_id(case)
+        for m in ref.MUTATIONS:
+            if neg == 0 and m in NEEDS_NEG:
+                continue
+            ym = ref.layout(rowptr, col, w, Y0, *uc.AB[ab], uc.LR, uc.T8, neg, seed, np.float64, mutate=m)
+            change = float(np.abs(ym - y64).max())
+            if change == 0.0:                                     # cannot act here (no self-draw, no term beyond the clamp)
+                assert m in ("keep_self", "clamp_coef"), (m, uc.case_id(case))
+                continue
+            if m == "no_eps" and scale != 0.5:
+                continue
+            assert change > 4.0 * d32, (m, uc.case_id(case), change / d32)
+            seen[m] = min(seen.get(m, np.inf), change / d32)
+    # every deviation acted, and was seen, in this group alone
+    assert set(seen) == set(ref.MUTATIONS), sorted(set(ref.MUTATIONS) - set(seen))
 
 
 def test_python_argument_errors(monkeypatch):

@@ -124,9 +124,24 @@ def fire_counts(p, T):
     return sum(int(np.floor(np.float32(t + 1) * p)) - int(np.floor(np.float32(t) * p)) >= 1 for t in range(T))
 
 
-def layout(rowptr, col, w, Y0, a, b, alpha0, T, neg, seed, dtype=np.float64):
+# One deliberate deviation each, named after the line of k_umap_layout it stands for; tests/test_umap_host.py shows that the
+# small-step criterion of the GPU tests sees every one of them.
+MUTATIONS = (
+    "philox_t_q",       # philox4x32_10(v, E, t, q): the counter words t and q exchanged
+    "philox_local_E",   # ... E the entry's index within its row (E - rowptr[v]) instead of the global CSR index
+    "fire_next",        # floorf(tf1 * pe) - floorf(tf0 * pe): the firing test of epoch t + 1
+    "alpha_next",       # alpha: the host passes the step of epoch t + 1
+    "keep_self",        # if (j == v) continue: the draw is not skipped (s = 0: it takes the +4 rule)
+    "no_eps",           # (0.001f + s): 0.001 left out of the repulsive denominator
+    "clamp_coef",       # clamp4(coef * d[c]): the clamp applied to the coefficient, clamp4(coef) * d[c]
+)
+
+
+def layout(rowptr, col, w, Y0, a, b, alpha0, T, neg, seed, dtype=np.float64, mutate=None):
     """U4 in `dtype` arithmetic.  The schedule (p_e, the firing test, alpha_t) is the specification's f32 / fp64 mix in both;
-    a, b, alpha0 are taken as f32 values.  A vertex's terms are added one by one in the specification's order."""
+    a, b, alpha0 are taken as f32 values.  A vertex's terms are added one by one in the specification's order.
+    `mutate`: None (the specification), or one of MUTATIONS: the specification with that one line wrong."""
+    assert mutate is None or mutate in MUTATIONS, mutate
     dt = np.dtype(dtype).type
     rowptr = np.asarray(rowptr, dtype=np.int64)
     col = np.asarray(col, dtype=np.int64)
@@ -143,6 +158,12 @@ def layout(rowptr, col, w, Y0, a, b, alpha0, T, neg, seed, dtype=np.float64):
     m2ab, twob, bm1 = dt(-2.0) * a * b, dt(2.0) * b, b - dt(1.0)
     k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
     E_all = np.arange(nnz, dtype=np.int64)
+    eps = dt(0.0) if mutate == "no_eps" else dt(0.001)
+
+    def force(coef, d):
+        if mutate == "clamp_coef":
+            return np.clip(coef, dt(-4.0), dt(4.0))[..., None] * d
+        return np.clip(coef[..., None] * d, dt(-4.0), dt(4.0))
 
     def sq(d):
         s = d[..., 0] * d[..., 0]
@@ -152,8 +173,9 @@ def layout(rowptr, col, w, Y0, a, b, alpha0, T, neg, seed, dtype=np.float64):
 
     qs = np.arange(neg, dtype=np.int64)[None, :]
     for t in range(T):
-        alpha = dt(np.float32(float(np.float32(alpha0)) * (1.0 - float(t) / float(T))))
-        fire = (np.floor(np.float32(t + 1) * p).astype(np.int64) - np.floor(np.float32(t) * p).astype(np.int64)) >= 1
+        ta, tf = t + (mutate == "alpha_next"), t + (mutate == "fire_next")
+        alpha = dt(np.float32(float(np.float32(alpha0)) * (1.0 - float(ta) / float(T))))
+        fire = (np.floor(np.float32(tf + 1) * p).astype(np.int64) - np.floor(np.float32(tf) * p).astype(np.int64)) >= 1
         E = E_all[fire]
         i, j = rows[E], col[E]
         terms = np.zeros((len(E), 1 + neg, c), dtype=dt)
@@ -163,16 +185,18 @@ def layout(rowptr, col, w, Y0, a, b, alpha0, T, neg, seed, dtype=np.float64):
             ok = s > 0
             ss = np.where(ok, s, dt(1.0))
             coef = (m2ab * np.power(ss, bm1)) / (a * np.power(ss, b) + dt(1.0))
-            terms[:, 0, :] = np.where(ok[:, None], np.clip(coef[:, None] * d, dt(-4.0), dt(4.0)), dt(0.0))
+            terms[:, 0, :] = np.where(ok[:, None], force(coef, d), dt(0.0))
             if neg:
-                jn = (philox4x32_10(i[:, None], E[:, None], t, qs, k0, k1)[0] % np.uint32(n)).astype(np.int64)
+                Ec = (E - rowptr[i] if mutate == "philox_local_E" else E)[:, None]
+                ctr = (i[:, None], Ec, qs, t) if mutate == "philox_t_q" else (i[:, None], Ec, t, qs)
+                jn = (philox4x32_10(*ctr, k0, k1)[0] % np.uint32(n)).astype(np.int64)
                 d = Y[i][:, None, :] - Y[jn]
                 s = sq(d)
                 ok = s > 0
                 ss = np.where(ok, s, dt(1.0))
-                coef = twob / ((dt(0.001) + ss) * (a * np.power(ss, b) + dt(1.0)))
-                term = np.where(ok[..., None], np.clip(coef[..., None] * d, dt(-4.0), dt(4.0)), dt(4.0))
-                terms[:, 1:, :] = np.where((jn == i[:, None])[..., None], dt(0.0), term)
+                coef = twob / ((eps + ss) * (a * np.power(ss, b) + dt(1.0)))
+                term = np.where(ok[..., None], force(coef, d), dt(4.0))
+                terms[:, 1:, :] = term if mutate == "keep_self" else np.where((jn == i[:, None])[..., None], dt(0.0), term)
         g = np.zeros((n, c), dtype=dt)
         np.add.at(g, np.repeat(i, 1 + neg), terms.reshape(-1, c))            # unbuffered: one term after the other
         Y = np.where(nonempty[:, None], Y + alpha * g, Y)
@@ -255,3 +279,50 @@ def random_graph(n, density, seed):
     rows, col = np.nonzero(W32)
     rowptr = np.concatenate([[0], np.cumsum((W32 > 0).sum(axis=1))]).astype(np.int64)
     return rowptr, col.astype(np.int32), W32[rows, col]
+
+
+def degree_graph(n, nnz, empty=(), hub=None, hub_deg=0, seed=0):
+    """A CSR of exactly `nnz` entries (mean row length nnz / n, any rational with denominator n): the rows in `empty` hold
+    nothing, the others form a ring; vertex `hub` is joined to hub_deg vertices in all; random pairs fill up to nnz // 2
+    edges, stored both ways with one weight U(0.15, 1), the largest weight exactly 1.  A symmetric CSR without a diagonal has
+    an even number of entries: an odd nnz adds ONE entry x -> y without its mirror (mi_umap_layout_f32 uses the rows as
+    given; symmetry is the caller's business)."""
+    rng = np.random.default_rng(seed)
+    live = [v for v in range(n) if v not in set(empty)]
+    W = np.zeros((n, n))
+    for x, y in zip(live, live[1:] + live[:1]):
+        W[x, y] = W[y, x] = rng.uniform(0.15, 1.0)
+    if hub is not None:
+        others = [v for v in live if v != hub and W[hub, v] == 0]
+        for v in rng.permutation(others)[:hub_deg - int((W[hub] > 0).sum())]:
+            W[hub, v] = W[v, hub] = rng.uniform(0.15, 1.0)
+    free = [(x, y) for x in live for y in live if x < y and W[x, y] == 0]
+    free = [free[q] for q in rng.permutation(len(free))]
+    more = nnz // 2 - int((W > 0).sum()) // 2
+    assert 0 <= more and more + (nnz & 1) <= len(free), "nnz = %d does not fit" % nnz
+    for x, y in free[:more]:
+        W[x, y] = W[y, x] = rng.uniform(0.15, 1.0)
+    if nnz & 1:
+        W[free[more]] = rng.uniform(0.15, 1.0)
+    W[live[0], live[1]] = W[live[1], live[0]] = 1.0
+    W32 = W.astype(np.float32)
+    rows, col = np.nonzero(W32)
+    rowptr = np.concatenate([[0], np.cumsum((W32 > 0).sum(axis=1))]).astype(np.int64)
+    return rowptr, col.astype(np.int32), W32[rows, col]
+
+
+def schedule_graph(T):
+    """Eight vertices on a path (plus the chord {0, 5}) whose weights are the firing ratios themselves (the largest is 1):
+    1, one f32 step below 1, float32(1/3), float32(2/3), float32(1/T), 1/2, 1/4 and, on {6, 7}, one f32 step below
+    float32(1/T), which never fires in T epochs.  {6, 7} is the only edge of vertex 7 and the last entry of the CSR in both
+    directions: removing it renumbers no other entry.  -> (rowptr, col, w, {edge: weight})"""
+    one, inv = np.float32(1.0), np.float32(1.0) / np.float32(T)
+    edges = {(0, 1): one, (1, 2): np.nextafter(one, np.float32(0.0)), (2, 3): np.float32(1.0 / 3.0),
+             (3, 4): np.float32(2.0 / 3.0), (4, 5): inv, (5, 6): np.float32(0.5), (0, 5): np.float32(0.25),
+             (6, 7): np.nextafter(inv, np.float32(0.0))}
+    W32 = np.zeros((8, 8), dtype=np.float32)
+    for (x, y), v in edges.items():
+        W32[x, y] = W32[y, x] = v
+    rows, col = np.nonzero(W32)
+    rowptr = np.concatenate([[0], np.cumsum((W32 > 0).sum(axis=1))]).astype(np.int64)
+    return rowptr, col.astype(np.int32), W32[rows, col], edges
