@@ -1174,12 +1174,12 @@ def test_structured_kernels_random_models(seed):
         assert all(np.bincount(row, minlength=K).min() >= min_size for row in lab)
 
 
-@pytest.mark.parametrize("n,max_deg,K", [(200, 100, 3), (700, 300, 8), (130, 129, 15)])
-@pytest.mark.parametrize("order", [None, "slots"])
-def test_rows_wider_than_64(n, max_deg, K, order):
-    """Models whose rows exceed the 64-entry register layout (the reference's UNTRIMMED SNN graphs reach degrees
-    of order k^2; (130, 129) is a complete graph): the runtime-width forms of K3 and K2 against the oracle."""
-    rs = np.random.RandomState(n + max_deg)
+def wide_row_edges(n, max_deg, rs=None):
+    """(edges, fp32 weights) of a graph with rows up to ``max_deg`` wide: the complete graph when ``max_deg >= n - 1``,
+    else a few hubs at the cap and a sparse rest (also the wide-row graphs of tests/potts_merge_cases.py).  ``rs``: the
+    random stream to draw from (default: a fresh RandomState(n + max_deg))."""
+    if rs is None:
+        rs = np.random.RandomState(n + max_deg)
     if max_deg >= n - 1:
         edges = [(i, j) for i in range(n) for j in range(i + 1, n)]
     else:
@@ -1202,6 +1202,16 @@ def test_rows_wider_than_64(n, max_deg, K, order):
                 deg[b] += 1
         edges = sorted(pairs)
     w = rs.choice(np.array([1 / 9, 0.25, 3 / 7, 2 / 3, 1.0]), size=len(edges)).astype(np.float32)
+    return edges, w
+
+
+@pytest.mark.parametrize("n,max_deg,K", [(200, 100, 3), (700, 300, 8), (130, 129, 15)])
+@pytest.mark.parametrize("order", [None, "slots"])
+def test_rows_wider_than_64(n, max_deg, K, order):
+    """Models whose rows exceed the 64-entry register layout (the reference's UNTRIMMED SNN graphs reach degrees
+    of order k^2; (130, 129) is a complete graph): the runtime-width forms of K3 and K2 against the oracle."""
+    rs = np.random.RandomState(n + max_deg)
+    edges, w = wide_row_edges(n, max_deg, rs)                    # (the binary model below draws on from the same stream)
     rowptr, col, val = _csr_from_edges(n, edges, -2.0 * w)
     assert int(np.diff(rowptr).max()) > 64
     betas = np.geomspace(0.05, 6.0, 9)

@@ -45,9 +45,10 @@ def fixed_point(val, f):
     return np.rint(np.asarray(val, dtype=np.float32).astype(np.float64) * math.ldexp(1.0, f)).astype(np.int64)
 
 
-def merge_phase(lab, rowptr, col, vq, wq, cq, K, P, s, gid, seed, T, f, hole):
+def merge_phase(lab, rowptr, col, vq, wq, cq, K, P, s, gid, seed, T, f, hole, trace=None, replica=None):
     """One merge phase of chain 2e on the labels ``lab`` (a list, relabelled in place) before global sweep ``s`` at the
-    fp32 temperature ``T``.  Returns the number of accepted merges."""
+    fp32 temperature ``T``.  Returns the number of accepted merges.  ``trace``: a list that receives one
+    ``(kind, replica, s, p, a, b, W_a W_b)`` per proposal, kind "accept", "empty" (the N == 0 skip) or "reject"."""
     W, N, B = merge_sums(lab, rowptr, col, vq, wq, K, hole)
     key = (seed & 0xFFFFFFFF, seed >> 32)
     mp = list(range(K))
@@ -57,9 +58,13 @@ def merge_phase(lab, rowptr, col, vq, wq, cq, K, P, s, gid, seed, T, f, hole):
         a = w[0] % K
         b = (a + 1 + w[1] % (K - 1)) % K
         if N[a] == 0 or N[b] == 0:
+            if trace is not None:
+                trace.append(("empty", replica, s, p, a, b, W[a] * W[b]))
             continue
         dE = merge_dE(B, W, a, b, f, cq)
         thr = float(np.float32(so.neglog_u(w[2])) * np.float32(T))
+        if trace is not None:
+            trace.append(("accept" if dE < thr else "reject", replica, s, p, a, b, W[a] * W[b]))
         if not dE < thr:
             continue
         for c in range(K):
@@ -83,11 +88,11 @@ def merge_phase(lab, rowptr, col, vq, wq, cq, K, P, s, gid, seed, T, f, hole):
 
 
 def chain2e(rowptr, col, val, wq, cw, cq, K, R, betas, seed, M, P, replica_offset=0, init=None, sweep_offset=0,
-            absent=None, replicas=None, per_replica=None):
+            absent=None, replicas=None, per_replica=None, trace=None):
     """Chain 2e: chain 2d with a merge phase of ``P`` proposals before every global sweep s = sweep_offset + local index
     with s > 0 and s % M == 0, at that sweep's temperature.  ``per_replica``: one constant beta per replica id (betas is
-    then ignored for the temperatures, its length gives the sweep count).  Returns (labels, accepted single-site moves,
-    accepted merges)."""
+    then ignored for the temperatures, its length gives the sweep count).  ``trace``: see :func:`merge_phase` (replica =
+    the id ``r``, without ``replica_offset``).  Returns (labels, accepted single-site moves, accepted merges)."""
     rowptr, col = np.asarray(rowptr, dtype=np.int64), np.asarray(col, dtype=np.int64)
     n = len(rowptr) - 1
     hole = np.zeros(n, dtype=bool) if absent is None else np.asarray(absent, dtype=bool)
@@ -110,7 +115,8 @@ def chain2e(rowptr, col, val, wq, cw, cq, K, R, betas, seed, M, P, replica_offse
             s = sweep_offset + s0
             if s > 0 and s % M == 0:
                 bt = rb[s0] if rb is not None else betas[s0]
-                merges += merge_phase(lab, rp, cl, vq, wq, cq, K, P, s, gid, seed, np.float32(1.0 / bt), f, hole)
+                merges += merge_phase(lab, rp, cl, vq, wq, cq, K, P, s, gid, seed, np.float32(1.0 / bt), f, hole,
+                                      trace=trace, replica=r)
             ln = min(S - s0, M - s % M)
             seg = (rb if rb is not None else np.asarray(betas))[s0:s0 + ln]
             lab2, a2, _ = chain2d(rowptr, col, val, wq, cw, K, R, seg, seed, replica_offset=replica_offset,
