@@ -23,11 +23,12 @@ def fmaf(a, b, c):
 
 
 def chain2d(rowptr, col, val, wq, cw, K, R, betas, seed, replica_offset=0, init=None, sweep_offset=0,
-            absent=None, replicas=None, energy=None):
+            absent=None, replicas=None, energy=None, trace=None):
     """Chain 2d, sequentially: the Potts chain 2c with the uniform size term replaced by integer node weights,
         dE = fmaf(cw_i, (float)(W_b - W_a + wq_i), hd),  accepted iff dE < neglog_u(word0) * T.
     ``replicas``: the replica ids to run (default 0..R-1, plus ``replica_offset``); ``init`` rows follow them.
     ``energy = (val64, w64, c64, offset)``: also the fp64 energies as the device reports them.
+    ``trace``: a list that receives (row of ``replicas``, sweep, i, W_b - W_a + wq_i, accepted) per evaluated move.
     Returns (labels, accepted, energies or None)."""
     rowptr, col = np.asarray(rowptr, dtype=np.int64), np.asarray(col, dtype=np.int64)
     val = np.asarray(val, dtype=np.float32)
@@ -66,8 +67,11 @@ def chain2d(rowptr, col, val, wq, cw, K, R, betas, seed, replica_offset=0, init=
                         hd = np.float32(hd + np.float32(v))
                     elif lj == a:
                         hd = np.float32(hd - np.float32(v))
-                dE = fmaf(cw[i], np.float32(W[b] - W[a] + int(wq[i])), hd)
+                d = W[b] - W[a] + int(wq[i])
+                dE = fmaf(cw[i], np.float32(d), hd)
                 thr = np.float32(so.neglog_u(so.chain_word(seed, i, s + sweep_offset, gid, 0))) * T
+                if trace is not None:
+                    trace.append((k, s, i, d, bool(dE < thr)))
                 if dE < thr:
                     lab[i] = b
                     W[a] -= int(wq[i])
