@@ -126,6 +126,18 @@ int mi_sa_debug_pace(mi_sa_problem *p, unsigned int *out, int words);
  * states back (scrna_seq_qannealing_clustering_amd/engine.py does).  Identity for n > 262144. */
 int mi_sa_plan_slot_order(const int32_t *rowptr, const int32_t *col, int n, int slot, int64_t *out_perm);
 
+/* Host-only planning (touches no device, makes no HIP call): which anneal kernel mi_sa_anneal would run for a structured
+ * model -- kind MI_KIND_CSR_RANK1 or MI_KIND_POTTS_CSR, the CSR as mi_sa_problem_create_* takes it, K cases (Potts) --
+ * in a run of R replicas on a device of `cus` compute units (0: 256).  options: "key=value,..." with the k2_* / k3_* keys
+ * of mi_sa_set_option (NULL or "": the defaults); pair_weight_slot: the slot of the pair-term weights other than 1
+ * (mi_sa_problem_set_pair_weights; -1: none); node_weights != 0: a Potts model with node weights; min_cluster_size as the
+ * option of that name.  MI_K2_STATE is read from the environment as at creation.  Writes the name
+ * mi_sa_last_kernel_name reports after such a run (without the merge phase's) and the bytes
+ * mi_sa_last_adjacency_bytes_per_slot does (nullable); returns the code creation or the anneal would fail with. */
+int mi_sa_plan_anneal(int kind, const int32_t *rowptr, const int32_t *col, int n, int K, int R, int cus, const char *options,
+                      int pair_weight_slot, int node_weights, int min_cluster_size, char *out_kernel, int len,
+                      int *out_adjacency_bytes);
+
 /* The same planning with HOLES allowed: variable i gets the seat out_pos[i] = slot_index * slot + rank in a layout of
  * *out_slots slots (>= ceil(n / slot), at most max_slots), the fewest -- tried from the packed count upwards -- for which
  * the greedy pass leaves NO edge inside a slot; unused seats are holes.  Small or strongly clustered graphs (the

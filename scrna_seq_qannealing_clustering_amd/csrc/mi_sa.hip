@@ -31,6 +31,7 @@
 #include "../../include/mi_sa.h"
 
 #include "mi_sa_device.h"
+#include "mi_sa_pack.h"
 
 namespace mi_sa_impl {
 
@@ -189,15 +190,14 @@ struct mi_sa_problem {
     std::vector<uint32_t> h_meta;            // host copy (mi_sa_problem_set_absent)
     std::vector<uint8_t> h_hole;             // structured binary: positions whose linear term is +inf (mi_sa_problem_set_pair_weights)
     uint4 *d_adj4 = nullptr;                 // K2: packed slot adjacency (see EllArgs::adj4)
-    uint4 *d_adj4p = nullptr;                // K2p (two replicas per wavefront): the same with neighbour word = 4 * index; null = not eligible
-    uint4 *d_adj4r = nullptr;                // K2p at D = 16 with rows of at most k2p_rw < 16 entries: the trimmed packing (pack_pair_adjacency)
-    int k2p_rw = 0;
+    SlotModelFacts facts;                    // what the model is eligible for (csrc/mi_sa_plan.h): which of the packings below exist
+    uint4 *d_adj4p = nullptr;                // facts.has_pair_packing: the same with neighbour word = 4 * index (K2p, K2w, K2s); facts.has_fast_packing: 2 * index (K3f)
+    uint4 *d_adj4r = nullptr;                // facts.trim_rw: K2p's trimmed packing (pack_pair_adjacency)
     std::vector<uint32_t> h_adj4r;           // ... its host image until the linear terms are in it (RW = 15; mi_sa_problem_create_csr_rank1)
     uint4 *d_adj16 = nullptr;                // K2p: the packing with 16-bit neighbour words (pack_pair_adjacency16); null = not built
     uint4 *d_adj16r = nullptr;               // ... the same with the linear term in the sixteenth value (rows of 13..15 entries at D = 16)
     std::vector<uint32_t> h_adj16;           // ... its host image until the linear terms are known (mi_sa_problem_create_csr_rank1)
     uint32_t *d_slot_flags = nullptr;        // K2: slots with internal edges
-    int k2_state_bytes = 0;                  // K2: byte-per-variable state (16 replicas x n bytes fit one CU's LDS)
     int32_t *d_wgt = nullptr;                // K2 family: the 64 pair-term weights of the weighted slot (mi_sa_problem_set_pair_weights)
     int wslot = -1;                          // ... its index; -1: every weight is 1
     int32_t *d_nwq = nullptr;                // Potts: node weights of the pair term per position (mi_sa_problem_set_node_weights)
@@ -210,7 +210,6 @@ struct mi_sa_problem {
     std::vector<double> merge_cq;            // ... coefficient of W_a W_b per resolution group (empty: c_pair, unweighted)
     double *d_merge_cq = nullptr;            // ... its device copy (256 slots)
     double merge_sumabs = 0.0;               // ... sum of |S_uv| over the stored couplings, in stored order (fixed-point exponent)
-    int k2_free_block = 0;                   // K2s: widest block of seats (256 / 128 / 64; 0 = none) that holds no edge anywhere in the model
     int cus = 0;
     // run buffers
     int cap_R = 0, cap_sweeps = 0;
@@ -234,19 +233,21 @@ struct mi_sa_problem {
     int opt_ondemand_permille = 40;          // K1w: on-demand sweeps below this acceptance (per mille); 0 = always stream
     int opt_debug = 0;                       // DenseArgs::debug (diagnostic timing only; results are wrong)
     int opt_min_cluster_size = 0;            // K3: hard lower bound on every cluster's size (CQM_clustering.py:46-48)
-    int opt_k2_waves = 0;                    // K2: replicas per workgroup (0 = auto)
-    int opt_k2_pair = 0;                     // K2p: 0 auto (runs of more replicas than the chip has SIMDs), 1 always when eligible, 2 never
-    int opt_k2_split = 0;                    // K2s (csrc/sparse_split_kernels.hip): 0 auto (few replicas: its one-wavefront form), 1 always when eligible (2 / 4 wavefronts per replica on models laid out in blocks of 128 / 256 seats), 2 never
-    int opt_k2_wide = 0;                     // models laid out in blocks of 128 / 256 seats, few replicas: 0 / 1 one wavefront sweeps a block per step (K2w), 2 a workgroup of 2 / 4 wavefronts does (K2s)
-    int opt_k3_fast = 0;                     // K3f (csrc/potts_fast_kernels.hip): 0 auto (when the model is eligible), 2 never
-    int opt_k2_tw = 0;                       // K2p with a threshold wavefront per workgroup: 0 auto (when built for the width), 1 on, 2 off
-    int opt_k2_trim = 0;                     // ... and its trimmed rows (rows of 13..15 entries at D = 16): 0 auto / 1 on (when built), 2 off
-    int opt_k2_nbr16 = 0;                    // ... and its 16-bit neighbour words: 0 auto / 1 on (wherever built), 2 off (the 32-bit packings)
+    PlanOptions plan_opts;                   // the k2_* / k3_* options: what the planner reads (csrc/mi_sa_plan.h)
     int last_adj_bytes = 0;                  // packed adjacency bytes a wavefront fetched per slot in the last anneal (0: a kernel without such a packing)
-    int opt_k2_split_max = 1024;             // ... auto: runs of up to this many replicas (a wavefront per SIMD at most)
     int opt_unit_rows = 0;                   // K1w ring unit (rows per rendezvous): 0 auto, 2 or 4
     int resident_waves = 0;                  // co-resident wavefronts of the anneal kernel on this device
     int last_launches = 1;                   // kernel launches that served the last anneal
+    const uint4 *packing(int which) const    // the packed adjacency a plan binds to EllArgs::adj4 (PlanPacking)
+    {
+        switch (which) {
+        case PACK_PAIR: case PACK_FAST: return d_adj4p;
+        case PACK_PAIR_TRIM: return d_adj4r;
+        case PACK_PAIR16: return d_adj16;
+        case PACK_PAIR16_TRIM: return d_adj16r;
+        default: return d_adj4;
+        }
+    }
     std::string last_kernel;                 // ... and the kernel(s) they ran
     size_t state_elem = 1;
     // parallel tempering (mi_sa_tempering_*): ladder, rung of every replica of the run, exchange statistics
@@ -462,82 +463,17 @@ int mi_sa_problem_create_dense_f32(const float *Qs, int n, double offset, int de
     return MI_OK;
 }
 
-// K2p's trimmed packing (csrc/sparse_pair_kernels.hip, RW < D): per slot, the groups of four entries that hold a real
-// neighbour somewhere -- [64 lanes][4] neighbour words, then [64][4] values -- with the last group cut to the LW = RW - 4 (G - 1)
-// entries a row can have: [64][LW] words, then [64][LW] values.  LW = 3 keeps every load 16 / 8 / 4-byte aligned instead:
-// [64][4] (three neighbour words, the lane's linear term -- filled in by the caller), [64][2] values, [64][1] value.
-// hc / hv: the slot-ELL ([slots][D][64], padding (self, +0)); the neighbour word of j is the LDS byte address of its cell, 4 j.
-static std::vector<uint32_t> pack_pair_adjacency(const std::vector<uint32_t> &hc, const std::vector<float> &hv, int slots, int D, int RW)
-{
-    const int G = D / 4, LW = RW - 4 * (G - 1);
-    const size_t slot_words = (size_t)(G - 1) * 512 + (LW == 3 ? 448 : (size_t)LW * 128);
-    std::vector<uint32_t> out((size_t)slots * slot_words, 0u);
-    for (int t = 0; t < slots; ++t)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int k = 0; k < RW; ++k) {
-                const int g = k / 4, w = g < G - 1 ? 4 : LW;     // entries per lane in this group
-                const size_t grp = (size_t)t * slot_words + (size_t)g * 512;
-                size_t at_col = grp + (size_t)lane * w + (k & 3), at_val = at_col + (size_t)w * 64;
-                if (w == 3) {
-                    at_col = grp + (size_t)lane * 4 + (k & 3);
-                    at_val = (k & 3) < 2 ? grp + 256 + (size_t)lane * 2 + (k & 3) : grp + 384 + (size_t)lane;
-                }
-                out[at_col] = 4u * hc[((size_t)t * D + k) * 64 + lane];
-                memcpy(&out[at_val], &hv[((size_t)t * D + k) * 64 + lane], 4);
-            }
-    return out;
-}
-
-// K2p's packing with 16-bit neighbour words (csrc/sparse_pair_kernels.hip, N16): the neighbour word of j is still the LDS
-// byte address of its cell, 4 j -- below 65 536 for every model of at most 256 slots -- so two share a dword: per slot
-// [G / 2 + G][64 lanes][4 dwords], first G / 2 blocks of neighbours (entry k in half k & 1 of dword k / 2 of the lane),
-// then G blocks of values (entry k in dword k).  Padding: (self, +0.0).  A slot is 6144 bytes at D = 16 (8448 unpacked).
-static std::vector<uint32_t> pack_pair_adjacency16(const std::vector<uint32_t> &hc, const std::vector<float> &hv, int slots, int D)
-{
-    const int G = D / 4;
-    const size_t slot_words = (size_t)(G / 2 + G) * 256;
-    std::vector<uint32_t> out((size_t)slots * slot_words, 0u);
-    for (int t = 0; t < slots; ++t)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int k = 0; k < D; ++k) {
-                const size_t src = ((size_t)t * D + k) * 64 + lane;
-                const size_t at_nbr = (size_t)t * slot_words + (size_t)(k / 8) * 256 + (size_t)lane * 4 + ((k / 2) & 3);
-                const size_t at_val = (size_t)t * slot_words + (size_t)(G / 2 + k / 4) * 256 + (size_t)lane * 4 + (k & 3);
-                out[at_nbr] |= (4u * hc[src]) << (16 * (k & 1));
-                memcpy(&out[at_val], &hv[src], 4);
-            }
-    return out;
-}
-
 // CSR (both directions stored) -> slot-ELL device arrays (D = 16 / 32 / 64)
 static int upload_slot_ell(mi_sa_problem *p, const int32_t *rowptr, const int32_t *col, const float *val, int n)
 {
-    int maxdeg = 0;
-    for (int i = 0; i < n; ++i) {
-        const int d = rowptr[i + 1] - rowptr[i];
-        if (d < 0) return fail(MI_EINVAL, "rowptr is not monotone at %d", i);
-        if (d > maxdeg) maxdeg = d;
-    }
-    // rows up to 64 wide are register resident in K2 and K3; wider ones (any multiple of 16 up to 4096) run on the
-    // runtime-width forms of the same kernels, which read the adjacency from L2 inside the field sum
-    if (maxdeg > 4096)
-        return fail(MI_EUNSUPPORTED, "max degree %d exceeds the widest adjacency layout (4096); use the dense kernel", maxdeg);
-    const int D = maxdeg <= 16 ? 16 : (maxdeg <= 32 ? 32 : (maxdeg <= 64 ? 64 : ((maxdeg + 15) / 16) * 16));
-    const int slots = (n + 63) / 64;
-    std::vector<uint32_t> hc((size_t)slots * D * 64);
-    std::vector<float> hv((size_t)slots * D * 64, 0.0f);
-    for (int t = 0; t < slots; ++t)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int i = t * 64 + lane;
-            for (int k = 0; k < D; ++k) hc[((size_t)t * D + k) * 64 + lane] = (uint32_t)(i < n ? i : 0);
-            if (i >= n) continue;
-            for (int e = rowptr[i], k = 0; e < rowptr[i + 1]; ++e, ++k) {
-                if (col[e] < 0 || col[e] >= n || col[e] == i)
-                    return fail(MI_EINVAL, "bad column %d in row %d", col[e], i);
-                hc[((size_t)t * D + k) * 64 + lane] = (uint32_t)col[e];
-                hv[((size_t)t * D + k) * 64 + lane] = val[e];
-            }
-        }
+    // what the model is eligible for decides which packings are built (MI_K2_STATE = bit | byte | half narrows K2's state)
+    std::string err;
+    if (const int rc = slot_model_facts(p->kind, rowptr, col, n, p->K, getenv("MI_K2_STATE"), &p->facts, &err)) return fail(rc, "%s", err.c_str());
+    const SlotModelFacts &f = p->facts;
+    const int D = f.D, slots = f.slots;
+    std::vector<uint32_t> hc;
+    std::vector<float> hv;
+    build_slot_ell(rowptr, col, val, n, slots, D, hc, hv);
     HIP_TRY(hipMalloc((void **)&p->d_ell_col, hc.size() * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&p->d_ell_val, hv.size() * sizeof(float)));
     HIP_TRY(hipMemcpy(p->d_ell_col, hc.data(), hc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -570,100 +506,37 @@ static int upload_slot_ell(mi_sa_problem *p, const int32_t *rowptr, const int32_
         HIP_TRY(hipMemcpy(p->d_rows, hr.data(), hr.size() * sizeof(uint2), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(p->d_meta, hm.data(), hm.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         p->h_meta = hm;
-        if (p->kind == MI_KIND_POTTS_CSR && (D == 16 || D == 32) && (size_t)slots * 128 + 256 <= 160 * 1024) {
-            // K3f's register image of a slot (csrc/potts_fast_kernels.hip), for models whose every slot is free of internal
-            // edges: groups of four (neighbour, value) per lane, the neighbour as the LDS byte address of its 16-bit label cell
-            bool any_in_slot = false;
-            for (size_t i = 0; i < hm.size(); ++i) any_in_slot = any_in_slot || (hm[i] & 0xffu) != 0u;
-            if (!any_in_slot) {
-                const int G = D / 4;
-                std::vector<uint32_t> ha((size_t)slots * G * 2 * 64 * 4, 0u);
-                for (int t = 0; t < slots; ++t)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int k = 0; k < D; ++k) {
-                            const size_t base = (((size_t)t * G + k / 4) * 2) * 256 + (size_t)lane * 4 + (k & 3);
-                            ha[base] = 2u * hc[((size_t)t * D + k) * 64 + lane];
-                            memcpy(&ha[base + 256], &hv[((size_t)t * D + k) * 64 + lane], 4);
-                        }
-                HIP_TRY(hipMalloc((void **)&p->d_adj4p, ha.size() * sizeof(uint32_t)));
-                HIP_TRY(hipMemcpy(p->d_adj4p, ha.data(), ha.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            }
-        }
+        auto upload = [](uint4 **dst, const std::vector<uint32_t> &image) -> int {
+            HIP_TRY(hipMalloc((void **)dst, image.size() * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpy(*dst, image.data(), image.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            return MI_OK;
+        };
+        // the packings the facts name (csrc/mi_sa_pack.h): a slot's register image, groups of four (neighbour word, value)
+        // per lane
+        if (f.has_fast_packing)          // K3f: the neighbour as the LDS byte address of its 16-bit label cell
+            if (const int rc = upload(&p->d_adj4p, pack_groups_of_four(hc, hv, slots, D, [](uint32_t c, int, int) { return 2u * c; }))) return rc;
         if (p->kind == MI_KIND_CSR_RANK1) {
-            // K2's register image of a slot: groups of four (neighbour, value) per lane, the neighbour already
-            // translated into where its state bit lives in LDS (the state masks start at LDS address 0)
-            const int G = D / 4;
-            // state in LDS: a half per variable while 16 replicas fit one CU (n <= 4608), else a byte (n <= 9216), else a bit
-            // (MI_K2_STATE = bit | byte | half narrows the choice: A/B timing of the three forms on one model)
-            const char *force = getenv("MI_K2_STATE");
-#ifdef MI_K2_DEBUG_BUILD
-            const bool debug_linear = getenv("MI_K2_DEBUG_LINEAR") != nullptr;   // (read once, not per adjacency entry)
+#ifdef MI_K2_DEBUG_BUILD                  /* timing-only builds, never in the shipped library: conflict-free gathers (wrong chain) */
+            const bool debug_linear = getenv("MI_K2_DEBUG_LINEAR") != nullptr;
+#else
+            constexpr bool debug_linear = false;
 #endif
-            const bool fits_half = (size_t)slots * 128 * 16 <= 144 * 1024, fits_byte = (size_t)slots * 64 * 16 <= 144 * 1024;
-            p->k2_state_bytes = fits_half ? 2 : (fits_byte ? 1 : 0);
-            if (force && !strcmp(force, "byte") && fits_byte) p->k2_state_bytes = 1;
-            if (force && !strcmp(force, "bit")) p->k2_state_bytes = 0;
-            std::vector<uint32_t> ha((size_t)slots * G * 2 * 64 * 4, 0u), hf((size_t)slots, 0u);
-            for (int t = 0; t < slots; ++t)
-                for (int lane = 0; lane < 64; ++lane) {
-                    if (hm[(size_t)t * 64 + lane] & 0xffu) hf[t] = 1u;
-                    for (int k = 0; k < D; ++k) {
-                        const uint32_t c = hc[((size_t)t * D + k) * 64 + lane];
-                        uint32_t vb;
-                        memcpy(&vb, &hv[((size_t)t * D + k) * 64 + lane], 4);
-                        const size_t base = (((size_t)t * G + k / 4) * 2) * 256 + (size_t)lane * 4 + (k & 3);
-#ifdef MI_K2_DEBUG_BUILD                                           /* timing-only builds: never in the shipped library */
-                        if (debug_linear) {                       // TIMING ONLY (wrong chain): conflict-free gathers
-                            ha[base] = (uint32_t)((lane * 2 + ((k * 128) % (slots * 128))));
-                            ha[base + 256] = vb;
-                            continue;
-                        }
-#endif
-                        ha[base] = p->k2_state_bytes == 2 ? 2u * c
-                                 : (p->k2_state_bytes == 1 ? c : ((((c >> 5) * 4u) << 8) | (c & 31u)));
-                        ha[base + 256] = vb;
-                    }
-                }
-            HIP_TRY(hipMalloc((void **)&p->d_adj4, ha.size() * sizeof(uint32_t)));
+            // K2: the neighbour already translated into where its state lives in LDS
+            if (const int rc = upload(&p->d_adj4, pack_groups_of_four(hc, hv, slots, D, [&](uint32_t c, int lane, int k) {
+                    return debug_linear ? (uint32_t)(lane * 2 + (k * 128) % (slots * 128)) : k2_state_word(c, f.state_bytes); }))) return rc;
+            std::vector<uint32_t> hf((size_t)slots, 0u);              // slots with internal edges
+            for (size_t i = 0; i < hm.size(); ++i)
+                if (hm[i] & 0xffu) hf[i / 64] = 1u;
             HIP_TRY(hipMalloc((void **)&p->d_slot_flags, hf.size() * sizeof(uint32_t)));
-            HIP_TRY(hipMemcpy(p->d_adj4, ha.data(), ha.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(p->d_slot_flags, hf.data(), hf.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            // K2p: every slot free of internal edges, D = 16 / 32, 8 wavefronts x 4 bytes per variable fit a CU's LDS
-            bool any_general = false;
-            for (int t = 0; t < slots; ++t) any_general = any_general || hf[t] != 0u;
-            // K2s: the widest block of whole slots that holds no edge (a layout planned with slot = 128 / 256 seats)
-            p->k2_free_block = any_general ? 0 : 64;
-            for (int B : {256, 128}) {
-                if (any_general || slots % 4 != 0) continue;         // (whole groups of four slots: one Philox block each)
-                bool ok = true;
-                for (int i = 0; i < n && ok; ++i)
-                    for (int e = rowptr[i]; e < rowptr[i + 1]; ++e)
-                        if (col[e] / B == i / B) { ok = false; break; }
-                if (ok) { p->k2_free_block = B; break; }
-            }
-            // (the pair packing serves K2p and the few-replica kernels: 4 bytes of LDS per seat and replica pair / replica;
-            // whether a RUN fits the CUs' LDS is decided per launch, mi_sa_anneal)
-            if (!any_general && (D == 16 || D == 32) && (size_t)slots * 256 + 4096 <= 160 * 1024) {
-                for (int t = 0; t < slots; ++t)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int k = 0; k < D; ++k)
-                            ha[(((size_t)t * G + k / 4) * 2) * 256 + (size_t)lane * 4 + (k & 3)] =
-#ifdef MI_K2_DEBUG_BUILD
-                                debug_linear ? (uint32_t)(lane * 4 + (k * 256) % (slots * 256)) :   // TIMING ONLY: conflict-free gathers
-#endif
-                                4u * hc[((size_t)t * D + k) * 64 + lane];
-                HIP_TRY(hipMalloc((void **)&p->d_adj4p, ha.size() * sizeof(uint32_t)));
-                HIP_TRY(hipMemcpy(p->d_adj4p, ha.data(), ha.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                if (slots <= 256) p->h_adj16 = pack_pair_adjacency16(hc, hv, slots, D);   // (addresses of 16 bits)
-                if (D == 16 && maxdeg >= 13 && maxdeg < 16) {
-                    // entries maxdeg.. 15 are padding in every row: K2p's trimmed form neither fetches nor gathers them
-                    p->h_adj4r = pack_pair_adjacency(hc, hv, slots, D, maxdeg);
-                    p->k2p_rw = maxdeg;
-                    if (maxdeg != 15) {
-                        HIP_TRY(hipMalloc((void **)&p->d_adj4r, p->h_adj4r.size() * sizeof(uint32_t)));
-                        HIP_TRY(hipMemcpy(p->d_adj4r, p->h_adj4r.data(), p->h_adj4r.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                        std::vector<uint32_t>().swap(p->h_adj4r);
-                    }
+            if (f.has_pair_packing) {    // K2p, K2w, K2s: the neighbour as the LDS byte address of its 32-bit cell
+                if (const int rc = upload(&p->d_adj4p, pack_groups_of_four(hc, hv, slots, D, [&](uint32_t c, int lane, int k) {
+                        return debug_linear ? (uint32_t)(lane * 4 + (k * 256) % (slots * 256)) : 4u * c; }))) return rc;
+                if (f.has_pair16) p->h_adj16 = pack_pair_adjacency16(hc, hv, slots, D);
+                if (f.trim_rw) p->h_adj4r = pack_pair_adjacency(hc, hv, slots, D, f.trim_rw);
+                if (f.trim_rw && f.trim_rw != 15) {      // (at 15 it waits for the linear terms: mi_sa_problem_create_csr_rank1_f32)
+                    if (const int rc = upload(&p->d_adj4r, p->h_adj4r)) return rc;
+                    std::vector<uint32_t>().swap(p->h_adj4r);
                 }
             }
         }
@@ -842,13 +715,47 @@ int mi_sa_plan_slot_order(const int32_t *rowptr, const int32_t *col, int n, int 
     return guarded([&]() -> int { return plan_slot_order_impl(rowptr, col, n, slot, out_perm); });
 }
 
+int mi_sa_plan_anneal(int kind, const int32_t *rowptr, const int32_t *col, int n, int K, int R, int cus, const char *options,
+                      int pair_weight_slot, int node_weights, int min_cluster_size, char *out_kernel, int len,
+                      int *out_adjacency_bytes)
+{
+    if (!rowptr || !out_kernel || len < 1 || (n > 0 && rowptr[n] > 0 && !col)) return fail(MI_EINVAL, "NULL argument");
+    if (kind != MI_KIND_CSR_RANK1 && kind != MI_KIND_POTTS_CSR) return fail(MI_EINVAL, "the structured kinds only (got %d)", kind);
+    if (R < 1) return fail(MI_EINVAL, "R must be >= 1 (got %d)", R);
+    return guarded([&]() -> int {
+        std::string err;
+        SlotModelFacts facts;
+        int rc = slot_model_size_check(kind, n, kind == MI_KIND_CSR_RANK1 ? 2 : K, &err);
+        if (!rc) rc = slot_model_facts(kind, rowptr, col, n, kind == MI_KIND_CSR_RANK1 ? 2 : K, getenv("MI_K2_STATE"), &facts, &err);
+        if (rc) return fail(rc, "%s", err.c_str());
+        PlanOptions opts;
+        for (const char *s = options ? options : ""; *s;) {         // "key=value,..." with the keys of mi_sa_set_option
+            const char *end = strchr(s, ','), *eq = strchr(s, '=');
+            if (!end) end = s + strlen(s);
+            const std::string key(s, eq && eq < end ? eq : end);
+            char *stop = nullptr;
+            const long value = eq && eq < end ? strtol(eq + 1, &stop, 10) : 0;
+            if (stop != end || stop == eq + 1 || !plan_option_set(opts, key.c_str(), value)) return fail(MI_EINVAL, "unknown option '%s'", key.c_str());
+            s = *end ? end + 1 : end;
+        }
+        RunFacts run;
+        run.R = R; run.cus = cus; run.pair_weight_slot = kind == MI_KIND_CSR_RANK1 ? pair_weight_slot : -1;
+        run.node_weights = node_weights != 0; run.min_cluster_size = min_cluster_size;
+        AnnealPlan plan;
+        if ((rc = plan_anneal(facts, run, opts, &plan, &err))) return fail(rc, "%s", err.c_str());
+        plan_kernel_name(plan, out_kernel, (size_t)len);
+        if (out_adjacency_bytes) *out_adjacency_bytes = plan.adj_bytes;
+        return MI_OK;
+    });
+}
+
 int mi_sa_problem_create_csr_rank1_f32(const int32_t *rowptr, const int32_t *col, const float *val,
                                        const float *lin, float c_pair, int n, double offset, int device,
                                        mi_sa_problem **out)
 {
     if (!rowptr || !lin || !out || (rowptr[n > 0 ? n : 0] > 0 && (!col || !val))) return fail(MI_EINVAL, "NULL argument");
-    if (n < 1) return fail(MI_EINVAL, "n must be >= 1 (got %d)", n);
-    if (n > (1 << 20)) return fail(MI_EUNSUPPORTED, "csr_rank1 kernel supports n <= 1048576 (got %d)", n);
+    std::string err;
+    if (const int rc_s = slot_model_size_check(MI_KIND_CSR_RANK1, n, 2, &err)) return fail(rc_s, "%s", err.c_str());
     int rc = select_device(device);
     if (rc) return rc;
     mi_sa_problem *p = new (std::nothrow) mi_sa_problem();
@@ -877,7 +784,7 @@ int mi_sa_problem_create_csr_rank1_f32(const int32_t *rowptr, const int32_t *col
         if (!p->h_adj16.empty()) {
             HIP_TRY(hipMalloc((void **)&p->d_adj16, p->h_adj16.size() * sizeof(uint32_t)));
             HIP_TRY(hipMemcpy(p->d_adj16, p->h_adj16.data(), p->h_adj16.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            if (p->k2p_rw) {
+            if (p->facts.trim_rw) {
                 // trimmed rows: the sixteenth value is padding in every row and carries the lane's linear term instead
                 for (int t = 0; t < p->slots; ++t)
                     for (int lane = 0; lane < 64; ++lane)
@@ -899,9 +806,8 @@ int mi_sa_problem_create_potts_csr_f32(const int32_t *rowptr, const int32_t *col
                                        mi_sa_problem **out)
 {
     if (!rowptr || !out || (rowptr[n > 0 ? n : 0] > 0 && (!col || !val))) return fail(MI_EINVAL, "NULL argument");
-    if (n < 1) return fail(MI_EINVAL, "n must be >= 1 (got %d)", n);
-    if (K < 1 || K > 64) return fail(MI_EUNSUPPORTED, "potts kernel supports 1 <= K <= 64 cases (got %d)", K);
-    if (n > 40000) return fail(MI_EUNSUPPORTED, "potts kernel supports n <= 40000 (got %d)", n);
+    std::string err;
+    if (const int rc_s = slot_model_size_check(MI_KIND_POTTS_CSR, n, K, &err)) return fail(rc_s, "%s", err.c_str());
     int rc = select_device(device);
     if (rc) return rc;
     mi_sa_problem *p = new (std::nothrow) mi_sa_problem();
@@ -1184,15 +1090,7 @@ int mi_sa_set_option(mi_sa_problem *p, const char *key, long value)
     if (!strcmp(key, "chunk_sweeps") && value >= 0) { p->opt_chunk_sweeps = (int)value; return MI_OK; }
     if (!strcmp(key, "ondemand_permille") && value >= 0 && value <= 1000) { p->opt_ondemand_permille = (int)value; return MI_OK; }
     if (!strcmp(key, "debug")) { p->opt_debug = (int)value; return MI_OK; }
-    if (!strcmp(key, "k2_waves") && ((value >= 0 && value <= 16) || value == 99)) { p->opt_k2_waves = (int)value; return MI_OK; }   // (99: K3 keeps its serial move loop -- A/B timing)
-    if (!strcmp(key, "k2_pair") && value >= 0 && value <= 2) { p->opt_k2_pair = (int)value; return MI_OK; }
-    if (!strcmp(key, "k2_split") && value >= 0 && value <= 2) { p->opt_k2_split = (int)value; return MI_OK; }
-    if (!strcmp(key, "k2_split_max") && value >= 0) { p->opt_k2_split_max = (int)value; return MI_OK; }
-    if (!strcmp(key, "k2_wide") && value >= 0 && value <= 2) { p->opt_k2_wide = (int)value; return MI_OK; }
-    if (!strcmp(key, "k2_tw") && value >= 0 && value <= 2) { p->opt_k2_tw = (int)value; return MI_OK; }
-    if (!strcmp(key, "k2_trim") && value >= 0 && value <= 2) { p->opt_k2_trim = (int)value; return MI_OK; }
-    if (!strcmp(key, "k2_nbr16") && value >= 0 && value <= 2) { p->opt_k2_nbr16 = (int)value; return MI_OK; }
-    if (!strcmp(key, "k3_fast") && value >= 0 && value <= 2) { p->opt_k3_fast = (int)value; return MI_OK; }
+    if (plan_option_set(p->plan_opts, key, value)) return MI_OK;       // (the k2_* / k3_* keys: csrc/mi_sa_plan.h)
     if (!strcmp(key, "min_cluster_size") && value >= 0) {
         if (p->kind != MI_KIND_POTTS_CSR) return fail(MI_EINVAL, "min_cluster_size applies to Potts problems");
         if (value > 0 && p->d_nwq) return fail(MI_EUNSUPPORTED, "min_cluster_size together with node weights is not supported");
@@ -1364,10 +1262,9 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
         a.resync = resync_interval; a.slots = p->slots; a.D = p->D;
         a.replica_offset = replica_offset; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
         a.sweep_offset = sweep_offset; a.temps_per_replica = per_replica ? 1 : 0;
-        a.rows = p->d_rows; a.meta = p->d_meta; a.adj4 = p->d_adj4; a.slot_flags = p->d_slot_flags; a.state_bytes = p->k2_state_bytes; a.waves_override = p->opt_k2_waves; a.min_size = p->opt_min_cluster_size;
+        a.rows = p->d_rows; a.meta = p->d_meta; a.adj4 = p->d_adj4; a.slot_flags = p->d_slot_flags; a.state_bytes = p->facts.state_bytes; a.waves_override = p->plan_opts.k2_waves; a.min_size = p->opt_min_cluster_size;
         a.ell_val64 = p->d_ell_val64; a.lin64 = p->d_lin64; a.c_pair64 = p->c_pair64;
         a.wgt = p->d_wgt; a.wslot = p->kind == MI_KIND_CSR_RANK1 ? p->wslot : -1;
-        a.adj4_trim = p->opt_k2_trim != 2 ? p->d_adj4r : nullptr; a.trim_rw = p->k2p_rw;
         a.nwq = p->d_nwq; a.ncw = p->d_ncw; a.nw64 = p->d_nw64;
         a.groups = G; a.temps_group_stride = per_group ? num_sweeps : 0; a.gconst = p->d_gconst;
         if (p->kind == MI_KIND_POTTS_CSR && init) {
@@ -1377,17 +1274,24 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
                 if (l[k] >= (uint16_t)p->K) return fail(MI_EINVAL, "initial label %u >= K = %d", (unsigned)l[k], p->K);
         }
         p->last_launches = 1;
+        // the kernel of this call, decided in one place (csrc/mi_sa_plan.h); the launchers only find its instantiation
+        RunFacts run;
+        run.R = R; run.cus = p->cus; run.pair_weight_slot = a.wslot; run.node_weights = p->d_nwq != nullptr; run.min_cluster_size = a.min_size;
+        AnnealPlan plan;
+        std::string plan_err;
+        if (const int rc_p = plan_anneal(p->facts, run, p->plan_opts, &plan, &plan_err)) return fail(rc_p, "%s", plan_err.c_str());
+        a.adj4 = p->packing(plan.packing); a.ring_off = plan.ring_off;
+        p->last_adj_bytes = plan.adj_bytes;
+        auto anneal_launch = [&](const EllArgs &b) -> int {
+            switch (plan.family) {
+            case PLAN_K2P: return mi_launch_csr_rank1_pair(b, plan, p->stream);
+            case PLAN_K2W: case PLAN_K2S: return mi_launch_csr_rank1_split(b, plan, p->stream);
+            case PLAN_K3F: return mi_launch_potts_fast(b, plan, p->stream);
+            default: return mi_launch_sparse(b, plan, p->stream);
+            }
+        };
         HIP_TRY(hipEventRecord(p->ev0, p->stream));
         if (p->kind == MI_KIND_POTTS_CSR) {
-            const bool fast = p->d_adj4p && p->opt_k3_fast != 2 && mi_potts_fast_eligible(p->D, p->K, a.min_size);
-            auto anneal_launch = [&](EllArgs &b) -> int {
-                if (fast) {
-                    b.adj4 = p->d_adj4p;              // every slot free of internal edges: the lean kernel (same chain)
-                    // (up to 1024 replicas every wavefront has a SIMD to itself: a threshold wavefront beside each)
-                    return mi_launch_potts_fast(b, p->opt_k2_tw != 2 && R <= 1024, p->stream);
-                }
-                return mi_launch_potts(b, p->stream);
-            };
             if (!merges) {
                 rc = anneal_launch(a);
             } else {
@@ -1427,65 +1331,7 @@ static int anneal_ex_impl(mi_sa_problem *p, int R, uint32_t replica_offset, int 
                 p->last_launches = launches;
             }
         } else {
-            // which of the kernels of the structured binary model (all run the same chain): an explicit option first;
-            // otherwise few replicas -> K2s in its one-wavefront form (random words a few rounds per step, 32-bit state
-            // cells: 5 % faster than K2 / K2p when every wavefront has a SIMD to itself; its 2 / 4-wavefront forms only on
-            // request: measured break-even), more replicas than the chip has SIMDs -> two replicas per wavefront, else one
-            const bool split_ok = p->k2_free_block >= 64 && p->d_adj4p != nullptr, pair_ok = p->d_adj4p != nullptr;
-            const bool tw = p->opt_k2_tw != 2;         // a threshold wavefront beside the sweeping one (same chain)
-            // these kernels keep 4 bytes of LDS per seat: the library's own choice takes them only when the workgroups of
-            // the run are resident in ONE round (else K2 with its bit / byte state, 16 replicas per CU at any size)
-            const long cus = p->cus > 0 ? p->cus : 256;
-            auto one_round = [&](size_t lds_per_wg, long wgs) {
-                return lds_per_wg * (size_t)((wgs + cus - 1) / cus) <= (size_t)160 * 1024;
-            };
-            const size_t cells = (size_t)p->slots * 256;
-            // K2p: with its threshold wavefront 8 workgroups (16 replicas) fill a CU -- for runs of up to that many; beyond,
-            // the kernel without it holds 16 workgroups per CU (6144 replicas: 4.3e11 against two rounds at 3.5e11).  Models
-            // of up to 4608 variables keep 8 workgroups' cells per CU at any replica count (several rounds if need be);
-            // larger ones take K2p only when one round holds the run.
-            const long pair_wgs = ((long)R + 1) / 2;
-            const long tw_rounds = (pair_wgs + 8 * cus - 1) / (8 * cus);
-            const bool tw_pair = tw && p->D == 16 &&
-                                 ((pair_wgs <= 8 * cus && one_round(cells + 4096, pair_wgs)) ||            // one round, or
-                                  (10 * pair_wgs >= 9 * tw_rounds * 8 * cus && (cells + 4096) * 8 <= (size_t)160 * 1024));   // nearly full ones
-            const bool pair_run = pair_ok && (cells * 8 <= (size_t)150 * 1024 || one_round(cells + (tw_pair ? 4096 : 0), pair_wgs));
-            int choice = 0;
-            // (a model with pair-term weights: the kernels that sweep its weighted slot are K2, K2p and K2w with one slot
-            // per step beside a threshold wavefront)
-            const bool weighted = p->wslot >= 0;
-            if (weighted) {
-                if (p->opt_k2_pair != 2 && pair_run && p->D == 16 && R > 1024) choice = 1;
-                else if (p->opt_k2_split != 2 && tw && p->opt_k2_wide != 2 && split_ok &&
-                         R <= p->opt_k2_split_max && one_round(cells + 2048, R)) choice = 2;
-            } else
-            if (p->opt_k2_split == 1 && split_ok) choice = 2;
-            else if (p->opt_k2_pair == 1 && pair_ok) choice = 1;
-            else if (p->opt_k2_split != 2 && split_ok && R <= p->opt_k2_split_max && one_round(cells + 2048, R)) choice = 2;
-            else if (p->opt_k2_pair != 2 && pair_run && R > 1024) choice = 1;
-            if (choice == 2 && weighted) {
-                a.adj4 = p->d_adj4p;                  // (an edge-free layout in wider blocks is one in 64-seat slots too)
-                rc = mi_launch_csr_rank1_wide(a, 1, true, p->stream);
-            } else if (choice == 2 && p->k2_free_block > 64 && p->opt_k2_wide != 2 && (p->D == 16 || p->k2_free_block == 128)) {
-                // blocks of 128 / 256 edge-free seats, few replicas: ONE wavefront sweeps a block per step
-                a.adj4 = p->d_adj4p;
-                rc = mi_launch_csr_rank1_wide(a, p->k2_free_block / 64, tw, p->stream);
-            } else if (choice == 2 && p->k2_free_block == 64 && p->opt_k2_wide != 2 && tw) {
-                a.adj4 = p->d_adj4p;                  // 64-seat layouts: one slot per step, thresholds from the second wavefront
-                rc = mi_launch_csr_rank1_wide(a, 1, true, p->stream);
-            } else if (choice == 2) {
-                a.adj4 = p->d_adj4p;
-                rc = mi_launch_csr_rank1_split(a, p->k2_free_block / 64, p->stream);
-            } else if (choice == 1) {
-                a.adj4 = p->d_adj4p;                  // two replicas per wavefront: half the adjacency traffic per update
-                // (the 16-bit packings go to the launcher beside the arguments: EllArgs, and with it every other kernel's code, stays as it is)
-                const bool n16 = p->opt_k2_nbr16 != 2;
-                rc = mi_launch_csr_rank1_pair(a, p->opt_k2_pair == 1 ? (tw && p->D == 16 && pair_wgs <= 8 * cus) : tw_pair, p->stream,
-                                              n16 ? p->d_adj16 : nullptr, n16 && p->opt_k2_trim != 2 ? p->d_adj16r : nullptr, &p->last_adj_bytes);
-            } else {
-                // K2: every wavefront alone on its SIMD (up to 1024 replicas) -> a threshold wavefront beside it
-                rc = mi_launch_csr_rank1(a, p->stream, tw && R <= 1024 && (p->D == 16 || p->D == 32) && p->k2_state_bytes <= 1);
-            }
+            rc = anneal_launch(a);
         }
         if (rc) return rc;
         HIP_TRY(hipEventRecord(p->ev1, p->stream));

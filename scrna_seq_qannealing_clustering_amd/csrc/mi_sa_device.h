@@ -10,8 +10,11 @@
 #include <type_traits>
 
 #include "../../include/mi_sa.h"
+#include "mi_sa_plan.h"
 
 namespace mi_sa_impl {
+
+using namespace mi_sa_plan;
 
 int fail(int code, const char *fmt, ...);
 void note_kernel(const char *fmt, ...);      // the launchers record which kernel serves the running anneal (mi_sa_last_kernel_name)
@@ -299,9 +302,9 @@ struct EllArgs {
     // sum_j w_j z_j where it carried sum_j z_j and sweeps that slot with a serial loop.  wslot < 0: all weights 1.
     const int32_t *wgt = nullptr;
     int wslot = -1;
-    int ring_off = 0;          // K2 with a threshold wavefront: byte offset of the ring of thresholds in LDS (set by its launcher)
-    // K2p with a threshold wavefront at D = 16: the pair packing without the entries past the model's longest row
-    // (trim_rw = 13..15 entries per lane, csrc/sparse_pair_kernels.hip); null = not built or switched off
+    int ring_off = 0;          // K2 with a threshold wavefront: byte offset of the ring of thresholds in LDS (AnnealPlan::ring_off)
+    // (unused: which packing adj4 holds, K2p's trimmed ones included, is the plan's to say -- csrc/mi_sa_plan.h; the two
+    // fields keep the struct, and with it every kernel's argument layout, as it was)
     const uint4 *adj4_trim = nullptr;
     int trim_rw = 0;
     // K3 / K3f: node weights of the pair term (mi_sa_problem_set_node_weights, chain 2d), per position [slots * 64]
@@ -384,18 +387,27 @@ __device__ __forceinline__ long long wave_sum_i64(long long v)
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
-int mi_launch_csr_rank1(const EllArgs &, hipStream_t, bool tw = false);   // tw: + a threshold wavefront (runs of up to 1024 replicas; bit / byte state, 16 / 32 entries)
-// sparse_pair_kernels.hip: two replicas per wavefront (tw: + a threshold wavefront).  adj16 / adj16_trim: the packings with
-// 16-bit neighbour words (full rows / linear term in the sixteenth value; null = not built or switched off);
-// adj_bytes (nullable): the packed adjacency bytes a wavefront fetches per slot in the kernel that was launched
-int mi_launch_csr_rank1_pair(const EllArgs &, bool tw, hipStream_t, const uint4 *adj16 = nullptr, const uint4 *adj16_trim = nullptr, int *adj_bytes = nullptr);
-int mi_launch_csr_rank1_split(const EllArgs &, int nw, hipStream_t);   // sparse_split_kernels.hip: nw wavefronts per replica
-int mi_launch_csr_rank1_wide(const EllArgs &, int spb, bool tw, hipStream_t);   // ... one wavefront per replica, spb slots per step (tw: + a threshold wavefront; spb = 1 only so)
-int mi_launch_potts(const EllArgs &, hipStream_t);
-// potts_fast_kernels.hip: K3f, the Potts chain for models whose every slot is free of internal edges (K <= 16, 16 / 32
-// entries per variable, no size constraint); adj4 = packed adjacency with neighbour word = 2 * index
-bool mi_potts_fast_eligible(int D, int K, int min_size);
-int mi_launch_potts_fast(const EllArgs &, bool tw, hipStream_t);
+// The launchers of the structured kernels, one per kernel file: a switch from the coordinates of a plan (csrc/mi_sa_plan.h,
+// the only place that decides) to the instantiation they name; MI_EUNSUPPORTED if they name nothing that is built.
+// EllArgs::adj4 holds the packing the plan names, EllArgs::ring_off its ring offset.
+int mi_launch_sparse(const EllArgs &, const AnnealPlan &, hipStream_t);            // sparse_kernels.hip: K2, K3
+int mi_launch_csr_rank1_pair(const EllArgs &, const AnnealPlan &, hipStream_t);    // sparse_pair_kernels.hip: K2p
+int mi_launch_csr_rank1_split(const EllArgs &, const AnnealPlan &, hipStream_t);   // sparse_split_kernels.hip: K2w, K2s
+int mi_launch_potts_fast(const EllArgs &, const AnnealPlan &, hipStream_t);        // potts_fast_kernels.hip: K3f
+
+// ... and what each does once it has found the kernel: LDS size, the kernel's name, the launch
+template <typename KernelT>
+int launch_planned(KernelT kernel, const EllArgs &a, const AnnealPlan &plan, hipStream_t st)
+{
+    if (plan.lds_bytes > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+    char name[128];
+    plan_kernel_name(plan, name, sizeof name);
+    note_kernel("%s", name);
+    hipLaunchKernelGGL(kernel, dim3(plan.grid), dim3(plan.block), plan.lds_bytes, st, a);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
 // potts_merge_kernels.hip: the merge phase of chain 2e (k_potts_merge), one workgroup per replica, between two launches of
 // K3 / K3f on the replica's labels in HBM
 struct MergeArgs {

@@ -480,51 +480,22 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
     }
 }
 
-template <typename KernelT>
-int launch_potts_fast(KernelT kernel, const EllArgs &a, int km, bool tw, hipStream_t st)
-{
-    const size_t lds = (size_t)a.slots * 128 + 256 + (tw ? 4096 : 0);   // 2 bytes per seat + the cluster sizes (+ the ring)
-    if (lds > 160 * 1024) return fail(MI_EUNSUPPORTED, "potts fast kernel: n = %d exceeds the label LDS budget", a.n);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (a.nwq) note_kernel(tw ? "k_anneal_potts_fast<%d, %d, tw, weighted>" : "k_anneal_potts_fast<%d, %d, weighted>", a.D, km);
-    else note_kernel(tw ? "k_anneal_potts_fast<%d, %d, tw>" : "k_anneal_potts_fast<%d, %d>", a.D, km);
-    hipLaunchKernelGGL(kernel, dim3(a.R), dim3(tw ? 128 : 64), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
-template <int D, int KM>
-int launch_potts_fast_dk(const EllArgs &a, bool tw, hipStream_t st)
-{
-    const bool um = a.min_size > 0;
-    if (a.nwq) {                                                    // node weights (chain 2d; never with a minimum size)
-        if (um) return fail(MI_EUNSUPPORTED, "node weights with min_cluster_size are not supported");
-        return tw ? launch_potts_fast(k_anneal_potts_fast<D, KM, false, true, true>, a, KM, true, st)
-                  : launch_potts_fast(k_anneal_potts_fast<D, KM, false, false, true>, a, KM, false, st);
-    }
-    if (tw) return um ? launch_potts_fast(k_anneal_potts_fast<D, KM, true, true>, a, KM, true, st)
-                      : launch_potts_fast(k_anneal_potts_fast<D, KM, false, true>, a, KM, true, st);
-    return um ? launch_potts_fast(k_anneal_potts_fast<D, KM, true, false>, a, KM, false, st)
-              : launch_potts_fast(k_anneal_potts_fast<D, KM, false, false>, a, KM, false, st);
-}
-
 }  // namespace
 
-bool mi_potts_fast_eligible(int D, int K, int min_size)
-{
-    (void)min_size;                                                 // (any: the kernels with the size test are built too)
-    return (D == 16 || D == 32) && K >= 2 && K <= 16;
-}
-
-// a.adj4 = the packed adjacency with neighbour word = 2 * index (the byte address of the neighbour's 16-bit cell);
-// tw: a threshold wavefront beside the sweeping one (runs of up to 1024 replicas)
-int mi_launch_potts_fast(const EllArgs &a, bool tw, hipStream_t st)
+// a.adj4 = the packed adjacency with neighbour word = 2 * index (the byte address of the neighbour's 16-bit cell)
+int mi_launch_potts_fast(const EllArgs &a, const AnnealPlan &plan, hipStream_t st)
 {
     if (!a.adj4) return fail(MI_EHIP, "potts fast kernel: packed adjacency missing");
-    if (!mi_potts_fast_eligible(a.D, a.K, a.min_size)) return fail(MI_EUNSUPPORTED, "potts fast kernel: not built for this model");
-    if (a.K <= 8) return a.D == 16 ? launch_potts_fast_dk<16, 8>(a, tw, st) : launch_potts_fast_dk<32, 8>(a, tw, st);
-    return a.D == 16 ? launch_potts_fast_dk<16, 16>(a, tw, st) : launch_potts_fast_dk<32, 16>(a, tw, st);
+#define MI_K3F(D_, KM_, UM_, TW_, WT_) \
+    if (plan.D == D_ && plan.KM == KM_ && plan.size_test == UM_ && plan.tw == TW_ && plan.weighted == WT_) \
+        return launch_planned(k_anneal_potts_fast<D_, KM_, UM_, TW_, WT_>, a, plan, st);
+#define MI_K3F_DK(D_, KM_) \
+    MI_K3F(D_, KM_, false, true, true) MI_K3F(D_, KM_, false, false, true)             /* node weights (chain 2d; never with a minimum size) */ \
+    MI_K3F(D_, KM_, true, true, false) MI_K3F(D_, KM_, false, true, false) MI_K3F(D_, KM_, true, false, false) MI_K3F(D_, KM_, false, false, false)
+    MI_K3F_DK(16, 8) MI_K3F_DK(32, 8) MI_K3F_DK(16, 16) MI_K3F_DK(32, 16)
+#undef MI_K3F_DK
+#undef MI_K3F
+    return fail(MI_EUNSUPPORTED, "potts fast kernel: not built for this model");
 }
 
 }  // namespace mi_sa_impl

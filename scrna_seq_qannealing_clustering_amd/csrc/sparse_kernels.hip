@@ -19,7 +19,6 @@ namespace mi_sa_impl {
 
 namespace {
 
-constexpr int kSparseWaves = 4;      // wavefronts (replicas) per workgroup
 
 // Philox words of the four slots 4*tg .. 4*tg+3 for this lane
 __device__ __forceinline__ void slot_words(uint32_t (&w)[4], int tg, int lane, uint32_t s, uint32_t g,
@@ -834,85 +833,27 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
     }
 }
 
-template <typename KernelT>
-int launch_sparse(KernelT kernel, const EllArgs &a, size_t lds_per_wave, hipStream_t st)
-{
-    note_kernel(a.nwq ? "k_anneal_potts<%d, weighted>" : "k_anneal_potts<%d>", a.D <= 64 ? a.D : 0);
-    int waves = kSparseWaves;                    // fewer replicas per workgroup when their LDS state is large
-    while (waves > 1 && lds_per_wave * waves > 160 * 1024) --waves;
-    const size_t lds = lds_per_wave * waves;
-    if (lds > 160 * 1024) return fail(MI_EUNSUPPORTED, "model too large for the LDS-resident sparse kernel (%zu B)", lds);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3((a.R + waves - 1) / waves), dim3(waves * 64), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
-template <typename KernelT>
-int launch_csr_rank1(KernelT kernel, const EllArgs &a0, size_t lds, hipStream_t st, bool tw = false)
-{
-    // one wavefront = one replica = one workgroup; the only LDS is the state (a bit or a byte per variable) -- and, with a
-    // threshold wavefront beside the sweeping one, the ring of thresholds behind it
-    EllArgs a = a0;
-    if (tw) {
-        a.ring_off = (int)((lds + 15) / 16 * 16);
-        lds = (size_t)a.ring_off + 2048;
-    }
-    if (lds > 160 * 1024) return fail(MI_EUNSUPPORTED, "csr_rank1: n = %d exceeds the state LDS budget", a.n);
-    if (!a.adj4 || !a.slot_flags) return fail(MI_EHIP, "csr_rank1: packed adjacency missing");
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    note_kernel(tw ? "k_anneal_csr_rank1<%d, %d, tw>" : "k_anneal_csr_rank1<%d, %d>", a.D <= 64 ? a.D : 0, a.state_bytes);
-    hipLaunchKernelGGL(kernel, dim3(a.R), dim3(tw ? 128 : 64), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
 }  // namespace
 
-int mi_launch_csr_rank1(const EllArgs &a, hipStream_t st, bool tw)
+int mi_launch_sparse(const EllArgs &a, const AnnealPlan &plan, hipStream_t st)
 {
-    const size_t bits = (size_t)a.slots * 8, bytes = (size_t)a.slots * 64, halves = (size_t)a.slots * 128;
-    if (tw) {          // built for the register-resident widths of large models: bit and byte state
-        if (a.state_bytes == 1 && a.D == 16) return launch_csr_rank1(k_anneal_csr_rank1<16, 1, true>, a, bytes, st, true);
-        if (a.state_bytes == 1 && a.D == 32) return launch_csr_rank1(k_anneal_csr_rank1<32, 1, true>, a, bytes, st, true);
-        if (a.state_bytes == 0 && a.D == 16) return launch_csr_rank1(k_anneal_csr_rank1<16, 0, true>, a, bits, st, true);
-        if (a.state_bytes == 0 && a.D == 32) return launch_csr_rank1(k_anneal_csr_rank1<32, 0, true>, a, bits, st, true);
-    }
-    if (a.state_bytes == 2) {
-        if (a.D == 16) return launch_csr_rank1(k_anneal_csr_rank1<16, 2>, a, halves, st);
-        if (a.D == 32) return launch_csr_rank1(k_anneal_csr_rank1<32, 2>, a, halves, st);
-        if (a.D == 64) return launch_csr_rank1(k_anneal_csr_rank1<64, 2>, a, halves, st);
-        if (a.D > 64 && a.D % 16 == 0) return launch_csr_rank1(k_anneal_csr_rank1<0, 2>, a, halves, st);
-    } else if (a.state_bytes == 1) {
-        if (a.D == 16) return launch_csr_rank1(k_anneal_csr_rank1<16, 1>, a, bytes, st);
-        if (a.D == 32) return launch_csr_rank1(k_anneal_csr_rank1<32, 1>, a, bytes, st);
-        if (a.D == 64) return launch_csr_rank1(k_anneal_csr_rank1<64, 1>, a, bytes, st);
-        if (a.D > 64 && a.D % 16 == 0) return launch_csr_rank1(k_anneal_csr_rank1<0, 1>, a, bytes, st);
-    } else {
-        if (a.D == 16) return launch_csr_rank1(k_anneal_csr_rank1<16, 0>, a, bits, st);
-        if (a.D == 32) return launch_csr_rank1(k_anneal_csr_rank1<32, 0>, a, bits, st);
-        if (a.D == 64) return launch_csr_rank1(k_anneal_csr_rank1<64, 0>, a, bits, st);
-        if (a.D > 64 && a.D % 16 == 0) return launch_csr_rank1(k_anneal_csr_rank1<0, 0>, a, bits, st);
-    }
-    return fail(MI_EUNSUPPORTED, "slot-ELL width %d not built", a.D);
-}
-
-int mi_launch_potts(const EllArgs &a, hipStream_t st)
-{
-    const size_t per_wave = (size_t)a.slots * 64 + 256;      // labels + cluster sizes
-    if (a.nwq) {                                             // node weights (chain 2d)
-        if (a.D == 16) return launch_sparse(k_anneal_potts<16, true>, a, per_wave, st);
-        if (a.D == 32) return launch_sparse(k_anneal_potts<32, true>, a, per_wave, st);
-        if (a.D == 64) return launch_sparse(k_anneal_potts<64, true>, a, per_wave, st);
-        if (a.D > 64 && a.D % 16 == 0) return launch_sparse(k_anneal_potts<0, true>, a, per_wave, st);
+    if (plan.family == PLAN_K3) {
+#define MI_K3(D_) \
+        if (plan.D == D_) return plan.weighted ? launch_planned(k_anneal_potts<D_, true>, a, plan, st) \
+                                               : launch_planned(k_anneal_potts<D_>, a, plan, st);
+        MI_K3(16) MI_K3(32) MI_K3(64) MI_K3(0)                      // (0: rows of any width)
+#undef MI_K3
         return fail(MI_EUNSUPPORTED, "slot-ELL width %d not built", a.D);
     }
-    if (a.D == 16) return launch_sparse(k_anneal_potts<16>, a, per_wave, st);
-    if (a.D == 32) return launch_sparse(k_anneal_potts<32>, a, per_wave, st);
-    if (a.D == 64) return launch_sparse(k_anneal_potts<64>, a, per_wave, st);
-    if (a.D > 64 && a.D % 16 == 0) return launch_sparse(k_anneal_potts<0>, a, per_wave, st);     // rows of any width
+    if (!a.adj4 || !a.slot_flags) return fail(MI_EHIP, "csr_rank1: packed adjacency missing");
+#define MI_K2(D_, XS_, TW_) \
+    if (plan.D == D_ && plan.state_bytes == XS_ && plan.tw == TW_) return launch_planned(k_anneal_csr_rank1<D_, XS_, TW_>, a, plan, st);
+#define MI_K2_WIDTHS(XS_) MI_K2(16, XS_, false) MI_K2(32, XS_, false) MI_K2(64, XS_, false) MI_K2(0, XS_, false)
+    MI_K2_WIDTHS(2) MI_K2_WIDTHS(1) MI_K2_WIDTHS(0)
+    // tw: built for the register-resident widths of large models, bit and byte state
+    MI_K2(16, 1, true) MI_K2(32, 1, true) MI_K2(16, 0, true) MI_K2(32, 0, true)
+#undef MI_K2_WIDTHS
+#undef MI_K2
     return fail(MI_EUNSUPPORTED, "slot-ELL width %d not built", a.D);
 }
 

@@ -542,66 +542,25 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
 #endif
 }
 
-template <typename KernelT>
-int launch_pair(KernelT kernel, const EllArgs &a, bool tw, hipStream_t st, int rw = 0)
-{
-    // 4 bytes per variable; TW: the two-deep ring of thresholds behind them (2 x 4 slots x 64 lanes x 8 bytes)
-    const size_t lds = (size_t)a.slots * 256 + (tw ? 4096 : 0);
-    if (lds > 160 * 1024) return fail(MI_EUNSUPPORTED, "csr_rank1 pair kernel: n = %d exceeds the state LDS budget", a.n);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (rw) note_kernel("k_anneal_csr_rank1_pair<%d, tw> r%d", a.D, rw);
-    else note_kernel(tw ? "k_anneal_csr_rank1_pair<%d, tw>" : "k_anneal_csr_rank1_pair<%d>", a.D);
-    hipLaunchKernelGGL(kernel, dim3((a.R + 1) / 2), dim3(tw ? 128 : 64), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
 }  // namespace
 
-// a.adj4 must hold the pair packing (neighbour word = 4 * index)
-int mi_launch_csr_rank1_pair(const EllArgs &a, bool tw, hipStream_t st, const uint4 *adj16, const uint4 *adj16_trim, int *adj_bytes)
+// a.adj4 holds the packing the plan names (plan_k2p, csrc/mi_sa_plan.h)
+int mi_launch_csr_rank1_pair(const EllArgs &a, const AnnealPlan &plan, hipStream_t st)
 {
     if (!a.adj4) return fail(MI_EHIP, "csr_rank1 pair kernel: packed adjacency missing");
 #ifdef MI_K2P_NOFETCH
-    adj16 = adj16_trim = nullptr;             // (the timing builds are arms of the 32-bit packing)
+    if (plan.nbr16) return fail(MI_EUNSUPPORTED, "the timing builds are arms of the 32-bit packing: set k2_nbr16 = 2");
 #endif
-    // the ring costs LDS: beyond 64 slots only seven workgroups (14 replicas) fit a CU, and a run that fills the chip
-    // (16 replicas per CU) would take two rounds -- such models keep the kernel without a threshold wavefront
-    if (tw && ((size_t)a.slots * 256 + 4096) * 8 > 160 * 1024 && a.R > 2 * 7 * 256) tw = false;
-    // (which packing the launched kernel reads, in bytes per slot and wavefront: mi_sa_last_adjacency_bytes_per_slot)
-    auto fetches = [&](int bytes) { if (adj_bytes) *adj_bytes = bytes; };
-    if (a.wslot >= 0) {                       // pair-term weights (16 entries per variable)
-        if (a.D != 16) return fail(MI_EUNSUPPORTED, "csr_rank1 pair kernel: pair-term weights at slot-ELL width %d not built", a.D);
-        fetches(8448);
-        return tw ? launch_pair(k_anneal_csr_rank1_pair<16, true, true>, a, true, st)
-                  : launch_pair(k_anneal_csr_rank1_pair<16, false, true>, a, false, st);
-    }
-    EllArgs b = a;
-    if (a.D == 16 && tw && a.adj4_trim && adj16_trim) {   // rows of at most 15 entries, 16-bit neighbour words
-        b.adj4 = adj16_trim;
-        fetches(6144);
-        if (a.trim_rw == 15) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 15, 2>, b, true, st, 15);
-        if (a.trim_rw == 14) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 14, 2>, b, true, st, 14);
-        if (a.trim_rw == 13) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 13, 2>, b, true, st, 13);
-    }
-    if (a.D == 16 && tw && a.adj4_trim) {     // rows of at most 15 entries: the trimmed packing (see the kernel)
-        b.adj4 = a.adj4_trim;
-        fetches(a.trim_rw == 15 ? 7936 : (a.trim_rw == 14 ? 7424 : 6912));
-        if (a.trim_rw == 15) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 15>, b, true, st, 15);
-        if (a.trim_rw == 14) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 14>, b, true, st, 14);
-        if (a.trim_rw == 13) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 13>, b, true, st, 13);
-    }
-    if (adj16 && ((a.D == 16 && tw) || a.D == 32)) {   // full rows, 16-bit neighbour words (+ the dword of linear terms)
-        b.adj4 = adj16;
-        fetches(a.D == 16 ? 6400 : 12544);
-        if (a.D == 16) return launch_pair(k_anneal_csr_rank1_pair<16, true, false, 16, 2>, b, true, st);
-        return launch_pair(k_anneal_csr_rank1_pair<32, false, false, 32, 1>, b, false, st);
-    }
-    fetches(a.D == 16 ? 8448 : 16640);
-    if (a.D == 16 && tw) return launch_pair(k_anneal_csr_rank1_pair<16, true>, a, true, st);
-    if (a.D == 16) return launch_pair(k_anneal_csr_rank1_pair<16, false>, a, false, st);
-    if (a.D == 32) return launch_pair(k_anneal_csr_rank1_pair<32, false>, a, false, st);
+    const int rw = plan.trim_rw ? plan.trim_rw : plan.D;
+#define MI_K2P(D_, TW_, WGT_, RW_, N16_) \
+    if (plan.D == D_ && plan.tw == TW_ && plan.weighted == WGT_ && rw == RW_ && (plan.nbr16 ? N16_ != 0 : N16_ == 0)) \
+        return launch_planned(k_anneal_csr_rank1_pair<D_, TW_, WGT_, RW_, N16_>, a, plan, st);
+    MI_K2P(16, true, true, 16, 0) MI_K2P(16, false, true, 16, 0)                          // pair-term weights
+    MI_K2P(16, true, false, 15, 2) MI_K2P(16, true, false, 14, 2) MI_K2P(16, true, false, 13, 2)   // trimmed rows, 16-bit neighbour words
+    MI_K2P(16, true, false, 15, 0) MI_K2P(16, true, false, 14, 0) MI_K2P(16, true, false, 13, 0)   // trimmed rows
+    MI_K2P(16, true, false, 16, 2) MI_K2P(32, false, false, 32, 1)                        // full rows, 16-bit neighbour words
+    MI_K2P(16, true, false, 16, 0) MI_K2P(16, false, false, 16, 0) MI_K2P(32, false, false, 32, 0)
+#undef MI_K2P
     return fail(MI_EUNSUPPORTED, "csr_rank1 pair kernel: slot-ELL width %d not built", a.D);
 }
 

@@ -40,8 +40,7 @@ typedef _Float16 half_t;
 #define K2S_TICK0(var) do { } while (0)
 #endif
 
-constexpr int kCommBytes = 8 * 16;               // eight exchange slots of four ints (the waves' net changes)
-constexpr int kRingBytes = 4 * 64 * 16;          // NW > 1: four groups of random words in flight, [4][64 lanes][4 words]
+// (kCommBytes, kRingBytes -- the exchange slots and the ring of random words behind the cells: csrc/mi_sa_plan.h)
 
 // One Philox4x32-10 block computed a few rounds per step: the ten rounds of the NEXT group of four slots ride in the
 // shadow of this group's LDS gathers instead of standing, all ten, at the head of every fourth slot.
@@ -773,74 +772,28 @@ __global__ void __launch_bounds__(TW ? 128 : 64, 1) k_anneal_csr_rank1_wide(EllA
     }
 }
 
-template <typename KernelT>
-int launch_wide(KernelT kernel, const EllArgs &a, int spb, bool tw, hipStream_t st)
-{
-    const size_t lds = (size_t)a.slots * 256 + (tw ? 2048 : 0);    // the cells; tw: + the ring of thresholds
-    if (lds > 160 * 1024) return fail(MI_EUNSUPPORTED, "csr_rank1 wide kernel: n = %d exceeds the state LDS budget", a.n);
-    if (a.slots % spb != 0) return fail(MI_EINVAL, "csr_rank1 wide kernel: %d slots are not whole blocks of %d", a.slots, spb);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    note_kernel(tw ? "k_anneal_csr_rank1_wide<%d, %d, tw>" : "k_anneal_csr_rank1_wide<%d, %d>", a.D, spb);
-    hipLaunchKernelGGL(kernel, dim3(a.R), dim3(tw ? 128 : 64), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
-template <typename KernelT>
-int launch_split(KernelT kernel, const EllArgs &a, int nw, hipStream_t st)
-{
-    const size_t lds = (size_t)a.slots * 256 + kCommBytes + (nw > 1 ? kRingBytes : 0);
-    if (lds > 160 * 1024) return fail(MI_EUNSUPPORTED, "csr_rank1 split kernel: n = %d exceeds the state LDS budget", a.n);
-    if (a.slots % nw != 0) return fail(MI_EINVAL, "csr_rank1 split kernel: %d slots are not whole blocks of %d", a.slots, nw);
-    if (nw > 1 && a.slots % 4 != 0)
-        return fail(MI_EINVAL, "csr_rank1 split kernel: with %d wavefronts per replica the slots (%d) must come in whole groups of four", nw, a.slots);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    note_kernel("k_anneal_csr_rank1_split<%d, %d>", a.D, nw);
-    hipLaunchKernelGGL(kernel, dim3(a.R), dim3(64 * nw), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
 }  // namespace
 
-// one wavefront per replica, spb = 2 / 4 slots per step (a model whose every block of 64 * spb seats is free of internal
-// edges; a.adj4 = the pair kernel's packing)
-int mi_launch_csr_rank1_wide(const EllArgs &a, int spb, bool tw, hipStream_t st)
+// a.adj4 holds the pair kernel's packing (neighbour word = 4 * index) of a model whose every block of 64 * plan.step seats is
+// free of internal edges.  K2w: one wavefront per replica, plan.step slots per step; K2s: plan.step wavefronts per replica
+int mi_launch_csr_rank1_split(const EllArgs &a, const AnnealPlan &plan, hipStream_t st)
 {
-    if (!a.adj4) return fail(MI_EHIP, "csr_rank1 wide kernel: packed adjacency missing");
-    if (a.wslot >= 0) {                       // pair-term weights: one slot per step beside a threshold wavefront
-        if (tw && a.D == 16 && spb == 1) return launch_wide(k_anneal_csr_rank1_wide<16, 1, true, true>, a, spb, true, st);
-        if (tw && a.D == 32 && spb == 1) return launch_wide(k_anneal_csr_rank1_wide<32, 1, true, true>, a, spb, true, st);
-        return fail(MI_EUNSUPPORTED, "csr_rank1 wide kernel: a model with pair-term weights runs one slot per step beside a threshold wavefront");
+    if (plan.family == PLAN_K2W) {
+        if (!a.adj4) return fail(MI_EHIP, "csr_rank1 wide kernel: packed adjacency missing");
+#define MI_K2W(D_, SPB_, TW_, WGT_) \
+        if (plan.D == D_ && plan.step == SPB_ && plan.tw == TW_ && plan.weighted == WGT_) \
+            return launch_planned(k_anneal_csr_rank1_wide<D_, SPB_, TW_, WGT_>, a, plan, st);
+        MI_K2W(16, 1, true, true) MI_K2W(32, 1, true, true)         // pair-term weights: one slot per step beside a threshold wavefront
+        MI_K2W(16, 1, true, false) MI_K2W(16, 2, true, false) MI_K2W(16, 4, true, false) MI_K2W(32, 1, true, false) MI_K2W(32, 2, true, false)
+        MI_K2W(16, 2, false, false) MI_K2W(16, 4, false, false) MI_K2W(32, 2, false, false)
+#undef MI_K2W
+        return fail(MI_EUNSUPPORTED, "csr_rank1 wide kernel: width %d / %d slots per step%s not built", a.D, plan.step, plan.tw ? " with a threshold wavefront" : "");
     }
-    if (tw) {
-        if (a.D == 16 && spb == 1) return launch_wide(k_anneal_csr_rank1_wide<16, 1, true>, a, spb, true, st);
-        if (a.D == 16 && spb == 2) return launch_wide(k_anneal_csr_rank1_wide<16, 2, true>, a, spb, true, st);
-        if (a.D == 16 && spb == 4) return launch_wide(k_anneal_csr_rank1_wide<16, 4, true>, a, spb, true, st);
-        if (a.D == 32 && spb == 1) return launch_wide(k_anneal_csr_rank1_wide<32, 1, true>, a, spb, true, st);
-        if (a.D == 32 && spb == 2) return launch_wide(k_anneal_csr_rank1_wide<32, 2, true>, a, spb, true, st);
-    } else {
-        if (a.D == 16 && spb == 2) return launch_wide(k_anneal_csr_rank1_wide<16, 2, false>, a, spb, false, st);
-        if (a.D == 16 && spb == 4) return launch_wide(k_anneal_csr_rank1_wide<16, 4, false>, a, spb, false, st);
-        if (a.D == 32 && spb == 2) return launch_wide(k_anneal_csr_rank1_wide<32, 2, false>, a, spb, false, st);
-    }
-    return fail(MI_EUNSUPPORTED, "csr_rank1 wide kernel: width %d / %d slots per step%s not built", a.D, spb, tw ? " with a threshold wavefront" : "");
-}
-
-// a.adj4 must hold the pair kernel's packing (neighbour word = 4 * index) of a model whose every block of 64 * nw seats
-// is free of internal edges
-int mi_launch_csr_rank1_split(const EllArgs &a, int nw, hipStream_t st)
-{
     if (!a.adj4) return fail(MI_EHIP, "csr_rank1 split kernel: packed adjacency missing");
-    if (a.D == 16 && nw == 4) return launch_split(k_anneal_csr_rank1_split<16, 4>, a, nw, st);
-    if (a.D == 16 && nw == 2) return launch_split(k_anneal_csr_rank1_split<16, 2>, a, nw, st);
-    if (a.D == 16 && nw == 1) return launch_split(k_anneal_csr_rank1_split<16, 1>, a, nw, st);
-    if (a.D == 32 && nw == 4) return launch_split(k_anneal_csr_rank1_split<32, 4>, a, nw, st);
-    if (a.D == 32 && nw == 2) return launch_split(k_anneal_csr_rank1_split<32, 2>, a, nw, st);
-    if (a.D == 32 && nw == 1) return launch_split(k_anneal_csr_rank1_split<32, 1>, a, nw, st);
-    return fail(MI_EUNSUPPORTED, "csr_rank1 split kernel: width %d / %d wavefronts not built", a.D, nw);
+#define MI_K2S(D_, NW_) if (plan.D == D_ && plan.step == NW_) return launch_planned(k_anneal_csr_rank1_split<D_, NW_>, a, plan, st);
+    MI_K2S(16, 4) MI_K2S(16, 2) MI_K2S(16, 1) MI_K2S(32, 4) MI_K2S(32, 2) MI_K2S(32, 1)
+#undef MI_K2S
+    return fail(MI_EUNSUPPORTED, "csr_rank1 split kernel: width %d / %d wavefronts not built", a.D, plan.step);
 }
 
 }  // namespace mi_sa_impl

@@ -173,52 +173,18 @@ class Problem:
 
     @classmethod
     def _csr_rank1_weighted(cls, rowptr, col, val, lin, c_pair, offset, device, order, energy_model, weights) -> "Problem":
-        """The padded layout of a model with pair-term weights: the unit-weight variables as usual (64-seat slots free of
-        internal edges), the others -- few, no sparse couplings -- in one more slot; mi_sa_problem_set_pair_weights."""
-        from .models import pad_csr, padded_slot_layout
+        """A model with pair-term weights in its padded layout (``weighted_layout_csr``);
+        mi_sa_problem_set_pair_weights."""
         if order != "padded":
             raise ValueError("a model with pair-term weights needs order='padded'")
-        rowptr = np.asarray(rowptr, dtype=np.int64)
-        col = np.asarray(col, dtype=np.int64)
         n_caller = len(lin)
-        deg = np.diff(rowptr)
-        heavy = np.flatnonzero(weights != 1)
-        light = np.flatnonzero(weights == 1)
-        if np.any(weights < 1) or len(heavy) > 64 or np.any(deg[heavy] != 0):
-            raise ValueError("pair-term weights: positive integers; at most 64 variables with a weight other than 1, "
-                             "and those without sparse couplings")
-        # the layout of the unit-weight variables alone (the others have no edges): their CSR renumbered 0 .. len(light) - 1
-        renum = np.full(n_caller, -1, dtype=np.int64)
-        renum[light] = np.arange(len(light))
-        rp_l = np.concatenate([[0], np.cumsum(deg[light])]).astype(np.int32)
-        keep = np.repeat(weights == 1, deg)
-        seats_l, nslots, _ = padded_slot_layout(rp_l, renum[col[keep]].astype(np.int32), slot=64)
-        seats = np.empty(n_caller, dtype=np.int64)
-        seats[light] = seats_l
-        seats[heavy] = nslots * 64 + np.arange(len(heavy))
-        n_dev = (nslots + 1) * 64
-        val64 = lin64 = None
-        if energy_model is not None:
-            val64, lin64 = np.asarray(energy_model[0], dtype=np.float64), np.asarray(energy_model[1], dtype=np.float64)
-            rp, cc, vv, val64 = pad_csr(rowptr, col, val, seats, n_dev, also=val64)
-            l64 = np.zeros(n_dev, dtype=np.float64)
-            l64[seats] = lin64
-            lin64 = l64
-        else:
-            rp, cc, vv = pad_csr(rowptr, col, val, seats, n_dev)
-        lpad = np.full(n_dev, np.inf, dtype=np.float32)
-        lpad[seats] = np.asarray(lin, dtype=np.float32)
-        rp = np.ascontiguousarray(rp, dtype=np.int32)
-        cc = np.ascontiguousarray(cc, dtype=np.int32)
-        vv = np.ascontiguousarray(vv, dtype=np.float32)
+        rp, cc, vv, lpad, wdev, seats, n_dev, val64, lin64 = weighted_layout_csr(rowptr, col, val, lin, weights, energy_model)
         lib = _lib.load()
         h = C.c_void_p()
         _lib.check(lib.mi_sa_problem_create_csr_rank1_f32(
             _ptr(rp, C.c_int32), _ptr(cc, C.c_int32), _ptr(vv, C.c_float),
             _ptr(lpad, C.c_float), float(c_pair), n_dev, float(offset), int(device), C.byref(h)))
         prob = cls(h, _lib.KIND_CSR_RANK1, n_caller, 2, device, seats=seats, n_dev=n_dev)
-        wdev = np.ones(n_dev, dtype=np.int32)
-        wdev[seats] = weights
         rc = lib.mi_sa_problem_set_pair_weights(h, _ptr(wdev, C.c_int32))
         if rc:
             prob.close()
@@ -614,6 +580,69 @@ class Problem:
         if st is not None and self._inv is not None:
             st = st[self._inv]
         return int(idx.value), float(en.value), int(key.value), st
+
+
+def weighted_layout_csr(rowptr, col, val, lin, weights, energy_model=None):
+    """The device-side model of a structured binary model with pair-term weights (host work only): the unit-weight
+    variables as usual (64-seat slots free of internal edges, models.padded_slot_layout), the others -- few, no sparse
+    couplings -- in one more slot.  Returns ``(rowptr, col, val, lin, weights, seats, n_dev, val64, lin64)``, the first
+    five in device order (holes: lin = +inf, weight 1), ``seats[i]`` the device column of the caller's variable i."""
+    from .models import pad_csr, padded_slot_layout
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    col = np.asarray(col, dtype=np.int64)
+    weights = np.asarray(weights, dtype=np.int64)
+    n_caller = len(lin)
+    deg = np.diff(rowptr)
+    heavy = np.flatnonzero(weights != 1)
+    light = np.flatnonzero(weights == 1)
+    if np.any(weights < 1) or len(heavy) > 64 or np.any(deg[heavy] != 0):
+        raise ValueError("pair-term weights: positive integers; at most 64 variables with a weight other than 1, "
+                         "and those without sparse couplings")
+    # the layout of the unit-weight variables alone (the others have no edges): their CSR renumbered 0 .. len(light) - 1
+    renum = np.full(n_caller, -1, dtype=np.int64)
+    renum[light] = np.arange(len(light))
+    rp_l = np.concatenate([[0], np.cumsum(deg[light])]).astype(np.int32)
+    keep = np.repeat(weights == 1, deg)
+    seats_l, nslots, _ = padded_slot_layout(rp_l, renum[col[keep]].astype(np.int32), slot=64)
+    seats = np.empty(n_caller, dtype=np.int64)
+    seats[light] = seats_l
+    seats[heavy] = nslots * 64 + np.arange(len(heavy))
+    n_dev = (nslots + 1) * 64
+    val64 = lin64 = None
+    if energy_model is not None:
+        val64, lin64 = np.asarray(energy_model[0], dtype=np.float64), np.asarray(energy_model[1], dtype=np.float64)
+        rp, cc, vv, val64 = pad_csr(rowptr, col, val, seats, n_dev, also=val64)
+        l64 = np.zeros(n_dev, dtype=np.float64)
+        l64[seats] = lin64
+        lin64 = l64
+    else:
+        rp, cc, vv = pad_csr(rowptr, col, val, seats, n_dev)
+    lpad = np.full(n_dev, np.inf, dtype=np.float32)
+    lpad[seats] = np.asarray(lin, dtype=np.float32)
+    wdev = np.ones(n_dev, dtype=np.int32)
+    wdev[seats] = weights
+    return (np.ascontiguousarray(rp, dtype=np.int32), np.ascontiguousarray(cc, dtype=np.int32),
+            np.ascontiguousarray(vv, dtype=np.float32), lpad, wdev, seats, n_dev, val64, lin64)
+
+
+def plan_anneal(kind, rowptr, col, n, num_reads, num_cases=2, cus=0, options=None, pair_weight_slot=-1,
+                node_weights=False, min_cluster_size=0):
+    """Which kernel an anneal of ``num_reads`` replicas would run for a structured model (``kind``: _lib.KIND_CSR_RANK1
+    or KIND_POTTS_CSR; the device-side CSR), decided on the host without touching a device (mi_sa_plan_anneal).
+    ``cus``: compute units of the device (0: 256); ``options``: ``{key: value}`` (or ``"key=value,..."``) with the
+    k2_* / k3_* keys of ``Problem.set_option``.  Returns ``(kernel_name, adjacency_bytes_per_slot)``; raises MiSaError
+    with the code and message that creating or annealing the problem would."""
+    if isinstance(options, dict):
+        options = ",".join("%s=%d" % (k, int(v)) for k, v in sorted(options.items()))
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    name = C.create_string_buffer(256)
+    nbytes = C.c_int(0)
+    _lib.check(_lib.load().mi_sa_plan_anneal(
+        int(kind), _ptr(rowptr, C.c_int32), _ptr(col, C.c_int32), int(n), int(num_cases), int(num_reads), int(cus),
+        (options or "").encode(), int(pair_weight_slot), int(bool(node_weights)), int(min_cluster_size), name, 256,
+        C.byref(nbytes)))
+    return name.value.decode(), int(nbytes.value)
 
 
 def energy_dense(Qs: np.ndarray, X: np.ndarray, offset: float = 0.0, device: int = 0, path: int = 0,
