@@ -306,20 +306,19 @@ int mi_label_agreement_dev(const AgreeArgs &in, hipStream_t st, double *out_ari,
     long long *d_s = nullptr, *d_S = nullptr;
     double *d_t = nullptr, *d_tab = nullptr, *d_ari = nullptr, *d_nmi = nullptr;
     int *d_k = nullptr, *d_tables = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = guarded([&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_lab, (size_t)rows * npad));
-        HIP_TRY(hipMalloc((void **)&d_s, (size_t)rows * sizeof(long long)));
-        HIP_TRY(hipMalloc((void **)&d_t, (size_t)rows * sizeof(double)));
-        HIP_TRY(hipMalloc((void **)&d_k, (size_t)rows * sizeof(int)));
-        HIP_TRY(hipMalloc((void **)&d_tab, ((size_t)in.n_real + 1) * sizeof(double)));
-        HIP_TRY(hipMalloc((void **)&d_ari, (size_t)pairs * sizeof(double)));
-        HIP_TRY(hipMalloc((void **)&d_nmi, (size_t)pairs * sizeof(double)));
-        HIP_TRY(hipMalloc((void **)&d_S, (size_t)pairs * sizeof(long long)));
-        if (out_tables) HIP_TRY(hipMalloc((void **)&d_tables, (size_t)pairs * Ka * Kb * sizeof(int)));
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        HIP_TRY(bufs.alloc(&d_lab, (size_t)rows * npad));
+        HIP_TRY(bufs.alloc(&d_s, (size_t)rows));
+        HIP_TRY(bufs.alloc(&d_t, (size_t)rows));
+        HIP_TRY(bufs.alloc(&d_k, (size_t)rows));
+        HIP_TRY(bufs.alloc(&d_tab, ((size_t)in.n_real + 1)));
+        HIP_TRY(bufs.alloc(&d_ari, (size_t)pairs));
+        HIP_TRY(bufs.alloc(&d_nmi, (size_t)pairs));
+        HIP_TRY(bufs.alloc(&d_S, (size_t)pairs));
+        if (out_tables) HIP_TRY(bufs.alloc(&d_tables, (size_t)pairs * Ka * Kb));
+        Timer tm;
+        MI_TRY(tm.start(st));
         hipLaunchKernelGGL(k_xlogx, dim3((unsigned)((in.n_real + 1 + 255) / 256)), dim3(256), 0, st, in.n_real, d_tab);
         hipLaunchKernelGGL(k_agree_prep, dim3((unsigned)Ra), dim3(256), 0, st, in.A, in.lda, in.cols, in.meta, npad,
                            (const double *)d_tab, d_lab, d_s, d_t, d_k);
@@ -343,22 +342,13 @@ int mi_label_agreement_dev(const AgreeArgs &in, hipStream_t st, double *out_ari,
         if (KB == 1) launch_agree<1>(g, blocks, st);
         else if (KB == 2) launch_agree<2>(g, blocks, st);
         else launch_agree<4>(g, blocks, st);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipEventSynchronize(e1));
-        if (out_kernel_ms) HIP_TRY(hipEventElapsedTime(out_kernel_ms, e0, e1));
+        MI_TRY(tm.stop(st, out_kernel_ms));
         if (out_ari) HIP_TRY(hipMemcpy(out_ari, d_ari, (size_t)pairs * sizeof(double), hipMemcpyDeviceToHost));
         if (out_nmi) HIP_TRY(hipMemcpy(out_nmi, d_nmi, (size_t)pairs * sizeof(double), hipMemcpyDeviceToHost));
         if (out_pair_sum) HIP_TRY(hipMemcpy(out_pair_sum, d_S, (size_t)pairs * sizeof(long long), hipMemcpyDeviceToHost));
         if (out_tables) HIP_TRY(hipMemcpy(out_tables, d_tables, (size_t)pairs * Ka * Kb * sizeof(int), hipMemcpyDeviceToHost));
         return MI_OK;
     });
-    void *bufs[] = {d_lab, d_s, d_t, d_k, d_tab, d_ari, d_nmi, d_S, d_tables};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
 }
 
 }  // namespace mi_sa_impl
@@ -393,16 +383,14 @@ extern "C" int mi_label_agreement_u16(const uint16_t *A, int Ra, const uint16_t 
     if (B)
         for (size_t e = 0; e < (size_t)Rb * n; ++e)
             if (B[e] >= Kb) return fail(MI_EINVAL, "label %d of B[%zu][%zu] outside [0, %d)", B[e], e / n, e % n, Kb);
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
-    HIP_TRY(hipSetDevice(device));
+    MI_TRY(pick_device(device));
     uint16_t *d_A = nullptr, *d_B = nullptr;
-    int rc = guarded([&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_A, (size_t)Ra * n * sizeof(uint16_t)));
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        HIP_TRY(bufs.alloc(&d_A, (size_t)Ra * n));
         HIP_TRY(hipMemcpy(d_A, A, (size_t)Ra * n * sizeof(uint16_t), hipMemcpyHostToDevice));
         if (B) {
-            HIP_TRY(hipMalloc((void **)&d_B, (size_t)Rb * n * sizeof(uint16_t)));
+            HIP_TRY(bufs.alloc(&d_B, (size_t)Rb * n));
             HIP_TRY(hipMemcpy(d_B, B, (size_t)Rb * n * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
         AgreeArgs a;
@@ -410,7 +398,4 @@ extern "C" int mi_label_agreement_u16(const uint16_t *A, int Ra, const uint16_t 
         a.Ra = Ra; a.Rb = Rb; a.cols = n; a.Ka = Ka; a.Kb = Kb; a.groups = groups; a.meta = nullptr; a.n_real = n;
         return mi_label_agreement_dev(a, 0, out_ari, out_nmi, out_pair_sum, out_tables, out_kernel_ms);
     });
-    if (d_A) (void)hipFree(d_A);
-    if (d_B) (void)hipFree(d_B);
-    return rc;
 }

@@ -323,8 +323,8 @@ int mi_coassociation_dev(const CoassocArgs &in, hipStream_t st, int64_t *out_his
     unsigned long long *d_part = nullptr, *d_rowsum = nullptr;
     long long *d_hist = nullptr;
     int *d_counts = nullptr, *d_eu = nullptr, *d_ev = nullptr, *d_edge = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = guarded([&]() -> int {
+    return guarded([&]() -> int {
+        DevBufs bufs;
         int dev = 0, cus = 256;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -334,35 +334,34 @@ int mi_coassociation_dev(const CoassocArgs &in, hipStream_t st, int64_t *out_his
         const long long floor_wgs = (tpg + 131071) / 131072;                         // 131072 tiles x 16384 pairs = 2^31
         if (want < floor_wgs) want = floor_wgs;
         const int wgs = (int)(want < tpg ? want : tpg);
-        HIP_TRY(hipMalloc((void **)&d_lab, (size_t)G * Rp * npad));
+        HIP_TRY(bufs.alloc(&d_lab, (size_t)G * Rp * npad));
         if (m2) {
             if (out_hist) {
-                HIP_TRY(hipMalloc((void **)&d_part, (size_t)G * wgs * ((size_t)Rg + 1) * sizeof(unsigned long long)));
-                HIP_TRY(hipMalloc((void **)&d_hist, (size_t)G * ((size_t)Rg + 1) * sizeof(long long)));
+                HIP_TRY(bufs.alloc(&d_part, (size_t)G * wgs * ((size_t)Rg + 1)));
+                HIP_TRY(bufs.alloc(&d_hist, (size_t)G * ((size_t)Rg + 1)));
             }
             if (out_rowsum) {
                 std::vector<uint8_t> ref8((size_t)G * npad, (uint8_t)kNoLabel);
                 for (int g = 0; g < G; ++g)
                     for (int i = 0; i < n; ++i) ref8[(size_t)g * npad + i] = (uint8_t)in.ref[(size_t)g * n + i];
-                HIP_TRY(hipMalloc((void **)&d_ref, ref8.size()));
+                HIP_TRY(bufs.alloc(&d_ref, ref8.size()));
                 HIP_TRY(hipMemcpyAsync(d_ref, ref8.data(), ref8.size(), hipMemcpyHostToDevice, st));
                 HIP_TRY(hipStreamSynchronize(st));                                   // (ref8 is a host temporary)
-                HIP_TRY(hipMalloc((void **)&d_rowsum, (size_t)G * n * in.Kref * sizeof(unsigned long long)));
+                HIP_TRY(bufs.alloc(&d_rowsum, (size_t)G * n * in.Kref));
                 HIP_TRY(hipMemsetAsync(d_rowsum, 0, (size_t)G * n * in.Kref * sizeof(unsigned long long), st));
             }
-            if (out_counts) HIP_TRY(hipMalloc((void **)&d_counts, (size_t)G * n * n * sizeof(int)));
+            if (out_counts) HIP_TRY(bufs.alloc(&d_counts, (size_t)G * n * n));
         }
         if (m3) {
-            HIP_TRY(hipMalloc((void **)&d_eu, (size_t)in.m * sizeof(int)));
-            HIP_TRY(hipMalloc((void **)&d_ev, (size_t)in.m * sizeof(int)));
-            HIP_TRY(hipMalloc((void **)&d_edge, (size_t)G * in.m * sizeof(int)));
+            HIP_TRY(bufs.alloc(&d_eu, (size_t)in.m));
+            HIP_TRY(bufs.alloc(&d_ev, (size_t)in.m));
+            HIP_TRY(bufs.alloc(&d_edge, (size_t)G * in.m));
             HIP_TRY(hipMemcpyAsync(d_eu, in.eu, (size_t)in.m * sizeof(int), hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(d_ev, in.ev, (size_t)in.m * sizeof(int), hipMemcpyHostToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
+        Timer tm;
+        MI_TRY(tm.start(st));
         hipLaunchKernelGGL(k_coassoc_prep, dim3((unsigned)(G * Rp)), dim3(256), 0, st, in.L, in.ld, n, Rg, Rp, in.meta, npad, d_lab);
         HIP_TRY(hipGetLastError());
         if (m2) {
@@ -393,21 +392,13 @@ int mi_coassociation_dev(const CoassocArgs &in, hipStream_t st, int64_t *out_his
                                (const uint8_t *)d_lab, npad, Rg, Rp, chunk, (const int *)d_eu, (const int *)d_ev, (long long)in.m, d_edge);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipEventSynchronize(e1));
-        if (out_kernel_ms) HIP_TRY(hipEventElapsedTime(out_kernel_ms, e0, e1));
+        MI_TRY(tm.stop(st, out_kernel_ms));
         if (out_hist) HIP_TRY(hipMemcpy(out_hist, d_hist, (size_t)G * ((size_t)Rg + 1) * sizeof(long long), hipMemcpyDeviceToHost));
         if (out_rowsum) HIP_TRY(hipMemcpy(out_rowsum, d_rowsum, (size_t)G * n * in.Kref * sizeof(long long), hipMemcpyDeviceToHost));
         if (out_counts) HIP_TRY(hipMemcpy(out_counts, d_counts, (size_t)G * n * n * sizeof(int), hipMemcpyDeviceToHost));
         if (m3) HIP_TRY(hipMemcpy(out_edge, d_edge, (size_t)G * in.m * sizeof(int), hipMemcpyDeviceToHost));
         return MI_OK;
     });
-    void *bufs[] = {d_lab, d_ref, d_part, d_rowsum, d_hist, d_counts, d_eu, d_ev, d_edge};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
 }
 
 // shapes, labels and edges that both entry points check the same way (everything here is host data)
@@ -449,19 +440,15 @@ extern "C" int mi_coassociation_u16(const uint16_t *L, int R, int n, int K, int 
         return fail(MI_EUNSUPPORTED, "%d reads per group exceed MI_COASSOC_MAX_READS = %d", R / groups, MI_COASSOC_MAX_READS);
     if (out_counts && (double)groups * n * n > (double)MI_COASSOC_MAX_COUNT_ENTRIES)
         return fail(MI_EUNSUPPORTED, "%d co-association matrices of %d x %d exceed %d entries", groups, n, n, MI_COASSOC_MAX_COUNT_ENTRIES);
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
-    HIP_TRY(hipSetDevice(device));
+    MI_TRY(pick_device(device));
     uint16_t *d_L = nullptr;
-    int rc = guarded([&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_L, (size_t)R * n * sizeof(uint16_t)));
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        HIP_TRY(bufs.alloc(&d_L, (size_t)R * n));
         HIP_TRY(hipMemcpy(d_L, L, (size_t)R * n * sizeof(uint16_t), hipMemcpyHostToDevice));
         CoassocArgs a;
         a.L = d_L; a.ld = (size_t)n; a.R = R; a.cols = n; a.K = K; a.groups = groups; a.meta = nullptr;
         a.ref = ref; a.Kref = ref ? Kref : 1; a.eu = eu; a.ev = ev; a.m = out_edge ? m : 0;
         return mi_coassociation_dev(a, 0, out_hist, out_rowsum, out_edge, out_counts, out_kernel_ms);
     });
-    if (d_L) (void)hipFree(d_L);
-    return rc;
 }

@@ -182,13 +182,12 @@ int mi_components_dev(const ComponentsArgs &a, int B, bool force_global, hipStre
     // small items: more workgroups per CU beat more threads per item
     const int threads = n <= 4096 ? 256 : 1024;
     int32_t *d_out = nullptr, *d_count = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = guarded([&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_out, (size_t)B * n * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&d_count, (size_t)B * sizeof(int32_t)));
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        HIP_TRY(bufs.alloc(&d_out, (size_t)B * n));
+        HIP_TRY(bufs.alloc(&d_count, (size_t)B));
+        Timer tm;
+        MI_TRY(tm.start(st));
         if (use_lds) {
             if (lds > 64 * 1024)
                 HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_components<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -196,19 +195,11 @@ int mi_components_dev(const ComponentsArgs &a, int B, bool force_global, hipStre
         } else {
             hipLaunchKernelGGL(k_components<false>, dim3((unsigned)B), dim3((unsigned)threads), 0, st, a, d_out, d_count);
         }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipEventSynchronize(e1));
-        if (out_kernel_ms) HIP_TRY(hipEventElapsedTime(out_kernel_ms, e0, e1));
+        MI_TRY(tm.stop(st, out_kernel_ms));
         HIP_TRY(hipMemcpy(out_labels, d_out, (size_t)B * n * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(out_count, d_count, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost));
         return MI_OK;
     });
-    if (d_out) (void)hipFree(d_out);
-    if (d_count) (void)hipFree(d_count);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
 }
 
 }  // namespace mi_sa_impl
@@ -231,24 +222,22 @@ extern "C" int mi_graph_components(const int32_t *rowptr, const int32_t *col, in
         if (col[e] < 0 || col[e] >= n) return fail(MI_EINVAL, "col[%lld] = %d outside [0, %d)", (long long)e, col[e], n);
     if ((double)B * (double)n > (double)MI_COMPONENTS_MAX_ENTRIES)
         return fail(MI_EUNSUPPORTED, "%d items of %d cells exceed %lld output entries", B, n, (long long)MI_COMPONENTS_MAX_ENTRIES);
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
-    HIP_TRY(hipSetDevice(device));
+    MI_TRY(pick_device(device));
     int32_t *d_rowptr = nullptr, *d_col = nullptr;
     uint16_t *d_L = nullptr;
     uint8_t *d_keep = nullptr;
-    int rc = guarded([&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_rowptr, ((size_t)n + 1) * sizeof(int32_t)));
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        HIP_TRY(bufs.alloc(&d_rowptr, ((size_t)n + 1)));
         HIP_TRY(hipMemcpy(d_rowptr, rowptr, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void **)&d_col, (size_t)(nnz > 0 ? nnz : 1) * sizeof(int32_t)));
+        HIP_TRY(bufs.alloc(&d_col, (size_t)(nnz > 0 ? nnz : 1)));
         if (nnz > 0) HIP_TRY(hipMemcpy(d_col, col, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
         if (L) {
-            HIP_TRY(hipMalloc((void **)&d_L, (size_t)B * n * sizeof(uint16_t)));
+            HIP_TRY(bufs.alloc(&d_L, (size_t)B * n));
             HIP_TRY(hipMemcpy(d_L, L, (size_t)B * n * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
         if (keep && nnz > 0) {
-            HIP_TRY(hipMalloc((void **)&d_keep, (size_t)B * (size_t)nnz));
+            HIP_TRY(bufs.alloc(&d_keep, (size_t)B * (size_t)nnz));
             HIP_TRY(hipMemcpy(d_keep, keep, (size_t)B * (size_t)nnz, hipMemcpyHostToDevice));
         }
         ComponentsArgs a;
@@ -256,8 +245,4 @@ extern "C" int mi_graph_components(const int32_t *rowptr, const int32_t *col, in
         a.L = d_L; a.ldl = (size_t)n; a.keep = d_keep;
         return mi_components_dev(a, B, (flags & MI_COMPONENTS_GLOBAL) != 0, 0, out_labels, out_count, out_kernel_ms);
     });
-    void *bufs[] = {d_rowptr, d_col, d_L, d_keep};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    return rc;
 }

@@ -270,8 +270,8 @@ extern "C" int mi_rank_sum_markers_f32(const float *X, int n, int g, const uint1
     double *d_sum = nullptr;
     unsigned long long *d_slab = nullptr;
     uint32_t *d_slab_mid = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = guarded([&]() -> int {
+    return guarded([&]() -> int {
+        DevBufs bufs;
         // host scans: the labels (range, cluster sizes, cell-major copy) and X (finite; non-zero cells per gene)
         std::vector<int32_t> sizes((size_t)B * K, 0), nnz((size_t)g, 0);
         std::vector<uint16_t> Lt((size_t)n * Bp, 0);
@@ -303,10 +303,7 @@ extern "C" int mi_rank_sum_markers_f32(const float *X, int n, int g, const uint1
         const size_t lds_bytes = ((size_t)lds_cap * 12 + (size_t)kMarkersChunk * K * 12 + 15) & ~(size_t)15;
         const int threads = (lds_cap > 2048 || slab_stride > 2048) ? 1024 : 256;
 
-        int cnt = 0;
-        if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
-        if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
-        HIP_TRY(hipSetDevice(device));
+        MI_TRY(pick_device(device));
         int cus = 0;
         HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
         size_t grid = (size_t)(cus > 0 ? cus : 1) * 8;
@@ -315,18 +312,18 @@ extern "C" int mi_rank_sum_markers_f32(const float *X, int n, int g, const uint1
         if (grid < 1) grid = 1;
 
         const size_t cells = (size_t)n * g;
-        HIP_TRY(hipMalloc((void **)&d_X, cells * sizeof(float)));
-        HIP_TRY(hipMalloc((void **)&d_Xt, cells * sizeof(float)));
-        HIP_TRY(hipMalloc((void **)&d_Lt, Lt.size() * sizeof(uint16_t)));
-        HIP_TRY(hipMalloc((void **)&d_sizes, sizes.size() * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&d_nnz, nnz.size() * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&d_rank2, entries * sizeof(long long)));
-        HIP_TRY(hipMalloc((void **)&d_npos, entries * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&d_tie, (size_t)g * sizeof(long long)));
-        if (want_sum) HIP_TRY(hipMalloc((void **)&d_sum, entries * sizeof(double)));
+        HIP_TRY(bufs.alloc(&d_X, cells));
+        HIP_TRY(bufs.alloc(&d_Xt, cells));
+        HIP_TRY(bufs.alloc(&d_Lt, Lt.size()));
+        HIP_TRY(bufs.alloc(&d_sizes, sizes.size()));
+        HIP_TRY(bufs.alloc(&d_nnz, nnz.size()));
+        HIP_TRY(bufs.alloc(&d_rank2, entries));
+        HIP_TRY(bufs.alloc(&d_npos, entries));
+        HIP_TRY(bufs.alloc(&d_tie, (size_t)g));
+        if (want_sum) HIP_TRY(bufs.alloc(&d_sum, entries));
         if (slab_stride) {
-            HIP_TRY(hipMalloc((void **)&d_slab, grid * slab_stride * sizeof(unsigned long long)));
-            HIP_TRY(hipMalloc((void **)&d_slab_mid, grid * slab_stride * sizeof(uint32_t)));
+            HIP_TRY(bufs.alloc(&d_slab, grid * slab_stride));
+            HIP_TRY(bufs.alloc(&d_slab_mid, grid * slab_stride));
         }
         HIP_TRY(hipMemcpy(d_X, X, cells * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_Lt, Lt.data(), Lt.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -340,9 +337,8 @@ extern "C" int mi_rank_sum_markers_f32(const float *X, int n, int g, const uint1
         a.rank2 = d_rank2; a.npos = d_npos; a.tie = d_tie;
         if (lds_bytes > 64 * 1024)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_markers_rank), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, 0));
+        Timer tm;
+        MI_TRY(tm.start(0));
         hipLaunchKernelGGL(k_markers_transpose, dim3((unsigned)((g + kMarkersTile - 1) / kMarkersTile), (unsigned)((n + kMarkersTile - 1) / kMarkersTile)),
                            dim3(256), 0, 0, d_X, d_Xt, n, g);
         HIP_TRY(hipGetLastError());
@@ -357,19 +353,11 @@ extern "C" int mi_rank_sum_markers_f32(const float *X, int n, int g, const uint1
                                rows ? (size_t)n : (size_t)1, d_Lt, n, g, B, Bp, K, (flags & MI_MARKERS_SUM_PLAIN) ? 1 : 0, d_sum);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipEventRecord(e1, 0));
-        HIP_TRY(hipEventSynchronize(e1));
-        if (out_kernel_ms) HIP_TRY(hipEventElapsedTime(out_kernel_ms, e0, e1));
+        MI_TRY(tm.stop(0, out_kernel_ms));
         HIP_TRY(hipMemcpy(out_rank2, d_rank2, entries * sizeof(long long), hipMemcpyDeviceToHost));
         if (out_npos) HIP_TRY(hipMemcpy(out_npos, d_npos, entries * sizeof(int32_t), hipMemcpyDeviceToHost));
         if (out_sum) HIP_TRY(hipMemcpy(out_sum, d_sum, entries * sizeof(double), hipMemcpyDeviceToHost));
         if (out_tie) HIP_TRY(hipMemcpy(out_tie, d_tie, (size_t)g * sizeof(long long), hipMemcpyDeviceToHost));
         return MI_OK;
     });
-    void *bufs[] = {d_X, d_Xt, d_Lt, d_sizes, d_nnz, d_rank2, d_npos, d_tie, d_sum, d_slab, d_slab_mid};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
 }

@@ -157,10 +157,7 @@ extern "C" int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, 
     if (lds > 160 * 1024) return fail(MI_EUNSUPPORTED, "gene rows of %d words exceed the LDS plan (%zu B)", words, lds);
     for (int i = 0; i < n; ++i)
         if (labels[i] < 0 || labels[i] >= K) return fail(MI_EINVAL, "label %d of cell %d outside [0, %d)", labels[i], i, K);
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
-    HIP_TRY(hipSetDevice(device));
+    MI_TRY(pick_device(device));
     unsigned long long *d_bits = nullptr, *d_diam = nullptr, *d_sep = nullptr;
     int *d_lab = nullptr, *d_orig = nullptr;
     double *d_rowsum = nullptr, *d_sqa = nullptr, *d_sqw = nullptr, *d_part = nullptr;
@@ -172,17 +169,17 @@ extern "C" int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, 
     S = (n + slice_len - 1) / slice_len;
     const size_t per_plane = (size_t)n * K + 2 * (size_t)n;                   // rowsum, rowsq_all, rowsq_within
     float *d_D = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = guarded([&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_bits, (size_t)n * words * 8));
-        HIP_TRY(hipMalloc((void **)&d_lab, (size_t)n * 4));
-        HIP_TRY(hipMalloc((void **)&d_rowsum, (size_t)n * K * 8));
-        HIP_TRY(hipMalloc((void **)&d_sqa, (size_t)n * 8));
-        HIP_TRY(hipMalloc((void **)&d_sqw, (size_t)n * 8));
-        HIP_TRY(hipMalloc((void **)&d_part, (size_t)S * per_plane * 8));
-        HIP_TRY(hipMalloc((void **)&d_diam, (size_t)K * 8));
-        HIP_TRY(hipMalloc((void **)&d_sep, (size_t)K * K * 8));
-        if (out_D) HIP_TRY(hipMalloc((void **)&d_D, (size_t)n * n * 4));
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        HIP_TRY(bufs.alloc(&d_bits, (size_t)n * words));
+        HIP_TRY(bufs.alloc(&d_lab, (size_t)n));
+        HIP_TRY(bufs.alloc(&d_rowsum, (size_t)n * K));
+        HIP_TRY(bufs.alloc(&d_sqa, (size_t)n));
+        HIP_TRY(bufs.alloc(&d_sqw, (size_t)n));
+        HIP_TRY(bufs.alloc(&d_part, (size_t)S * per_plane));
+        HIP_TRY(bufs.alloc(&d_diam, (size_t)K));
+        HIP_TRY(bufs.alloc(&d_sep, (size_t)K * K));
+        if (out_D) HIP_TRY(bufs.alloc(&d_D, (size_t)n * n));
         // cells sorted by cluster (counting sort: stable, index order inside a cluster)
         std::vector<int> start((size_t)K + 1, 0), order((size_t)n), lab_s((size_t)n);
         for (int i = 0; i < n; ++i) start[labels[i] + 1]++;
@@ -193,7 +190,7 @@ extern "C" int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, 
             lab_s[p] = labels[order[p]];
             memcpy(&bits_s[(size_t)p * words], &bits[(size_t)order[p] * words], (size_t)words * 8);
         }
-        HIP_TRY(hipMalloc((void **)&d_orig, (size_t)n * 4));
+        HIP_TRY(bufs.alloc(&d_orig, (size_t)n));
         HIP_TRY(hipMemcpy(d_bits, bits_s.data(), (size_t)n * words * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_lab, lab_s.data(), (size_t)n * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_orig, order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -201,11 +198,10 @@ extern "C" int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, 
         HIP_TRY(hipMemset(d_diam, 0, (size_t)K * 8));
         std::vector<double> inf((size_t)K * K, INFINITY);
         HIP_TRY(hipMemcpy(d_sep, inf.data(), inf.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
         if (lds > 64 * 1024)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_jaccard_stats), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipEventRecord(e0, 0));
+        Timer tm;
+        MI_TRY(tm.start(0));
         // planes: [S][n][K] distance sums, then [S][n] squared sums (all), then [S][n] squared sums (within)
         double *p_rowsum = d_part, *p_sqa = d_part + (size_t)S * n * K, *p_sqw = p_sqa + (size_t)S * n;
         hipLaunchKernelGGL(k_jaccard_stats, dim3(blocks, S), dim3(kMetRows), lds, 0, d_bits, n, words, d_lab, d_orig, K, slice_len,
@@ -215,10 +211,7 @@ extern "C" int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, 
         hipLaunchKernelGGL(k_reduce_slices, dim3((unsigned)((c1 + 255) / 256)), dim3(256), 0, 0, p_rowsum, S, c1, d_rowsum);
         hipLaunchKernelGGL(k_reduce_slices, dim3((unsigned)((c2 + 255) / 256)), dim3(256), 0, 0, p_sqa, S, c2, d_sqa);
         hipLaunchKernelGGL(k_reduce_slices, dim3((unsigned)((c2 + 255) / 256)), dim3(256), 0, 0, p_sqw, S, c2, d_sqw);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e1, 0));
-        HIP_TRY(hipEventSynchronize(e1));
-        if (out_kernel_ms) HIP_TRY(hipEventElapsedTime(out_kernel_ms, e0, e1));
+        MI_TRY(tm.stop(0, out_kernel_ms));
         HIP_TRY(hipMemcpy(rowsum, d_rowsum, (size_t)n * K * 8, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(rowsq_all, d_sqa, (size_t)n * 8, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(rowsq_within, d_sqw, (size_t)n * 8, hipMemcpyDeviceToHost));
@@ -228,10 +221,4 @@ extern "C" int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, 
         if (out_D) HIP_TRY(hipMemcpy(out_D, d_D, (size_t)n * n * 4, hipMemcpyDeviceToHost));
         return MI_OK;
     });
-    void *bufs[] = {d_orig, d_bits, d_lab, d_rowsum, d_sqa, d_sqw, d_part, d_diam, d_sep, d_D};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
 }

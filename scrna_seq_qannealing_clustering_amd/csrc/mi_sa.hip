@@ -261,17 +261,6 @@ struct mi_sa_problem {
 
 namespace {
 
-int select_device(int device)
-{
-    int cnt = 0;
-    hipError_t e = hipGetDeviceCount(&cnt);
-    if (e != hipSuccess || cnt <= 0)
-        return fail(MI_ENODEV, "no HIP device visible (%s)", hipGetErrorString(e));
-    if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
-    HIP_TRY(hipSetDevice(device));
-    return MI_OK;
-}
-
 int ensure_run_buffers(mi_sa_problem *p, int R, int num_sweeps, bool need_init)
 {
     if (R > p->cap_R) {
@@ -359,8 +348,7 @@ int mi_device_count(int *out_count)
 
 int mi_device_info(int device, char *name, int len, int *out_cus, uint64_t *out_hbm_bytes)
 {
-    int rc = select_device(device);
-    if (rc) return rc;
+    MI_TRY(pick_device(device));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (name && len > 0) snprintf(name, (size_t)len, "%s (%s)", prop.name, prop.gcnArchName);
@@ -389,7 +377,7 @@ int mi_sa_problem_create_dense_f32(const float *Qs, int n, double offset, int de
     if (n < 1) return fail(MI_EINVAL, "n must be >= 1 (got %d)", n);
     if (n > kMaxDenseXlN)
         return fail(MI_EUNSUPPORTED, "dense kernels support n <= %d (got %d)", kMaxDenseXlN, n);
-    int rc = select_device(device);
+    int rc = pick_device(device);
     if (rc) return rc;
     mi_sa_problem *p = new (std::nothrow) mi_sa_problem();
     if (!p) return fail(MI_ENOMEM, "out of host memory");
@@ -756,7 +744,7 @@ int mi_sa_problem_create_csr_rank1_f32(const int32_t *rowptr, const int32_t *col
     if (!rowptr || !lin || !out || (rowptr[n > 0 ? n : 0] > 0 && (!col || !val))) return fail(MI_EINVAL, "NULL argument");
     std::string err;
     if (const int rc_s = slot_model_size_check(MI_KIND_CSR_RANK1, n, 2, &err)) return fail(rc_s, "%s", err.c_str());
-    int rc = select_device(device);
+    int rc = pick_device(device);
     if (rc) return rc;
     mi_sa_problem *p = new (std::nothrow) mi_sa_problem();
     if (!p) return fail(MI_ENOMEM, "out of host memory");
@@ -808,7 +796,7 @@ int mi_sa_problem_create_potts_csr_f32(const int32_t *rowptr, const int32_t *col
     if (!rowptr || !out || (rowptr[n > 0 ? n : 0] > 0 && (!col || !val))) return fail(MI_EINVAL, "NULL argument");
     std::string err;
     if (const int rc_s = slot_model_size_check(MI_KIND_POTTS_CSR, n, K, &err)) return fail(rc_s, "%s", err.c_str());
-    int rc = select_device(device);
+    int rc = pick_device(device);
     if (rc) return rc;
     mi_sa_problem *p = new (std::nothrow) mi_sa_problem();
     if (!p) return fail(MI_ENOMEM, "out of host memory");
@@ -1739,42 +1727,30 @@ int mi_energy_dense_f32_ex(const float *Qs, int n, const uint8_t *X, int R, doub
         }
     }
     if (path == 0) path = (R >= 32) ? 2 : 1;      // MFMA only when the batch is a real dense contraction
-    int rc = select_device(device);
-    if (rc) return rc;
-    float *dQ = nullptr; uint8_t *dX = nullptr, *dXt = nullptr; double *dE = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    rc = [&]() -> int {
+    MI_TRY(pick_device(device));
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        float *dQ = nullptr; uint8_t *dX = nullptr, *dXt = nullptr; double *dE = nullptr;
         // the MFMA kernel reads whole 128 x 128 blocks: rows padded to n_pad floats, n_pad rows, padding zero
         const size_t ldq = path == 2 ? ((size_t)n + 127) / 128 * 128 : (size_t)n;
         const size_t rows = path == 2 ? ldq : (size_t)n;
-        HIP_TRY(hipMalloc((void **)&dQ, rows * ldq * sizeof(float)));
-        HIP_TRY(hipMalloc((void **)&dX, (size_t)R * n));
-        HIP_TRY(hipMalloc((void **)&dE, (size_t)R * sizeof(double)));
+        HIP_TRY(bufs.alloc(&dQ, rows * ldq));
+        HIP_TRY(bufs.alloc(&dX, (size_t)R * n));
+        HIP_TRY(bufs.alloc(&dE, (size_t)R));
         if (path == 2) {
-            HIP_TRY(hipMalloc((void **)&dXt, mi_energy_dense_scratch_bytes(n, R)));
+            HIP_TRY(bufs.alloc(&dXt, mi_energy_dense_scratch_bytes(n, R)));
             HIP_TRY(hipMemset(dQ, 0, rows * ldq * sizeof(float)));
         }
         HIP_TRY(hipMemcpy2D(dQ, ldq * sizeof(float), Qs, (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)n,
                             hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dX, X, (size_t)R * n, hipMemcpyHostToDevice));
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, 0));
-        int r2 = mi_launch_energy_dense(dQ, n, (int)ldq, dX, R, offset, dE, dXt, path, 0);
-        if (r2) return r2;
-        HIP_TRY(hipEventRecord(e1, 0));
-        HIP_TRY(hipEventSynchronize(e1));
-        if (out_kernel_ms) HIP_TRY(hipEventElapsedTime(out_kernel_ms, e0, e1));
+        Timer tm;
+        MI_TRY(tm.start(0));
+        MI_TRY(mi_launch_energy_dense(dQ, n, (int)ldq, dX, R, offset, dE, dXt, path, 0));
+        MI_TRY(tm.stop(0, out_kernel_ms));
         HIP_TRY(hipMemcpy(out_energy, dE, (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
         return MI_OK;
-    }();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (dQ) (void)hipFree(dQ);
-    if (dX) (void)hipFree(dX);
-    if (dXt) (void)hipFree(dXt);
-    if (dE) (void)hipFree(dE);
-    return rc;
+    });
 }
 
 int mi_energy_dense_f64(const double *Qs, int n, const uint8_t *X, int R, double offset,
@@ -1782,24 +1758,19 @@ int mi_energy_dense_f64(const double *Qs, int n, const uint8_t *X, int R, double
 {
     if (!Qs || !X || !out_energy) return fail(MI_EINVAL, "NULL argument");
     if (n < 1 || R < 1) return fail(MI_EINVAL, "n and R must be >= 1");
-    int rc = select_device(device);
-    if (rc) return rc;
-    double *dQ = nullptr, *dE = nullptr; uint8_t *dX = nullptr;
-    rc = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&dQ, (size_t)n * n * sizeof(double)));
-        HIP_TRY(hipMalloc((void **)&dX, (size_t)R * n));
-        HIP_TRY(hipMalloc((void **)&dE, (size_t)R * sizeof(double)));
+    MI_TRY(pick_device(device));
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        double *dQ = nullptr, *dE = nullptr; uint8_t *dX = nullptr;
+        HIP_TRY(bufs.alloc(&dQ, (size_t)n * n));
+        HIP_TRY(bufs.alloc(&dX, (size_t)R * n));
+        HIP_TRY(bufs.alloc(&dE, (size_t)R));
         HIP_TRY(hipMemcpy(dQ, Qs, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dX, X, (size_t)R * n, hipMemcpyHostToDevice));
-        int r2 = mi_launch_energy_dense_f64(dQ, n, dX, R, offset, dE, 0);
-        if (r2) return r2;
+        MI_TRY(mi_launch_energy_dense_f64(dQ, n, dX, R, offset, dE, 0));
         HIP_TRY(hipMemcpy(out_energy, dE, (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
         return MI_OK;
-    }();
-    if (dQ) (void)hipFree(dQ);
-    if (dX) (void)hipFree(dX);
-    if (dE) (void)hipFree(dE);
-    return rc;
+    });
 }
 
 int mi_energy_dense_f32(const float *Qs, int n, const uint8_t *X, int R, double offset,

@@ -277,50 +277,6 @@ __global__ void __launch_bounds__(256) k_prep_project(const float *__restrict__ 
         }
 }
 
-struct Timer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Timer()
-    {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    int start()
-    {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, 0));
-        return MI_OK;
-    }
-    int stop(float *out_ms)
-    {
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e1, 0));
-        HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        if (out_ms) *out_ms = ms;
-        return MI_OK;
-    }
-};
-
-struct DevBufs {                                                  // scratch of one call, freed on every way out
-    std::vector<void *> p;
-    ~DevBufs()
-    {
-        for (void *b : p)
-            if (b) (void)hipFree(b);
-    }
-    template <typename T>
-    hipError_t alloc(T **out, size_t count)
-    {
-        void *b = nullptr;
-        const hipError_t e = hipMalloc(&b, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(b);
-        *out = static_cast<T *>(b);
-        return e;
-    }
-};
-
 }  // namespace
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
@@ -330,12 +286,6 @@ struct mi_prep_matrix {
     bool normalized = false;
     float *d_X = nullptr, *d_Y = nullptr, *d_Z = nullptr;
 };
-
-#define TRY(expr)                   \
-    do {                            \
-        const int rc_ = (expr);     \
-        if (rc_ != MI_OK) return rc_; \
-    } while (0)
 
 namespace {
 
@@ -382,10 +332,7 @@ int mi_prep_create_f32(const float *X, int n, int g, int device, mi_prep_matrix 
     for (size_t e = 0; e < cells; ++e)
         if (!(X[e] >= 0.0f) || std::isinf(X[e]))
             return fail(MI_EINVAL, "X[%lld, %lld] is NaN, infinite or negative", (long long)(e / g), (long long)(e % g));
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
-    HIP_TRY(hipSetDevice(device));
+    MI_TRY(pick_device(device));
     mi_prep_matrix *m = new (std::nothrow) mi_prep_matrix();
     if (!m) return fail(MI_ENOMEM, "out of host memory");
     m->n = n; m->g = g; m->device = device;
@@ -411,10 +358,10 @@ int mi_prep_normalize(mi_prep_matrix *m, double scale_factor, float *out_kernel_
     if (!m->d_Y) HIP_TRY(hipMalloc((void **)&m->d_Y, (size_t)m->n * m->g * sizeof(float)));
     m->normalized = false;
     Timer t;
-    TRY(t.start());
+    MI_TRY(t.start(0));
     hipLaunchKernelGGL(k_prep_normalize, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_X, m->d_Y, m->n, m->g,
                        scale_factor);
-    TRY(t.stop(out_kernel_ms));
+    MI_TRY(t.stop(0, out_kernel_ms));
     m->normalized = true;
     return MI_OK;
 }
@@ -436,24 +383,26 @@ int mi_prep_gene_stats(mi_prep_matrix *m, int which, double *mean, double *var, 
     if (which == 1 && !m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
     HIP_TRY(hipSetDevice(m->device));
     const size_t g = (size_t)m->g, slices = (size_t)(m->n + kRowSlice - 1) / kRowSlice;
-    DevBufs bufs;
-    double *d_psum, *d_mean, *d_var;
-    int32_t *d_pnnz, *d_nnz;
-    HIP_TRY(bufs.alloc(&d_psum, slices * g));
-    HIP_TRY(bufs.alloc(&d_pnnz, slices * g));
-    HIP_TRY(bufs.alloc(&d_mean, g));
-    HIP_TRY(bufs.alloc(&d_var, g));
-    HIP_TRY(bufs.alloc(&d_nnz, g));
-    const float *M = which ? m->d_Y : m->d_X;
-    Timer t;
-    TRY(t.start());
-    TRY(col_reduce<kColSum>(m, M, nullptr, nullptr, 0.0, (double)m->n, d_psum, d_pnnz, d_mean, d_nnz));
-    TRY(col_reduce<kColCentred>(m, M, d_mean, nullptr, 0.0, (double)(m->n - 1), d_psum, nullptr, d_var, nullptr));
-    TRY(t.stop(out_kernel_ms));
-    if (mean) HIP_TRY(hipMemcpy(mean, d_mean, g * sizeof(double), hipMemcpyDeviceToHost));
-    if (var) HIP_TRY(hipMemcpy(var, d_var, g * sizeof(double), hipMemcpyDeviceToHost));
-    if (nnz) HIP_TRY(hipMemcpy(nnz, d_nnz, g * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return guarded([&]() -> int {                             // (the scratch owner holds a vector)
+        DevBufs bufs;
+        double *d_psum, *d_mean, *d_var;
+        int32_t *d_pnnz, *d_nnz;
+        HIP_TRY(bufs.alloc(&d_psum, slices * g));
+        HIP_TRY(bufs.alloc(&d_pnnz, slices * g));
+        HIP_TRY(bufs.alloc(&d_mean, g));
+        HIP_TRY(bufs.alloc(&d_var, g));
+        HIP_TRY(bufs.alloc(&d_nnz, g));
+        const float *M = which ? m->d_Y : m->d_X;
+        Timer t;
+        MI_TRY(t.start(0));
+        MI_TRY(col_reduce<kColSum>(m, M, nullptr, nullptr, 0.0, (double)m->n, d_psum, d_pnnz, d_mean, d_nnz));
+        MI_TRY(col_reduce<kColCentred>(m, M, d_mean, nullptr, 0.0, (double)(m->n - 1), d_psum, nullptr, d_var, nullptr));
+        MI_TRY(t.stop(0, out_kernel_ms));
+        if (mean) HIP_TRY(hipMemcpy(mean, d_mean, g * sizeof(double), hipMemcpyDeviceToHost));
+        if (var) HIP_TRY(hipMemcpy(var, d_var, g * sizeof(double), hipMemcpyDeviceToHost));
+        if (nnz) HIP_TRY(hipMemcpy(nnz, d_nnz, g * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
 }
 
 int mi_prep_clipped_variance(mi_prep_matrix *m, const double *mean, const double *sd, double clip, double *out,
@@ -468,20 +417,22 @@ int mi_prep_clipped_variance(mi_prep_matrix *m, const double *mean, const double
     }
     HIP_TRY(hipSetDevice(m->device));
     const size_t g = (size_t)m->g, slices = (size_t)(m->n + kRowSlice - 1) / kRowSlice;
-    DevBufs bufs;
-    double *d_psum, *d_mean, *d_sd, *d_out;
-    HIP_TRY(bufs.alloc(&d_psum, slices * g));
-    HIP_TRY(bufs.alloc(&d_mean, g));
-    HIP_TRY(bufs.alloc(&d_sd, g));
-    HIP_TRY(bufs.alloc(&d_out, g));
-    HIP_TRY(hipMemcpy(d_mean, mean, g * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_sd, sd, g * sizeof(double), hipMemcpyHostToDevice));
-    Timer t;
-    TRY(t.start());
-    TRY(col_reduce<kColClipped>(m, m->d_X, d_mean, d_sd, clip, (double)(m->n - 1), d_psum, nullptr, d_out, nullptr));
-    TRY(t.stop(out_kernel_ms));
-    HIP_TRY(hipMemcpy(out, d_out, g * sizeof(double), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        double *d_psum, *d_mean, *d_sd, *d_out;
+        HIP_TRY(bufs.alloc(&d_psum, slices * g));
+        HIP_TRY(bufs.alloc(&d_mean, g));
+        HIP_TRY(bufs.alloc(&d_sd, g));
+        HIP_TRY(bufs.alloc(&d_out, g));
+        HIP_TRY(hipMemcpy(d_mean, mean, g * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_sd, sd, g * sizeof(double), hipMemcpyHostToDevice));
+        Timer t;
+        MI_TRY(t.start(0));
+        MI_TRY(col_reduce<kColClipped>(m, m->d_X, d_mean, d_sd, clip, (double)(m->n - 1), d_psum, nullptr, d_out, nullptr));
+        MI_TRY(t.stop(0, out_kernel_ms));
+        HIP_TRY(hipMemcpy(out, d_out, g * sizeof(double), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
 }
 
 int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double *mu, const double *sigma, double clip,
@@ -529,7 +480,7 @@ int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double 
         HIP_TRY(hipMemcpy(d_inv, inv.data(), (size_t)h * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_flat, flat.data(), (size_t)h, hipMemcpyHostToDevice));
         Timer t;
-        TRY(t.start());
+        MI_TRY(t.start(0));
         // (one cell per grid.y, whose limit is 65535: slabs of 32768 cells)
         for (int r0 = 0; r0 < m->n; r0 += 32768) {
             const int rows = m->n - r0 < 32768 ? m->n - r0 : 32768;
@@ -538,7 +489,7 @@ int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double 
                                m->d_Z + (size_t)r0 * ldz);
             HIP_TRY(hipGetLastError());
         }
-        TRY(t.stop(out_kernel_ms));
+        MI_TRY(t.stop(0, out_kernel_ms));
         m->h = h;
         return MI_OK;
     });
@@ -565,25 +516,27 @@ int mi_prep_gram(mi_prep_matrix *m, double *out_G, float *out_kernel_ms)
     const size_t tile_bytes = (size_t)kTile * kTile * sizeof(float), ldg = (size_t)T * kTile;
     int batch = (int)(kGramWorkspace / (tile_bytes * tiles));
     batch = batch < 1 ? 1 : (batch > chunks ? chunks : batch);
-    DevBufs bufs;
-    float *d_P;
-    double *d_G;
-    HIP_TRY(bufs.alloc(&d_P, (size_t)batch * tiles * kTile * kTile));
-    HIP_TRY(bufs.alloc(&d_G, ldg * ldg));
-    Timer t;
-    TRY(t.start());
-    HIP_TRY(hipMemsetAsync(d_G, 0, ldg * ldg * sizeof(double), 0));
-    for (int c0 = 0; c0 < chunks; c0 += batch) {
-        const int nb = chunks - c0 < batch ? chunks - c0 : batch;
-        hipLaunchKernelGGL(k_prep_gram, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, 0, m->d_Z, m->ldz, m->n, T, c0, d_P);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_prep_gram_reduce, dim3((unsigned)tiles), dim3(256), 0, 0, d_P, tiles, nb, T, d_G);
-        HIP_TRY(hipGetLastError());
-    }
-    TRY(t.stop(out_kernel_ms));
-    HIP_TRY(hipMemcpy2D(out_G, (size_t)m->h * sizeof(double), d_G, ldg * sizeof(double), (size_t)m->h * sizeof(double),
-                        (size_t)m->h, hipMemcpyDeviceToHost));
-    return MI_OK;
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        float *d_P;
+        double *d_G;
+        HIP_TRY(bufs.alloc(&d_P, (size_t)batch * tiles * kTile * kTile));
+        HIP_TRY(bufs.alloc(&d_G, ldg * ldg));
+        Timer t;
+        MI_TRY(t.start(0));
+        HIP_TRY(hipMemsetAsync(d_G, 0, ldg * ldg * sizeof(double), 0));
+        for (int c0 = 0; c0 < chunks; c0 += batch) {
+            const int nb = chunks - c0 < batch ? chunks - c0 : batch;
+            hipLaunchKernelGGL(k_prep_gram, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, 0, m->d_Z, m->ldz, m->n, T, c0, d_P);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_prep_gram_reduce, dim3((unsigned)tiles), dim3(256), 0, 0, d_P, tiles, nb, T, d_G);
+            HIP_TRY(hipGetLastError());
+        }
+        MI_TRY(t.stop(0, out_kernel_ms));
+        HIP_TRY(hipMemcpy2D(out_G, (size_t)m->h * sizeof(double), d_G, ldg * sizeof(double), (size_t)m->h * sizeof(double),
+                            (size_t)m->h, hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
 }
 
 int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float *out_kernel_ms)
@@ -608,10 +561,10 @@ int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float 
         HIP_TRY(bufs.alloc(&d_out, (size_t)m->n * p));
         HIP_TRY(hipMemcpy(d_V, Vp.data(), Vp.size() * sizeof(float), hipMemcpyHostToDevice));
         Timer t;
-        TRY(t.start());
+        MI_TRY(t.start(0));
         hipLaunchKernelGGL(k_prep_project, dim3((unsigned)((m->n + kProjCells - 1) / kProjCells)), dim3(256), 0, 0, m->d_Z, m->ldz,
                            m->n, (m->h + kKC - 1) / kKC * kKC, d_V, p, d_out);
-        TRY(t.stop(out_kernel_ms));
+        MI_TRY(t.stop(0, out_kernel_ms));
         HIP_TRY(hipMemcpy(out, d_out, (size_t)m->n * p * sizeof(float), hipMemcpyDeviceToHost));
         return MI_OK;
     });

@@ -625,56 +625,47 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
     if (!(prune >= 0.0)) return fail(MI_EINVAL, "prune must be >= 0");
     if ((size_t)n + kRowCap * 8 + 64 > 160 * 1024)
         return fail(MI_EUNSUPPORTED, "SNN kernel keeps one byte per point in LDS: n <= %d (got %d)", 160 * 1024 - kRowCap * 8 - 64, n);
-    if (const int rc0 = mi_snn_check_points(X, n, dim)) return rc0;
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
-    HIP_TRY(hipSetDevice(device));
+    MI_TRY(mi_snn_check_points(X, n, dim));
+    MI_TRY(pick_device(device));
     mi_snn_graph *g = new (std::nothrow) mi_snn_graph();
     if (!g) return fail(MI_ENOMEM, "out of host memory");
     g->n = n; g->dim = dim; g->k = k; g->ord = ord; g->device = device; g->flags = (int)flags; g->ord2 = ord2;
-
-    float *dX = nullptr;
-    int *d_cnt = nullptr, *d_rn_ptr = nullptr, *d_cursor = nullptr, *d_deg = nullptr, *d_ptr0 = nullptr, *d_err = nullptr;
-    int32_t *d_rn_idx = nullptr, *d_col0 = nullptr, *d_sh0 = nullptr;
-    unsigned char *d_alive = nullptr, *d_alive2 = nullptr, *d_code0 = nullptr;
-    int32_t *d_key = nullptr, *d_table = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t st = nullptr;
-    int rc = guarded([&]() -> int {
+    const int rc = guarded([&]() -> int {
         int cus = 0;
         HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipMalloc((void **)&dX, (size_t)n * dim * sizeof(float)));
+        ScopedStream stream;                                     // (declared first: destroyed after the events and the scratch)
+        HIP_TRY(hipStreamCreateWithFlags(&stream.st, hipStreamNonBlocking));
+        const hipStream_t st = stream.st;
+        Events<4> ev;
+        for (auto &e : ev.e) HIP_TRY(hipEventCreate(&e));
+        DevBufs bufs;
+        float *dX = nullptr;
+        int *d_cnt = nullptr, *d_rn_ptr = nullptr, *d_cursor = nullptr, *d_deg = nullptr, *d_ptr0 = nullptr, *d_err = nullptr;
+        int32_t *d_rn_idx = nullptr, *d_col0 = nullptr, *d_sh0 = nullptr;
+        unsigned char *d_alive = nullptr, *d_alive2 = nullptr, *d_code0 = nullptr;
+        int32_t *d_key = nullptr, *d_table = nullptr;
+        HIP_TRY(bufs.alloc(&dX, (size_t)n * dim));
         HIP_TRY(hipMemcpy(dX, X, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMalloc((void **)&g->d_nn, (size_t)n * k * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&d_cnt, (size_t)(n + 1) * sizeof(int)));
-        HIP_TRY(hipMalloc((void **)&d_rn_ptr, (size_t)(n + 1) * sizeof(int)));
-        HIP_TRY(hipMalloc((void **)&d_cursor, (size_t)(n + 1) * sizeof(int)));
-        HIP_TRY(hipMalloc((void **)&d_rn_idx, (size_t)n * k * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&d_deg, (size_t)(n + 1) * sizeof(int)));
-        HIP_TRY(hipMalloc((void **)&d_ptr0, (size_t)(n + 1) * sizeof(int)));
+        HIP_TRY(bufs.alloc(&d_cnt, (size_t)(n + 1)));
+        HIP_TRY(bufs.alloc(&d_rn_ptr, (size_t)(n + 1)));
+        HIP_TRY(bufs.alloc(&d_cursor, (size_t)(n + 1)));
+        HIP_TRY(bufs.alloc(&d_rn_idx, (size_t)n * k));
+        HIP_TRY(bufs.alloc(&d_deg, (size_t)(n + 1)));
+        HIP_TRY(bufs.alloc(&d_ptr0, (size_t)(n + 1)));
         HIP_TRY(hipMalloc((void **)&g->d_ptr, (size_t)(n + 1) * sizeof(int)));
-        HIP_TRY(hipMalloc((void **)&d_err, 2 * sizeof(int)));
+        HIP_TRY(bufs.alloc(&d_err, 2));
         HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)(n + 1) * sizeof(int), st));
         HIP_TRY(hipMemsetAsync(d_cursor, 0, (size_t)(n + 1) * sizeof(int), st));
         HIP_TRY(hipMemsetAsync(d_err, 0, 2 * sizeof(int), st));
 
         // S1: exact kNN
-        HIP_TRY(hipEventRecord(ev[0], st));
-        int r2 = dim <= 16 ? launch_knn<16>(dX, n, dim, k, g->d_nn, st)
-                           : (dim <= 32 ? launch_knn<32>(dX, n, dim, k, g->d_nn, st) : launch_knn<64>(dX, n, dim, k, g->d_nn, st));
-        if (r2) return r2;
-        HIP_TRY(hipEventRecord(ev[1], st));
+        HIP_TRY(hipEventRecord(ev.e[0], st));
+        MI_TRY(mi_snn_knn_dev(dX, n, dim, k, g->d_nn, st));
+        HIP_TRY(hipEventRecord(ev.e[1], st));
 
         // S2: reverse-neighbour lists
-        const long long total = (long long)n * k;
-        const int gblocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        hipLaunchKernelGGL(k_rn_count, dim3(gblocks), dim3(256), 0, st, g->d_nn, total, d_cnt);
-        hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, st, d_cnt, d_rn_ptr, n);
-        hipLaunchKernelGGL(k_rn_fill, dim3(gblocks), dim3(256), 0, st, g->d_nn, n, k, d_rn_ptr, d_cursor, d_rn_idx);
-        HIP_TRY(hipGetLastError());
+        MI_TRY(mi_snn_reverse_lists_dev(g->d_nn, n, k, d_cnt, d_rn_ptr, d_cursor, d_rn_idx, st));
 
         // S3: shared-neighbour rows (count, scan, emit)
         const size_t lds = (size_t)(((n + 3) / 4 * 4 + 15) / 16) * 16 + (size_t)kRowCap * 8;
@@ -691,14 +682,14 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
         HIP_TRY(hipStreamSynchronize(st));
         if (h_err) return fail(MI_EUNSUPPORTED, "a point shares neighbours with more than %d others (hub): not supported", kRowCap);
         if (nnz0 < 0) return fail(MI_EUNSUPPORTED, "SNN graph has more than 2^31 entries");
-        HIP_TRY(hipMalloc((void **)&d_col0, (size_t)(nnz0 > 0 ? nnz0 : 1) * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&d_sh0, (size_t)(nnz0 > 0 ? nnz0 : 1) * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&d_alive, (size_t)(nnz0 > 0 ? nnz0 : 1)));
+        HIP_TRY(bufs.alloc(&d_col0, (size_t)(nnz0 > 0 ? nnz0 : 1)));
+        HIP_TRY(bufs.alloc(&d_sh0, (size_t)(nnz0 > 0 ? nnz0 : 1)));
+        HIP_TRY(bufs.alloc(&d_alive, (size_t)(nnz0 > 0 ? nnz0 : 1)));
         HIP_TRY(hipMemsetAsync(d_alive, 1, (size_t)(nnz0 > 0 ? nnz0 : 1), st));
         hipLaunchKernelGGL(k_snn_rows<1>, dim3(rblocks), dim3(256), lds, st, g->d_nn, n, k, prune, d_rn_ptr, d_rn_idx, d_deg,
                            (const int *)d_ptr0, d_col0, d_sh0, d_err);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[2], st));
+        HIP_TRY(hipEventRecord(ev.e[2], st));
 
         // S4: trim(s) and enhancement, S5: compaction
         // the sequential symmetric trim on `keys` (shared counts, or ranks of the enhanced weights) with degree cap `cap`
@@ -706,11 +697,12 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
             if (!getenv("MI_SNN_TRIM_SEQUENTIAL")) {
                 // many columns in flight (k_trim_par); the sequential kernel is the fallback should a dependency
                 // wait ever hit its bound (MI_SNN_TRIM_SEQUENTIAL=1 forces it)
+                DevBufs own;                                     // (released where this branch ends, before the function returns)
                 unsigned int *d_tctrl = nullptr, *d_done = nullptr;
                 unsigned char *d_save = nullptr;
-                HIP_TRY(hipMalloc((void **)&d_tctrl, 2 * sizeof(unsigned int)));
-                HIP_TRY(hipMalloc((void **)&d_done, (size_t)n * sizeof(unsigned int)));
-                HIP_TRY(hipMalloc((void **)&d_save, (size_t)(nnz0 > 0 ? nnz0 : 1)));
+                HIP_TRY(own.alloc(&d_tctrl, 2));
+                HIP_TRY(own.alloc(&d_done, (size_t)n));
+                HIP_TRY(own.alloc(&d_save, (size_t)(nnz0 > 0 ? nnz0 : 1)));
                 HIP_TRY(hipMemcpyAsync(d_save, d_alive, (size_t)(nnz0 > 0 ? nnz0 : 1), hipMemcpyDeviceToDevice, st));
                 HIP_TRY(hipMemsetAsync(d_tctrl, 0, 2 * sizeof(unsigned int), st));
                 HIP_TRY(hipMemsetAsync(d_done, 0, (size_t)n * sizeof(unsigned int), st));
@@ -720,15 +712,12 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
                 unsigned int terr = 0;
                 HIP_TRY(hipMemcpyAsync(&terr, d_tctrl + 1, sizeof terr, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
-                (void)hipFree(d_tctrl);
-                (void)hipFree(d_done);
                 if (terr) {
                     fprintf(stderr, "mi_snn: parallel trim hit a wait bound; redoing sequentially\n");
                     HIP_TRY(hipMemcpyAsync(d_alive, d_save, (size_t)(nnz0 > 0 ? nnz0 : 1), hipMemcpyDeviceToDevice, st));
                     hipLaunchKernelGGL(k_trim, dim3(1), dim3(kTrimThreads), 0, st, n, cap, (const int *)d_ptr0, d_col0, keys, d_alive);
                     HIP_TRY(hipStreamSynchronize(st));
                 }
-                (void)hipFree(d_save);
             } else {
                 hipLaunchKernelGGL(k_trim, dim3(1), dim3(kTrimThreads), 0, st, n, cap, (const int *)d_ptr0, d_col0, keys, d_alive);
             }
@@ -765,28 +754,24 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
                     return fail(MI_EUNSUPPORTED, "negative edges on a graph this small (n = %d, densest column %d entries, ord = %d) "
                                 "could survive the trim; not supported", n, maxdeg0, ord);
             }
-            HIP_TRY(hipMalloc((void **)&d_table, table.size() * sizeof(int32_t)));
-            HIP_TRY(hipMalloc((void **)&d_key, (size_t)(nnz0 > 0 ? nnz0 : 1) * sizeof(int32_t)));
-            HIP_TRY(hipMalloc((void **)&d_code0, (size_t)(nnz0 > 0 ? nnz0 : 1)));
+            HIP_TRY(bufs.alloc(&d_table, table.size()));
+            HIP_TRY(bufs.alloc(&d_key, (size_t)(nnz0 > 0 ? nnz0 : 1)));
+            HIP_TRY(bufs.alloc(&d_code0, (size_t)(nnz0 > 0 ? nnz0 : 1)));
             HIP_TRY(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(k_round_keys, dim3(1024), dim3(256), 0, st, (long long)nnz0, d_sh0, d_table, d_key, d_alive, d_code0,
                                ord > 0 ? 1 : 0);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(st));                   // (table goes out of scope)
-            if (ord > 0) {
-                const int r3 = trim_symmetric(d_key, ord);
-                if (r3) return r3;
-            }
+            if (ord > 0) MI_TRY(trim_symmetric(d_key, ord));
         } else if (ord > 0 && (flags & MI_SNN_TRIM_UNSYMMETRIC)) {
             hipLaunchKernelGGL(k_trim_cols, dim3((n + 3) / 4), dim3(256), 0, st, n, ord, (const int *)d_ptr0, d_col0, d_sh0, d_alive);
             HIP_TRY(hipGetLastError());
         } else if (ord > 0) {
-            const int r3 = trim_symmetric(d_sh0, ord);
-            if (r3) return r3;
+            MI_TRY(trim_symmetric(d_sh0, ord));
         }
         if (flags & (MI_SNN_ENHANCE_MUTUAL | MI_SNN_ENHANCE_SUM)) {
-            HIP_TRY(hipMalloc((void **)&d_alive2, (size_t)(nnz0 > 0 ? nnz0 : 1)));
-            HIP_TRY(hipMalloc((void **)&d_code0, (size_t)(nnz0 > 0 ? nnz0 : 1)));
+            HIP_TRY(bufs.alloc(&d_alive2, (size_t)(nnz0 > 0 ? nnz0 : 1)));
+            HIP_TRY(bufs.alloc(&d_code0, (size_t)(nnz0 > 0 ? nnz0 : 1)));
             hipLaunchKernelGGL(k_enhance, dim3((n + 255) / 256), dim3(256), 0, st, n, (flags & MI_SNN_ENHANCE_MUTUAL) ? 1 : 2,
                                (const int *)d_ptr0, d_col0, d_alive, d_alive2, d_code0);
             HIP_TRY(hipGetLastError());
@@ -805,14 +790,13 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
             std::vector<int32_t> table(vals.size());
             for (size_t q = 0; q < vals.size(); ++q)
                 table[q] = (int32_t)(std::lower_bound(uniq.begin(), uniq.end(), vals[q]) - uniq.begin());
-            HIP_TRY(hipMalloc((void **)&d_table, table.size() * sizeof(int32_t)));
-            HIP_TRY(hipMalloc((void **)&d_key, (size_t)(nnz0 > 0 ? nnz0 : 1) * sizeof(int32_t)));
+            HIP_TRY(bufs.alloc(&d_table, table.size()));
+            HIP_TRY(bufs.alloc(&d_key, (size_t)(nnz0 > 0 ? nnz0 : 1)));
             HIP_TRY(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(k_make_keys, dim3(1024), dim3(256), 0, st, (long long)nnz0, d_sh0, d_code0, d_table, d_key);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(st));                   // (table goes out of scope)
-            const int r3 = trim_symmetric(d_key, ord2);
-            if (r3) return r3;
+            MI_TRY(trim_symmetric(d_key, ord2));
         }
         HIP_TRY(hipMemsetAsync(d_err + 1, 0, sizeof(int), st));
         hipLaunchKernelGGL(k_compact_count, dim3((n + 255) / 256), dim3(256), 0, st, n, (const int *)d_ptr0, d_alive, d_deg, d_err + 1);
@@ -829,19 +813,13 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
         hipLaunchKernelGGL(k_compact_fill, dim3((n + 255) / 256), dim3(256), 0, st, n, (const int *)d_ptr0, d_col0, d_sh0, d_alive,
                            (const int *)g->d_ptr, g->d_col, g->d_shared, (const unsigned char *)d_code0, g->d_code);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[3], st));
+        HIP_TRY(hipEventRecord(ev.e[3], st));
         HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipEventElapsedTime(&g->ms_knn, ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&g->ms_snn, ev[1], ev[2]));
-        HIP_TRY(hipEventElapsedTime(&g->ms_trim, ev[2], ev[3]));
+        HIP_TRY(hipEventElapsedTime(&g->ms_knn, ev.e[0], ev.e[1]));
+        HIP_TRY(hipEventElapsedTime(&g->ms_snn, ev.e[1], ev.e[2]));
+        HIP_TRY(hipEventElapsedTime(&g->ms_trim, ev.e[2], ev.e[3]));
         return MI_OK;
     });
-    void *tmp[] = {dX, d_cnt, d_rn_ptr, d_cursor, d_rn_idx, d_deg, d_ptr0, d_err, d_col0, d_sh0, d_alive, d_alive2, d_code0, d_key, d_table};
-    for (void *b : tmp)
-        if (b) (void)hipFree(b);
-    for (auto &e : ev)
-        if (e) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
     if (rc) { mi_snn_destroy(g); return rc; }
     *out = g;
     return MI_OK;

@@ -287,59 +287,6 @@ void launch_layout(int n, const uint32_t *rowptr, const int32_t *col, const floa
                        neg, k0, k1);
 }
 
-struct Timer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Timer()
-    {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    int start()
-    {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, 0));
-        return MI_OK;
-    }
-    int stop(float *out_ms)
-    {
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e1, 0));
-        HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        if (out_ms) *out_ms = ms;
-        return MI_OK;
-    }
-};
-
-struct DevBufs {                                                  // scratch of one call, freed on every way out
-    std::vector<void *> p;
-    ~DevBufs()
-    {
-        for (void *b : p)
-            if (b) (void)hipFree(b);
-    }
-    template <typename T>
-    hipError_t alloc(T **out, size_t count)
-    {
-        void *b = nullptr;
-        const hipError_t e = hipMalloc(&b, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(b);
-        *out = static_cast<T *>(b);
-        return e;
-    }
-};
-
-int pick_device(int device)
-{
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(MI_ENODEV, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fail(MI_EINVAL, "device %d out of range [0,%d)", device, cnt);
-    HIP_TRY(hipSetDevice(device));
-    return MI_OK;
-}
-
 }  // namespace
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
@@ -354,12 +301,6 @@ struct mi_umap_graph {
     double *d_rho = nullptr, *d_sigma = nullptr, *d_mean = nullptr;
     int *d_ptr = nullptr;
 };
-
-#define TRY(expr)                   \
-    do {                            \
-        const int rc_ = (expr);     \
-        if (rc_ != MI_OK) return rc_; \
-    } while (0)
 
 extern "C" {
 
@@ -404,7 +345,7 @@ int mi_umap_knn_f32(const float *X, int n, int dim, int k, int metric, int devic
         return mi_snn_check_points(src, n, dim);
     });
     if (rc0) return rc0;
-    TRY(pick_device(device));
+    MI_TRY(pick_device(device));
     mi_umap_graph *g = nullptr;
     const int rc = guarded([&]() -> int {
         g = new mi_umap_graph();
@@ -416,12 +357,12 @@ int mi_umap_knn_f32(const float *X, int n, int dim, int k, int metric, int devic
         HIP_TRY(hipMalloc((void **)&g->d_dist, (size_t)n * k * sizeof(float)));
         HIP_TRY(hipMemcpy(dX, src, cells * sizeof(float), hipMemcpyHostToDevice));
         Timer tm;
-        TRY(tm.start());
-        TRY(mi_snn_knn_dev(dX, n, dim, k, g->d_nn, 0));
+        MI_TRY(tm.start(0));
+        MI_TRY(mi_snn_knn_dev(dX, n, dim, k, g->d_nn, 0));
         const long long total = (long long)n * k;
         const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
         hipLaunchKernelGGL(k_umap_dist, dim3(blocks), dim3(256), 0, 0, dX, n, dim, k, metric, g->d_nn, g->d_dist);
-        TRY(tm.stop(out_kernel_ms));
+        MI_TRY(tm.stop(0, out_kernel_ms));
         return MI_OK;
     });
     if (rc) { mi_umap_destroy(g); return rc; }
@@ -453,9 +394,9 @@ int mi_umap_smooth(mi_umap_graph *g, float *out_kernel_ms)
         float ms0 = 0.0f, ms1 = 0.0f;
         {
             Timer tm;
-            TRY(tm.start());
+            MI_TRY(tm.start(0));
             hipLaunchKernelGGL(k_umap_rho, dim3(blocks), dim3(256), 0, 0, n, k, g->d_dist, g->d_rho, g->d_mean);
-            TRY(tm.stop(&ms0));
+            MI_TRY(tm.stop(0, &ms0));
         }
         std::vector<double> mean((size_t)n);
         HIP_TRY(hipMemcpy(mean.data(), g->d_mean, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
@@ -464,10 +405,10 @@ int mi_umap_smooth(mi_umap_graph *g, float *out_kernel_ms)
         const double mean_all = tot / (double)n;
         {
             Timer tm;
-            TRY(tm.start());
+            MI_TRY(tm.start(0));
             hipLaunchKernelGGL(k_umap_sigma, dim3(blocks), dim3(256), 0, 0, n, k, std::log2((double)k), mean_all, g->d_dist,
                                g->d_rho, g->d_mean, g->d_sigma);
-            TRY(tm.stop(&ms1));
+            MI_TRY(tm.stop(0, &ms1));
         }
         if (out_kernel_ms) *out_kernel_ms = ms0 + ms1;
         g->stage = 2;
@@ -519,12 +460,12 @@ int mi_umap_union(mi_umap_graph *g, float *out_kernel_ms)
         float ms0 = 0.0f, ms1 = 0.0f;
         {
             Timer tm;
-            TRY(tm.start());
-            TRY(mi_snn_reverse_lists_dev(g->d_nn, n, k, d_cnt, d_rn_ptr, d_cursor, d_rn_idx, 0));
+            MI_TRY(tm.start(0));
+            MI_TRY(mi_snn_reverse_lists_dev(g->d_nn, n, k, d_cnt, d_rn_ptr, d_cursor, d_rn_idx, 0));
             hipLaunchKernelGGL(k_umap_union_raw, dim3(rows), dim3(256), 0, 0, n, k, g->d_nn, g->d_dist, g->d_rho, g->d_sigma,
                                d_rn_ptr, d_rn_idx, d_raw_col, d_raw_w, d_deg);
-            TRY(mi_scan_exclusive_dev(d_deg, g->d_ptr, n, 0));
-            TRY(tm.stop(&ms0));
+            MI_TRY(mi_scan_exclusive_dev(d_deg, g->d_ptr, n, 0));
+            MI_TRY(tm.stop(0, &ms0));
         }
         int nnz = 0;
         HIP_TRY(hipMemcpy(&nnz, g->d_ptr + n, sizeof(int), hipMemcpyDeviceToHost));
@@ -532,10 +473,10 @@ int mi_umap_union(mi_umap_graph *g, float *out_kernel_ms)
         HIP_TRY(hipMalloc((void **)&g->d_w, (size_t)(nnz > 0 ? nnz : 1) * sizeof(float)));
         {
             Timer tm;
-            TRY(tm.start());
+            MI_TRY(tm.start(0));
             hipLaunchKernelGGL(k_umap_union_sort, dim3(rows), dim3(256), 0, 0, n, k, d_rn_ptr, d_raw_col, d_raw_w, g->d_ptr,
                                g->d_col, g->d_w, d_stats);
-            TRY(tm.stop(&ms1));
+            MI_TRY(tm.stop(0, &ms1));
         }
         unsigned int stats[2] = {0u, 0u};
         HIP_TRY(hipMemcpy(stats, d_stats, sizeof stats, hipMemcpyDeviceToHost));
@@ -606,7 +547,7 @@ int mi_umap_layout_f32(int n, int c, const int64_t *rowptr, const int32_t *col, 
     const size_t cells = (size_t)n * c;
     for (size_t e = 0; e < cells; ++e)
         if (!std::isfinite(Y0[e])) return fail(MI_EINVAL, "Y0[%lld, %lld] is not finite", (long long)(e / c), (long long)(e % c));
-    TRY(pick_device(device));
+    MI_TRY(pick_device(device));
     return guarded([&]() -> int {
         std::vector<uint32_t> ptr32((size_t)n + 1);
         for (size_t i = 0; i < ptr32.size(); ++i) ptr32[i] = (uint32_t)rowptr[i];
@@ -632,7 +573,7 @@ int mi_umap_layout_f32(int n, int c, const int64_t *rowptr, const int32_t *col, 
         const int G = mean_deg > 32.0 ? 64 : (mean_deg > 16.0 ? 32 : 16);
         const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
         Timer tm;
-        TRY(tm.start());
+        MI_TRY(tm.start(0));
         for (int t = 0; t < T; ++t) {
             const float alpha = (float)((double)alpha0 * (1.0 - (double)t / (double)T));
             const float *in = d_Y[t & 1];
@@ -645,7 +586,7 @@ int mi_umap_layout_f32(int n, int c, const int64_t *rowptr, const int32_t *col, 
             }
 #undef MI_UMAP_LAUNCH
         }
-        TRY(tm.stop(out_kernel_ms));
+        MI_TRY(tm.stop(0, out_kernel_ms));
         HIP_TRY(hipMemcpy(Y_out, d_Y[T & 1], cells * sizeof(float), hipMemcpyDeviceToHost));
         return MI_OK;
     });
