@@ -8,6 +8,7 @@
 
 #include <exception>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/mi_sa.h"
@@ -63,7 +64,7 @@ struct NoCopy {
     NoCopy &operator=(const NoCopy &) = delete;
 };
 
-// device scratch of one call (buffers that outlive the call belong to a handle and its mi_*_destroy, not here)
+// device scratch of one call (a buffer that outlives the call is a DevArray member of its handle)
 struct DevBufs : NoCopy {
     std::vector<void *> p;
     ~DevBufs()
@@ -81,6 +82,49 @@ struct DevBufs : NoCopy {
         if (e != hipSuccess) p.back() = nullptr;
         *out = static_cast<T *>(p.back());
         return e;
+    }
+};
+
+// One device array of T that outlives a call, with its element count: a member of a handle, freed when the handle is
+// deleted (mi_*_destroy).  Never dangling: null with count 0 after reset() and after a failed allocation, whatever the
+// failed hipMalloc wrote.  Contents are not kept when the size changes.
+template <typename T>
+struct DevArray : NoCopy {
+    T *p = nullptr;
+    size_t count = 0;
+    ~DevArray() { reset(); }
+    operator T *() const { return p; }
+    void reset()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        count = 0;
+    }
+    // exactly n elements; allocates at least one, so that a count of 0 still yields a pointer
+    hipError_t resize(size_t n)
+    {
+        if (p && count == n) return hipSuccess;
+        reset();
+        void *raw = nullptr;
+        const hipError_t e = hipMalloc(&raw, (n ? n : 1) * sizeof(T));
+        if (e != hipSuccess) return e;
+        p = static_cast<T *>(raw);
+        count = n;
+        return hipSuccess;
+    }
+    // at least n elements
+    hipError_t reserve(size_t n) { return p && count >= n ? hipSuccess : resize(n); }
+    // exactly n elements, copied from the host
+    hipError_t upload(const T *host, size_t n)
+    {
+        const hipError_t e = resize(n);
+        return e != hipSuccess || n == 0 ? e : hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    hipError_t upload(const std::vector<T> &host) { return upload(host.data(), host.size()); }
+    void swap(DevArray &o)
+    {
+        std::swap(p, o.p);
+        std::swap(count, o.count);
     }
 };
 
@@ -117,9 +161,10 @@ struct Timer {
     }
 };
 
-// a stream the holder creates into `st`; the scope destroys it
+// a stream the holder creates into `st`; the scope (or the handle it is a member of) destroys it
 struct ScopedStream : NoCopy {
     hipStream_t st = nullptr;
+    operator hipStream_t() const { return st; }
     ~ScopedStream()
     {
         if (st) (void)hipStreamDestroy(st);

@@ -284,7 +284,7 @@ using namespace mi_sa_impl;
 struct mi_prep_matrix {
     int n = 0, g = 0, device = 0, h = 0, ldz = 0;
     bool normalized = false;
-    float *d_X = nullptr, *d_Y = nullptr, *d_Z = nullptr;
+    DevArray<float> d_X, d_Y, d_Z;
 };
 
 namespace {
@@ -312,9 +312,6 @@ int mi_prep_destroy(mi_prep_matrix *m)
 {
     if (!m) return MI_OK;
     (void)hipSetDevice(m->device);
-    void *bufs[] = {m->d_X, m->d_Y, m->d_Z};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
     delete m;
     return MI_OK;
 }
@@ -337,8 +334,7 @@ int mi_prep_create_f32(const float *X, int n, int g, int device, mi_prep_matrix 
     if (!m) return fail(MI_ENOMEM, "out of host memory");
     m->n = n; m->g = g; m->device = device;
     const int rc = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&m->d_X, cells * sizeof(float)));
-        HIP_TRY(hipMemcpy(m->d_X, X, cells * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(m->d_X.upload(X, cells));
         return MI_OK;
     }();
     if (rc != MI_OK) {
@@ -355,7 +351,7 @@ int mi_prep_normalize(mi_prep_matrix *m, double scale_factor, float *out_kernel_
     if (!m) return fail(MI_EINVAL, "NULL argument");
     if (!(scale_factor > 0.0) || std::isinf(scale_factor)) return fail(MI_EINVAL, "scale_factor must be finite and > 0");
     HIP_TRY(hipSetDevice(m->device));
-    if (!m->d_Y) HIP_TRY(hipMalloc((void **)&m->d_Y, (size_t)m->n * m->g * sizeof(float)));
+    HIP_TRY(m->d_Y.reserve((size_t)m->n * m->g));
     m->normalized = false;
     Timer t;
     MI_TRY(t.start(0));
@@ -461,11 +457,7 @@ int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double 
         HIP_TRY(hipSetDevice(m->device));
         const int ldz = (h + kTile - 1) / kTile * kTile;
         m->h = 0;
-        if (m->d_Z && m->ldz != ldz) {
-            (void)hipFree(m->d_Z);
-            m->d_Z = nullptr;
-        }
-        if (!m->d_Z) HIP_TRY(hipMalloc((void **)&m->d_Z, (size_t)m->n * ldz * sizeof(float)));
+        HIP_TRY(m->d_Z.resize((size_t)m->n * ldz));      // (a failure leaves it empty, with h = 0: mi_prep_select has not run)
         m->ldz = ldz;
         DevBufs bufs;
         int32_t *d_genes;

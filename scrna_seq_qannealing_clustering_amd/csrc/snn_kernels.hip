@@ -566,10 +566,10 @@ struct mi_snn_graph {
     int n = 0, dim = 0, k = 0, ord = 0, device = 0, max_degree = 0;
     long long nnz = 0;
     float ms_knn = 0, ms_snn = 0, ms_trim = 0;
-    int32_t *d_nn = nullptr;
-    int *d_ptr = nullptr;            // final rowptr (n+1)
-    int32_t *d_col = nullptr, *d_shared = nullptr;
-    unsigned char *d_code = nullptr;  // per entry: 0 plain, 1 present in both directions (mutual bonus), 2 doubled (A + t(A))
+    DevArray<int32_t> d_nn;
+    DevArray<int> d_ptr;             // final rowptr (n+1)
+    DevArray<int32_t> d_col, d_shared;
+    DevArray<unsigned char> d_code;  // per entry: 0 plain, 1 present in both directions (mutual bonus), 2 doubled (A + t(A))
     int flags = 0, ord2 = 0;
 };
 
@@ -579,9 +579,6 @@ int mi_snn_destroy(mi_snn_graph *g)
 {
     if (!g) return MI_OK;
     (void)hipSetDevice(g->device);
-    void *bufs[] = {g->d_nn, g->d_ptr, g->d_col, g->d_shared, g->d_code};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
     delete g;
     return MI_OK;
 }
@@ -646,14 +643,14 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
         int32_t *d_key = nullptr, *d_table = nullptr;
         HIP_TRY(bufs.alloc(&dX, (size_t)n * dim));
         HIP_TRY(hipMemcpy(dX, X, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void **)&g->d_nn, (size_t)n * k * sizeof(int32_t)));
+        HIP_TRY(g->d_nn.resize((size_t)n * k));
         HIP_TRY(bufs.alloc(&d_cnt, (size_t)(n + 1)));
         HIP_TRY(bufs.alloc(&d_rn_ptr, (size_t)(n + 1)));
         HIP_TRY(bufs.alloc(&d_cursor, (size_t)(n + 1)));
         HIP_TRY(bufs.alloc(&d_rn_idx, (size_t)n * k));
         HIP_TRY(bufs.alloc(&d_deg, (size_t)(n + 1)));
         HIP_TRY(bufs.alloc(&d_ptr0, (size_t)(n + 1)));
-        HIP_TRY(hipMalloc((void **)&g->d_ptr, (size_t)(n + 1) * sizeof(int)));
+        HIP_TRY(g->d_ptr.resize((size_t)n + 1));
         HIP_TRY(bufs.alloc(&d_err, 2));
         HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)(n + 1) * sizeof(int), st));
         HIP_TRY(hipMemsetAsync(d_cursor, 0, (size_t)(n + 1) * sizeof(int), st));
@@ -807,9 +804,9 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
         HIP_TRY(hipMemcpyAsync(&g->max_degree, d_err + 1, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         g->nnz = nnz1;
-        HIP_TRY(hipMalloc((void **)&g->d_col, (size_t)(nnz1 > 0 ? nnz1 : 1) * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&g->d_shared, (size_t)(nnz1 > 0 ? nnz1 : 1) * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&g->d_code, (size_t)(nnz1 > 0 ? nnz1 : 1)));
+        HIP_TRY(g->d_col.resize((size_t)(nnz1 > 0 ? nnz1 : 0)));
+        HIP_TRY(g->d_shared.resize((size_t)(nnz1 > 0 ? nnz1 : 0)));
+        HIP_TRY(g->d_code.resize((size_t)(nnz1 > 0 ? nnz1 : 0)));
         hipLaunchKernelGGL(k_compact_fill, dim3((n + 255) / 256), dim3(256), 0, st, n, (const int *)d_ptr0, d_col0, d_sh0, d_alive,
                            (const int *)g->d_ptr, g->d_col, g->d_shared, (const unsigned char *)d_code0, g->d_code);
         HIP_TRY(hipGetLastError());

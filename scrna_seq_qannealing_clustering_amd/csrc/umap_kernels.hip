@@ -296,10 +296,10 @@ struct mi_umap_graph {
     int stage = 1;                   // 1 = kNN, 2 = smoothed, 3 = union built
     long long nnz = 0;
     float w_max = 0.0f;
-    int32_t *d_nn = nullptr, *d_col = nullptr;
-    float *d_dist = nullptr, *d_w = nullptr;
-    double *d_rho = nullptr, *d_sigma = nullptr, *d_mean = nullptr;
-    int *d_ptr = nullptr;
+    DevArray<int32_t> d_nn, d_col;
+    DevArray<float> d_dist, d_w;
+    DevArray<double> d_rho, d_sigma, d_mean;
+    DevArray<int> d_ptr;
 };
 
 extern "C" {
@@ -308,9 +308,6 @@ int mi_umap_destroy(mi_umap_graph *g)
 {
     if (!g) return MI_OK;
     (void)hipSetDevice(g->device);
-    void *bufs[] = {g->d_nn, g->d_col, g->d_dist, g->d_w, g->d_rho, g->d_sigma, g->d_mean, g->d_ptr};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
     delete g;
     return MI_OK;
 }
@@ -353,8 +350,8 @@ int mi_umap_knn_f32(const float *X, int n, int dim, int k, int metric, int devic
         DevBufs tmp;
         float *dX = nullptr;
         HIP_TRY(tmp.alloc(&dX, cells));
-        HIP_TRY(hipMalloc((void **)&g->d_nn, (size_t)n * k * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&g->d_dist, (size_t)n * k * sizeof(float)));
+        HIP_TRY(g->d_nn.resize((size_t)n * k));
+        HIP_TRY(g->d_dist.resize((size_t)n * k));
         HIP_TRY(hipMemcpy(dX, src, cells * sizeof(float), hipMemcpyHostToDevice));
         Timer tm;
         MI_TRY(tm.start(0));
@@ -386,9 +383,9 @@ int mi_umap_smooth(mi_umap_graph *g, float *out_kernel_ms)
     HIP_TRY(hipSetDevice(g->device));
     return guarded([&]() -> int {
         const int n = g->n, k = g->k;
-        if (!g->d_rho) HIP_TRY(hipMalloc((void **)&g->d_rho, (size_t)n * sizeof(double)));
-        if (!g->d_sigma) HIP_TRY(hipMalloc((void **)&g->d_sigma, (size_t)n * sizeof(double)));
-        if (!g->d_mean) HIP_TRY(hipMalloc((void **)&g->d_mean, (size_t)n * sizeof(double)));
+        HIP_TRY(g->d_rho.resize((size_t)n));
+        HIP_TRY(g->d_sigma.resize((size_t)n));
+        HIP_TRY(g->d_mean.resize((size_t)n));
         g->stage = 1; g->nnz = 0; g->max_degree = 0; g->w_max = 0.0f;
         const unsigned blocks = (unsigned)((n + 255) / 256);
         float ms0 = 0.0f, ms1 = 0.0f;
@@ -433,10 +430,7 @@ int mi_umap_union(mi_umap_graph *g, float *out_kernel_ms)
     HIP_TRY(hipSetDevice(g->device));
     return guarded([&]() -> int {
         const int n = g->n, k = g->k;
-        void *old[] = {g->d_ptr, g->d_col, g->d_w};
-        for (void *b : old)
-            if (b) (void)hipFree(b);
-        g->d_ptr = nullptr; g->d_col = nullptr; g->d_w = nullptr;
+        g->d_ptr.reset(); g->d_col.reset(); g->d_w.reset();
         g->stage = 2; g->nnz = 0; g->max_degree = 0; g->w_max = 0.0f;
         DevBufs tmp;
         int *d_cnt = nullptr, *d_rn_ptr = nullptr, *d_cursor = nullptr, *d_deg = nullptr;
@@ -452,7 +446,7 @@ int mi_umap_union(mi_umap_graph *g, float *out_kernel_ms)
         HIP_TRY(tmp.alloc(&d_raw_col, raw));
         HIP_TRY(tmp.alloc(&d_raw_w, raw));
         HIP_TRY(tmp.alloc(&d_stats, 2));
-        HIP_TRY(hipMalloc((void **)&g->d_ptr, ((size_t)n + 1) * sizeof(int)));
+        HIP_TRY(g->d_ptr.resize((size_t)n + 1));
         HIP_TRY(hipMemsetAsync(d_cnt, 0, ((size_t)n + 1) * sizeof(int), 0));
         HIP_TRY(hipMemsetAsync(d_cursor, 0, ((size_t)n + 1) * sizeof(int), 0));
         HIP_TRY(hipMemsetAsync(d_stats, 0, 2 * sizeof(unsigned int), 0));
@@ -469,8 +463,8 @@ int mi_umap_union(mi_umap_graph *g, float *out_kernel_ms)
         }
         int nnz = 0;
         HIP_TRY(hipMemcpy(&nnz, g->d_ptr + n, sizeof(int), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMalloc((void **)&g->d_col, (size_t)(nnz > 0 ? nnz : 1) * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&g->d_w, (size_t)(nnz > 0 ? nnz : 1) * sizeof(float)));
+        HIP_TRY(g->d_col.resize((size_t)(nnz > 0 ? nnz : 0)));
+        HIP_TRY(g->d_w.resize((size_t)(nnz > 0 ? nnz : 0)));
         {
             Timer tm;
             MI_TRY(tm.start(0));

@@ -1,6 +1,7 @@
-"""The scope owners of csrc/mi_sa_host.h (device scratch, events, stream) and its device check under AddressSanitizer and
-UBSan: a stand-alone host program (tests/host/scratch_main.cpp) brings its own fake HIP runtime, fails every runtime call
-of a library-shaped entry in turn, and checks that each way out frees everything once."""
+"""The owners of csrc/mi_sa_host.h (a call's device scratch, events and stream; a handle's device arrays) and its device
+check under AddressSanitizer and UBSan: a stand-alone host program (tests/host/scratch_main.cpp) brings its own fake HIP
+runtime, fails every runtime call of a library-shaped entry and of a handle's life in turn, and checks that each way out
+frees everything once and that an owner whose allocation failed is empty."""
 import os
 import subprocess
 
