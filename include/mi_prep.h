@@ -39,6 +39,24 @@
  *                       transposed operand (lane l needs Z[cell l & 31][k + (l >> 5)]), sits in LDS as [cell][33] floats
  *                       (odd stride: the 32 cells of a half-wave fall in 32 different banks), V's as [k][128]; 8.25 + 16 KB.
  *                       f32 accumulation over all h in feature order.
+ *
+ * Sparse input (mi_prep_create_csr_f32): the second kind of handle keeps the counts as CSR (int64 row pointers, int32
+ * columns, f32 values) and the transpose as a position map (per gene: its rows, ascending, and the CSR position of each
+ * entry), so one value array in the caller's order serves the per-cell and the per-gene walks; the normalised values are a
+ * second value array of the same structure.  Resident memory is O(nnz + n + g + n ldz): no n x g buffer exists and n * g
+ * is not limited.  CONTRACT: every output of a sparse handle equals, bit for bit, that of a dense handle on the densified
+ * matrix -- the kernels add in the dense kernels' order (csrc/prep_kernels.hip, DESIGN.md section 5c "Sparse input"):
+ *   k_prep_csr_normalize    one wavefront per cell, 64 entries at a time, each broadcast (v_readlane) to the lane
+ *                           `column & 63`, columns ascending; the same butterfly; y for the stored entries only.  No LDS.
+ *   k_prep_csc_col_partial  the workgroup and slice of k_prep_col_partial on the transpose: a thread finds its gene's first
+ *                           entry of the slice by a lower bound in the gene's row list.  SUM adds the stored entries; CENTRED
+ *                           and CLIPPED walk every row of the slice and add the stored value's term or the per-gene constant
+ *                           of a zero ((0 - mean)^2, min((0 - mean) / sd, clip)^2) at that row's place: sparse in memory,
+ *                           n * g fp64 additions in arithmetic (the closed form (n - nnz) c gives other bits).
+ *   k_prep_csr_select       one workgroup per cell builds its row of Z in LDS (ldz <= 4096 floats, 16 KB): every column's
+ *                           value of y = 0, a barrier, the cell's stored entries of chosen genes (gene -> column map of g
+ *                           int32) over their columns, a barrier, one coalesced store.  Z has the dense layout, so
+ *                           mi_prep_fetch_scaled, k_prep_gram and k_prep_project run unchanged.
  */
 #ifndef MI_PREP_H
 #define MI_PREP_H
@@ -53,6 +71,7 @@ typedef struct mi_prep_matrix mi_prep_matrix;
 
 #define MI_PREP_MAX_CELLS    (1 << 23)      /* n: the row slices of the column reductions are one grid dimension */
 #define MI_PREP_MAX_ENTRIES  (1ll << 32)    /* n * g (16 GiB of f32 per matrix; counts and normalised are both resident) */
+#define MI_PREP_MAX_NNZ      2147483647ll   /* stored entries of a sparse handle: positions stay 32-bit */
 #define MI_PREP_MAX_FEATURES 4096           /* h of mi_prep_select (G: 128 MiB of fp64) */
 #define MI_PREP_MAX_PCS      128            /* p of mi_prep_project */
 #define MI_PREP_ROW_SLICE    256            /* rows per partial sum of the column reductions */
@@ -62,14 +81,27 @@ typedef struct mi_prep_matrix mi_prep_matrix;
  * n < 2, g < 1, a NaN, an infinity or a negative value; MI_EUNSUPPORTED for n > MI_PREP_MAX_CELLS or
  * n * g > MI_PREP_MAX_ENTRIES. */
 int mi_prep_create_f32(const float *X, int n, int g, int device, mi_prep_matrix **out);
+/* The same matrix as CSR: indptr n + 1 entries, indices and data indptr[n] entries.  Checks everything, transposes on the
+ * host (one counting sort), uploads.  MI_EINVAL for NULL arguments, n < 2, g < 1, indptr[0] != 0, a decreasing indptr, a
+ * column outside [0, g), columns of a row not strictly ascending, a NaN, infinite or negative value; MI_EUNSUPPORTED for
+ * n > MI_PREP_MAX_CELLS or indptr[n] > MI_PREP_MAX_NNZ.  n * g is not limited.  A stored zero is legal and behaves as an
+ * absent entry in every result (it keeps its place in mi_prep_fetch_normalized_csr, with the value 0). */
+int mi_prep_create_csr_f32(const int64_t *indptr, const int32_t *indices, const float *data, int n, int g, int device,
+                           mi_prep_matrix **out);
 int mi_prep_destroy(mi_prep_matrix *m);
+/* Either kind of handle; every output is nullable.  nnz: the stored entries of a sparse handle, n * g for a dense one.
+ * device_bytes: what the handle holds resident on the device now (the scratch of a running pass is not the handle's). */
+int mi_prep_info(const mi_prep_matrix *m, int *n, int *g, int64_t *nnz, int *sparse, int64_t *device_bytes);
 
 /* Seurat's LogNormalize: per-cell totals in fp64, y = (float) log1p((double) x * scale_factor / total), kept as a second
  * device-resident matrix (a second call replaces it).  A cell whose total is 0 keeps all zeros (Seurat divides by the
  * zero total and returns NaN for that cell).  MI_EINVAL unless scale_factor is finite and > 0. */
 int mi_prep_normalize(mi_prep_matrix *m, double scale_factor, float *out_kernel_ms);
-/* out: n x g.  MI_ESTATE before mi_prep_normalize. */
+/* out: n x g.  MI_ESTATE before mi_prep_normalize; MI_EUNSUPPORTED on a sparse handle. */
 int mi_prep_fetch_normalized(mi_prep_matrix *m, float *out);
+/* out_data: the normalised values of the stored entries, in the caller's CSR order (indptr[n] entries).  MI_EINVAL on a
+ * dense handle, MI_ESTATE before mi_prep_normalize.  Every other pass below serves both kinds of handle. */
+int mi_prep_fetch_normalized_csr(mi_prep_matrix *m, float *out_data);
 
 /* which: 0 = counts, 1 = normalised matrix (MI_ESTATE before mi_prep_normalize).  Per gene, in fp64, two passes: mean =
  * (sum of x) / n, then var = (sum of (x - mean)^2) / (n - 1); nnz = cells with x != 0.  Outputs: g entries each, nullable. */

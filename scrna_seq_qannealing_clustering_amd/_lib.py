@@ -109,7 +109,10 @@ def _declare(lib):
                                               C.POINTER(C.c_int64), i32p, f64p, C.POINTER(C.c_int64), f32p]),
         # include/mi_prep.h
         "mi_prep_create_f32": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, pp]),
+        "mi_prep_create_csr_f32": (C.c_int, [C.POINTER(C.c_int64), i32p, f32p, C.c_int, C.c_int, C.c_int, pp]),
         "mi_prep_destroy": (C.c_int, [vp]),
+        "mi_prep_info": (C.c_int, [vp, ip, ip, C.POINTER(C.c_int64), ip, C.POINTER(C.c_int64)]),
+        "mi_prep_fetch_normalized_csr": (C.c_int, [vp, f32p]),
         "mi_prep_normalize": (C.c_int, [vp, C.c_double, f32p]),
         "mi_prep_fetch_normalized": (C.c_int, [vp, f32p]),
         "mi_prep_gene_stats": (C.c_int, [vp, C.c_int, f64p, f64p, i32p, f32p]),
@@ -148,7 +151,7 @@ EXPORTS = (
     "mi_coassociation_u16", "mi_sa_problem_coassociation",
     "mi_graph_components", "mi_sa_problem_components",
     "mi_rank_sum_markers_f32",
-    "mi_prep_create_f32", "mi_prep_destroy", "mi_prep_normalize", "mi_prep_fetch_normalized", "mi_prep_gene_stats",
+    "mi_prep_create_f32", "mi_prep_create_csr_f32", "mi_prep_info", "mi_prep_fetch_normalized_csr", "mi_prep_destroy", "mi_prep_normalize", "mi_prep_fetch_normalized", "mi_prep_gene_stats",
     "mi_prep_clipped_variance", "mi_prep_select", "mi_prep_fetch_scaled", "mi_prep_gram", "mi_prep_project",
     "mi_umap_knn_f32", "mi_umap_destroy", "mi_umap_fetch_knn", "mi_umap_smooth", "mi_umap_fetch_smooth", "mi_umap_union",
     "mi_umap_info", "mi_umap_fetch_graph", "mi_umap_layout_f32",

@@ -9,12 +9,15 @@
 //   k_prep_gram          one (upper-triangle 128 x 128 tile, chunk of kChunk cells) per workgroup on the f32-input MFMA,
 //                        f32 tile out; k_prep_gram_reduce adds the chunks in fp64 in chunk order and mirrors.
 //   k_prep_project       out = Z V, 64 cells x 128 columns per workgroup on the same MFMA.
+// A sparse handle (mi_prep_create_csr_f32) keeps the counts as CSR and is served by k_prep_csr_normalize,
+// k_prep_csc_col_partial and k_prep_csr_select, which add in the order of the three kernels above: the same bits come out.
 // Operand maps of v_mfma_f32_32x32x2_f32 as in energy_kernels.hip: A: lane l holds A[i = l & 31][k = l >> 5]; B: lane l
 // holds B[k = l >> 5][j = l & 31]; C/D: register q of lane l is C[row = (q & 3) + 8 (q >> 2) + 4 (l >> 5)][col = l & 31].
 // No floating-point atomics; stores are ordinary vector stores.
 #include <vector>
 
 #include "../../include/mi_prep.h"
+#include "mi_prep_csr.h"
 #include "mi_sa_device.h"
 
 namespace mi_sa_impl {
@@ -111,6 +114,150 @@ __global__ void __launch_bounds__(256) k_prep_select(const float *__restrict__ Y
         z = fminf(d * inv[c], clip);
     }
     Z[row * ldz + c] = z;
+}
+
+// ---- the sparse handle: counts as CSR (indptr, indices, values) plus the transpose as a position map (csrc/mi_prep_csr.h) ----
+// Every kernel below reproduces the order of additions of its dense counterpart above on the densified matrix, so the
+// results are the same bits: a skipped zero of a SUM adds +0.0 to a non-negative accumulator; a zero of the centred and
+// clipped modes adds its per-gene constant, computed by the same operations, at that row's place in the order.
+
+// one wavefront per cell: lane `col & 63` adds the entry, columns ascending (k_prep_normalize's lane-strided order)
+__global__ void __launch_bounds__(256) k_prep_csr_normalize(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                            const float *__restrict__ X, float *__restrict__ Y, int n, double scale)
+{
+    const int lane = threadIdx.x & 63;
+    const int row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (row >= n) return;
+    const int64_t e0 = indptr[row], e1 = indptr[row + 1];
+    double t = 0.0;
+    for (int64_t b = e0; b < e1; b += 64) {
+        const int cnt = __builtin_amdgcn_readfirstlane((int)(e1 - b < 64 ? e1 - b : 64));
+        const int c = lane < cnt ? indices[b + lane] : 0;
+        const float x = lane < cnt ? X[b + lane] : 0.0f;
+        for (int i = 0; i < cnt; ++i) {
+            const int ci = __builtin_amdgcn_readlane(c, i);
+            const float xi = readlane_f(x, i);
+            if (lane == (ci & 63)) t += (double)xi;
+        }
+    }
+    t = wave_sum_f64(t);
+    for (int64_t e = e0 + lane; e < e1; e += 64) Y[e] = t > 0.0 ? (float)log1p((double)X[e] * scale / t) : 0.0f;
+}
+
+// k_prep_col_partial on the transpose: thread (tx, ty) owns gene j and the rows r = ty (mod 4) of the slice; `vals` is in
+// the caller's order and reached through pos.  SUM walks the stored entries of the slice; CENTRED and CLIPPED walk all its
+// rows and add the stored value's term or the constant of a zero.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_prep_csc_col_partial(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rows,
+                                                              const int32_t *__restrict__ pos, const float *__restrict__ vals,
+                                                              int n, int g, const double *__restrict__ mean,
+                                                              const double *__restrict__ sd, double clip,
+                                                              double *__restrict__ psum, int32_t *__restrict__ pnnz)
+{
+    __shared__ double s_sum[4][64];
+    __shared__ int32_t s_cnt[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int j = blockIdx.x * 64 + tx;
+    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
+    double acc = 0.0;
+    int32_t cnt = 0;
+    if (j < g) {
+        int64_t lo = colptr[j], hi = colptr[j + 1];
+        while (lo < hi) {                                         // the column's first entry at or below row r0
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (rows[mid] < r0) lo = mid + 1; else hi = mid;
+        }
+        const int64_t end = colptr[j + 1];
+        int64_t k = lo;
+        // the next stored row of this thread's row lane inside the slice, r1 when there is none
+        auto seek = [&]() -> int {
+            for (; k < end; ++k) {
+                const int r = rows[k];
+                if (r >= r1) break;
+                if ((r & 3) == ty) return r;
+            }
+            return r1;
+        };
+        int nr = seek();
+        if (MODE == kColSum) {
+            while (nr < r1) {
+                const float v = vals[pos[k]];
+                acc += (double)v;
+                cnt += v != 0.0f;
+                ++k;
+                nr = seek();
+            }
+        } else {
+            const double mj = mean[j], sj = MODE == kColClipped ? sd[j] : 1.0;
+            double zero;                                          // a zero's term, by the operations of the dense kernel
+            if (MODE == kColCentred) {
+                const double d = (double)0.0f - mj;
+                zero = d * d;
+            } else {
+                double d = ((double)0.0f - mj) / (sj != 0.0 ? sj : 1.0);
+                d = d < clip ? d : clip;
+                zero = d * d;
+            }
+            if (MODE == kColCentred || sj != 0.0) {
+                int r = r0 + ty;
+                while (r < r1) {
+                    for (; r < nr; r += 4) acc += zero;
+                    if (r >= r1) break;
+                    const float v = vals[pos[k]];                 // (r == nr: both are = ty mod 4)
+                    if (MODE == kColCentred) {
+                        const double d = (double)v - mj;
+                        acc += d * d;
+                    } else {
+                        double d = ((double)v - mj) / sj;
+                        d = d < clip ? d : clip;
+                        acc += d * d;
+                    }
+                    r += 4;
+                    ++k;
+                    nr = seek();
+                }
+            }
+        }
+    }
+    s_sum[ty][tx] = acc;
+    s_cnt[ty][tx] = cnt;
+    __syncthreads();
+    if (ty == 0 && j < g) {
+        const size_t o = (size_t)blockIdx.y * g + j;
+        psum[o] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
+        if (MODE == kColSum) pnnz[o] = s_cnt[0][tx] + s_cnt[1][tx] + s_cnt[2][tx] + s_cnt[3][tx];
+    }
+}
+
+// k_prep_select from CSR: one workgroup per cell builds its row of Z in LDS -- every column's value for y = 0 first, then,
+// past a barrier, the cell's stored entries of chosen genes over their columns (a gene is stored at most once per cell and
+// chosen at most once: no two lanes write one word) -- and stores it coalesced.  gmap: gene -> column of Z, -1 = not chosen.
+__global__ void __launch_bounds__(256) k_prep_csr_select(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                         const float *__restrict__ Y, const int32_t *__restrict__ gmap, int h,
+                                                         int ldz, const float *__restrict__ mu, const float *__restrict__ inv,
+                                                         const uint8_t *__restrict__ flat, float clip, float *__restrict__ Z)
+{
+    __shared__ float s_row[MI_PREP_MAX_FEATURES];
+    const size_t row = blockIdx.x;
+    for (int c = threadIdx.x; c < ldz; c += 256) {
+        float z = 0.0f;
+        if (c < h && !flat[c]) {
+            const float d = 0.0f - mu[c];
+            z = fminf(d * inv[c], clip);
+        }
+        s_row[c] = z;
+    }
+    __syncthreads();
+    const int64_t e1 = indptr[row + 1];
+    for (int64_t e = indptr[row] + threadIdx.x; e < e1; e += 256) {
+        const int c = gmap[indices[e]];
+        if (c >= 0 && !flat[c]) {
+            const float d = Y[e] - mu[c];
+            s_row[c] = fminf(d * inv[c], clip);
+        }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < ldz; c += 256) Z[row * ldz + c] = s_row[c];
 }
 
 // tile s of the row-major list of the upper block triangle: row I holds the tiles J = I .. T - 1
@@ -283,8 +430,11 @@ using namespace mi_sa_impl;
 
 struct mi_prep_matrix {
     int n = 0, g = 0, device = 0, h = 0, ldz = 0;
-    bool normalized = false;
-    DevArray<float> d_X, d_Y, d_Z;
+    bool normalized = false, sparse = false;
+    int64_t nnz = 0;                                              // stored entries of a sparse handle
+    DevArray<float> d_X, d_Y, d_Z;                                // sparse: d_X, d_Y hold nnz values in the caller's CSR order
+    DevArray<int64_t> d_indptr, d_colptr;                         // sparse: the caller's CSR structure and its transpose,
+    DevArray<int32_t> d_indices, d_rows, d_pos;                   // whose entry k is entry d_pos[k] of the CSR order
 };
 
 namespace {
@@ -295,8 +445,12 @@ int col_reduce(const mi_prep_matrix *m, const float *M, const double *d_mean, co
                double *d_psum, int32_t *d_pnnz, double *d_out, int32_t *d_out_nnz)
 {
     const int slices = (m->n + kRowSlice - 1) / kRowSlice;
-    hipLaunchKernelGGL(k_prep_col_partial<MODE>, dim3((unsigned)((m->g + 63) / 64), (unsigned)slices), dim3(256), 0, 0, M, m->n,
-                       m->g, d_mean, d_sd, clip, d_psum, d_pnnz);
+    const dim3 grid((unsigned)((m->g + 63) / 64), (unsigned)slices);
+    if (m->sparse)
+        hipLaunchKernelGGL(k_prep_csc_col_partial<MODE>, grid, dim3(256), 0, 0, m->d_colptr, m->d_rows, m->d_pos, M, m->n, m->g,
+                           d_mean, d_sd, clip, d_psum, d_pnnz);
+    else
+        hipLaunchKernelGGL(k_prep_col_partial<MODE>, grid, dim3(256), 0, 0, M, m->n, m->g, d_mean, d_sd, clip, d_psum, d_pnnz);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_prep_col_finish, dim3((unsigned)((m->g + 255) / 256)), dim3(256), 0, 0, d_psum,
                        MODE == kColSum ? d_pnnz : nullptr, slices, m->g, denom, d_out, d_out_nnz);
@@ -345,18 +499,70 @@ int mi_prep_create_f32(const float *X, int n, int g, int device, mi_prep_matrix 
     return MI_OK;
 }
 
+int mi_prep_create_csr_f32(const int64_t *indptr, const int32_t *indices, const float *data, int n, int g, int device,
+                           mi_prep_matrix **out)
+{
+    if (out) *out = nullptr;
+    if (!out) return fail(MI_EINVAL, "NULL argument");
+    char msg[160];
+    const int bad = mi_prep_csr::check(indptr, indices, data, n, g, MI_PREP_MAX_CELLS, MI_PREP_MAX_NNZ, msg, sizeof msg);
+    if (bad != mi_prep_csr::kOk) return fail(bad == mi_prep_csr::kEinval ? MI_EINVAL : MI_EUNSUPPORTED, "%s", msg);
+    return guarded([&]() -> int {
+        std::vector<int64_t> colptr;
+        std::vector<int32_t> rows, pos;
+        mi_prep_csr::transpose(indptr, indices, n, g, colptr, rows, pos);
+        MI_TRY(pick_device(device));
+        mi_prep_matrix *m = new mi_prep_matrix();
+        m->n = n; m->g = g; m->device = device; m->sparse = true; m->nnz = indptr[n];
+        const size_t nnz = (size_t)m->nnz;
+        const int rc = [&]() -> int {
+            HIP_TRY(m->d_indptr.upload(indptr, (size_t)n + 1));
+            HIP_TRY(m->d_indices.upload(indices, nnz));
+            HIP_TRY(m->d_X.upload(data, nnz));
+            HIP_TRY(m->d_colptr.upload(colptr));
+            HIP_TRY(m->d_rows.upload(rows));
+            HIP_TRY(m->d_pos.upload(pos));
+            return MI_OK;
+        }();
+        if (rc != MI_OK) {
+            mi_prep_destroy(m);
+            return rc;
+        }
+        *out = m;
+        return MI_OK;
+    });
+}
+
+int mi_prep_info(const mi_prep_matrix *m, int *n, int *g, int64_t *nnz, int *sparse, int64_t *device_bytes)
+{
+    if (!m) return fail(MI_EINVAL, "NULL argument");
+    if (n) *n = m->n;
+    if (g) *g = m->g;
+    if (nnz) *nnz = m->sparse ? m->nnz : (int64_t)m->n * m->g;
+    if (sparse) *sparse = m->sparse;
+    if (device_bytes)
+        *device_bytes = (int64_t)((m->d_X.count + m->d_Y.count + m->d_Z.count) * sizeof(float) +
+                                  (m->d_indptr.count + m->d_colptr.count) * sizeof(int64_t) +
+                                  (m->d_indices.count + m->d_rows.count + m->d_pos.count) * sizeof(int32_t));
+    return MI_OK;
+}
+
 int mi_prep_normalize(mi_prep_matrix *m, double scale_factor, float *out_kernel_ms)
 {
     if (out_kernel_ms) *out_kernel_ms = 0.0f;
     if (!m) return fail(MI_EINVAL, "NULL argument");
     if (!(scale_factor > 0.0) || std::isinf(scale_factor)) return fail(MI_EINVAL, "scale_factor must be finite and > 0");
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(m->d_Y.reserve((size_t)m->n * m->g));
+    HIP_TRY(m->d_Y.reserve(m->sparse ? (size_t)m->nnz : (size_t)m->n * m->g));
     m->normalized = false;
     Timer t;
     MI_TRY(t.start(0));
-    hipLaunchKernelGGL(k_prep_normalize, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_X, m->d_Y, m->n, m->g,
-                       scale_factor);
+    if (m->sparse)
+        hipLaunchKernelGGL(k_prep_csr_normalize, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_indptr, m->d_indices,
+                           m->d_X, m->d_Y, m->n, scale_factor);
+    else
+        hipLaunchKernelGGL(k_prep_normalize, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_X, m->d_Y, m->n, m->g,
+                           scale_factor);
     MI_TRY(t.stop(0, out_kernel_ms));
     m->normalized = true;
     return MI_OK;
@@ -365,9 +571,20 @@ int mi_prep_normalize(mi_prep_matrix *m, double scale_factor, float *out_kernel_
 int mi_prep_fetch_normalized(mi_prep_matrix *m, float *out)
 {
     if (!m || !out) return fail(MI_EINVAL, "NULL argument");
+    if (m->sparse) return fail(MI_EUNSUPPORTED, "a sparse handle has no dense normalised matrix: mi_prep_fetch_normalized_csr");
     if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipMemcpy(out, m->d_Y, (size_t)m->n * m->g * sizeof(float), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_prep_fetch_normalized_csr(mi_prep_matrix *m, float *out_data)
+{
+    if (!m || !out_data) return fail(MI_EINVAL, "NULL argument");
+    if (!m->sparse) return fail(MI_EINVAL, "the handle is dense: mi_prep_fetch_normalized");
+    if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
+    HIP_TRY(hipSetDevice(m->device));
+    if (m->nnz) HIP_TRY(hipMemcpy(out_data, m->d_Y, (size_t)m->nnz * sizeof(float), hipMemcpyDeviceToHost));
     return MI_OK;
 }
 
@@ -441,6 +658,7 @@ int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double 
     if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
     return guarded([&]() -> int {
         std::vector<uint8_t> seen((size_t)m->g, 0), flat((size_t)h, 0);
+        std::vector<int32_t> gmap;                                // sparse: gene -> column of Z
         std::vector<float> muf((size_t)h), inv((size_t)h);
         for (int c = 0; c < h; ++c) {
             const int32_t j = genes[c];
@@ -454,6 +672,10 @@ int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double 
             inv[c] = flat[c] ? 0.0f : (float)(1.0 / sigma[c]);
         }
         if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
+        if (m->sparse) {
+            gmap.assign((size_t)m->g, -1);
+            for (int c = 0; c < h; ++c) gmap[genes[c]] = c;
+        }
         HIP_TRY(hipSetDevice(m->device));
         const int ldz = (h + kTile - 1) / kTile * kTile;
         m->h = 0;
@@ -471,10 +693,20 @@ int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double 
         HIP_TRY(hipMemcpy(d_mu, muf.data(), (size_t)h * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_inv, inv.data(), (size_t)h * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_flat, flat.data(), (size_t)h, hipMemcpyHostToDevice));
+        int32_t *d_gmap = nullptr;
+        if (m->sparse) {
+            HIP_TRY(bufs.alloc(&d_gmap, gmap.size()));
+            HIP_TRY(hipMemcpy(d_gmap, gmap.data(), gmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
         Timer t;
         MI_TRY(t.start(0));
-        // (one cell per grid.y, whose limit is 65535: slabs of 32768 cells)
-        for (int r0 = 0; r0 < m->n; r0 += 32768) {
+        if (m->sparse) {
+            hipLaunchKernelGGL(k_prep_csr_select, dim3((unsigned)m->n), dim3(256), 0, 0, m->d_indptr, m->d_indices, m->d_Y, d_gmap,
+                               h, ldz, d_mu, d_inv, d_flat, (float)clip, m->d_Z);
+            HIP_TRY(hipGetLastError());
+        }
+        // dense: (one cell per grid.y, whose limit is 65535: slabs of 32768 cells)
+        for (int r0 = 0; r0 < m->n && !m->sparse; r0 += 32768) {
             const int rows = m->n - r0 < 32768 ? m->n - r0 : 32768;
             hipLaunchKernelGGL(k_prep_select, dim3((unsigned)(ldz / 256 + (ldz % 256 != 0)), (unsigned)rows), dim3(256), 0, 0,
                                m->d_Y + (size_t)r0 * m->g, rows, m->g, d_genes, h, ldz, d_mu, d_inv, d_flat, (float)clip,

@@ -7,7 +7,12 @@ This is the first chunk of every data-preparation notebook of the reference, in 
 `Kidney_data.Rmd:47-48`).  The passes over the cells x genes matrix and the Gram and projection products run in libmi_sa.so
 (csrc/prep_kernels.hip, C ABI include/mi_prep.h); only the loess curve of ``vst`` and the h x h eigen-solve are host fp64.
 
-Out of scope: ``SCTransform``, ``vars.to.regress``, sparse (CSR / 10x) input, more than ``MAX_FEATURES`` = 4096 features.
+Sparse counts: every entry point takes a ``scipy.sparse`` matrix or array as well; the handle then keeps the counts as CSR
+plus its transpose on the device, never an n x g buffer (``n * g`` is not limited), and every result equals, bit for bit,
+that of the dense handle on the densified matrix.  :func:`read_10x_mtx` reads a 10x directory into such a matrix.
+
+Out of scope: ``SCTransform``, ``vars.to.regress``, more than ``MAX_FEATURES`` = 4096 features, sparse input to
+:func:`metrics.find_all_markers` and to the ``--counts`` option of ``run``.
 
     emb = preprocess.embed(counts, nfeatures=2000, npcs=50)
     g = snn.build_snn(emb.coords[:, :15], k=5, ord=15)
@@ -16,6 +21,8 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
+import sys
 import time
 from typing import Optional
 
@@ -27,30 +34,77 @@ MAX_FEATURES = 4096        # MI_PREP_MAX_FEATURES (include/mi_prep.h)
 MAX_PCS = 128              # MI_PREP_MAX_PCS
 GRAM_CHUNK = 512           # MI_PREP_GRAM_CHUNK
 
-_f32p, _f64p, _i32p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)
+MAX_NNZ = 2 ** 31 - 1      # MI_PREP_MAX_NNZ
+
+_f32p, _f64p, _i32p, _i64p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 
 
 def _p(a, t):
     return a.ctypes.data_as(t)
 
 
+def is_sparse(X) -> bool:
+    """Is ``X`` a ``scipy.sparse`` matrix or array (scipy is imported only if the caller has done so)"""
+    sp = sys.modules.get("scipy.sparse")
+    return sp is not None and sp.issparse(X)
+
+
+def canonical_csr(X):
+    """``(indptr int64, indices int32, data float32, (n, g))`` of a ``scipy.sparse`` matrix or array of any format, as
+    ``mi_prep_create_csr_f32`` takes it: CSR, duplicates summed, the columns of every row ascending.  Stored zeros are kept.
+    ``X`` is not modified.  Host only (no library load).  ``ValueError`` for ``g >= 2^31``."""
+    if not is_sparse(X):
+        raise ValueError("X must be a scipy.sparse matrix or array")
+    if X.ndim != 2:
+        raise ValueError("X must be (cells, genes) (got shape %s)" % (X.shape,))
+    n, g = (int(s) for s in X.shape)
+    if g >= 2 ** 31:
+        raise ValueError("%d genes: column indices must fit 32 bits" % g)
+    A = X.tocsr()
+    if not A.has_canonical_format:
+        A = A.copy() if A is X else A
+        A.sum_duplicates()                                       # (sorts the indices as well)
+    return (np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int32),
+            np.ascontiguousarray(A.data, dtype=np.float32), (n, g))
+
+
 class ExpressionMatrix:
     """A cells x genes count matrix resident on the GPU (uploaded once), with one method per pass of include/mi_prep.h.
-    A context manager; ``timing`` collects the device milliseconds of every pass that has run."""
+    ``X`` is a dense array or a ``scipy.sparse`` matrix / array (``sparse`` tells which; ``nnz``: its stored entries, ``n * g``
+    for a dense one).  A context manager; ``timing`` collects the device milliseconds of every pass that has run."""
 
     def __init__(self, X, device: int = 0):
-        X = np.ascontiguousarray(X, dtype=np.float32)
-        if X.ndim != 2:
-            raise ValueError("X must be (cells, genes) (got shape %s)" % (X.shape,))
-        self.n, self.g = (int(s) for s in X.shape)
+        self.sparse = is_sparse(X)
+        if self.sparse:
+            self._indptr, self._indices, data, shape = canonical_csr(X)
+        else:
+            X = np.ascontiguousarray(X, dtype=np.float32)
+            if X.ndim != 2:
+                raise ValueError("X must be (cells, genes) (got shape %s)" % (X.shape,))
+            shape = X.shape
+        self.n, self.g = (int(s) for s in shape)
+        self.nnz = len(data) if self.sparse else self.n * self.g
         self.device = int(device)
         self.h = 0
         self.timing = {}
         self._stats = {}
+        self._h = None
         self._lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self._lib.mi_prep_create_f32(_p(X, _f32p), self.n, self.g, self.device, C.byref(h)))
+        if self.sparse:
+            t0 = time.perf_counter()
+            _lib.check(self._lib.mi_prep_create_csr_f32(_p(self._indptr, _i64p), _p(self._indices, _i32p), _p(data, _f32p),
+                                                        self.n, self.g, self.device, C.byref(h)))
+            self.timing["create_s"] = time.perf_counter() - t0   # the checks, the transpose (host) and the upload
+        else:
+            _lib.check(self._lib.mi_prep_create_f32(_p(X, _f32p), self.n, self.g, self.device, C.byref(h)))
         self._h = h
+
+    def device_bytes(self) -> int:
+        """Bytes the handle holds resident on the device now."""
+        out = C.c_int64(0)
+        _lib.check(self._lib.mi_prep_info(self._handle(), None, None, None, None, C.byref(out)))
+        return int(out.value)
 
     def close(self):
         if self._h is not None:
@@ -83,7 +137,14 @@ class ExpressionMatrix:
         self.timing["normalize_ms"] = float(ms.value)
         return self
 
-    def fetch_normalized(self) -> np.ndarray:
+    def fetch_normalized(self):
+        """The normalised matrix: an ndarray (n x g, fp32), or for a sparse handle a ``csr_matrix`` with the uploaded
+        structure (stored zeros included) and fp32 data."""
+        if self.sparse:
+            from scipy.sparse import csr_matrix
+            data = np.empty(self.nnz, dtype=np.float32)
+            _lib.check(self._lib.mi_prep_fetch_normalized_csr(self._handle(), _p(data, _f32p)))
+            return csr_matrix((data, self._indices, self._indptr), shape=(self.n, self.g))
         out = np.empty((self.n, self.g), dtype=np.float32)
         _lib.check(self._lib.mi_prep_fetch_normalized(self._handle(), _p(out, _f32p)))
         return out
@@ -174,8 +235,9 @@ class Result(dict):
             raise AttributeError(name) from None
 
 
-def log_normalize(X, scale_factor: float = 1e4, device: int = 0) -> np.ndarray:
-    """The log-normalised fp32 matrix (cells x genes) :func:`metrics.find_all_markers` takes."""
+def log_normalize(X, scale_factor: float = 1e4, device: int = 0):
+    """The log-normalised fp32 matrix (cells x genes) :func:`metrics.find_all_markers` takes; sparse in, sparse
+    (``csr_matrix``) out."""
     with ExpressionMatrix(X, device=device) as m:
         return m.normalize(scale_factor).fetch_normalized()
 
@@ -336,7 +398,8 @@ def embed(X, nfeatures: int = 2000, npcs: int = 50, scale_factor: float = 1e4, m
           device: int = 0) -> Result:
     """The whole chain on one upload: normalise, ``vst`` variable genes, scale, PCA.  Returns the fields of :func:`pca`
     plus ``genes`` and ``features`` (the table of :func:`find_variable_features`).  ``coords[:, :dim]`` is what
-    :func:`snn.build_snn` takes.  ``SCTransform``, ``vars.to.regress`` and sparse input are not supported."""
+    :func:`snn.build_snn` takes.  ``X`` is dense or ``scipy.sparse`` (the same genes and coordinates either way).
+    ``SCTransform`` and ``vars.to.regress`` are not supported."""
     with ExpressionMatrix(X, device=device) as m:
         m.normalize(scale_factor)
         feats = find_variable_features(m, nfeatures=nfeatures, span=span)
@@ -344,3 +407,36 @@ def embed(X, nfeatures: int = 2000, npcs: int = 50, scale_factor: float = 1e4, m
     r["genes"] = feats.genes
     r["features"] = feats
     return r
+
+
+def _first_existing(path, names):
+    for name in names:
+        f = os.path.join(path, name)
+        if os.path.exists(f):
+            return f
+    raise FileNotFoundError("%s holds none of %s" % (path, ", ".join(names)))
+
+
+def _read_tsv(f):
+    import gzip
+    with (gzip.open(f, "rt") if f.endswith(".gz") else open(f)) as fh:
+        return [line.rstrip("\r\n").split("\t") for line in fh if line.strip()]
+
+
+def read_10x_mtx(path):
+    """A 10x Genomics matrix directory -- ``matrix.mtx`` (genes x cells, Matrix Market), ``genes.tsv`` (id, name) or
+    ``features.tsv`` (id, name, type) and ``barcodes.tsv``, each plain or ``.gz`` -- as ``(counts, barcodes, gene_ids,
+    gene_names)``: counts a cells x genes ``csr_matrix`` of float32 (``scipy.io.mmread``, transposed), the three lists in
+    file order.  Host only."""
+    from scipy.io import mmread
+    M = mmread(_first_existing(path, ("matrix.mtx", "matrix.mtx.gz")))
+    genes = _read_tsv(_first_existing(path, ("genes.tsv", "genes.tsv.gz", "features.tsv", "features.tsv.gz")))
+    barcodes = [row[0] for row in _read_tsv(_first_existing(path, ("barcodes.tsv", "barcodes.tsv.gz")))]
+    if not is_sparse(M):
+        raise ValueError("matrix.mtx must be a coordinate (sparse) Matrix Market file")
+    counts = M.T.tocsr().astype(np.float32)
+    counts.sum_duplicates()
+    if counts.shape != (len(barcodes), len(genes)):
+        raise ValueError("matrix.mtx is %d genes x %d cells, the lists name %d genes and %d cells"
+                         % (counts.shape[1], counts.shape[0], len(genes), len(barcodes)))
+    return counts, barcodes, [row[0] for row in genes], [row[1] if len(row) > 1 else row[0] for row in genes]
