@@ -57,6 +57,30 @@
  *                           value of y = 0, a barrier, the cell's stored entries of chosen genes (gene -> column map of g
  *                           int32) over their columns, a barrier, one coalesced store.  Z has the dense layout, so
  *                           mi_prep_fetch_scaled, k_prep_gram and k_prep_project run unchanged.
+ *
+ * Cell QC (mi_prep_cell_qc), on the counts of either kind of handle:
+ *   k_prep_cell_qc          one wavefront per cell, k_prep_normalize's walk: the lane-strided fp64 total and the same butterfly
+ *                           (n_count is bit for bit the total the normaliser divides by), the same walk over the masked
+ *                           genes (subset_count), an integer wave reduction over x != 0 (n_feature).
+ *   k_prep_csr_cell_qc      k_prep_csr_normalize's order: each entry to lane `column & 63`, columns ascending; a stored
+ *                           zero is no feature.
+ *
+ * Regression (mi_prep_select_regressed): Z = the scaled residuals of y ~ design, for vars.to.regress.  Stage 1 gathers the
+ * chosen columns of Y into Z unscaled, with the two select kernels (mu = 0, inv = 1, an infinite clip:
+ * fminf((y - 0) * 1, inf) is y); every later stage reads the dense Z alone, so a sparse handle gives the bits of a dense
+ * one.  Q: n x q row-major fp64, an orthonormal basis of the design.  The three kernels have k_prep_col_partial's shape and
+ * order: a workgroup is 64 columns x 4 row lanes over a slice of MI_PREP_ROW_SLICE rows; lane ty (one wavefront, so its row
+ * of Q is uniform) adds rows r0 + ty, r0 + ty + 4, ... ascending; the four lanes meet in LDS as ((s0 + s1) + s2) + s3;
+ * k_prep_col_finish adds the slices in ascending order.  Every product is a separate multiply and add (no contraction).
+ *   k_prep_regress_coef     c_kj = sum_i Q_ik (double) y_ij and S_j = sum_i (double) y_ij^2.
+ *   k_prep_regress_moment   mean_j = (sum_i r_ij) / n, then ss_j = sum_i (r_ij - mean_j)^2, var_j = ss_j / (n - 1); r is
+ *                           recomputed each time as (double) y - acc with acc = Q_i0 c_0, then acc = acc + Q_ik c_k for k
+ *                           ascending: no n x h fp64 buffer exists.
+ *   host, inside the entry  flat_j = ss_j <= 1e-16 S_j (a convention of this package: an all-zero gene, a constant gene and
+ *                           a gene in the span of the design leave a residual that is fp64 noise of order n 2^-53 relative
+ *                           to y, which 1 / sd would scale up to the clip; 1e-8 rms(y) is three decades above that noise at
+ *                           n = 10^5 and far below any real residual); inv_j = 1.0 / sqrt(var_j) in fp64.
+ *   k_prep_regress_scale    in place: z = flat ? 0 : (float) fmin((r - mean) * inv, clip), fp64 with one rounding to f32.
  */
 #ifndef MI_PREP_H
 #define MI_PREP_H
@@ -76,6 +100,7 @@ typedef struct mi_prep_matrix mi_prep_matrix;
 #define MI_PREP_MAX_PCS      128            /* p of mi_prep_project */
 #define MI_PREP_ROW_SLICE    256            /* rows per partial sum of the column reductions */
 #define MI_PREP_GRAM_CHUNK   512            /* cells whose products accumulate in f32 before the fp64 sum over chunks */
+#define MI_PREP_MAX_DESIGN_COLS 9           /* q of mi_prep_select_regressed: the intercept + 8 covariates */
 
 /* X: n x g row-major counts (any non-negative finite values).  Uploads X to `device`.  MI_EINVAL for NULL arguments,
  * n < 2, g < 1, a NaN, an infinity or a negative value; MI_EUNSUPPORTED for n > MI_PREP_MAX_CELLS or
@@ -121,6 +146,25 @@ int mi_prep_clipped_variance(mi_prep_matrix *m, const double *mean, const double
 int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double *mu, const double *sigma, double clip,
                    float *out_kernel_ms);
 int mi_prep_fetch_scaled(mi_prep_matrix *m, float *out);
+
+/* Per cell, on the counts (no mi_prep_normalize needed): n_count = the fp64 total (the one mi_prep_normalize divides by),
+ * n_feature = genes with x != 0, subset_count = the total over the genes with gene_mask[j] == 1 (Seurat's nCount_RNA,
+ * nFeature_RNA and the numerator of PercentageFeatureSet).  gene_mask: g bytes, nullable; outputs: n entries each,
+ * nullable.  MI_EINVAL for a NULL handle, a mask byte other than 0 or 1, subset_count without a mask. */
+int mi_prep_cell_qc(mi_prep_matrix *m, const uint8_t *gene_mask, double *n_count, int32_t *n_feature, double *subset_count,
+                    float *out_kernel_ms);
+
+/* mi_prep_select on the residuals of a linear model (ScaleData(vars.to.regress)): with y the chosen column of the
+ * normalised matrix, r = y - Q (Q^T y), z = (float) fmin((r - mean(r)) / sd(r), clip) (sd with n - 1), z = 0 for a flat
+ * column (see above).  Q: n x q row-major, an orthonormal basis of [1, covariates]; orthonormality is the caller's
+ * contract, the entry computes the expression whatever Q is.  Z has mi_prep_select's layout, so mi_prep_fetch_scaled,
+ * mi_prep_gram and mi_prep_project follow unchanged.  Outputs, each nullable: out_coef q x h (Q^T y), out_mean, out_var
+ * (of the residuals) and out_flat, h entries each, in the order of `genes`.  All checks before any device work: MI_EINVAL
+ * for a NULL argument, h < 1, q < 1, a gene outside [0, g) or chosen twice, a non-finite Q entry, clip NaN or <= 0;
+ * MI_EUNSUPPORTED for h > MI_PREP_MAX_FEATURES or q > MI_PREP_MAX_DESIGN_COLS; MI_ESTATE before mi_prep_normalize.  A
+ * failure leaves nothing selected (mi_prep_fetch_scaled: MI_ESTATE). */
+int mi_prep_select_regressed(mi_prep_matrix *m, const int32_t *genes, int h, const double *Q, int q, double clip,
+                             double *out_coef, double *out_mean, double *out_var, uint8_t *out_flat, float *out_kernel_ms);
 
 /* out_G: h x h fp64, G = Z^T Z (not divided by n - 1).  Every entry is the fp64 sum, in chunk order, of the f32 fmaf chains
  * over the cells of each chunk of MI_PREP_GRAM_CHUNK cells.  MI_ESTATE before mi_prep_select. */

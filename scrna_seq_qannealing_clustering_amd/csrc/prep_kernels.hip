@@ -9,11 +9,16 @@
 //   k_prep_gram          one (upper-triangle 128 x 128 tile, chunk of kChunk cells) per workgroup on the f32-input MFMA,
 //                        f32 tile out; k_prep_gram_reduce adds the chunks in fp64 in chunk order and mirrors.
 //   k_prep_project       out = Z V, 64 cells x 128 columns per workgroup on the same MFMA.
+//   k_prep_cell_qc       per cell: the normaliser's fp64 total, the total of a gene subset, the count of x != 0.
+//   k_prep_regress_*     mi_prep_select_regressed on the gathered Z: c = Q^T y and sum y^2, the residuals' mean and centred
+//                        squares, the in-place scaling; the shape and order of k_prep_col_partial, fp64, no contraction.
 // A sparse handle (mi_prep_create_csr_f32) keeps the counts as CSR and is served by k_prep_csr_normalize,
-// k_prep_csc_col_partial and k_prep_csr_select, which add in the order of the three kernels above: the same bits come out.
+// k_prep_csc_col_partial, k_prep_csr_select and k_prep_csr_cell_qc, which add in the order of their dense kernels: the same
+// bits come out.
 // Operand maps of v_mfma_f32_32x32x2_f32 as in energy_kernels.hip: A: lane l holds A[i = l & 31][k = l >> 5]; B: lane l
 // holds B[k = l >> 5][j = l & 31]; C/D: register q of lane l is C[row = (q & 3) + 8 (q >> 2) + 4 (l >> 5)][col = l & 31].
 // No floating-point atomics; stores are ordinary vector stores.
+#include <algorithm>
 #include <vector>
 
 #include "../../include/mi_prep.h"
@@ -424,6 +429,189 @@ __global__ void __launch_bounds__(256) k_prep_project(const float *__restrict__ 
         }
 }
 
+// ---- per-cell QC: nCount, nFeature and the count of a gene subset (mask: g bytes of 0 / 1, or null) -----------------------
+// The total is k_prep_normalize's (the same lane-strided fp64 sum, the same butterfly), so n_count is bit for bit what the
+// normaliser divides by; the subset is the same walk over the masked genes; the features are counted in integers.
+
+__device__ __forceinline__ int wave_sum_i32(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(256) k_prep_cell_qc(const float *__restrict__ X, const uint8_t *__restrict__ mask, int n, int g,
+                                                      double *__restrict__ n_count, int32_t *__restrict__ n_feature,
+                                                      double *__restrict__ subset)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (size_t)n) return;
+    const float *x = X + row * g;
+    double t = 0.0, s = 0.0;
+    int c = 0;
+    for (int j = lane; j < g; j += 64) {
+        const float v = x[j];
+        t += (double)v;
+        if (mask && mask[j]) s += (double)v;
+        c += v != 0.0f;
+    }
+    t = wave_sum_f64(t);
+    s = wave_sum_f64(s);
+    c = wave_sum_i32(c);
+    if (lane == 0) {
+        n_count[row] = t;
+        n_feature[row] = c;
+        subset[row] = s;
+    }
+}
+
+// the same from CSR, in k_prep_csr_normalize's order: lane `col & 63` adds the entry, columns ascending (a skipped zero of the
+// dense walk adds +0.0 to a non-negative sum); a stored zero is no feature
+__global__ void __launch_bounds__(256) k_prep_csr_cell_qc(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                          const float *__restrict__ X, const uint8_t *__restrict__ mask, int n,
+                                                          double *__restrict__ n_count, int32_t *__restrict__ n_feature,
+                                                          double *__restrict__ subset)
+{
+    const int lane = threadIdx.x & 63;
+    const int row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (row >= n) return;
+    const int64_t e0 = indptr[row], e1 = indptr[row + 1];
+    double t = 0.0, s = 0.0;
+    int c = 0;
+    for (int64_t b = e0; b < e1; b += 64) {
+        const int cnt = __builtin_amdgcn_readfirstlane((int)(e1 - b < 64 ? e1 - b : 64));
+        const int col = lane < cnt ? indices[b + lane] : 0;
+        const float x = lane < cnt ? X[b + lane] : 0.0f;
+        const int in = lane < cnt && mask ? (int)mask[col] : 0;
+        for (int i = 0; i < cnt; ++i) {
+            const int ci = __builtin_amdgcn_readlane(col, i);
+            const float xi = readlane_f(x, i);
+            const int mi = __builtin_amdgcn_readlane(in, i);
+            if (lane == (ci & 63)) {
+                t += (double)xi;
+                if (mi) s += (double)xi;
+                c += xi != 0.0f;
+            }
+        }
+    }
+    t = wave_sum_f64(t);
+    s = wave_sum_f64(s);
+    c = wave_sum_i32(c);
+    if (lane == 0) {
+        n_count[row] = t;
+        n_feature[row] = c;
+        subset[row] = s;
+    }
+}
+
+// ---- regression of covariates out of the gathered columns (mi_prep_select_regressed) --------------------------------------
+// Z holds the h chosen columns of Y, unscaled; Q is the n x q orthonormal basis of the design (fp64, q <= kMaxQ).  The three
+// kernels below share k_prep_col_partial's shape and order: a workgroup is 64 columns x 4 row lanes over a slice of kRowSlice
+// rows, lane ty (one wavefront: its row of Q is uniform, fetched by scalar loads) adds rows r0 + ty, r0 + ty + 4, ...
+// ascending, the four lanes meet in LDS as ((s0 + s1) + s2) + s3, and k_prep_col_finish adds the slices in ascending order.
+// They read Z alone, so a sparse handle gives the bits of a dense one.  Every product is a multiply, then an add.
+constexpr int kMaxQ = MI_PREP_MAX_DESIGN_COLS;
+
+// r = y - sum_k Q_ik c_k: acc = Q_i0 c_0, then acc = acc + Q_ik c_k for k ascending
+__device__ __forceinline__ double regress_residual(float y, const double *__restrict__ qr, const double (&c)[kMaxQ], int q)
+{
+    double acc = qr[0] * c[0];
+#pragma unroll
+    for (int k = 1; k < kMaxQ; ++k)
+        if (k < q) acc = acc + qr[k] * c[k];
+    return (double)y - acc;
+}
+
+// psum[(slice * (q + 1) + k) * h + j]: k < q: sum_i Q_ik y_ij; k = q: sum_i y_ij^2
+__global__ void __launch_bounds__(256) k_prep_regress_coef(const float *__restrict__ Z, int n, int h, int ldz,
+                                                           const double *__restrict__ Q, int q, double *__restrict__ psum)
+{
+    __shared__ double s_sum[4][64];
+    const int tx = threadIdx.x & 63, ty = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int j = blockIdx.x * 64 + tx;
+    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
+    double acc[kMaxQ + 1];
+#pragma unroll
+    for (int k = 0; k <= kMaxQ; ++k) acc[k] = 0.0;
+    if (j < h) {
+        for (int r = r0 + ty; r < r1; r += 4) {
+            const double y = (double)Z[(size_t)r * ldz + j];
+            const double *qr = Q + (size_t)r * q;
+#pragma unroll
+            for (int k = 0; k < kMaxQ; ++k)
+                if (k < q) acc[k] += qr[k] * y;
+            acc[kMaxQ] += y * y;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k <= kMaxQ; ++k) {
+        if (k >= q && k < kMaxQ) continue;                        // (uniform)
+        s_sum[ty][tx] = acc[k];
+        __syncthreads();
+        if (ty == 0 && j < h)
+            psum[((size_t)blockIdx.y * (q + 1) + (k < q ? k : q)) * h + j] =
+                ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
+        __syncthreads();
+    }
+}
+
+// MODE 0: psum[slice * h + j] = sum_i r_ij;  MODE 1: sum_i (r_ij - mean_j)^2.  coef: q x h.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_prep_regress_moment(const float *__restrict__ Z, int n, int h, int ldz,
+                                                             const double *__restrict__ Q, int q,
+                                                             const double *__restrict__ coef, const double *__restrict__ mean,
+                                                             double *__restrict__ psum)
+{
+    __shared__ double s_sum[4][64];
+    const int tx = threadIdx.x & 63, ty = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int j = blockIdx.x * 64 + tx;
+    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
+    double acc = 0.0;
+    if (j < h) {
+        double c[kMaxQ];
+#pragma unroll
+        for (int k = 0; k < kMaxQ; ++k) c[k] = k < q ? coef[(size_t)k * h + j] : 0.0;
+        const double mj = MODE ? mean[j] : 0.0;
+        for (int r = r0 + ty; r < r1; r += 4) {
+            const double res = regress_residual(Z[(size_t)r * ldz + j], Q + (size_t)r * q, c, q);
+            if (MODE) {
+                const double d = res - mj;
+                acc += d * d;
+            } else {
+                acc += res;
+            }
+        }
+    }
+    s_sum[ty][tx] = acc;
+    __syncthreads();
+    if (ty == 0 && j < h)
+        psum[(size_t)blockIdx.y * h + j] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
+}
+
+// in place: z = flat ? 0 : (float) fmin((r - mean) * inv, clip), fp64 with one rounding to f32 (the padding columns keep
+// the zeros of the gather)
+__global__ void __launch_bounds__(256) k_prep_regress_scale(float *__restrict__ Z, int n, int h, int ldz,
+                                                            const double *__restrict__ Q, int q, const double *__restrict__ coef,
+                                                            const double *__restrict__ mean, const double *__restrict__ inv,
+                                                            const uint8_t *__restrict__ flat, double clip)
+{
+    const int tx = threadIdx.x & 63, ty = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int j = blockIdx.x * 64 + tx;
+    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
+    if (j >= h) return;
+    double c[kMaxQ];
+#pragma unroll
+    for (int k = 0; k < kMaxQ; ++k) c[k] = k < q ? coef[(size_t)k * h + j] : 0.0;
+    const double mj = mean[j], ij = inv[j];
+    const bool fj = flat[j] != 0;
+    for (int r = r0 + ty; r < r1; r += 4) {
+        float *z = Z + (size_t)r * ldz + j;
+        const double res = regress_residual(*z, Q + (size_t)r * q, c, q);
+        *z = fj ? 0.0f : (float)fmin((res - mj) * ij, clip);
+    }
+}
+
 }  // namespace
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
@@ -454,6 +642,35 @@ int col_reduce(const mi_prep_matrix *m, const float *M, const double *d_mean, co
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_prep_col_finish, dim3((unsigned)((m->g + 255) / 256)), dim3(256), 0, 0, d_psum,
                        MODE == kColSum ? d_pnnz : nullptr, slices, m->g, denom, d_out, d_out_nnz);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+// Z (n x ldz) = the scaled chosen columns of Y, by the select kernel of the handle's kind (device pointers; d_gmap: sparse only)
+int launch_select(const mi_prep_matrix *m, const int32_t *d_genes, const int32_t *d_gmap, int h, int ldz, const float *d_mu,
+                  const float *d_inv, const uint8_t *d_flat, float clip)
+{
+    if (m->sparse) {
+        hipLaunchKernelGGL(k_prep_csr_select, dim3((unsigned)m->n), dim3(256), 0, 0, m->d_indptr, m->d_indices, m->d_Y, d_gmap,
+                           h, ldz, d_mu, d_inv, d_flat, clip, m->d_Z);
+        HIP_TRY(hipGetLastError());
+    }
+    // dense: (one cell per grid.y, whose limit is 65535: slabs of 32768 cells)
+    for (int r0 = 0; r0 < m->n && !m->sparse; r0 += 32768) {
+        const int rows = m->n - r0 < 32768 ? m->n - r0 : 32768;
+        hipLaunchKernelGGL(k_prep_select, dim3((unsigned)(ldz / 256 + (ldz % 256 != 0)), (unsigned)rows), dim3(256), 0, 0,
+                           m->d_Y + (size_t)r0 * m->g, rows, m->g, d_genes, h, ldz, d_mu, d_inv, d_flat, clip,
+                           m->d_Z + (size_t)r0 * ldz);
+        HIP_TRY(hipGetLastError());
+    }
+    return MI_OK;
+}
+
+// out[e] = (sum over the slices, ascending, of psum[slice * count + e]) / denom
+int finish_slices(const double *d_psum, int slices, size_t count, double denom, double *d_out)
+{
+    hipLaunchKernelGGL(k_prep_col_finish, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, d_psum, nullptr, slices,
+                       (int)count, denom, d_out, nullptr);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -700,20 +917,157 @@ int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double 
         }
         Timer t;
         MI_TRY(t.start(0));
-        if (m->sparse) {
-            hipLaunchKernelGGL(k_prep_csr_select, dim3((unsigned)m->n), dim3(256), 0, 0, m->d_indptr, m->d_indices, m->d_Y, d_gmap,
-                               h, ldz, d_mu, d_inv, d_flat, (float)clip, m->d_Z);
-            HIP_TRY(hipGetLastError());
-        }
-        // dense: (one cell per grid.y, whose limit is 65535: slabs of 32768 cells)
-        for (int r0 = 0; r0 < m->n && !m->sparse; r0 += 32768) {
-            const int rows = m->n - r0 < 32768 ? m->n - r0 : 32768;
-            hipLaunchKernelGGL(k_prep_select, dim3((unsigned)(ldz / 256 + (ldz % 256 != 0)), (unsigned)rows), dim3(256), 0, 0,
-                               m->d_Y + (size_t)r0 * m->g, rows, m->g, d_genes, h, ldz, d_mu, d_inv, d_flat, (float)clip,
-                               m->d_Z + (size_t)r0 * ldz);
-            HIP_TRY(hipGetLastError());
-        }
+        MI_TRY(launch_select(m, d_genes, d_gmap, h, ldz, d_mu, d_inv, d_flat, (float)clip));
         MI_TRY(t.stop(0, out_kernel_ms));
+        m->h = h;
+        return MI_OK;
+    });
+}
+
+int mi_prep_cell_qc(mi_prep_matrix *m, const uint8_t *gene_mask, double *n_count, int32_t *n_feature, double *subset_count,
+                    float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m) return fail(MI_EINVAL, "NULL argument");
+    if (subset_count && !gene_mask) return fail(MI_EINVAL, "subset_count needs a gene_mask");
+    for (int j = 0; gene_mask && j < m->g; ++j)
+        if (gene_mask[j] > 1) return fail(MI_EINVAL, "gene_mask[%d] = %d is neither 0 nor 1", j, (int)gene_mask[j]);
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t n = (size_t)m->n;
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        uint8_t *d_mask = nullptr;
+        double *d_count, *d_subset;
+        int32_t *d_feature;
+        if (gene_mask) {
+            HIP_TRY(bufs.alloc(&d_mask, (size_t)m->g));
+            HIP_TRY(hipMemcpy(d_mask, gene_mask, (size_t)m->g, hipMemcpyHostToDevice));
+        }
+        HIP_TRY(bufs.alloc(&d_count, n));
+        HIP_TRY(bufs.alloc(&d_subset, n));
+        HIP_TRY(bufs.alloc(&d_feature, n));
+        Timer t;
+        MI_TRY(t.start(0));
+        if (m->sparse)
+            hipLaunchKernelGGL(k_prep_csr_cell_qc, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_indptr, m->d_indices,
+                               m->d_X, d_mask, m->n, d_count, d_feature, d_subset);
+        else
+            hipLaunchKernelGGL(k_prep_cell_qc, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_X, d_mask, m->n, m->g,
+                               d_count, d_feature, d_subset);
+        MI_TRY(t.stop(0, out_kernel_ms));
+        if (n_count) HIP_TRY(hipMemcpy(n_count, d_count, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (n_feature) HIP_TRY(hipMemcpy(n_feature, d_feature, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (subset_count) HIP_TRY(hipMemcpy(subset_count, d_subset, n * sizeof(double), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
+}
+
+int mi_prep_select_regressed(mi_prep_matrix *m, const int32_t *genes, int h, const double *Q, int q, double clip,
+                             double *out_coef, double *out_mean, double *out_var, uint8_t *out_flat, float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m) return fail(MI_EINVAL, "NULL argument");
+    m->h = 0;                                                     // (whatever fails below, nothing is selected)
+    if (!genes || !Q) return fail(MI_EINVAL, "NULL argument");
+    if (h < 1) return fail(MI_EINVAL, "h must be >= 1 (got %d)", h);
+    if (q < 1) return fail(MI_EINVAL, "q must be >= 1 (got %d)", q);
+    if (h > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d features exceed %d", h, MI_PREP_MAX_FEATURES);
+    if (q > MI_PREP_MAX_DESIGN_COLS) return fail(MI_EUNSUPPORTED, "%d design columns exceed %d", q, MI_PREP_MAX_DESIGN_COLS);
+    if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
+    return guarded([&]() -> int {
+        const size_t n = (size_t)m->n, hs = (size_t)h, qs = (size_t)q;
+        std::vector<uint8_t> seen((size_t)m->g, 0);
+        for (int c = 0; c < h; ++c) {
+            const int32_t j = genes[c];
+            if (j < 0 || j >= m->g) return fail(MI_EINVAL, "genes[%d] = %d is outside [0, %d)", c, (int)j, m->g);
+            if (seen[j]) return fail(MI_EINVAL, "gene %d is chosen twice", (int)j);
+            seen[j] = 1;
+        }
+        for (size_t e = 0; e < n * qs; ++e)
+            if (!std::isfinite(Q[e])) return fail(MI_EINVAL, "Q[%lld, %lld] is not finite", (long long)(e / qs), (long long)(e % qs));
+        if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
+        std::vector<int32_t> gmap;                                // sparse: gene -> column of Z
+        if (m->sparse) {
+            gmap.assign((size_t)m->g, -1);
+            for (int c = 0; c < h; ++c) gmap[genes[c]] = c;
+        }
+        const std::vector<float> zero(hs, 0.0f), one(hs, 1.0f);
+        std::vector<uint8_t> flat(hs, 0);
+        std::vector<double> S(hs), ss(hs), inv(hs), var(hs);
+        HIP_TRY(hipSetDevice(m->device));
+        const int ldz = (h + kTile - 1) / kTile * kTile;
+        const int slices = (m->n + kRowSlice - 1) / kRowSlice;
+        HIP_TRY(m->d_Z.resize(n * ldz));                 // (a failure leaves it empty, with h = 0)
+        m->ldz = ldz;
+        DevBufs bufs;
+        int32_t *d_genes, *d_gmap = nullptr;
+        float *d_mu, *d_one;
+        uint8_t *d_flat;
+        double *d_Q, *d_psum, *d_coef, *d_mean, *d_ss, *d_inv;
+        HIP_TRY(bufs.alloc(&d_genes, hs));
+        HIP_TRY(bufs.alloc(&d_mu, hs));
+        HIP_TRY(bufs.alloc(&d_one, hs));
+        HIP_TRY(bufs.alloc(&d_flat, hs));
+        HIP_TRY(bufs.alloc(&d_Q, n * qs));
+        HIP_TRY(bufs.alloc(&d_psum, (size_t)slices * (qs + 1) * hs));
+        HIP_TRY(bufs.alloc(&d_coef, (qs + 1) * hs));              // q rows of coefficients, then S
+        HIP_TRY(bufs.alloc(&d_mean, hs));
+        HIP_TRY(bufs.alloc(&d_ss, hs));
+        HIP_TRY(bufs.alloc(&d_inv, hs));
+        HIP_TRY(hipMemcpy(d_genes, genes, hs * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_mu, zero.data(), hs * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_one, one.data(), hs * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_flat, flat.data(), hs, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_Q, Q, n * qs * sizeof(double), hipMemcpyHostToDevice));
+        if (m->sparse) {
+            HIP_TRY(bufs.alloc(&d_gmap, gmap.size()));
+            HIP_TRY(hipMemcpy(d_gmap, gmap.data(), gmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        const dim3 grid((unsigned)((h + 63) / 64), (unsigned)slices);
+        float ms1 = 0.0f, ms2 = 0.0f;
+        {
+            Timer t;
+            MI_TRY(t.start(0));
+            // 1. the gather: fminf((y - 0) * 1, inf) is y
+            MI_TRY(launch_select(m, d_genes, d_gmap, h, ldz, d_mu, d_one, d_flat, HUGE_VALF));
+            // 2. c = Q^T y and S = sum y^2
+            hipLaunchKernelGGL(k_prep_regress_coef, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_psum);
+            HIP_TRY(hipGetLastError());
+            MI_TRY(finish_slices(d_psum, slices, (qs + 1) * hs, 1.0, d_coef));
+            // 3. the mean of the residuals, then their squares about it
+            hipLaunchKernelGGL(k_prep_regress_moment<0>, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, nullptr,
+                               d_psum);
+            HIP_TRY(hipGetLastError());
+            MI_TRY(finish_slices(d_psum, slices, hs, (double)m->n, d_mean));
+            hipLaunchKernelGGL(k_prep_regress_moment<1>, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, d_mean,
+                               d_psum);
+            HIP_TRY(hipGetLastError());
+            MI_TRY(finish_slices(d_psum, slices, hs, 1.0, d_ss));
+            MI_TRY(t.stop(0, &ms1));
+        }
+        // 4. the flat rule and the inverse standard deviation, in host fp64
+        HIP_TRY(hipMemcpy(S.data(), d_coef + qs * hs, hs * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ss.data(), d_ss, hs * sizeof(double), hipMemcpyDeviceToHost));
+        for (int c = 0; c < h; ++c) {
+            var[c] = ss[c] / (double)(m->n - 1);
+            flat[c] = ss[c] <= 1e-16 * S[c];
+            inv[c] = flat[c] ? 0.0 : 1.0 / std::sqrt(var[c]);
+        }
+        HIP_TRY(hipMemcpy(d_flat, flat.data(), hs, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_inv, inv.data(), hs * sizeof(double), hipMemcpyHostToDevice));
+        {
+            Timer t;
+            MI_TRY(t.start(0));
+            // 5. scale in place
+            hipLaunchKernelGGL(k_prep_regress_scale, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, d_mean, d_inv,
+                               d_flat, clip);
+            MI_TRY(t.stop(0, &ms2));
+        }
+        if (out_kernel_ms) *out_kernel_ms = ms1 + ms2;
+        if (out_coef) HIP_TRY(hipMemcpy(out_coef, d_coef, qs * hs * sizeof(double), hipMemcpyDeviceToHost));
+        if (out_mean) HIP_TRY(hipMemcpy(out_mean, d_mean, hs * sizeof(double), hipMemcpyDeviceToHost));
+        if (out_var) std::copy(var.begin(), var.end(), out_var);
+        if (out_flat) std::copy(flat.begin(), flat.end(), out_flat);
         m->h = h;
         return MI_OK;
     });

@@ -11,10 +11,19 @@ Sparse counts: every entry point takes a ``scipy.sparse`` matrix or array as wel
 plus its transpose on the device, never an n x g buffer (``n * g`` is not limited), and every result equals, bit for bit,
 that of the dense handle on the densified matrix.  :func:`read_10x_mtx` reads a 10x directory into such a matrix.
 
-Out of scope: ``SCTransform``, ``vars.to.regress``, more than ``MAX_FEATURES`` = 4096 features, sparse input to
-:func:`metrics.find_all_markers` and to the ``--counts`` option of ``run``.
+Cell QC and ``vars.to.regress`` (the three lines every notebook starts with: ``PercentageFeatureSet(pattern = "^MT-")``,
+``subset(nFeature_RNA > 200 & nFeature_RNA < 2500 & percent.mt < 5)``, ``ScaleData(vars.to.regress = "percent.mt")``;
+`Pbmc3k_prepare_data_for_QA_clustering.Rmd:40-51`, `Kidney_data.Rmd:40-47`): :func:`cell_qc` and :func:`qc_filter` give the
+per-cell columns and the mask, and ``vars_to_regress`` of :func:`scale_data`, :func:`pca` and :func:`embed` scales the
+residuals of the linear model ``y ~ 1 + covariates`` per gene (device; the QR of the design is host fp64).
 
-    emb = preprocess.embed(counts, nfeatures=2000, npcs=50)
+Out of scope: ``SCTransform`` and Poisson or negative-binomial regression models, more than ``MAX_FEATURES`` = 4096
+features or ``MAX_COVARIATES`` = 8 covariates, sparse input to :func:`metrics.find_all_markers` and to the ``--counts``
+option of ``run``.
+
+    qc = preprocess.cell_qc(counts, gene_names)
+    keep = preprocess.qc_filter(qc)
+    emb = preprocess.embed(counts[keep], nfeatures=2000, npcs=50, vars_to_regress=qc.percent[keep])
     g = snn.build_snn(emb.coords[:, :15], k=5, ord=15)
 """
 from __future__ import annotations
@@ -22,6 +31,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import re
 import sys
 import time
 from typing import Optional
@@ -33,10 +43,12 @@ from . import _lib
 MAX_FEATURES = 4096        # MI_PREP_MAX_FEATURES (include/mi_prep.h)
 MAX_PCS = 128              # MI_PREP_MAX_PCS
 GRAM_CHUNK = 512           # MI_PREP_GRAM_CHUNK
+MAX_COVARIATES = 8         # MI_PREP_MAX_DESIGN_COLS - 1 (the intercept)
 
 MAX_NNZ = 2 ** 31 - 1      # MI_PREP_MAX_NNZ
 
 _f32p, _f64p, _i32p, _i64p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+_u8p = C.POINTER(C.c_uint8)
 
 
 def _p(a, t):
@@ -88,6 +100,7 @@ class ExpressionMatrix:
         self.h = 0
         self.timing = {}
         self._stats = {}
+        self.coef_q = self.resid_mean = self.resid_var = self.flat = self.regression = None     # of select_regressed
         self._h = None
         self._lib = _lib.load()
         h = C.c_void_p()
@@ -198,6 +211,53 @@ class ExpressionMatrix:
                                             float(clip), C.byref(ms)))
         self.h = len(genes)
         self.timing["select_ms"] = float(ms.value)
+        return self
+
+    def cell_qc(self, gene_mask=None):
+        """``(n_count, n_feature, subset_count)`` per cell of the counts: the fp64 total (the one :meth:`normalize` divides
+        by), the genes with a non-zero count, and the total over the genes of ``gene_mask`` (g booleans; ``None`` without
+        a mask)."""
+        mask = None
+        if gene_mask is not None:
+            mask = np.asarray(gene_mask)
+            if mask.dtype != np.bool_ or mask.shape != (self.g,):
+                raise ValueError("gene_mask must be a boolean array with one entry per gene (%d)" % self.g)
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        n_count, n_feature = np.empty(self.n), np.empty(self.n, dtype=np.int32)
+        subset = None if mask is None else np.empty(self.n)
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_cell_qc(self._handle(), None if mask is None else _p(mask, _u8p), _p(n_count, _f64p),
+                                             _p(n_feature, _i32p), None if mask is None else _p(subset, _f64p),
+                                             C.byref(ms)))
+        self.timing["qc_ms"] = float(ms.value)
+        return n_count, n_feature, subset
+
+    def select_regressed(self, genes, Q, clip: float = 10.0):
+        """:meth:`select` on the residuals of a linear model: with ``y`` the chosen column of the normalised matrix and
+        ``Q`` (n, q) an orthonormal basis of the design (:func:`design_basis`), ``r = y - Q (Q^T y)`` and
+        ``Z[:, c] = f32(min((r - mean(r)) / sd(r), clip))`` in fp64 with one rounding, 0 for a flat column
+        (``sum (r - mean)^2 <= 1e-16 sum y^2``: an all-zero gene, a constant gene, a gene in the span of the design).
+        Stores ``coef_q`` (q, h: ``Q^T y``), ``resid_mean``, ``resid_var`` and ``flat`` (h each) on the handle."""
+        genes = np.asarray(genes)
+        if genes.ndim != 1 or genes.dtype.kind not in "iu":
+            raise ValueError("genes must be a 1-d integer array")
+        if len(genes) and (genes.min() < -2 ** 31 or genes.max() >= 2 ** 31):
+            raise ValueError("gene index out of range")
+        genes = np.ascontiguousarray(genes, dtype=np.int32)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        if Q.ndim != 2 or Q.shape[0] != self.n:
+            raise ValueError("Q must be (n, q) with n = %d (got shape %s)" % (self.n, Q.shape))
+        h, q = len(genes), Q.shape[1]
+        coef, mean, var = np.empty((max(q, 1), max(h, 1))), np.empty(max(h, 1)), np.empty(max(h, 1))
+        flat = np.empty(max(h, 1), dtype=np.uint8)
+        ms = C.c_float(0.0)
+        self.h = 0
+        _lib.check(self._lib.mi_prep_select_regressed(self._handle(), _p(genes, _i32p), h, _p(Q, _f64p), q, float(clip),
+                                                      _p(coef, _f64p), _p(mean, _f64p), _p(var, _f64p), _p(flat, _u8p),
+                                                      C.byref(ms)))
+        self.h = h
+        self.coef_q, self.resid_mean, self.resid_var, self.flat = coef, mean, var, flat.astype(bool)
+        self.timing["regress_ms"] = float(ms.value)
         return self
 
     def fetch_scaled(self) -> np.ndarray:
@@ -336,21 +396,112 @@ def find_variable_features(X_or_handle, nfeatures: int = 2000, span: float = 0.3
                   genes=top_features(vs, nfeatures))
 
 
-def _select_scaled(m: ExpressionMatrix, genes, max_value: float):
+def feature_mask(gene_names, pattern: str = "^MT-") -> np.ndarray:
+    """Booleans, one per gene: does ``re.search(pattern, name)`` match (case-sensitive, as R's ``grep`` in
+    ``PercentageFeatureSet(pattern = ...)``)."""
+    rx = re.compile(pattern)
+    return np.array([rx.search(str(name)) is not None for name in gene_names], dtype=bool)
+
+
+def cell_qc(X_or_handle, gene_names=None, pattern: str = "^MT-", mask=None, device: int = 0) -> Result:
+    """Seurat's per-cell QC columns of the counts: ``n_count`` (``nCount_RNA``, fp64), ``n_feature`` (``nFeature_RNA``) and
+    ``percent`` = ``100 * (total of the gene subset) / n_count`` in host fp64 (``PercentageFeatureSet``), the subset being
+    ``mask`` (g booleans) or else the genes whose name matches ``pattern`` (:func:`feature_mask`); ``percent`` is ``None``
+    when neither ``mask`` nor ``gene_names`` is given.  A cell without counts gets ``percent`` 0 (Seurat gives NaN there;
+    :meth:`ExpressionMatrix.normalize` follows the same convention)."""
+    if not isinstance(X_or_handle, ExpressionMatrix):
+        with ExpressionMatrix(X_or_handle, device=device) as m:
+            return cell_qc(m, gene_names, pattern, mask)
+    m = X_or_handle
+    if mask is None and gene_names is not None:
+        if len(gene_names) != m.g:
+            raise ValueError("gene_names must name every gene (%d, got %d)" % (m.g, len(gene_names)))
+        mask = feature_mask(gene_names, pattern)
+    n_count, n_feature, subset = m.cell_qc(mask)
+    percent = None
+    if subset is not None:
+        percent = np.where(n_count > 0, 100.0 * subset / np.where(n_count > 0, n_count, 1.0), 0.0)
+    return Result(n_count=n_count, n_feature=n_feature, percent=percent)
+
+
+def qc_filter(qc, min_features=200, max_features=2500, max_percent=5.0, min_counts=None, max_counts=None) -> np.ndarray:
+    """The cells the notebooks' ``subset(x, nFeature_RNA > 200 & nFeature_RNA < 2500 & percent.mt < 5)`` keeps, as a boolean
+    mask: every inequality is strict, ``None`` disables a bound.  ``qc``: the result of :func:`cell_qc`."""
+    keep = np.ones(len(qc["n_feature"]), dtype=bool)
+    if max_percent is not None and qc["percent"] is None:
+        raise ValueError("max_percent needs qc.percent: give cell_qc gene names or a mask, or pass max_percent=None")
+    for values, lo, hi in ((qc["n_feature"], min_features, max_features), (qc["n_count"], min_counts, max_counts),
+                           (qc["percent"], None, max_percent)):
+        if lo is not None:
+            keep &= np.asarray(values) > lo
+        if hi is not None:
+            keep &= np.asarray(values) < hi
+    return keep
+
+
+def design_basis(covariates, n: Optional[int] = None):
+    """``(Q, R)`` of the design matrix ``[1, covariates]`` (``numpy.linalg.qr``, fp64): ``Q`` (n, 1 + p) is the orthonormal
+    basis :meth:`ExpressionMatrix.select_regressed` takes, ``R`` turns its coefficients into those of the design
+    (:func:`regression_betas`).  ``covariates``: (n,) or (n, p) with ``p <= MAX_COVARIATES``, finite.  ``ValueError`` for a
+    length other than ``n`` (when given), a non-finite value, too many columns, and a rank-deficient design -- a constant
+    covariate or collinear columns: some ``|R_kk| <= n 2^-52 max |R_kk|``."""
+    A = np.asarray(covariates, dtype=np.float64)
+    if A.ndim == 1:
+        A = A[:, None]
+    if A.ndim != 2 or A.shape[0] < 2 or A.shape[1] < 1:
+        raise ValueError("covariates must be (n,) or (n, p) with n >= 2, p >= 1 (got shape %s)" % (A.shape,))
+    if n is not None and A.shape[0] != int(n):
+        raise ValueError("covariates must have one row per cell (%d, got %d)" % (int(n), A.shape[0]))
+    if A.shape[1] > MAX_COVARIATES:
+        raise ValueError("%d covariates exceed %d" % (A.shape[1], MAX_COVARIATES))
+    if not np.isfinite(A).all():
+        raise ValueError("covariates must be finite")
+    if A.shape[0] < A.shape[1] + 1:
+        raise ValueError("%d cells cannot carry a design of %d columns" % (A.shape[0], A.shape[1] + 1))
+    const = np.flatnonzero(A.min(axis=0) == A.max(axis=0))
+    if len(const):
+        raise ValueError("covariate %d is constant: the design is rank-deficient" % const[0])
+    Q, R = np.linalg.qr(np.column_stack([np.ones(A.shape[0]), A]))
+    d = np.abs(np.diag(R))
+    if (d <= A.shape[0] * 2.0 ** -52 * d.max()).any():
+        raise ValueError("the design [1, covariates] is rank-deficient (column %d depends on those before it)"
+                         % int(np.argmin(d)))
+    return np.ascontiguousarray(Q), R
+
+
+def regression_betas(R, coef_q) -> np.ndarray:
+    """The coefficients of the design ``[1, covariates]`` from those of its basis: ``beta = R^-1 c`` (row 0 the intercept,
+    then one row per covariate; one column per gene)."""
+    from scipy.linalg import solve_triangular
+    return solve_triangular(np.asarray(R, dtype=np.float64), np.asarray(coef_q, dtype=np.float64), lower=False)
+
+
+def _select_scaled(m: ExpressionMatrix, genes, max_value: float, vars_to_regress=None):
+    """-> the ``regression`` table when ``vars_to_regress`` is given, else ``None``"""
     genes = np.asarray(genes)
     if genes.ndim != 1 or genes.dtype.kind not in "iu" or len(genes) < 1:
         raise ValueError("genes must be a non-empty 1-d integer array")
     if genes.min() < 0 or genes.max() >= m.g:
         raise ValueError("gene indices must lie in [0, %d)" % m.g)
-    mean, var, _ = m.gene_stats("normalized")
-    m.select(genes, mean[genes], np.sqrt(var[genes]), max_value)
+    if vars_to_regress is None:
+        mean, var, _ = m.gene_stats("normalized")
+        m.select(genes, mean[genes], np.sqrt(var[genes]), max_value)
+        return None
+    t0 = time.perf_counter()
+    Q, R = design_basis(vars_to_regress, n=m.n)
+    m.timing["design_qr_s"] = time.perf_counter() - t0
+    m.select_regressed(genes, Q, max_value)
+    return Result(betas=regression_betas(R, m.coef_q), resid_mean=m.resid_mean, resid_var=m.resid_var, flat=m.flat)
 
 
-def scale_data(handle: ExpressionMatrix, genes, max_value: float = 10.0) -> np.ndarray:
+def scale_data(handle: ExpressionMatrix, genes, max_value: float = 10.0, vars_to_regress=None) -> np.ndarray:
     """Seurat's ``ScaleData`` on the chosen genes of the normalised matrix: centred by the gene's mean, divided by its
     standard deviation (ddof 1), clipped above at ``max_value``; a constant gene gives zeros.  Returns ``Z`` (n x h, fp32).
-    ``vars.to.regress`` is not supported."""
-    _select_scaled(handle, genes, max_value)
+    ``vars_to_regress`` ((n,) or (n, p <= 8) covariates, e.g. ``cell_qc(...).percent``): Seurat's ``vars.to.regress`` with
+    its default linear model -- per gene the residuals of ``y ~ 1 + covariates`` are centred, scaled and clipped instead
+    (:meth:`ExpressionMatrix.select_regressed`), and ``handle.regression`` holds ``betas`` (:func:`regression_betas`),
+    ``resid_mean``, ``resid_var`` and ``flat``."""
+    handle.regression = _select_scaled(handle, genes, max_value, vars_to_regress)
     return handle.fetch_scaled()
 
 
@@ -376,34 +527,38 @@ def pca_from_gram(G, n: int, npcs: int) -> Result:
     return Result(loadings=V, eigenvalues=w, stdev=np.sqrt(np.maximum(w, 0.0)), total_variance=float(np.trace(Cm)))
 
 
-def pca(handle: ExpressionMatrix, genes, npcs: int = 50, max_value: float = 10.0) -> Result:
+def pca(handle: ExpressionMatrix, genes, npcs: int = 50, max_value: float = 10.0, vars_to_regress=None) -> Result:
     """Seurat's ``ScaleData`` + ``RunPCA(features = genes)``: the scaled matrix, its Gram matrix (device),
     :func:`pca_from_gram` (host), and ``coords = Z @ f32(loadings)`` (device): Seurat's ``cell.embeddings``.  Returns the
     fields of :func:`pca_from_gram`, ``coords`` (n x npcs, fp32) and ``timing`` (every kernel's ms, the eigen-solve's
-    seconds)."""
+    seconds).  With ``vars_to_regress`` (see :func:`scale_data`) the scaled matrix is that of the residuals and
+    ``regression`` (``betas``, ``resid_mean``, ``resid_var``, ``flat``) is returned as well."""
     npcs = int(npcs)
     if npcs < 1 or npcs > min(MAX_PCS, len(np.atleast_1d(genes))):
         raise ValueError("npcs must lie in [1, min(%d, number of genes)] (got %d)" % (MAX_PCS, npcs))
-    _select_scaled(handle, genes, max_value)
+    regression = _select_scaled(handle, genes, max_value, vars_to_regress)
     G = handle.gram()
     t0 = time.perf_counter()
     r = pca_from_gram(G, handle.n, npcs)
     handle.timing["eigh_s"] = time.perf_counter() - t0
     r["coords"] = handle.project(r.loadings.astype(np.float32))
     r["timing"] = dict(handle.timing)
+    if regression is not None:
+        r["regression"] = regression
     return r
 
 
 def embed(X, nfeatures: int = 2000, npcs: int = 50, scale_factor: float = 1e4, max_value: float = 10.0, span: float = 0.3,
-          device: int = 0) -> Result:
+          device: int = 0, vars_to_regress=None) -> Result:
     """The whole chain on one upload: normalise, ``vst`` variable genes, scale, PCA.  Returns the fields of :func:`pca`
     plus ``genes`` and ``features`` (the table of :func:`find_variable_features`).  ``coords[:, :dim]`` is what
     :func:`snn.build_snn` takes.  ``X`` is dense or ``scipy.sparse`` (the same genes and coordinates either way).
-    ``SCTransform`` and ``vars.to.regress`` are not supported."""
+    ``vars_to_regress``: one row per cell of ``X``, regressed out of the chosen genes before scaling (see
+    :func:`scale_data`).  ``SCTransform`` is not supported."""
     with ExpressionMatrix(X, device=device) as m:
         m.normalize(scale_factor)
         feats = find_variable_features(m, nfeatures=nfeatures, span=span)
-        r = pca(m, feats.genes, npcs=npcs, max_value=max_value)
+        r = pca(m, feats.genes, npcs=npcs, max_value=max_value, vars_to_regress=vars_to_regress)
     r["genes"] = feats.genes
     r["features"] = feats
     return r
