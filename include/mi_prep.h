@@ -81,6 +81,43 @@
  *                           to y, which 1 / sd would scale up to the clip; 1e-8 rms(y) is three decades above that noise at
  *                           n = 10^5 and far below any real residual); inv_j = 1.0 / sqrt(var_j) in fp64.
  *   k_prep_regress_scale    in place: z = flat ? 0 : (float) fmin((r - mean) * inv, clip), fp64 with one rounding to f32.
+ *
+ * SCTransform (mi_prep_gene_log1p_sum, mi_prep_nb_fit, mi_prep_sct_residual_moments, mi_prep_sct_select; DESIGN.md section 5c
+ * "SCTransform").  The chain is this package's specification, modelled on sctransform::vst; it is unpinned against R.
+ *   k_prep_col_partial<LOG1P>  sum_i log1p((double) x_ij): the SUM mode's walk with another term, dense and sparse (a zero adds
+ *                           +0.0 either way), for sctransform's geometric mean.
+ *   k_sct_gather            the counts of the fit cells x fit genes as a dense f32 block, gene-major (one thread per element);
+ *   k_sct_csr_gather        the same from CSR: one workgroup per fit cell, its row in LDS (zeros, a barrier, the stored entries
+ *                           of fit genes over them).  The fit reads the block alone: a sparse handle gives a dense one's bits.
+ *   k_sct_nb_fit            one workgroup of 256 threads per gene.  The gene's counts sit in LDS (MI_PREP_SCT_MAX_FIT_CELLS
+ *                           floats, 32 KB, + 160 B for the sums), the centred covariate xc is one fp64 array shared by all genes;
+ *                           mu = exp(b0 + b1 xc) is recomputed in every pass, nothing per cell is kept between rounds.  Every sum
+ *                           is per thread over the cells t, t + 256, ... ascending, then the wave butterfly, then the four waves
+ *                           in LDS as ((s0 + s1) + s2) + s3: no atomics, two runs are bit-identical.  Every thread computes the
+ *                           scalar logic of a round from the same sums, so control flow is workgroup-uniform.  psi and psi' are
+ *                           csrc/mi_sct_math.h.  The model is y ~ NB(mu, alpha), variance mu + alpha mu^2, theta = 1 / alpha:
+ *                             1. Poisson start: mu = y + 0.1, eta = log mu, then 8 IRLS steps with w = mu, z = eta + (y - mu) / mu,
+ *                                each the closed form of the 2 x 2 weighted normal equations (5 sums).
+ *                             2. Poisson rule, once: T = sum (y - mu)^2 - y; T <= 0: alpha = 0, poisson = 1, only b moves below;
+ *                                else alpha = T / sum mu^2.
+ *                             3. at most 40 rounds.  s = sum (psi(y + theta) - psi(theta)) + log1p(-mu / (theta + mu)) - (y - mu) /
+ *                                (theta + mu) and s' = sum (psi'(y + theta) - psi'(theta)) + mu / (theta (theta + mu)) + (y - mu) /
+ *                                (theta + mu)^2 (the derivatives of the log-likelihood in theta, each bracket a small difference
+ *                                taken first); l1 = -theta^2 s, l2 = theta^4 s' + 2 theta^3 s.  l2 < 0: alpha' = alpha - l1 / l2,
+ *                                else 2 alpha if l1 > 0 and alpha / 2 if not; a proposal that is not > 0 becomes alpha / 4; then
+ *                                alpha' is limited to [alpha / 8, 8 alpha].  One Fisher-scoring step of b at alpha' and the old
+ *                                mu: U = sum (y - mu) / (1 + alpha' mu) [1, xc], I = sum w [1, xc]^T [1, xc], w = mu / (1 + alpha'
+ *                                mu), b += I^-1 U.  lambda^2 = U^T I^-1 U + l1^2 / (-l2) (infinite while l2 >= 0): the squared
+ *                                distance to the optimum in standard errors.  A gene with lambda^2 <= 1e-16 takes the update and
+ *                                stops, converged = 1; after 40 rounds it keeps its last iterate, converged = 0.
+ *                             4. se_b0c = sqrt(I_11 / det I), se_b1 = sqrt(I_00 / det I), se_alpha = 1 / sqrt(-l2) of the last
+ *                                round (NaN for a Poisson gene or while l2 >= 0).
+ *   k_sct_col_partial       k_prep_col_partial's shape, slices and order on r = clip((x - mu) / sqrt(mu + alpha mu^2), +-clip),
+ *                           mu = exp(b0 + b1 log_umi_i): the sum, then the squares about the mean;
+ *   k_sct_csc_col_partial   the same on the transpose.  A zero's residual depends on the cell, so every row of the slice is
+ *                           walked, as in the CENTRED mode, and the contract holds bit for bit.
+ *   k_sct_select            Z = (float) r for the chosen genes, k_prep_select's shape;
+ *   k_sct_csr_select        k_prep_csr_select's: the zeros' residuals fill the cell's LDS row, the stored entries overwrite.
  */
 #ifndef MI_PREP_H
 #define MI_PREP_H
@@ -101,6 +138,7 @@ typedef struct mi_prep_matrix mi_prep_matrix;
 #define MI_PREP_ROW_SLICE    256            /* rows per partial sum of the column reductions */
 #define MI_PREP_GRAM_CHUNK   512            /* cells whose products accumulate in f32 before the fp64 sum over chunks */
 #define MI_PREP_MAX_DESIGN_COLS 9           /* q of mi_prep_select_regressed: the intercept + 8 covariates */
+#define MI_PREP_SCT_MAX_FIT_CELLS 8192      /* cells of mi_prep_nb_fit: a gene's counts are 32 KB of LDS */
 
 /* X: n x g row-major counts (any non-negative finite values).  Uploads X to `device`.  MI_EINVAL for NULL arguments,
  * n < 2, g < 1, a NaN, an infinity or a negative value; MI_EUNSUPPORTED for n > MI_PREP_MAX_CELLS or
@@ -165,6 +203,43 @@ int mi_prep_cell_qc(mi_prep_matrix *m, const uint8_t *gene_mask, double *n_count
  * failure leaves nothing selected (mi_prep_fetch_scaled: MI_ESTATE). */
 int mi_prep_select_regressed(mi_prep_matrix *m, const int32_t *genes, int h, const double *Q, int q, double clip,
                              double *out_coef, double *out_mean, double *out_var, uint8_t *out_flat, float *out_kernel_ms);
+
+/* out[j] = sum_i log1p((double) x_ij) over the counts, fp64, g entries: sctransform's geometric mean of a gene is
+ * expm1(out[j] / n).  The order of mi_prep_gene_stats' sum. */
+int mi_prep_gene_log1p_sum(mi_prep_matrix *m, double *out, float *out_kernel_ms);
+
+/* The negative-binomial regression of SCTransform's step 1 (k_sct_nb_fit above): for each of the g1 `genes`, over the mc
+ * `cells` (any order, no repeats), y ~ NB(mu, alpha) with log mu = b0 + b1 log_umi.  log_umi: mc entries, in the order of
+ * `cells` (log10 of the cell's total count); the kernel regresses on log_umi - mean, the mean being the sum in that order
+ * divided by mc.  Outputs, g1 entries each, all required: b0 (on the uncentred covariate: b0c - b1 mean), b1, alpha, the
+ * standard errors se_b0c (of the centred intercept), se_b1, se_alpha (NaN for a Poisson gene), iterations (rounds of step
+ * 3), converged, poisson.  Natural-log coefficients.  MI_EINVAL for a NULL argument, a cell outside [0, n) or a gene outside
+ * [0, g) or either repeated, mc < 3, g1 < 1, a non-finite log_umi (a cell without counts), a log_umi that is the same in
+ * every cell; MI_EUNSUPPORTED for mc > MI_PREP_SCT_MAX_FIT_CELLS or g1 > MI_PREP_MAX_FEATURES.  Needs no mi_prep_normalize. */
+int mi_prep_nb_fit(mi_prep_matrix *m, const int32_t *cells, int mc, const int32_t *genes, int g1, const double *log_umi,
+                   double *out_b0, double *out_b1, double *out_alpha, double *out_se_b0c, double *out_se_b1,
+                   double *out_se_alpha, int32_t *out_iterations, uint8_t *out_converged, uint8_t *out_poisson,
+                   float *out_kernel_ms);
+
+/* Per chosen gene, over all n cells: mean and variance (n - 1, about that mean, two passes, fp64) of the Pearson residual
+ *     r = min(max((x - mu) / sqrt(mu + alpha mu^2), -clip), clip),     mu = exp(b0 + b1 log_umi_i).
+ * b0, b1, alpha, out_mean, out_var: gp entries in the order of `genes`; log_umi: n entries.  MI_EINVAL for a NULL argument,
+ * gp < 1 or > g, a gene outside [0, g) or repeated, a non-finite b0, b1 or log_umi, alpha negative or not finite, clip NaN
+ * or <= 0. */
+int mi_prep_sct_residual_moments(mi_prep_matrix *m, const int32_t *genes, int gp, const double *b0, const double *b1,
+                                 const double *alpha, const double *log_umi, double clip, double *out_mean, double *out_var,
+                                 float *out_kernel_ms);
+
+/* SCTransform's scale.data: Z = (float) r (above, clipped at +-clip) for the h chosen genes, then stages 2 - 5 of
+ * mi_prep_select_regressed on that Z with unit scale and no further clip: z = flat ? 0 : (float) (r - Q (Q^T r) - mean).
+ * With Q the basis of [1] this is centring (do.center = TRUE, do.scale = FALSE); with [1, covariates] vars.to.regress.
+ * Arguments, outputs and the flat rule as mi_prep_select_regressed; the same checks, and those of
+ * mi_prep_sct_residual_moments on the parameters; MI_EUNSUPPORTED for h > MI_PREP_MAX_FEATURES or q >
+ * MI_PREP_MAX_DESIGN_COLS.  Q = NULL with q = 0 stops after stage 1: Z holds the clipped residuals themselves, uncentred, and
+ * the four outputs are not written.  Needs no mi_prep_normalize.  A failure leaves nothing selected. */
+int mi_prep_sct_select(mi_prep_matrix *m, const int32_t *genes, int h, const double *b0, const double *b1, const double *alpha,
+                       const double *log_umi, double clip, const double *Q, int q, double *out_coef, double *out_mean,
+                       double *out_var, uint8_t *out_flat, float *out_kernel_ms);
 
 /* out_G: h x h fp64, G = Z^T Z (not divided by n - 1).  Every entry is the fp64 sum, in chunk order, of the f32 fmaf chains
  * over the cells of each chunk of MI_PREP_GRAM_CHUNK cells.  MI_ESTATE before mi_prep_select. */

@@ -12,6 +12,8 @@
 //   k_prep_cell_qc       per cell: the normaliser's fp64 total, the total of a gene subset, the count of x != 0.
 //   k_prep_regress_*     mi_prep_select_regressed on the gathered Z: c = Q^T y and sum y^2, the residuals' mean and centred
 //                        squares, the in-place scaling; the shape and order of k_prep_col_partial, fp64, no contraction.
+//   k_sct_*              SCTransform: the gather of the fit block, the per-gene negative-binomial fit (one workgroup per gene,
+//                        its counts in LDS), the residual moments and the residual selection, each dense and sparse.
 // A sparse handle (mi_prep_create_csr_f32) keeps the counts as CSR and is served by k_prep_csr_normalize,
 // k_prep_csc_col_partial, k_prep_csr_select and k_prep_csr_cell_qc, which add in the order of their dense kernels: the same
 // bits come out.
@@ -24,6 +26,7 @@
 #include "../../include/mi_prep.h"
 #include "mi_prep_csr.h"
 #include "mi_sa_device.h"
+#include "mi_sct_math.h"
 
 namespace mi_sa_impl {
 namespace {
@@ -35,7 +38,7 @@ constexpr int kChunk = MI_PREP_GRAM_CHUNK;
 constexpr int kTile = 128, kKC = 32;
 constexpr int kProjCells = 64, kProjCols = MI_PREP_MAX_PCS;
 constexpr size_t kGramWorkspace = (size_t)256 << 20;                    // bytes of f32 tiles in flight between the two Gram kernels
-enum { kColSum = 0, kColCentred = 1, kColClipped = 2 };
+enum { kColSum = 0, kColCentred = 1, kColClipped = 2, kColLog1p = 3 };
 
 __global__ void __launch_bounds__(256) k_prep_normalize(const float *__restrict__ X, float *__restrict__ Y, int n, int g,
                                                         double scale)
@@ -64,12 +67,14 @@ __global__ void __launch_bounds__(256) k_prep_col_partial(const float *__restric
     double acc = 0.0;
     int32_t cnt = 0;
     if (j < g) {
-        const double mj = MODE == kColSum ? 0.0 : mean[j], sj = MODE == kColClipped ? sd[j] : 1.0;
+        const double mj = MODE == kColSum || MODE == kColLog1p ? 0.0 : mean[j], sj = MODE == kColClipped ? sd[j] : 1.0;
         for (int r = r0 + ty; r < r1; r += 4) {
             const float v = M[(size_t)r * g + j];
             if (MODE == kColSum) {
                 acc += (double)v;
                 cnt += v != 0.0f;
+            } else if (MODE == kColLog1p) {
+                acc += log1p((double)v);
             } else if (MODE == kColCentred) {
                 const double d = (double)v - mj;
                 acc += d * d;
@@ -184,10 +189,10 @@ __global__ void __launch_bounds__(256) k_prep_csc_col_partial(const int64_t *__r
             return r1;
         };
         int nr = seek();
-        if (MODE == kColSum) {
+        if (MODE == kColSum || MODE == kColLog1p) {                 // (log1p(0) is +0.0, like the 0 of a sum)
             while (nr < r1) {
                 const float v = vals[pos[k]];
-                acc += (double)v;
+                acc += MODE == kColLog1p ? log1p((double)v) : (double)v;
                 cnt += v != 0.0f;
                 ++k;
                 nr = seek();
@@ -612,6 +617,297 @@ __global__ void __launch_bounds__(256) k_prep_regress_scale(float *__restrict__ 
     }
 }
 
+// ---- SCTransform: negative-binomial regression on sequencing depth and Pearson residuals (include/mi_prep.h) -----------------
+// The fit reads a dense f32 block of the counts (fit genes x fit cells, gene-major), written by one of two gathers, so it
+// never sees the handle's kind: a sparse handle gives the bits of a dense one.
+constexpr int kFitCells = MI_PREP_SCT_MAX_FIT_CELLS;
+constexpr int kFitPoissonSteps = 8, kFitRounds = 40;
+constexpr double kFitTol = 1e-16;
+
+// B[jj * mc + ii] = X[cells[ii], genes[jj]]: one thread per element
+__global__ void __launch_bounds__(256) k_sct_gather(const float *__restrict__ X, int g, const int32_t *__restrict__ cells, int mc,
+                                                    const int32_t *__restrict__ genes, int g1, float *__restrict__ B)
+{
+    const int jj = blockIdx.x * 256 + threadIdx.x, ii = blockIdx.y;
+    if (jj >= g1) return;
+    B[(size_t)jj * mc + ii] = X[(size_t)cells[ii] * g + genes[jj]];
+}
+
+// the same from CSR: one workgroup per fit cell, its row of the block in LDS (zeros, then the stored entries of fit genes)
+__global__ void __launch_bounds__(256) k_sct_csr_gather(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                        const float *__restrict__ X, const int32_t *__restrict__ gmap,
+                                                        const int32_t *__restrict__ cells, int mc, int g1, float *__restrict__ B)
+{
+    __shared__ float s_row[MI_PREP_MAX_FEATURES];
+    const int ii = blockIdx.x;
+    const size_t row = (size_t)cells[ii];
+    for (int c = threadIdx.x; c < g1; c += 256) s_row[c] = 0.0f;
+    __syncthreads();
+    const int64_t e1 = indptr[row + 1];
+    for (int64_t e = indptr[row] + threadIdx.x; e < e1; e += 256) {
+        const int c = gmap[indices[e]];
+        if (c >= 0) s_row[c] = X[e];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < g1; c += 256) B[(size_t)c * mc + ii] = s_row[c];
+}
+
+// K sums of a workgroup of 256: the wave butterfly, then the four waves in LDS as ((s0 + s1) + s2) + s3; every thread
+// leaves with the same bits, so the scalar logic that follows is workgroup-uniform
+template <int K>
+__device__ __forceinline__ void fit_block_sum(double (&v)[K], double (*s_red)[4])
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_sum_f64(v[k]);
+    __syncthreads();                                              // (the readers of the previous sums are through)
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) s_red[k][w] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = ((s_red[k][0] + s_red[k][1]) + s_red[k][2]) + s_red[k][3];
+}
+
+// One workgroup per gene: y ~ NB(mu, alpha), log mu = b0 + b1 xc.  The gene's counts sit in LDS (<= kFitCells floats), xc is
+// shared by all genes (fp64, L2), mu is recomputed in every pass: nothing per cell is kept between rounds.  Thread t adds the
+// cells t, t + 256, ... ascending.  The algorithm, step by step: include/mi_prep.h (mi_prep_nb_fit).
+__global__ void __launch_bounds__(256) k_sct_nb_fit(const float *__restrict__ B, int mc, const double *__restrict__ xc, double xmean,
+                                                    double *__restrict__ o_b0, double *__restrict__ o_b1,
+                                                    double *__restrict__ o_alpha, double *__restrict__ o_se_b0c,
+                                                    double *__restrict__ o_se_b1, double *__restrict__ o_se_alpha,
+                                                    int32_t *__restrict__ o_iter, uint8_t *__restrict__ o_conv,
+                                                    uint8_t *__restrict__ o_pois)
+{
+    __shared__ float s_y[kFitCells];
+    __shared__ double s_red[5][4];
+    const int j = blockIdx.x, t = threadIdx.x;
+    for (int i = t; i < mc; i += 256) s_y[i] = B[(size_t)j * mc + i];
+    __syncthreads();
+    double b0 = 0.0, b1 = 0.0;
+    // 1. the Poisson start: IRLS from mu = y + 0.1, each step the closed form of the 2 x 2 weighted normal equations
+    for (int it = 0; it < kFitPoissonSteps; ++it) {
+        double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int i = t; i < mc; i += 256) {
+            const double y = (double)s_y[i], x = xc[i];
+            double mu, eta;
+            if (it == 0) {
+                mu = y + 0.1;
+                eta = log(mu);
+            } else {
+                eta = b0 + b1 * x;
+                mu = exp(eta);
+            }
+            const double z = eta + (y - mu) / mu, wx = mu * x;
+            a[0] += mu;
+            a[1] += wx;
+            a[2] += wx * x;
+            a[3] += mu * z;
+            a[4] += wx * z;
+        }
+        fit_block_sum<5>(a, s_red);
+        const double det = a[0] * a[2] - a[1] * a[1];
+        b0 = (a[2] * a[3] - a[1] * a[4]) / det;
+        b1 = (a[0] * a[4] - a[1] * a[3]) / det;
+    }
+    // 2. the Poisson rule, once, at the Poisson fit
+    double alpha;
+    bool pois;
+    {
+        double a[2] = {0.0, 0.0};
+        for (int i = t; i < mc; i += 256) {
+            const double y = (double)s_y[i], mu = exp(b0 + b1 * xc[i]), d = y - mu;
+            a[0] += d * d - y;
+            a[1] += mu * mu;
+        }
+        fit_block_sum<2>(a, s_red);
+        pois = !(a[0] > 0.0);
+        alpha = pois ? 0.0 : a[0] / a[1];
+    }
+    // 3. the rounds
+    int iters = 0;
+    bool conv = false;
+    double l2 = 0.0, i00 = 0.0, i11 = 0.0, det = 0.0;
+    for (int round = 0; round < kFitRounds && !conv; ++round) {
+        double l1 = 0.0, anew = alpha;
+        if (!pois) {
+            const double th = 1.0 / alpha, psi0 = mi_sct::digamma(th), tri0 = mi_sct::trigamma(th);
+            double a[2] = {0.0, 0.0};
+            for (int i = t; i < mc; i += 256) {
+                const double y = (double)s_y[i], mu = exp(b0 + b1 * xc[i]);
+                const double tm = th + mu, d = y - mu;
+                double dpsi = 0.0, dtri = 0.0;                    // (psi(th) - psi(th) is +0.0: a zero count skips both)
+                if (y != 0.0) {
+                    dpsi = mi_sct::digamma(y + th) - psi0;
+                    dtri = mi_sct::trigamma(y + th) - tri0;
+                }
+                a[0] += (dpsi + log1p(-(mu / tm))) - d / tm;
+                a[1] += (dtri + mu / (th * tm)) + d / (tm * tm);
+            }
+            fit_block_sum<2>(a, s_red);
+            const double th2 = th * th;
+            l1 = -(th2 * a[0]);
+            l2 = (th2 * th2) * a[1] + 2.0 * ((th2 * th) * a[0]);
+            if (l2 < 0.0)
+                anew = alpha - l1 / l2;
+            else
+                anew = l1 > 0.0 ? 2.0 * alpha : 0.5 * alpha;
+            if (!(anew > 0.0)) anew = 0.25 * alpha;
+            anew = fmin(fmax(anew, 0.125 * alpha), 8.0 * alpha);
+        }
+        double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int i = t; i < mc; i += 256) {
+            const double y = (double)s_y[i], x = xc[i], mu = exp(b0 + b1 * x);
+            const double den = 1.0 + anew * mu, w = mu / den, u = (y - mu) / den, wx = w * x;
+            a[0] += u;
+            a[1] += u * x;
+            a[2] += w;
+            a[3] += wx;
+            a[4] += wx * x;
+        }
+        fit_block_sum<5>(a, s_red);
+        det = a[2] * a[4] - a[3] * a[3];
+        i00 = a[2];
+        i11 = a[4];
+        const double d0 = (a[4] * a[0] - a[3] * a[1]) / det, d1 = (a[2] * a[1] - a[3] * a[0]) / det;
+        double lam2 = a[0] * d0 + a[1] * d1;
+        if (!pois) lam2 = l2 < 0.0 ? lam2 + (l1 * l1) / -l2 : HUGE_VAL;
+        b0 = b0 + d0;
+        b1 = b1 + d1;
+        alpha = anew;
+        ++iters;
+        conv = lam2 <= kFitTol;
+    }
+    if (t == 0) {
+        o_b0[j] = b0 - b1 * xmean;
+        o_b1[j] = b1;
+        o_alpha[j] = alpha;
+        o_se_b0c[j] = sqrt(i11 / det);
+        o_se_b1[j] = sqrt(i00 / det);
+        o_se_alpha[j] = !pois && l2 < 0.0 ? 1.0 / sqrt(-l2) : __builtin_nan("");
+        o_iter[j] = iters;
+        o_conv[j] = conv;
+        o_pois[j] = pois;
+    }
+}
+
+// the Pearson residual of count x under mu = exp(b0 + b1 log_umi), variance mu + alpha mu^2, clipped to +- clip
+__device__ __forceinline__ double sct_residual(float x, double b0, double b1, double alpha, double lu, double clip)
+{
+    const double mu = exp(b0 + b1 * lu);
+    const double r = ((double)x - mu) / sqrt(mu + alpha * (mu * mu));
+    return fmin(fmax(r, -clip), clip);
+}
+
+// k_prep_col_partial's shape, slices and order on the residuals of the chosen genes.  MODE 0: psum[slice * gp + jj] =
+// sum_i r;  MODE 1: sum_i (r - mean_jj)^2.  par: b0, b1, alpha, gp entries each.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_sct_col_partial(const float *__restrict__ X, int n, int g,
+                                                         const int32_t *__restrict__ genes, int gp,
+                                                         const double *__restrict__ par, const double *__restrict__ lu, double clip,
+                                                         const double *__restrict__ mean, double *__restrict__ psum)
+{
+    __shared__ double s_sum[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int jj = blockIdx.x * 64 + tx;
+    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
+    double acc = 0.0;
+    if (jj < gp) {
+        const int j = genes[jj];
+        const double b0 = par[jj], b1 = par[gp + jj], al = par[2 * (size_t)gp + jj], mj = MODE ? mean[jj] : 0.0;
+        for (int r = r0 + ty; r < r1; r += 4) {
+            const double res = sct_residual(X[(size_t)r * g + j], b0, b1, al, lu[r], clip);
+            if (MODE) {
+                const double d = res - mj;
+                acc += d * d;
+            } else {
+                acc += res;
+            }
+        }
+    }
+    s_sum[ty][tx] = acc;
+    __syncthreads();
+    if (ty == 0 && jj < gp)
+        psum[(size_t)blockIdx.y * gp + jj] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
+}
+
+// the same on the transpose of a sparse handle.  The residual of a zero depends on the cell, so every row of the slice is
+// walked (as in k_prep_csc_col_partial's CENTRED mode) and each adds its own term at its place in the order.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_sct_csc_col_partial(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rows,
+                                                             const int32_t *__restrict__ pos, const float *__restrict__ vals, int n,
+                                                             const int32_t *__restrict__ genes, int gp,
+                                                             const double *__restrict__ par, const double *__restrict__ lu,
+                                                             double clip, const double *__restrict__ mean,
+                                                             double *__restrict__ psum)
+{
+    __shared__ double s_sum[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int jj = blockIdx.x * 64 + tx;
+    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
+    double acc = 0.0;
+    if (jj < gp) {
+        const int j = genes[jj];
+        const double b0 = par[jj], b1 = par[gp + jj], al = par[2 * (size_t)gp + jj], mj = MODE ? mean[jj] : 0.0;
+        int64_t lo = colptr[j], hi = colptr[j + 1];
+        while (lo < hi) {                                         // the column's first entry at or below row r0
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (rows[mid] < r0) lo = mid + 1; else hi = mid;
+        }
+        const int64_t end = colptr[j + 1];
+        int64_t k = lo;
+        for (int r = r0 + ty; r < r1; r += 4) {
+            while (k < end && rows[k] < r) ++k;
+            const float x = k < end && rows[k] == r ? vals[pos[k]] : 0.0f;
+            const double res = sct_residual(x, b0, b1, al, lu[r], clip);
+            if (MODE) {
+                const double d = res - mj;
+                acc += d * d;
+            } else {
+                acc += res;
+            }
+        }
+    }
+    s_sum[ty][tx] = acc;
+    __syncthreads();
+    if (ty == 0 && jj < gp)
+        psum[(size_t)blockIdx.y * gp + jj] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
+}
+
+// stage 1 of mi_prep_sct_select: Z = (float) the clipped residual of the chosen genes, k_prep_select's two forms
+__global__ void __launch_bounds__(256) k_sct_select(const float *__restrict__ X, int g, const int32_t *__restrict__ genes, int h,
+                                                    int ldz, const double *__restrict__ par, const double *__restrict__ lu,
+                                                    double clip, float *__restrict__ Z)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const size_t row = blockIdx.y;
+    if (c >= ldz) return;
+    float z = 0.0f;
+    if (c < h) z = (float)sct_residual(X[row * g + genes[c]], par[c], par[h + c], par[2 * (size_t)h + c], lu[row], clip);
+    Z[row * ldz + c] = z;
+}
+
+__global__ void __launch_bounds__(256) k_sct_csr_select(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                        const float *__restrict__ X, const int32_t *__restrict__ gmap, int h, int ldz,
+                                                        const double *__restrict__ par, const double *__restrict__ lu, double clip,
+                                                        float *__restrict__ Z)
+{
+    __shared__ float s_row[MI_PREP_MAX_FEATURES];
+    const size_t row = blockIdx.x;
+    const double l = lu[row];
+    for (int c = threadIdx.x; c < ldz; c += 256)
+        s_row[c] = c < h ? (float)sct_residual(0.0f, par[c], par[h + c], par[2 * (size_t)h + c], l, clip) : 0.0f;
+    __syncthreads();
+    const int64_t e1 = indptr[row + 1];
+    for (int64_t e = indptr[row] + threadIdx.x; e < e1; e += 256) {
+        const int c = gmap[indices[e]];
+        if (c >= 0) s_row[c] = (float)sct_residual(X[e], par[c], par[h + c], par[2 * (size_t)h + c], l, clip);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < ldz; c += 256) Z[row * ldz + c] = s_row[c];
+}
+
 }  // namespace
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
@@ -672,6 +968,104 @@ int finish_slices(const double *d_psum, int slices, size_t count, double denom, 
     hipLaunchKernelGGL(k_prep_col_finish, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, d_psum, nullptr, slices,
                        (int)count, denom, d_out, nullptr);
     HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+// stages 2 - 5 of mi_prep_select_regressed on the gathered Z (n x ldz, h columns): c = Q^T y and S, the residuals' mean and
+// squares, the flat rule and 1 / sd in host fp64 (unit_scale: 1 in place of 1 / sd), the scaling in place.  d_Q: device.
+int regress_stages(mi_prep_matrix *m, int h, const double *d_Q, int q, double clip, bool unit_scale, double *out_coef,
+                   double *out_mean, double *out_var, uint8_t *out_flat, float *out_ms)
+{
+    const size_t hs = (size_t)h, qs = (size_t)q;
+    const int ldz = m->ldz, slices = (m->n + kRowSlice - 1) / kRowSlice;
+    std::vector<uint8_t> flat(hs, 0);
+    std::vector<double> S(hs), ss(hs), inv(hs), var(hs);
+    DevBufs bufs;
+    uint8_t *d_flat;
+    double *d_psum, *d_coef, *d_mean, *d_ss, *d_inv;
+    HIP_TRY(bufs.alloc(&d_flat, hs));
+    HIP_TRY(bufs.alloc(&d_psum, (size_t)slices * (qs + 1) * hs));
+    HIP_TRY(bufs.alloc(&d_coef, (qs + 1) * hs));                  // q rows of coefficients, then S
+    HIP_TRY(bufs.alloc(&d_mean, hs));
+    HIP_TRY(bufs.alloc(&d_ss, hs));
+    HIP_TRY(bufs.alloc(&d_inv, hs));
+    const dim3 grid((unsigned)((h + 63) / 64), (unsigned)slices);
+    float ms1 = 0.0f, ms2 = 0.0f;
+    {
+        Timer t;
+        MI_TRY(t.start(0));
+        // 2. c = Q^T y and S = sum y^2
+        hipLaunchKernelGGL(k_prep_regress_coef, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_psum);
+        HIP_TRY(hipGetLastError());
+        MI_TRY(finish_slices(d_psum, slices, (qs + 1) * hs, 1.0, d_coef));
+        // 3. the mean of the residuals, then their squares about it
+        hipLaunchKernelGGL(k_prep_regress_moment<0>, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, nullptr,
+                           d_psum);
+        HIP_TRY(hipGetLastError());
+        MI_TRY(finish_slices(d_psum, slices, hs, (double)m->n, d_mean));
+        hipLaunchKernelGGL(k_prep_regress_moment<1>, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, d_mean,
+                           d_psum);
+        HIP_TRY(hipGetLastError());
+        MI_TRY(finish_slices(d_psum, slices, hs, 1.0, d_ss));
+        MI_TRY(t.stop(0, &ms1));
+    }
+    // 4. the flat rule and the inverse standard deviation, in host fp64
+    HIP_TRY(hipMemcpy(S.data(), d_coef + qs * hs, hs * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ss.data(), d_ss, hs * sizeof(double), hipMemcpyDeviceToHost));
+    for (int c = 0; c < h; ++c) {
+        var[c] = ss[c] / (double)(m->n - 1);
+        flat[c] = ss[c] <= 1e-16 * S[c];
+        inv[c] = flat[c] ? 0.0 : (unit_scale ? 1.0 : 1.0 / std::sqrt(var[c]));
+    }
+    HIP_TRY(hipMemcpy(d_flat, flat.data(), hs, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_inv, inv.data(), hs * sizeof(double), hipMemcpyHostToDevice));
+    {
+        Timer t;
+        MI_TRY(t.start(0));
+        // 5. scale in place
+        hipLaunchKernelGGL(k_prep_regress_scale, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, d_mean, d_inv,
+                           d_flat, clip);
+        MI_TRY(t.stop(0, &ms2));
+    }
+    if (out_ms) *out_ms = ms1 + ms2;
+    if (out_coef) HIP_TRY(hipMemcpy(out_coef, d_coef, qs * hs * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_mean) HIP_TRY(hipMemcpy(out_mean, d_mean, hs * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_var) std::copy(var.begin(), var.end(), out_var);
+    if (out_flat) std::copy(flat.begin(), flat.end(), out_flat);
+    return MI_OK;
+}
+
+// MI_EINVAL unless the `count` indices are distinct and inside [0, limit)
+int check_indices(const int32_t *idx, int count, int limit, const char *what)
+{
+    std::vector<uint8_t> seen((size_t)limit, 0);
+    for (int c = 0; c < count; ++c) {
+        const int32_t j = idx[c];
+        if (j < 0 || j >= limit) return fail(MI_EINVAL, "%s[%d] = %d is outside [0, %d)", what, c, (int)j, limit);
+        if (seen[j]) return fail(MI_EINVAL, "%s %d is chosen twice", what, (int)j);
+        seen[j] = 1;
+    }
+    return MI_OK;
+}
+
+// the three parameter rows of the residual kernels (b0, b1, alpha: count entries each), checked, as one array
+int pack_nb_parameters(const double *b0, const double *b1, const double *alpha, int count, std::vector<double> &par)
+{
+    par.resize(3 * (size_t)count);
+    for (int c = 0; c < count; ++c) {
+        if (!std::isfinite(b0[c]) || !std::isfinite(b1[c])) return fail(MI_EINVAL, "b0[%d] or b1[%d] is not finite", c, c);
+        if (!(alpha[c] >= 0.0) || std::isinf(alpha[c])) return fail(MI_EINVAL, "alpha[%d] must be finite and >= 0", c);
+        par[c] = b0[c];
+        par[(size_t)count + c] = b1[c];
+        par[2 * (size_t)count + c] = alpha[c];
+    }
+    return MI_OK;
+}
+
+int check_log_umi(const double *log_umi, int count)
+{
+    for (int i = 0; i < count; ++i)
+        if (!std::isfinite(log_umi[i])) return fail(MI_EINVAL, "log_umi[%d] is not finite (a cell without counts?)", i);
     return MI_OK;
 }
 
@@ -992,82 +1386,40 @@ int mi_prep_select_regressed(mi_prep_matrix *m, const int32_t *genes, int h, con
             for (int c = 0; c < h; ++c) gmap[genes[c]] = c;
         }
         const std::vector<float> zero(hs, 0.0f), one(hs, 1.0f);
-        std::vector<uint8_t> flat(hs, 0);
-        std::vector<double> S(hs), ss(hs), inv(hs), var(hs);
+        const std::vector<uint8_t> none(hs, 0);
         HIP_TRY(hipSetDevice(m->device));
         const int ldz = (h + kTile - 1) / kTile * kTile;
-        const int slices = (m->n + kRowSlice - 1) / kRowSlice;
         HIP_TRY(m->d_Z.resize(n * ldz));                 // (a failure leaves it empty, with h = 0)
         m->ldz = ldz;
         DevBufs bufs;
         int32_t *d_genes, *d_gmap = nullptr;
         float *d_mu, *d_one;
-        uint8_t *d_flat;
-        double *d_Q, *d_psum, *d_coef, *d_mean, *d_ss, *d_inv;
+        uint8_t *d_none;
+        double *d_Q;
         HIP_TRY(bufs.alloc(&d_genes, hs));
         HIP_TRY(bufs.alloc(&d_mu, hs));
         HIP_TRY(bufs.alloc(&d_one, hs));
-        HIP_TRY(bufs.alloc(&d_flat, hs));
+        HIP_TRY(bufs.alloc(&d_none, hs));
         HIP_TRY(bufs.alloc(&d_Q, n * qs));
-        HIP_TRY(bufs.alloc(&d_psum, (size_t)slices * (qs + 1) * hs));
-        HIP_TRY(bufs.alloc(&d_coef, (qs + 1) * hs));              // q rows of coefficients, then S
-        HIP_TRY(bufs.alloc(&d_mean, hs));
-        HIP_TRY(bufs.alloc(&d_ss, hs));
-        HIP_TRY(bufs.alloc(&d_inv, hs));
         HIP_TRY(hipMemcpy(d_genes, genes, hs * sizeof(int32_t), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_mu, zero.data(), hs * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_one, one.data(), hs * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_flat, flat.data(), hs, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_none, none.data(), hs, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_Q, Q, n * qs * sizeof(double), hipMemcpyHostToDevice));
         if (m->sparse) {
             HIP_TRY(bufs.alloc(&d_gmap, gmap.size()));
             HIP_TRY(hipMemcpy(d_gmap, gmap.data(), gmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         }
-        const dim3 grid((unsigned)((h + 63) / 64), (unsigned)slices);
         float ms1 = 0.0f, ms2 = 0.0f;
         {
             Timer t;
             MI_TRY(t.start(0));
             // 1. the gather: fminf((y - 0) * 1, inf) is y
-            MI_TRY(launch_select(m, d_genes, d_gmap, h, ldz, d_mu, d_one, d_flat, HUGE_VALF));
-            // 2. c = Q^T y and S = sum y^2
-            hipLaunchKernelGGL(k_prep_regress_coef, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_psum);
-            HIP_TRY(hipGetLastError());
-            MI_TRY(finish_slices(d_psum, slices, (qs + 1) * hs, 1.0, d_coef));
-            // 3. the mean of the residuals, then their squares about it
-            hipLaunchKernelGGL(k_prep_regress_moment<0>, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, nullptr,
-                               d_psum);
-            HIP_TRY(hipGetLastError());
-            MI_TRY(finish_slices(d_psum, slices, hs, (double)m->n, d_mean));
-            hipLaunchKernelGGL(k_prep_regress_moment<1>, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, d_mean,
-                               d_psum);
-            HIP_TRY(hipGetLastError());
-            MI_TRY(finish_slices(d_psum, slices, hs, 1.0, d_ss));
+            MI_TRY(launch_select(m, d_genes, d_gmap, h, ldz, d_mu, d_one, d_none, HUGE_VALF));
             MI_TRY(t.stop(0, &ms1));
         }
-        // 4. the flat rule and the inverse standard deviation, in host fp64
-        HIP_TRY(hipMemcpy(S.data(), d_coef + qs * hs, hs * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(ss.data(), d_ss, hs * sizeof(double), hipMemcpyDeviceToHost));
-        for (int c = 0; c < h; ++c) {
-            var[c] = ss[c] / (double)(m->n - 1);
-            flat[c] = ss[c] <= 1e-16 * S[c];
-            inv[c] = flat[c] ? 0.0 : 1.0 / std::sqrt(var[c]);
-        }
-        HIP_TRY(hipMemcpy(d_flat, flat.data(), hs, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_inv, inv.data(), hs * sizeof(double), hipMemcpyHostToDevice));
-        {
-            Timer t;
-            MI_TRY(t.start(0));
-            // 5. scale in place
-            hipLaunchKernelGGL(k_prep_regress_scale, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, d_mean, d_inv,
-                               d_flat, clip);
-            MI_TRY(t.stop(0, &ms2));
-        }
+        MI_TRY(regress_stages(m, h, d_Q, q, clip, false, out_coef, out_mean, out_var, out_flat, &ms2));
         if (out_kernel_ms) *out_kernel_ms = ms1 + ms2;
-        if (out_coef) HIP_TRY(hipMemcpy(out_coef, d_coef, qs * hs * sizeof(double), hipMemcpyDeviceToHost));
-        if (out_mean) HIP_TRY(hipMemcpy(out_mean, d_mean, hs * sizeof(double), hipMemcpyDeviceToHost));
-        if (out_var) std::copy(var.begin(), var.end(), out_var);
-        if (out_flat) std::copy(flat.begin(), flat.end(), out_flat);
         m->h = h;
         return MI_OK;
     });
@@ -1144,6 +1496,229 @@ int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float 
                            m->n, (m->h + kKC - 1) / kKC * kKC, d_V, p, d_out);
         MI_TRY(t.stop(0, out_kernel_ms));
         HIP_TRY(hipMemcpy(out, d_out, (size_t)m->n * p * sizeof(float), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
+}
+
+int mi_prep_gene_log1p_sum(mi_prep_matrix *m, double *out, float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m || !out) return fail(MI_EINVAL, "NULL argument");
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t g = (size_t)m->g, slices = (size_t)(m->n + kRowSlice - 1) / kRowSlice;
+    return guarded([&]() -> int {
+        DevBufs bufs;
+        double *d_psum, *d_out;
+        HIP_TRY(bufs.alloc(&d_psum, slices * g));
+        HIP_TRY(bufs.alloc(&d_out, g));
+        Timer t;
+        MI_TRY(t.start(0));
+        MI_TRY(col_reduce<kColLog1p>(m, m->d_X, nullptr, nullptr, 0.0, 1.0, d_psum, nullptr, d_out, nullptr));
+        MI_TRY(t.stop(0, out_kernel_ms));
+        HIP_TRY(hipMemcpy(out, d_out, g * sizeof(double), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
+}
+
+int mi_prep_nb_fit(mi_prep_matrix *m, const int32_t *cells, int mc, const int32_t *genes, int g1, const double *log_umi,
+                   double *out_b0, double *out_b1, double *out_alpha, double *out_se_b0c, double *out_se_b1,
+                   double *out_se_alpha, int32_t *out_iterations, uint8_t *out_converged, uint8_t *out_poisson,
+                   float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m || !cells || !genes || !log_umi || !out_b0 || !out_b1 || !out_alpha || !out_se_b0c || !out_se_b1 || !out_se_alpha ||
+        !out_iterations || !out_converged || !out_poisson)
+        return fail(MI_EINVAL, "NULL argument");
+    if (mc < 3) return fail(MI_EINVAL, "at least 3 fit cells are needed (got %d)", mc);
+    if (g1 < 1) return fail(MI_EINVAL, "at least 1 fit gene is needed (got %d)", g1);
+    if (mc > MI_PREP_SCT_MAX_FIT_CELLS) return fail(MI_EUNSUPPORTED, "%d fit cells exceed %d", mc, MI_PREP_SCT_MAX_FIT_CELLS);
+    if (g1 > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d fit genes exceed %d", g1, MI_PREP_MAX_FEATURES);
+    return guarded([&]() -> int {
+        MI_TRY(check_indices(cells, mc, m->n, "cells"));
+        MI_TRY(check_indices(genes, g1, m->g, "genes"));
+        MI_TRY(check_log_umi(log_umi, mc));
+        const size_t ms = (size_t)mc, gs = (size_t)g1;
+        // the centred covariate, in host fp64: the mean is the sum in the order of `cells`, divided by their number
+        double total = 0.0;
+        for (int i = 0; i < mc; ++i) total += log_umi[i];
+        const double xmean = total / (double)mc;
+        std::vector<double> xc(ms);
+        bool constant = true;
+        for (int i = 0; i < mc; ++i) {
+            xc[i] = log_umi[i] - xmean;
+            constant = constant && log_umi[i] == log_umi[0];
+        }
+        if (constant) return fail(MI_EINVAL, "log_umi is the same in every fit cell: the slope is not identified");
+        std::vector<int32_t> gmap;                                // sparse: gene -> row of the block
+        if (m->sparse) {
+            gmap.assign((size_t)m->g, -1);
+            for (int c = 0; c < g1; ++c) gmap[genes[c]] = c;
+        }
+        HIP_TRY(hipSetDevice(m->device));
+        DevBufs bufs;
+        int32_t *d_cells, *d_genes, *d_gmap = nullptr, *d_iter;
+        float *d_B;
+        double *d_xc, *d_out;
+        uint8_t *d_flags;
+        HIP_TRY(bufs.alloc(&d_cells, ms));
+        HIP_TRY(bufs.alloc(&d_genes, gs));
+        HIP_TRY(bufs.alloc(&d_B, ms * gs));
+        HIP_TRY(bufs.alloc(&d_xc, ms));
+        HIP_TRY(bufs.alloc(&d_out, 6 * gs));
+        HIP_TRY(bufs.alloc(&d_iter, gs));
+        HIP_TRY(bufs.alloc(&d_flags, 2 * gs));
+        HIP_TRY(hipMemcpy(d_cells, cells, ms * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_genes, genes, gs * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_xc, xc.data(), ms * sizeof(double), hipMemcpyHostToDevice));
+        if (m->sparse) {
+            HIP_TRY(bufs.alloc(&d_gmap, gmap.size()));
+            HIP_TRY(hipMemcpy(d_gmap, gmap.data(), gmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        Timer t;
+        MI_TRY(t.start(0));
+        if (m->sparse)
+            hipLaunchKernelGGL(k_sct_csr_gather, dim3((unsigned)mc), dim3(256), 0, 0, m->d_indptr, m->d_indices, m->d_X, d_gmap,
+                               d_cells, mc, g1, d_B);
+        else
+            hipLaunchKernelGGL(k_sct_gather, dim3((unsigned)((g1 + 255) / 256), (unsigned)mc), dim3(256), 0, 0, m->d_X, m->g,
+                               d_cells, mc, d_genes, g1, d_B);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_sct_nb_fit, dim3((unsigned)g1), dim3(256), 0, 0, d_B, mc, d_xc, xmean, d_out, d_out + gs,
+                           d_out + 2 * gs, d_out + 3 * gs, d_out + 4 * gs, d_out + 5 * gs, d_iter, d_flags, d_flags + gs);
+        MI_TRY(t.stop(0, out_kernel_ms));
+        double *outs[6] = {out_b0, out_b1, out_alpha, out_se_b0c, out_se_b1, out_se_alpha};
+        for (int k = 0; k < 6; ++k) HIP_TRY(hipMemcpy(outs[k], d_out + k * gs, gs * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_iterations, d_iter, gs * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_converged, d_flags, gs, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_poisson, d_flags + gs, gs, hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
+}
+
+int mi_prep_sct_residual_moments(mi_prep_matrix *m, const int32_t *genes, int gp, const double *b0, const double *b1,
+                                 const double *alpha, const double *log_umi, double clip, double *out_mean, double *out_var,
+                                 float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m || !genes || !b0 || !b1 || !alpha || !log_umi || !out_mean || !out_var) return fail(MI_EINVAL, "NULL argument");
+    if (gp < 1) return fail(MI_EINVAL, "at least 1 gene is needed (got %d)", gp);
+    if (gp > m->g) return fail(MI_EINVAL, "%d genes are chosen of %d", gp, m->g);
+    if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
+    return guarded([&]() -> int {
+        std::vector<double> par;
+        MI_TRY(check_indices(genes, gp, m->g, "genes"));
+        MI_TRY(pack_nb_parameters(b0, b1, alpha, gp, par));
+        MI_TRY(check_log_umi(log_umi, m->n));
+        HIP_TRY(hipSetDevice(m->device));
+        const size_t gs = (size_t)gp, n = (size_t)m->n;
+        const int slices = (m->n + kRowSlice - 1) / kRowSlice;
+        DevBufs bufs;
+        int32_t *d_genes;
+        double *d_par, *d_lu, *d_psum, *d_mean, *d_var;
+        HIP_TRY(bufs.alloc(&d_genes, gs));
+        HIP_TRY(bufs.alloc(&d_par, 3 * gs));
+        HIP_TRY(bufs.alloc(&d_lu, n));
+        HIP_TRY(bufs.alloc(&d_psum, (size_t)slices * gs));
+        HIP_TRY(bufs.alloc(&d_mean, gs));
+        HIP_TRY(bufs.alloc(&d_var, gs));
+        HIP_TRY(hipMemcpy(d_genes, genes, gs * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_par, par.data(), 3 * gs * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_lu, log_umi, n * sizeof(double), hipMemcpyHostToDevice));
+        const dim3 grid((unsigned)((gp + 63) / 64), (unsigned)slices);
+        Timer t;
+        MI_TRY(t.start(0));
+        if (m->sparse)
+            hipLaunchKernelGGL(k_sct_csc_col_partial<0>, grid, dim3(256), 0, 0, m->d_colptr, m->d_rows, m->d_pos, m->d_X, m->n,
+                               d_genes, gp, d_par, d_lu, clip, nullptr, d_psum);
+        else
+            hipLaunchKernelGGL(k_sct_col_partial<0>, grid, dim3(256), 0, 0, m->d_X, m->n, m->g, d_genes, gp, d_par, d_lu, clip,
+                               nullptr, d_psum);
+        HIP_TRY(hipGetLastError());
+        MI_TRY(finish_slices(d_psum, slices, gs, (double)m->n, d_mean));
+        if (m->sparse)
+            hipLaunchKernelGGL(k_sct_csc_col_partial<1>, grid, dim3(256), 0, 0, m->d_colptr, m->d_rows, m->d_pos, m->d_X, m->n,
+                               d_genes, gp, d_par, d_lu, clip, d_mean, d_psum);
+        else
+            hipLaunchKernelGGL(k_sct_col_partial<1>, grid, dim3(256), 0, 0, m->d_X, m->n, m->g, d_genes, gp, d_par, d_lu, clip,
+                               d_mean, d_psum);
+        HIP_TRY(hipGetLastError());
+        MI_TRY(finish_slices(d_psum, slices, gs, (double)(m->n - 1), d_var));
+        MI_TRY(t.stop(0, out_kernel_ms));
+        HIP_TRY(hipMemcpy(out_mean, d_mean, gs * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_var, d_var, gs * sizeof(double), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
+}
+
+int mi_prep_sct_select(mi_prep_matrix *m, const int32_t *genes, int h, const double *b0, const double *b1, const double *alpha,
+                       const double *log_umi, double clip, const double *Q, int q, double *out_coef, double *out_mean,
+                       double *out_var, uint8_t *out_flat, float *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (!m) return fail(MI_EINVAL, "NULL argument");
+    m->h = 0;                                                     // (whatever fails below, nothing is selected)
+    const bool raw = !Q && q == 0;                                // stage 1 alone: the residuals as they are
+    if (!genes || !b0 || !b1 || !alpha || !log_umi || (!Q && !raw)) return fail(MI_EINVAL, "NULL argument");
+    if (h < 1) return fail(MI_EINVAL, "h must be >= 1 (got %d)", h);
+    if (q < 1 && !raw) return fail(MI_EINVAL, "q must be >= 1, or 0 without Q (got %d)", q);
+    if (h > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d features exceed %d", h, MI_PREP_MAX_FEATURES);
+    if (q > MI_PREP_MAX_DESIGN_COLS) return fail(MI_EUNSUPPORTED, "%d design columns exceed %d", q, MI_PREP_MAX_DESIGN_COLS);
+    if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
+    return guarded([&]() -> int {
+        const size_t n = (size_t)m->n, hs = (size_t)h, qs = (size_t)q;
+        std::vector<double> par;
+        MI_TRY(check_indices(genes, h, m->g, "genes"));
+        MI_TRY(pack_nb_parameters(b0, b1, alpha, h, par));
+        MI_TRY(check_log_umi(log_umi, m->n));
+        for (size_t e = 0; e < n * qs; ++e)
+            if (!std::isfinite(Q[e])) return fail(MI_EINVAL, "Q[%lld, %lld] is not finite", (long long)(e / qs), (long long)(e % qs));
+        std::vector<int32_t> gmap;                                // sparse: gene -> column of Z
+        if (m->sparse) {
+            gmap.assign((size_t)m->g, -1);
+            for (int c = 0; c < h; ++c) gmap[genes[c]] = c;
+        }
+        HIP_TRY(hipSetDevice(m->device));
+        const int ldz = (h + kTile - 1) / kTile * kTile;
+        HIP_TRY(m->d_Z.resize(n * ldz));                 // (a failure leaves it empty, with h = 0)
+        m->ldz = ldz;
+        DevBufs bufs;
+        int32_t *d_genes, *d_gmap = nullptr;
+        double *d_par, *d_lu, *d_Q;
+        HIP_TRY(bufs.alloc(&d_genes, hs));
+        HIP_TRY(bufs.alloc(&d_par, 3 * hs));
+        HIP_TRY(bufs.alloc(&d_lu, n));
+        HIP_TRY(bufs.alloc(&d_Q, n * qs));
+        HIP_TRY(hipMemcpy(d_genes, genes, hs * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_par, par.data(), 3 * hs * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_lu, log_umi, n * sizeof(double), hipMemcpyHostToDevice));
+        if (!raw) HIP_TRY(hipMemcpy(d_Q, Q, n * qs * sizeof(double), hipMemcpyHostToDevice));
+        if (m->sparse) {
+            HIP_TRY(bufs.alloc(&d_gmap, gmap.size()));
+            HIP_TRY(hipMemcpy(d_gmap, gmap.data(), gmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        float ms1 = 0.0f, ms2 = 0.0f;
+        {
+            Timer t;
+            MI_TRY(t.start(0));
+            // 1. Z = (float) the clipped residual
+            if (m->sparse) {
+                hipLaunchKernelGGL(k_sct_csr_select, dim3((unsigned)m->n), dim3(256), 0, 0, m->d_indptr, m->d_indices, m->d_X,
+                                   d_gmap, h, ldz, d_par, d_lu, clip, m->d_Z);
+                HIP_TRY(hipGetLastError());
+            }
+            for (int r0 = 0; r0 < m->n && !m->sparse; r0 += 32768) {  // (one cell per grid.y: slabs, as launch_select)
+                const int rows = m->n - r0 < 32768 ? m->n - r0 : 32768;
+                hipLaunchKernelGGL(k_sct_select, dim3((unsigned)(ldz / 256 + (ldz % 256 != 0)), (unsigned)rows), dim3(256), 0, 0,
+                                   m->d_X + (size_t)r0 * m->g, m->g, d_genes, h, ldz, d_par, d_lu + r0, clip,
+                                   m->d_Z + (size_t)r0 * ldz);
+                HIP_TRY(hipGetLastError());
+            }
+            MI_TRY(t.stop(0, &ms1));
+        }
+        // 2 - 5. centring (and regression) by the projection off Q, unit scale, no further clip
+        if (!raw) MI_TRY(regress_stages(m, h, d_Q, q, HUGE_VAL, true, out_coef, out_mean, out_var, out_flat, &ms2));
+        if (out_kernel_ms) *out_kernel_ms = ms1 + ms2;
+        m->h = h;
         return MI_OK;
     });
 }

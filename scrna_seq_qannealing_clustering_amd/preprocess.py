@@ -17,9 +17,16 @@ Cell QC and ``vars.to.regress`` (the three lines every notebook starts with: ``P
 per-cell columns and the mask, and ``vars_to_regress`` of :func:`scale_data`, :func:`pca` and :func:`embed` scales the
 residuals of the linear model ``y ~ 1 + covariates`` per gene (device; the QR of the design is host fp64).
 
-Out of scope: ``SCTransform`` and Poisson or negative-binomial regression models, more than ``MAX_FEATURES`` = 4096
-features or ``MAX_COVARIATES`` = 8 covariates, sparse input to :func:`metrics.find_all_markers` and to the ``--counts``
-option of ``run``.
+``SCTransform`` (the normalisation every data-preparation notebook but one uses: ``SCTransform(obj, method = "glmGamPoi",
+vars.to.regress = "percent.mt")`` then ``RunPCA``; `Pbmc3k_prepare_data_for_QA_clustering.Rmd:51-52`,
+`Kidney_data.Rmd:47-48`): :func:`sctransform` -- a per-gene negative-binomial regression on sequencing depth (device),
+its regularisation over the genes (host fp64), Pearson residuals and their variance as the variable-gene criterion (device),
+into the same Gram / eigen / project path.  The chain is this package's specification, modelled on ``sctransform::vst``;
+agreement with R is UNPINNED.
+
+Out of scope: SCTransform's corrected counts and ``data`` slot, ``vst.flavor = "v2"``, ``batch_var``, latent variables other
+than ``log_umi``, glmGamPoi's Cox-Reid adjustment; more than ``MAX_FEATURES`` = 4096 features or ``MAX_COVARIATES`` = 8
+covariates, sparse input to :func:`metrics.find_all_markers` and to the ``--counts`` option of ``run``.
 
     qc = preprocess.cell_qc(counts, gene_names)
     keep = preprocess.qc_filter(qc)
@@ -258,6 +265,110 @@ class ExpressionMatrix:
         self.h = h
         self.coef_q, self.resid_mean, self.resid_var, self.flat = coef, mean, var, flat.astype(bool)
         self.timing["regress_ms"] = float(ms.value)
+        return self
+
+    def gene_log1p_sum(self) -> np.ndarray:
+        """``sum_i log1p(x_ij)`` per gene of the counts, fp64 (``expm1`` of it over n is sctransform's geometric mean)."""
+        out = np.empty(self.g)
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_gene_log1p_sum(self._handle(), _p(out, _f64p), C.byref(ms)))
+        self.timing["gene_log1p_ms"] = float(ms.value)
+        return out
+
+    @staticmethod
+    def _index_array(idx, what):
+        idx = np.asarray(idx)
+        if idx.ndim != 1 or idx.dtype.kind not in "iu":
+            raise ValueError("%s must be a 1-d integer array" % what)
+        if len(idx) and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
+            raise ValueError("%s: index out of range" % what)
+        return np.ascontiguousarray(idx, dtype=np.int32)
+
+    def nb_fit(self, cells, genes, log_umi) -> "Result":
+        """The negative-binomial regression of SCTransform's step 1 on the device (``mi_prep_nb_fit``; the algorithm is in
+        include/mi_prep.h): per gene of ``genes``, over ``cells``, ``y ~ NB(mu, alpha)`` with ``log mu = b0 + b1 log_umi``.
+        ``log_umi``: one entry per entry of ``cells``.  Returns ``b0``, ``b1``, ``alpha``, ``se_b0c``, ``se_b1``,
+        ``se_alpha``, ``iterations``, ``converged``, ``poisson`` (one entry per gene) and ``log_umi_mean``."""
+        cells, genes = self._index_array(cells, "cells"), self._index_array(genes, "genes")
+        log_umi = np.ascontiguousarray(log_umi, dtype=np.float64)
+        if log_umi.shape != cells.shape:
+            raise ValueError("log_umi must have one entry per fit cell (%d)" % len(cells))
+        if not np.isfinite(log_umi).all():
+            raise ValueError("log_umi must be finite: a cell without counts cannot be fitted (run qc_filter first)")
+        k = max(len(genes), 1)
+        f = [np.empty(k) for _ in range(6)]
+        it, conv, pois = np.empty(k, dtype=np.int32), np.empty(k, dtype=np.uint8), np.empty(k, dtype=np.uint8)
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_nb_fit(self._handle(), _p(cells, _i32p), len(cells), _p(genes, _i32p), len(genes),
+                                            _p(log_umi, _f64p), *[_p(a, _f64p) for a in f], _p(it, _i32p), _p(conv, _u8p),
+                                            _p(pois, _u8p), C.byref(ms)))
+        self.timing["nb_fit_ms"] = float(ms.value)
+        total = 0.0
+        for v in log_umi.tolist():                               # (the entry's mean: the sum in this order)
+            total += v
+        return Result(b0=f[0], b1=f[1], alpha=f[2], se_b0c=f[3], se_b1=f[4], se_alpha=f[5], iterations=it,
+                      converged=conv.astype(bool), poisson=pois.astype(bool), log_umi_mean=total / len(log_umi))
+
+    def _nb_parameters(self, genes, b0, b1, alpha, log_umi):
+        genes = self._index_array(genes, "genes")
+        par = [np.ascontiguousarray(a, dtype=np.float64) for a in (b0, b1, alpha)]
+        if any(a.shape != genes.shape for a in par):
+            raise ValueError("b0, b1 and alpha must have one entry per chosen gene")
+        log_umi = np.ascontiguousarray(log_umi, dtype=np.float64)
+        if log_umi.shape != (self.n,):
+            raise ValueError("log_umi must have one entry per cell (%d)" % self.n)
+        if not np.isfinite(log_umi).all():
+            raise ValueError("log_umi must be finite: a cell without counts has no residual (run qc_filter first)")
+        return genes, par, log_umi
+
+    def sct_residual_moments(self, genes, b0, b1, alpha, log_umi, clip: Optional[float] = None):
+        """``(mean, variance)`` (ddof 1) per chosen gene of the Pearson residual ``(x - mu) / sqrt(mu + alpha mu^2)``,
+        ``mu = exp(b0 + b1 log_umi)``, clipped to ``+-clip`` (default ``sqrt(n)``), over all cells."""
+        genes, par, log_umi = self._nb_parameters(genes, b0, b1, alpha, log_umi)
+        clip = math.sqrt(self.n) if clip is None else float(clip)
+        k = max(len(genes), 1)
+        mean, var = np.empty(k), np.empty(k)
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_sct_residual_moments(self._handle(), _p(genes, _i32p), len(genes), _p(par[0], _f64p),
+                                                          _p(par[1], _f64p), _p(par[2], _f64p), _p(log_umi, _f64p), clip,
+                                                          _p(mean, _f64p), _p(var, _f64p), C.byref(ms)))
+        self.timing["sct_moments_ms"] = float(ms.value)
+        return mean, var
+
+    def select_pearson(self, genes, b0, b1, alpha, log_umi, Q=None, clip: Optional[float] = None, center: bool = True):
+        """SCTransform's ``scale.data`` as ``Z``: the Pearson residuals of the chosen genes clipped to ``+-clip`` (default
+        ``sqrt(n / 30)``) and rounded to float32, then projected off ``Q`` (n, q) -- the basis of ``[1]`` when ``None``
+        (centring), of ``[1, covariates]`` (:func:`design_basis`) for ``vars.to.regress`` -- at unit scale.  Stores
+        ``coef_q``, ``resid_mean``, ``resid_var`` and ``flat`` like :meth:`select_regressed`; :meth:`fetch_scaled`,
+        :meth:`gram` and :meth:`project` follow.  ``center=False`` (without ``Q``) keeps the clipped residuals as they are."""
+        genes, par, log_umi = self._nb_parameters(genes, b0, b1, alpha, log_umi)
+        clip = math.sqrt(self.n / 30.0) if clip is None else float(clip)
+        if not center:
+            if Q is not None:
+                raise ValueError("center=False takes no Q")
+            ms = C.c_float(0.0)
+            self.h = 0
+            _lib.check(self._lib.mi_prep_sct_select(self._handle(), _p(genes, _i32p), len(genes), _p(par[0], _f64p),
+                                                    _p(par[1], _f64p), _p(par[2], _f64p), _p(log_umi, _f64p), clip, None, 0,
+                                                    None, None, None, None, C.byref(ms)))
+            self.h = len(genes)
+            self.coef_q = self.resid_mean = self.resid_var = self.flat = None
+            self.timing["sct_select_ms"] = float(ms.value)
+            return self
+        Q = np.full((self.n, 1), 1.0 / math.sqrt(self.n)) if Q is None else np.ascontiguousarray(Q, dtype=np.float64)
+        if Q.ndim != 2 or Q.shape[0] != self.n:
+            raise ValueError("Q must be (n, q) with n = %d (got shape %s)" % (self.n, Q.shape))
+        h, q = len(genes), Q.shape[1]
+        coef, mean, var = np.empty((max(q, 1), max(h, 1))), np.empty(max(h, 1)), np.empty(max(h, 1))
+        flat = np.empty(max(h, 1), dtype=np.uint8)
+        ms = C.c_float(0.0)
+        self.h = 0
+        _lib.check(self._lib.mi_prep_sct_select(self._handle(), _p(genes, _i32p), h, _p(par[0], _f64p), _p(par[1], _f64p),
+                                                _p(par[2], _f64p), _p(log_umi, _f64p), clip, _p(Q, _f64p), q,
+                                                _p(coef, _f64p), _p(mean, _f64p), _p(var, _f64p), _p(flat, _u8p), C.byref(ms)))
+        self.h = h
+        self.coef_q, self.resid_mean, self.resid_var, self.flat = coef, mean, var, flat.astype(bool)
+        self.timing["sct_select_ms"] = float(ms.value)
         return self
 
     def fetch_scaled(self) -> np.ndarray:
@@ -554,13 +665,278 @@ def embed(X, nfeatures: int = 2000, npcs: int = 50, scale_factor: float = 1e4, m
     plus ``genes`` and ``features`` (the table of :func:`find_variable_features`).  ``coords[:, :dim]`` is what
     :func:`snn.build_snn` takes.  ``X`` is dense or ``scipy.sparse`` (the same genes and coordinates either way).
     ``vars_to_regress``: one row per cell of ``X``, regressed out of the chosen genes before scaling (see
-    :func:`scale_data`).  ``SCTransform`` is not supported."""
+    :func:`scale_data`).  For ``SCTransform`` see :func:`sctransform`."""
     with ExpressionMatrix(X, device=device) as m:
         m.normalize(scale_factor)
         feats = find_variable_features(m, nfeatures=nfeatures, span=span)
         r = pca(m, feats.genes, npcs=npcs, max_value=max_value, vars_to_regress=vars_to_regress)
     r["genes"] = feats.genes
     r["features"] = feats
+    return r
+
+
+# ---- SCTransform -----------------------------------------------------------------------------------------------------------
+# A specification of this package, modelled on sctransform::vst as Seurat's SCTransform calls it; R is not available to
+# compare against and its sub-sampling draws from R's generator, so agreement with R is UNPINNED (DESIGN.md section 5c).
+
+SCT_MAX_FIT_CELLS = 8192   # MI_PREP_SCT_MAX_FIT_CELLS
+_EPS = 2.0 ** -52
+
+
+def sct_cell_subsample(n: int, ncells: int = 5000, seed: int = 0) -> np.ndarray:
+    """The cells of step 1: all when ``n <= ncells``, else ``ncells`` drawn without replacement
+    (``default_rng(seed).choice``), sorted."""
+    n, ncells = int(n), int(ncells)
+    if ncells < 3:
+        raise ValueError("ncells must be at least 3")
+    if n <= ncells:
+        return np.arange(n, dtype=np.int32)
+    return np.sort(np.random.default_rng(seed).choice(n, ncells, replace=False)).astype(np.int32)
+
+
+def _bw_nrd(x) -> float:
+    q75, q25 = np.percentile(x, [75, 25])
+    return 1.06 * min(np.std(x, ddof=1), (q75 - q25) / 1.34) * len(x) ** -0.2
+
+
+def _gauss_density(x, bw, block=2048) -> np.ndarray:
+    """the Gaussian kernel density estimate of the sample ``x`` at its own points, evaluated directly"""
+    out = np.empty(len(x))
+    for s in range(0, len(x), block):
+        u = (x[s:s + block, None] - x[None, :]) / bw
+        out[s:s + block] = np.exp(-0.5 * u * u).sum(axis=1)
+    return out / (len(x) * bw * math.sqrt(2.0 * math.pi))
+
+
+def sct_gene_subsample(log_gmean, n_genes: int = 2000, seed: int = 0) -> np.ndarray:
+    """The genes of step 1, as positions in ``log_gmean``: all when at most ``n_genes``, else ``n_genes`` drawn without
+    replacement with probability proportional to ``1 / (density(log_gmean) + 2^-52)`` (a Gaussian kernel estimate with the
+    bandwidth ``1.06 min(sd, IQR / 1.34) G^(-1/5)``; ``default_rng([1, seed])``), sorted: sctransform's way of covering
+    the range of expression evenly."""
+    x = np.asarray(log_gmean, dtype=np.float64)
+    n_genes = int(n_genes)
+    if x.ndim != 1 or not np.isfinite(x).all():
+        raise ValueError("log_gmean must be a finite 1-d array")
+    if n_genes < 1:
+        raise ValueError("n_genes must be at least 1")
+    if len(x) <= n_genes:
+        return np.arange(len(x), dtype=np.int64)
+    bw = _bw_nrd(x)
+    w = 1.0 / (_gauss_density(x, bw if bw > 0 else 1.0) + _EPS)
+    return np.sort(np.random.default_rng([1, int(seed)]).choice(len(x), n_genes, replace=False, p=w / w.sum()))
+
+
+def _sj_functionals(x):
+    """-> (n, scale, SD(h), TD(h)) of Sheather and Jones: the estimates of the integrated squared second and third
+    derivative of the density from all pairs (diagonal included), unbinned"""
+    n = len(x)
+    iu = np.triu_indices(n, 1)
+    d2 = (x[iu[0]] - x[iu[1]]) ** 2
+    q75, q25 = np.percentile(x, [75, 25])
+    scale = min(np.std(x, ddof=1), (q75 - q25) / 1.349)
+    root2pi = math.sqrt(2.0 * math.pi)
+
+    def SD(h):
+        t = d2 / (h * h)
+        s = (np.exp(-0.5 * t) * (t * t - 6.0 * t + 3.0)).sum()
+        return (2.0 * s + 3.0 * n) / (n * (n - 1.0) * h ** 5 * root2pi)
+
+    def TD(h):
+        t = d2 / (h * h)
+        s = (np.exp(-0.5 * t) * (t * t * t - 15.0 * t * t + 45.0 * t - 15.0)).sum()
+        return -(2.0 * s - 15.0 * n) / (n * (n - 1.0) * h ** 7 * root2pi)
+
+    return n, scale, SD, TD
+
+
+def bw_sj(x, rtol: float = 1e-10) -> float:
+    """The Sheather-Jones "solve-the-equation" bandwidth of a Gaussian kernel density estimate (R's ``bw.SJ``), by direct
+    evaluation over all pairs and bisection: the root ``h`` of ``(1 / (2 sqrt(pi) n SD(alpha2 h^(5/7))))^(1/5) = h`` with
+    ``alpha2 = 1.357 (SD(a) / TD(b))^(1/7)``, ``a = 1.24 s n^(-1/7)``, ``b = 1.23 s n^(-1/9)``, ``s = min(sd, IQR / 1.349)``.
+    The bracket starts at R's ``[0.1, 1] * 1.144 s n^(-1/5)`` and widens by 1.2 until the sign changes."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 1 or len(x) < 3 or not np.isfinite(x).all():
+        raise ValueError("x must be a finite 1-d array of at least 3 values")
+    n, scale, SD, TD = _sj_functionals(x)
+    if not scale > 0:
+        raise ValueError("x has no spread: the bandwidth is undefined")
+    c1 = 1.0 / (2.0 * math.sqrt(math.pi) * n)
+    alph2 = 1.357 * (SD(1.24 * scale * n ** (-1.0 / 7.0)) / TD(1.23 * scale * n ** (-1.0 / 9.0))) ** (1.0 / 7.0)
+    if not np.isfinite(alph2):
+        raise ValueError("the sample is too sparse for the Sheather-Jones bandwidth")
+
+    def f(h):
+        return (c1 / SD(alph2 * h ** (5.0 / 7.0))) ** 0.2 - h
+
+    hi = 1.144 * scale * n ** -0.2
+    lo = 0.1 * hi
+    flo, fhi = f(lo), f(hi)
+    for _ in range(100):
+        if flo * fhi <= 0:
+            break
+        lo, hi = lo / 1.2, hi * 1.2
+        flo, fhi = f(lo), f(hi)
+    else:
+        raise ValueError("no solution of the Sheather-Jones equation was bracketed")
+    while hi - lo > rtol * hi:
+        mid = 0.5 * (lo + hi)
+        fm = f(mid)
+        if flo * fm <= 0:
+            hi = mid
+        else:
+            lo, flo = mid, fm
+    return 0.5 * (lo + hi)
+
+
+def kernel_smooth(x, y, x_out, bandwidth: float, block: int = 2048) -> np.ndarray:
+    """Nadaraya-Watson with a normal kernel in R's ``ksmooth`` scaling: the kernel's sd is ``0.3706506 * bandwidth`` (its
+    quartiles at ``+-bandwidth / 4``), truncated at 4 sd.  ``y``: (m,) or (m, k).  NaN where no point lies in reach."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    xo = np.asarray(x_out, dtype=np.float64)
+    sd = 0.3706506 * float(bandwidth)
+    if not sd > 0:
+        raise ValueError("bandwidth must be > 0")
+    y2 = y if y.ndim == 2 else y[:, None]
+    out = np.empty((len(xo), y2.shape[1]))
+    for s in range(0, len(xo), block):
+        d = xo[s:s + block, None] - x[None, :]
+        w = np.where(np.abs(d) <= 4.0 * sd, np.exp(-0.5 * (d / sd) ** 2), 0.0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[s:s + block] = (w @ y2) / w.sum(axis=1)[:, None]
+    return out if y.ndim == 2 else out[:, 0]
+
+
+def _binned_robust_score(v, x, lo, width):
+    b = np.floor((x - lo) / width).astype(np.int64)
+    score = np.zeros(len(v))
+    for k in np.unique(b):
+        sel = b == k
+        med = np.median(v[sel])
+        mad = 1.4826 * np.median(np.abs(v[sel] - med))
+        score[sel] = (v[sel] - med) / (mad + _EPS)
+    return score
+
+
+def sct_outliers(values, x, threshold: float = 10.0) -> np.ndarray:
+    """sctransform's ``is_outlier``: the robust z-score ``(v - median) / (1.4826 MAD + 2^-52)`` within bins of ``x`` of
+    width ``(max - min) bw_sj(x) / 2``, on two grids offset by half a bin; an outlier exceeds ``threshold`` in absolute
+    value on both."""
+    v, x = np.asarray(values, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    width = (x.max() - x.min()) * bw_sj(x) / 2.0
+    s1 = _binned_robust_score(v, x, x.min(), width)
+    s2 = _binned_robust_score(v, x, x.min() - 0.5 * width, width)
+    return np.minimum(np.abs(s1), np.abs(s2)) > threshold
+
+
+def sct_regularize(log_gmean_fit, b0, b1, alpha, log_gmean_all, bw_adjust: float = 3.0, threshold: float = 10.0) -> Result:
+    """sctransform's ``reg_model_pars``, host fp64.  The fitted ``alpha`` becomes the overdispersion factor
+    ``od = log10(1 + 10^log_gmean alpha)`` (0 for a Poisson gene); genes that are outliers (:func:`sct_outliers`, or a
+    non-finite parameter) in ``b0``, ``b1`` or ``od`` are dropped; the three are smoothed over ``log_gmean`` by
+    :func:`kernel_smooth` with ``bandwidth = bw_adjust * bw_sj(log_gmean of the kept genes)`` and evaluated at every gene of
+    ``log_gmean_all``, clamped to the range of the kept genes; ``alpha = (10^od - 1) / 10^log_gmean``.  Returns ``b0``,
+    ``b1``, ``alpha``, ``od`` (per gene of ``log_gmean_all``), ``outlier`` (per fitted gene) and ``bandwidth``."""
+    x = np.asarray(log_gmean_fit, dtype=np.float64)
+    par = np.column_stack([np.asarray(a, dtype=np.float64) for a in (b0, b1, alpha)])
+    xa = np.asarray(log_gmean_all, dtype=np.float64)
+    if x.ndim != 1 or par.shape != (len(x), 3) or len(x) < 3:
+        raise ValueError("log_gmean_fit, b0, b1 and alpha must be 1-d arrays of one length >= 3")
+    if not (np.isfinite(x).all() and np.isfinite(xa).all()):
+        raise ValueError("log_gmean must be finite")
+    bad = ~np.isfinite(par).all(axis=1) | (par[:, 2] < 0)
+    par = np.where(bad[:, None], 0.0, par)
+    par[:, 2] = np.log10(1.0 + 10.0 ** x * par[:, 2])
+    outlier = bad.copy()
+    ok = ~bad
+    for k in range(3):
+        outlier[ok] |= sct_outliers(par[ok, k], x[ok], threshold)
+    keep = ~outlier
+    if keep.sum() < 3:
+        raise ValueError("fewer than 3 fitted genes are left to regularise")
+    bw = float(bw_adjust) * bw_sj(x[keep])
+    xs = np.clip(xa, x[keep].min(), x[keep].max())
+    sm = kernel_smooth(x[keep], par[keep], xs, bw)
+    return Result(b0=sm[:, 0], b1=sm[:, 1], od=sm[:, 2], alpha=np.maximum(10.0 ** sm[:, 2] - 1.0, 0.0) / 10.0 ** xa,
+                  outlier=outlier, bandwidth=bw)
+
+
+def _detected_in(X, cells) -> np.ndarray:
+    """cells with a non-zero count per gene among ``cells`` (host)"""
+    if is_sparse(X):
+        return np.asarray((X.tocsr()[cells] != 0).sum(axis=0)).ravel()
+    return (np.asarray(X)[cells] != 0).sum(axis=0)
+
+
+def sctransform(X, variable_features_n: int = 3000, npcs: int = 50, vars_to_regress=None, ncells: int = 5000,
+                n_genes: int = 2000, min_cells: int = 5, seed: int = 0, clip: Optional[float] = None, device: int = 0,
+                cells=None, genes=None) -> Result:
+    """Seurat's ``SCTransform(vars.to.regress = ...)`` + ``RunPCA(features = VariableFeatures)`` on one upload, as this
+    package specifies it (unpinned against R): per-cell ``log_umi = log10(total)`` and per-gene ``detected`` and
+    ``log_gmean`` (device); the step-1 sub-samples (:func:`sct_cell_subsample`, :func:`sct_gene_subsample`; ``cells=`` and
+    ``genes=`` override them); the per-gene negative-binomial regression on ``log_umi`` (device,
+    :meth:`ExpressionMatrix.nb_fit`); :func:`sct_regularize` (host); the variance of the Pearson residuals of every gene
+    detected in ``min_cells`` cells, clipped at ``sqrt(n)`` (device), whose top ``variable_features_n`` are the variable
+    features; their residuals clipped at ``clip`` (default ``sqrt(n / 30)``), centred and, with ``vars_to_regress``,
+    regressed (device, :meth:`ExpressionMatrix.select_pearson`); Gram matrix, eigen-solve, projection as :func:`pca`.
+
+    Returns the fields of :func:`pca` plus ``genes`` (rank order), ``gene_attr`` (per gene of ``X``: ``detected``,
+    ``log_gmean``, ``passing``, the regularised ``b0``, ``b1``, ``alpha`` and ``residual_mean`` / ``residual_variance``,
+    NaN where not passing), ``model`` (the step-1 table: ``genes``, ``cells``, the fields of ``nb_fit``, ``outlier``),
+    ``log_umi`` and ``timing``.  ``ValueError`` for a cell without counts: run :func:`qc_filter` first.  Not built:
+    corrected counts and the ``data`` slot, ``vst.flavor = "v2"``, ``batch_var``, latent variables other than ``log_umi``,
+    glmGamPoi's Cox-Reid adjustment, more than ``MAX_FEATURES`` features."""
+    with ExpressionMatrix(X, device=device) as m:
+        n = m.n
+        n_count, _, _ = m.cell_qc()
+        if (n_count <= 0).any():
+            raise ValueError("cell %d has no counts: SCTransform needs log10 of every cell's total (run qc_filter first)"
+                             % int(np.flatnonzero(n_count <= 0)[0]))
+        log_umi = np.log10(n_count)
+        _, _, detected = m.gene_stats("counts")
+        log_gmean = np.full(m.g, -np.inf)
+        with np.errstate(divide="ignore"):
+            log_gmean = np.log10(np.expm1(m.gene_log1p_sum() / n))
+        passing = np.flatnonzero(detected >= int(min_cells)).astype(np.int32)
+        if len(passing) < 3:
+            raise ValueError("fewer than 3 genes are detected in %d cells" % int(min_cells))
+        t0 = time.perf_counter()
+        cells = sct_cell_subsample(n, min(int(ncells), SCT_MAX_FIT_CELLS), seed) if cells is None else np.asarray(cells)
+        if genes is None:
+            cand = passing if len(cells) == n else passing[_detected_in(X, cells)[passing] >= int(min_cells)]
+            genes = cand[sct_gene_subsample(log_gmean[cand], min(int(n_genes), MAX_FEATURES), seed)]
+        genes = np.asarray(genes)
+        m.timing["sct_subsample_s"] = time.perf_counter() - t0
+        fit = m.nb_fit(cells, genes, log_umi[cells])
+        t0 = time.perf_counter()
+        reg = sct_regularize(log_gmean[genes], fit.b0, fit.b1, fit.alpha, log_gmean[passing])
+        m.timing["sct_regularize_s"] = time.perf_counter() - t0
+        rmean, rvar = m.sct_residual_moments(passing, reg.b0, reg.b1, reg.alpha, log_umi)
+        top = top_features(rvar, min(int(variable_features_n), len(passing), MAX_FEATURES))
+        feats = passing[top]
+        npcs = int(npcs)
+        if npcs < 1 or npcs > min(MAX_PCS, len(feats)):
+            raise ValueError("npcs must lie in [1, min(%d, number of features)] (got %d)" % (MAX_PCS, npcs))
+        Q = R = None
+        if vars_to_regress is not None:
+            Q, R = design_basis(vars_to_regress, n=n)
+        m.select_pearson(feats, reg.b0[top], reg.b1[top], reg.alpha[top], log_umi, Q=Q, clip=clip)
+        G = m.gram()
+        t0 = time.perf_counter()
+        r = pca_from_gram(G, n, npcs)
+        m.timing["eigh_s"] = time.perf_counter() - t0
+        r["coords"] = m.project(r.loadings.astype(np.float32))
+        if R is not None:
+            r["regression"] = Result(betas=regression_betas(R, m.coef_q), resid_mean=m.resid_mean, resid_var=m.resid_var,
+                                     flat=m.flat)
+        r["timing"] = dict(m.timing)
+    attr = Result(detected=detected, log_gmean=log_gmean, passing=np.isin(np.arange(len(detected)), passing))
+    for name, values in (("b0", reg.b0), ("b1", reg.b1), ("alpha", reg.alpha), ("residual_mean", rmean),
+                         ("residual_variance", rvar)):
+        attr[name] = np.full(len(detected), np.nan)
+        attr[name][passing] = values
+    r["genes"] = feats
+    r["gene_attr"] = attr
+    r["model"] = Result(fit, genes=genes, cells=np.asarray(cells), outlier=reg.outlier, bandwidth=reg.bandwidth)
+    r["log_umi"] = log_umi
     return r
 
 
