@@ -23,12 +23,15 @@
 // the label is c; every byte of x is < 0x80 (labels and c < 64, padding 0x7F), so x + 0x7F7F7F7F carries out of no
 // byte and its bit 7 is clear exactly at the zero bytes.  All of it is vector work of the wavefront that issues the
 // MFMAs (vector instructions do not issue beside MFMA-streaming waves of the same SIMD, so no
-// SIMD mate does it): one wavefront per SIMD, a persistent loop over tiles, loads two chunks ahead.
+// SIMD mate does it): one wavefront per SIMD, a persistent loop over tiles, loads two chunks ahead.  In WITHIN mode the
+// tiles on or above the diagonal are numbered row by row; mi_tri_tiles.h turns a tile's number into (bi, bj), the same
+// text as in coassoc_kernels.hip and in the host program that checks it (tests/host/tri_tiles_main.cpp).
 #include <cmath>
 #include <vector>
 
 #include "../../include/mi_metrics.h"
 #include "mi_sa_device.h"
+#include "mi_tri_tiles.h"
 
 namespace mi_sa_impl {
 namespace {
@@ -142,15 +145,7 @@ __global__ void __launch_bounds__(256) k_agree_mfma(AgreeDev g)
         if (g.within) {
             const int grpi = (int)(w / g.tpg);
             const long long q = w - (long long)grpi * g.tpg;
-            const int nb = g.nbj;
-            // tile row bi holds the nb - bi tiles bj = bi .. nb - 1; it starts at f(bi) = bi nb - bi (bi - 1) / 2
-            const double b2 = 2.0 * nb + 1.0;
-            bi = (int)floor((b2 - sqrt(b2 * b2 - 8.0 * (double)q)) * 0.5);
-            bi = bi < 0 ? 0 : (bi > nb - 1 ? nb - 1 : bi);
-            auto f = [&](int x) { return (long long)x * nb - (long long)x * (x - 1) / 2; };
-            while (bi > 0 && f(bi) > q) --bi;
-            while (bi + 1 < nb && f(bi + 1) <= q) ++bi;
-            bj = bi + (int)(q - f(bi));
+            mi_tri::tile_of(q, g.nbj, &bi, &bj);               // tiles on or above the diagonal, row by row (mi_tri_tiles.h)
             base = grpi * g.Rg;
             rowsA = rowsB = g.Rg;
         } else {

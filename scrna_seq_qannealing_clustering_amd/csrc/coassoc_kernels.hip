@@ -9,7 +9,8 @@
 //   k_coassoc_prep   uint16 labels -> one byte per (read, cell), rows of npad bytes (npad a multiple of 128), hole seats,
 //                    cells past n and reads past Rg: 0xFF, a byte that matches no label
 //   k_coassoc_mfma   M2.  One workgroup of 4 wavefronts per tile of 128 x 128 cells on or above the diagonal of the block
-//                    grid (a persistent loop over the tiles of its group); wavefront (wi, wj) owns 64 x 64 cells = 4 x 4
+//                    grid (a persistent loop over the tiles of its group, numbered row by row: mi_tri_tiles.h turns the
+//                    number into the tile, the text agreement_kernels.hip uses and a host program checks); wavefront (wi, wj) owns 64 x 64 cells = 4 x 4
 //                    accumulators of 16 x 16.  The two operand panels (128 cells x 128 reads, bytes, cells contiguous per
 //                    read) are staged in LDS once per workgroup and read chunk; every wavefront builds its own one-hot
 //                    fragments from them (no SIMD mate can do vector work beside an MFMA stream).
@@ -34,6 +35,7 @@
 
 #include "../../include/mi_metrics.h"
 #include "mi_sa_device.h"
+#include "mi_tri_tiles.h"
 
 namespace mi_sa_impl {
 namespace {
@@ -104,15 +106,8 @@ __global__ void __launch_bounds__(256) k_coassoc_mfma(CoDev g)
     if (g.part)
         for (int v = tid; v <= g.Rg; v += 256) bins[v] = 0u;
     for (long long q = blockIdx.x; q < g.tpg; q += gridDim.x) {
-        // tile q -> (bi, bj), bi <= bj: tile row bi starts at f(bi) = bi nb - bi (bi - 1) / 2
-        const int nb = g.nb;
-        const double b2 = 2.0 * nb + 1.0;
-        int bi = (int)floor((b2 - sqrt(b2 * b2 - 8.0 * (double)q)) * 0.5);
-        bi = bi < 0 ? 0 : (bi > nb - 1 ? nb - 1 : bi);
-        auto f = [&](int x) { return (long long)x * nb - (long long)x * (x - 1) / 2; };
-        while (bi > 0 && f(bi) > q) --bi;
-        while (bi + 1 < nb && f(bi + 1) <= q) ++bi;
-        const int bj = bi + (int)(q - f(bi));
+        int bi, bj;
+        mi_tri::tile_of(q, g.nb, &bi, &bj);                      // tile q -> (bi, bj), bi <= bj (mi_tri_tiles.h)
         const bool diag = bi == bj;
         const int I0 = bi * kTile, J0 = bj * kTile;
         i32x4 acc[4][4];

@@ -138,12 +138,20 @@ def test_compaction_of_labels_outside_range():
     assert L.tolist() == [[0, 1, 0]] and K == 2
 
 
-def _abi(A, Ra, B, Rb, n, Ka, Kb, mode, groups):
+def _abi(A, Ra, B, Rb, n, Ka, Kb, mode, groups, tables=None):
+    """``tables``: an out_tables pointer for a call that is refused before anything is written (None: NULL)"""
     u16p = C.POINTER(C.c_uint16)
     A = np.ascontiguousarray(A, dtype=np.uint16)
     Bp = np.ascontiguousarray(B, dtype=np.uint16).ctypes.data_as(u16p) if B is not None else None
     return _lib.load().mi_label_agreement_u16(A.ctypes.data_as(u16p), Ra, Bp, Rb, n, Ka, Kb, mode, groups, 0,
-                                              None, None, None, None, None)
+                                              None, None, None, tables, None)
+
+
+# never dereferenced: mi_label_agreement_u16 refuses the call on its shape, before it reads a label or looks for a device
+DUMMY_TABLES = C.cast(C.c_void_p(8), C.POINTER(C.c_int32))
+
+
+REFUSAL_CODE = {"exceed": -5}     # MI_EUNSUPPORTED; every other message comes with MI_EINVAL (-1)
 
 
 @pytest.mark.parametrize("args,msg", [
@@ -158,9 +166,14 @@ def _abi(A, Ra, B, Rb, n, Ka, Kb, mode, groups):
     ((np.zeros((2, 4)), 2, np.zeros((2, 4)), 2, 4, 2, 2, 0, 2), "groups = 1"),
     ((np.zeros((2, 4)), 2, np.zeros((2, 4)), 2, 4, 2, 2, 7, 1), "mode must be"),
     ((np.zeros((2, 4)), 0, np.zeros((2, 4)), 2, 4, 2, 2, 0, 1), "Ra must be"),
+    # above MI_AGREE_MAX_LABELLINGS: refused on the shape, before the labels (here 8 of them) are read
+    ((np.zeros((2, 4)), 65537, np.zeros((2, 4)), 2, 4, 2, 2, 0, 1), "Ra must be"),
+    ((np.zeros((2, 4)), 2, np.zeros((2, 4)), 65537, 4, 2, 2, 0, 1), "Rb must be"),
+    # 300 x 300 tables of 64 x 64 = 3.7e8 entries > MI_AGREE_MAX_TABLE_ENTRIES = 2^28: MI_EUNSUPPORTED, with tables only
+    ((np.zeros((300, 4)), 300, np.zeros((300, 4)), 300, 4, 64, 64, 0, 1, DUMMY_TABLES), "exceed"),
 ])
 def test_abi_validation_before_device(args, msg):
-    assert _abi(*args) == -1                                     # MI_EINVAL, not MI_ENODEV: no device is looked for
+    assert _abi(*args) == REFUSAL_CODE.get(msg, -1)              # MI_EINVAL / MI_EUNSUPPORTED, not MI_ENODEV: no device is looked for
     assert msg in _lib.load().mi_last_error().decode()
 
 

@@ -150,8 +150,8 @@ def test_large_n_exact():
 
 # ---- 4. padded layout, holes, continuation ---------------------------------------------------------------------------
 
-def padded_run(continued):
-    pm = models.build_modularity_potts(graph("s16"), 1.0, 16)
+def padded_run(continued, K=16):
+    pm = models.build_modularity_potts(graph("s16"), 1.0, K)
     betas = models.make_beta_schedule(40, default_potts_beta_range(pm))
     with problem(pm, order="padded") as p:
         assert p.n_dev > pm.num_variables                       # holes present
