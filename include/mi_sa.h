@@ -361,8 +361,11 @@ int mi_sa_qubo_dense_f32(const float *Qs, int n, double offset, int R, int num_s
  * when the batch is >= 32 states wide, i.e. a true dense contraction; exact-fp64 VALU otherwise),
  * 1 = VALU (every fp32 entry added once into fp64), 2 = MFMA (Qs SYMMETRIC, as everywhere in this header: only the
  * 128 x 128 blocks on and above the diagonal are multiplied, an off-diagonal block counts twice; fp32 partial
- * sums of <= 128 terms folded into fp64: ~1e-7 of sum|terms|).  out_kernel_ms (nullable): device time of the
- * evaluation kernels. */
+ * sums of <= 128 terms (one fmaf chain per block) plus a 16-way fp32 tree, folded into fp64: ~1e-7 of sum|terms|,
+ * and EXACT when every such partial sum is representable, e.g. integer Qs with 128 * 16 * max|Qs| < 2^24).
+ * X: R x n bytes, each 0 or 1; any other byte (255 from a -1 spin cast to uint8, say) is refused with MI_EINVAL,
+ * cell and state named in the message, on every path and by mi_energy_dense_f64 too.  out_kernel_ms (nullable):
+ * device time of the evaluation kernels. */
 int mi_energy_dense_f32(const float *Qs, int n, const uint8_t *X, int R, double offset,
                         double *out_energy, int device);
 /* The same evaluation over an fp64 matrix (the caller's own coefficients, every entry added once into fp64):

@@ -12,6 +12,7 @@
 // Serves SampleSet energy re-evaluation for the sampler surface (BQM_clustering.py:93-98 prints these
 // energies; the "conf" rule :133-146 divides them).
 #include "mi_sa_device.h"
+#include "mi_energy_plan.h"
 
 namespace mi_sa_impl {
 
@@ -79,8 +80,8 @@ __global__ void __launch_bounds__(256) k_transpose_states(const uint8_t *__restr
 // barriers: operand reads two k-steps ahead; the LDS stores of chunk t + 1 in k-steps 0-3 of chunk t; the global loads
 // of chunk t + 2 in k-steps 4-7.  (Left to the compiler these were phases of their own, and the two workgroups of a CU
 // ran them in lock-step: 0.53 of the MFMA rate where the bare loop reaches 0.92, scripts/ubench_mfma.hip.)
-// After every block the <= 128-term fp32 partial sums are folded into fp64 under the state mask of the row tile
-// (bit tile Xs, prefetched one block ahead when the next block starts a new row).  Inputs are padded: Qp has
+// After every block the <= 128-term fp32 partial sums (+ the 16-way fp32 tree) are folded into fp64 under the state mask
+// of the row tile (bit tile Xs, prefetched one block ahead when the next block starts a new row).  Inputs are padded: Qp has
 // n_pad = 128 * ceil(n / 128) rows of n_pad floats, Xt / Xm have n_pad rows, all padding zero.
 // Operand maps of v_mfma_f32_32x32x2_f32:  A: lane l holds A[i = l & 31][k = l >> 5];  B: lane l holds
 // B[k = l >> 5][j = l & 31];  C/D: register q of lane l is C[row = (q & 3) + 8 (q >> 2) + 4 (l >> 5)][col = l & 31].
@@ -102,7 +103,8 @@ __global__ void __launch_bounds__(256, 2) k_energy_dense_mfma(const float *__res
     const int rtiles = Rpad / kGemmTile;
     const int piece = w / rtiles, r0 = (w % rtiles) * kGemmTile;
     const int S = T * (T + 1) / 2;
-    const int s0 = (int)((long long)S * piece / pieces), s1 = (int)((long long)S * (piece + 1) / pieces);
+    int s0, s1;
+    mi_energy_plan::piece_range(S, piece, pieces, &s0, &s1);
     if (s0 >= s1) return;
     const int NT = 4 * (s1 - s0);
     const int wi = (wave & 1) * 64, wr = (wave >> 1) * 64;       // this wave's 64 x 64 corner inside the block
@@ -110,11 +112,7 @@ __global__ void __launch_bounds__(256, 2) k_energy_dense_mfma(const float *__res
     const int W = Rpad / 32;
 
     int cI = 0, cK = 0;                                          // block s0: row I holds the blocks K = I .. T - 1
-    {
-        int s = s0;
-        while (s >= T - cI) { s -= T - cI; ++cI; }
-        cK = cI + s;
-    }
+    mi_energy_plan::block_of(s0, T, &cI, &cK);
     int lI = cI, lK = cK, lcc = 0;                               // the loader's position in the chunk stream
     const int kk = tid >> 5, c4 = (tid & 31) * 4;
     // chunk loads through buffer descriptors rebuilt per chunk from a UNIFORM base (scalar arithmetic) with per-thread
@@ -129,7 +127,7 @@ __global__ void __launch_bounds__(256, 2) k_energy_dense_mfma(const float *__res
         rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Qp + krow * ldq + (size_t)lI * kGemmTile), 0,
                                                kGemmKC * ldq * 4, 0x00020000);
         rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(Xt + krow * Rpad + r0), 0, kGemmKC * Rpad, 0x00020000);
-        if (++lcc == 4) { lcc = 0; if (++lK == T) { ++lI; lK = lI; } }
+        if (++lcc == 4) { lcc = 0; mi_energy_plan::next_block(T, &lI, &lK); }
     };
     auto load_piece = [&](int q) {
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rq, va, q * 8 * ldq * 4, 0);
@@ -234,7 +232,7 @@ __global__ void __launch_bounds__(256, 2) k_energy_dense_mfma(const float *__res
                 e_lo += weight * (double)m0[0];
                 e_hi += weight * (double)m1[0];
             }
-            if (++cK == T) { ++cI; cK = cI; mb ^= 1; }
+            if (mi_energy_plan::next_block(T, &cI, &cK)) mb ^= 1;
         }
         __syncthreads();
     }
@@ -268,24 +266,12 @@ int mi_launch_energy_dense(const float *dQ, int n, int ldq, const uint8_t *dX, i
         if (ldq != T * kGemmTile) return fail(MI_EINVAL, "MFMA energy path needs rows padded to %d floats", T * kGemmTile);
         unsigned int *dXm = reinterpret_cast<unsigned int *>(dXt + (size_t)ldq * Rpad);
         hipLaunchKernelGGL(k_transpose_states, dim3(Rpad / 64, ldq / 64), dim3(256), 0, st, dX, R, n, dXt, dXm, Rpad, offset, dE);
-        // pieces per state tile: the units should fill whole rounds of the resident workgroups (68 KB of LDS each: two
-        // per CU) with pieces of (nearly) equal length
+        // pieces per state tile (mi_energy_plan.h), from the CU count of the device
         int dev = 0, cus = 256;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const long long rtiles = Rpad / kGemmTile, resident = 2LL * (cus > 0 ? cus : 256);
-        const long long S = (long long)T * (T + 1) / 2;
-        long long pieces = 1;
-        double best = 0.0;
-        for (long long rounds = 1; rounds <= 4; ++rounds) {
-            long long p = rounds * resident / rtiles;
-            if (p < 1) p = 1;
-            if (p > S) p = S;
-            const long long units = p * rtiles, longest = (S + p - 1) / p;
-            const double fill = (double)(S * rtiles) / (double)(((units + resident - 1) / resident) * resident * longest);
-            if (fill > best + 0.02) { best = fill; pieces = p; }
-            if (p == S) break;
-        }
+        const long long rtiles = Rpad / kGemmTile;
+        const long long pieces = mi_energy_plan::pieces(T, rtiles, cus);
         hipLaunchKernelGGL(k_energy_dense_mfma, dim3((unsigned)(pieces * rtiles)), dim3(256), 0, st, dQ, ldq, dXt, dXm, R, Rpad,
                            T, (int)pieces, dE);
     } else {

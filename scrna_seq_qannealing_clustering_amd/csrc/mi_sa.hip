@@ -1670,12 +1670,27 @@ int mi_sa_qubo_dense_f32(const float *Qs, int n, double offset, int R, int num_s
     return rc;
 }
 
+// K4's states are bytes 0 / 1.  The VALU form takes any non-zero byte as set, the MFMA form multiplies by the byte's value
+// and masks with its bit 0: another byte (255 from a -1 spin cast to uint8) would give energies that depend on the path,
+// so it is refused.  One pass that ORs the high seven bits of every byte, and a search only when one is set.
+static int check_state_bytes(const uint8_t *X, int n, int R)
+{
+    const size_t total = (size_t)R * n;
+    unsigned int high = 0u;
+    for (size_t e = 0; e < total; ++e) high |= X[e];
+    if (!(high & 0xfeu)) return MI_OK;
+    size_t e = 0;
+    while (X[e] <= 1) ++e;
+    return fail(MI_EINVAL, "states must be bytes 0 or 1: cell %lld of state %lld is %d", (long long)(e % n), (long long)(e / n), (int)X[e]);
+}
+
 int mi_energy_dense_f32_ex(const float *Qs, int n, const uint8_t *X, int R, double offset,
                            double *out_energy, int device, int path, float *out_kernel_ms)
 {
     if (!Qs || !X || !out_energy) return fail(MI_EINVAL, "NULL argument");
     if (n < 1 || R < 1) return fail(MI_EINVAL, "n and R must be >= 1");
     if (path < 0 || path > 2) return fail(MI_EINVAL, "path must be 0 (auto), 1 (VALU) or 2 (MFMA)");
+    MI_TRY(check_state_bytes(X, n, R));
     if (path != 1 && (path == 2 || R >= 32)) {
         // the MFMA kernel multiplies only the blocks on and above the diagonal of a SYMMETRIC Qs: a matrix that is not
         // (e.g. an upper-triangular QUBO) goes to the exact path when the choice is the library's, and is refused when
@@ -1721,6 +1736,7 @@ int mi_energy_dense_f64(const double *Qs, int n, const uint8_t *X, int R, double
 {
     if (!Qs || !X || !out_energy) return fail(MI_EINVAL, "NULL argument");
     if (n < 1 || R < 1) return fail(MI_EINVAL, "n and R must be >= 1");
+    MI_TRY(check_state_bytes(X, n, R));
     MI_TRY(pick_device(device));
     return guarded([&]() -> int {
         DevBufs bufs;

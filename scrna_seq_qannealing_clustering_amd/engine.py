@@ -648,7 +648,8 @@ def plan_anneal(kind, rowptr, col, n, num_reads, num_cases=2, cus=0, options=Non
 def energy_dense(Qs: np.ndarray, X: np.ndarray, offset: float = 0.0, device: int = 0, path: int = 0,
                  return_ms: bool = False):
     """Batched ``E_r = x_r^T Qs x_r + offset`` on the GPU (kernel K4).  ``path``: 0 auto (MFMA for
-    batches of >= 32 states), 1 exact-fp64 VALU, 2 f32-input MFMA."""
+    batches of >= 32 states), 1 exact-fp64 VALU, 2 f32-input MFMA.  ``X`` holds 0 / 1; any other value after the cast to
+    uint8 (a -1 spin becomes 255) is refused by the library."""
     Qs = np.ascontiguousarray(Qs, dtype=np.float32)
     X = np.ascontiguousarray(X, dtype=np.uint8)
     if X.ndim != 2 or X.shape[1] != Qs.shape[0]:

@@ -163,7 +163,7 @@ def test_circles_reaches_proven_optimum(kat):
 
 def test_energy_kernel_parity():
     """K4, both forms: exact-fp64 VALU (rel 1e-12) and the f32-input MFMA contraction (rel 1e-6, stated in
-    include/mi_sa.h: fp32 partial sums of <= 32 terms folded into fp64)."""
+    include/mi_sa.h: fp32 partial sums of <= 128 terms plus a 16-way fp32 tree, folded into fp64)."""
     fx, m, Qs = fixture_model("aniso")
     rng = np.random.RandomState(3)
     X = rng.randint(0, 2, size=(37, 256)).astype(np.uint8)
