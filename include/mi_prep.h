@@ -249,6 +249,33 @@ int mi_prep_gram(mi_prep_matrix *m, double *out_G, float *out_kernel_ms);
  * MI_EINVAL for p < 1, MI_EUNSUPPORTED for p > MI_PREP_MAX_PCS, MI_ESTATE before mi_prep_select. */
 int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float *out_kernel_ms);
 
+#define MI_PREP_MARKERS_COUNTS     0   /* the uploaded values */
+#define MI_PREP_MARKERS_NORMALIZED 1   /* the output of mi_prep_normalize */
+#define MI_PREP_MARKERS_GATHER_INPLACE 4u   /* flags bit 2: a sparse handle reads its values through the position map */
+#define MI_PREP_MARKERS_GATHER_PERMUTE 8u   /* flags bit 3: ... from a gene-major copy made first (nnz floats of scratch) */
+
+/* The rank-sum marker pass of mi_metrics.h (mi_rank_sum_markers_f32: the same L, B, K, outputs, label rules, limits and the
+ * flags MI_MARKERS_SUM_PLAIN and MI_MARKERS_GLOBAL) on the matrix the handle holds on the device, with no upload: `which`
+ * picks the uploaded values or the normalised ones; n and g are the handle's.  Every output equals, bit for bit, that of
+ * mi_rank_sum_markers_f32 on the same (densified) matrix.  The handle is not modified and all scratch is freed on return:
+ * mi_prep_info's device_bytes is the same before and after.
+ *   dense handle   the kernels of mi_rank_sum_markers_f32 on the resident matrix; the per-gene non-zero counts its host scan
+ *                  gives come from k_markers_count (csrc/markers_kernels.hip).
+ *   sparse handle  no transpose and no n x g buffer: gene j's candidates are its stored entries (cells rows[k] ascending,
+ *                  values V[pos[k]]).  A stored zero is a zero: the compaction skips it, it joins the zero block, and
+ *                  zeros = n - (true non-zeros).  The launch (LDS capacity, slab stride, LDS or HBM form per gene) is
+ *                  planned from the stored counts, an upper bound read from colptr; the true non-zero count comes out of the
+ *                  compaction and the sort is padded to the planned power of two.  The sums walk the stored entries in
+ *                  ascending cell order, one thread per (gene, labelling): the dense kernel's additions in its order.
+ *                  The two GATHER flags pick how the values are read (neither: the form kept by measurement, DESIGN.md
+ *                  section 5c; they change no result and a dense handle ignores them).
+ * All checks before any device work, in this order: MI_EINVAL for NULL m, L or out_rank2, `which` outside {0, 1}, B < 1, K
+ * outside [1, 64], unknown flags or both GATHER flags, a label >= K; MI_ESTATE for which == 1 before mi_prep_normalize;
+ * MI_EUNSUPPORTED for n > MI_MARKERS_MAX_CELLS and for B * g * K > MI_MARKERS_MAX_ENTRIES. */
+int mi_prep_rank_sum_markers(mi_prep_matrix *m, int which, const uint16_t *L, int B, int K, uint32_t flags,
+                             int64_t *out_rank2, int32_t *out_npos, double *out_sum, int64_t *out_tie,
+                             float *out_kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

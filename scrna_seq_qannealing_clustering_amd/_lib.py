@@ -129,6 +129,8 @@ def _declare(lib):
                                          u8p, f32p]),
         "mi_prep_gram": (C.c_int, [vp, f64p, f32p]),
         "mi_prep_project": (C.c_int, [vp, f32p, C.c_int, f32p, f32p]),
+        "mi_prep_rank_sum_markers": (C.c_int, [vp, C.c_int, u16p, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int64), i32p, f64p,
+                                               C.POINTER(C.c_int64), f32p]),
         # include/mi_umap.h
         "mi_umap_knn_f32": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, pp, f32p]),
         "mi_umap_destroy": (C.c_int, [vp]),
@@ -162,6 +164,7 @@ EXPORTS = (
     "mi_prep_create_f32", "mi_prep_create_csr_f32", "mi_prep_info", "mi_prep_fetch_normalized_csr", "mi_prep_destroy", "mi_prep_normalize", "mi_prep_fetch_normalized", "mi_prep_gene_stats",
     "mi_prep_clipped_variance", "mi_prep_select", "mi_prep_fetch_scaled", "mi_prep_cell_qc", "mi_prep_select_regressed", "mi_prep_gram", "mi_prep_project",
     "mi_prep_gene_log1p_sum", "mi_prep_nb_fit", "mi_prep_sct_residual_moments", "mi_prep_sct_select",
+    "mi_prep_rank_sum_markers",
     "mi_umap_knn_f32", "mi_umap_destroy", "mi_umap_fetch_knn", "mi_umap_smooth", "mi_umap_fetch_smooth", "mi_umap_union",
     "mi_umap_info", "mi_umap_fetch_graph", "mi_umap_layout_f32",
 )

@@ -25,6 +25,7 @@
 
 #include "../../include/mi_prep.h"
 #include "mi_prep_csr.h"
+#include "mi_prep_handle.h"
 #include "mi_sa_device.h"
 #include "mi_sct_math.h"
 
@@ -912,14 +913,7 @@ __global__ void __launch_bounds__(256) k_sct_csr_select(const int64_t *__restric
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
 
-struct mi_prep_matrix {
-    int n = 0, g = 0, device = 0, h = 0, ldz = 0;
-    bool normalized = false, sparse = false;
-    int64_t nnz = 0;                                              // stored entries of a sparse handle
-    DevArray<float> d_X, d_Y, d_Z;                                // sparse: d_X, d_Y hold nnz values in the caller's CSR order
-    DevArray<int64_t> d_indptr, d_colptr;                         // sparse: the caller's CSR structure and its transpose,
-    DevArray<int32_t> d_indices, d_rows, d_pos;                   // whose entry k is entry d_pos[k] of the CSR order
-};
+// (mi_prep_matrix: mi_prep_handle.h)
 
 namespace {
 

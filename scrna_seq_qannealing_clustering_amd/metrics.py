@@ -567,8 +567,8 @@ def cell_confidence_any(rowsum_fn, labels, reads: int) -> np.ndarray:
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Marker genes: the Wilcoxon rank-sum test of every cluster against all other cells, per gene (Seurat's FindAllMarkers with
-# its default test), for many labellings in one device call (include/mi_metrics.h mi_rank_sum_markers_f32,
-# csrc/markers_kernels.hip).  A gene's ranks do not depend on the labelling: the device sorts every gene once and returns
+# its default test), for many labellings in one device call (include/mi_metrics.h mi_rank_sum_markers_f32 on a host array,
+# include/mi_prep.h mi_prep_rank_sum_markers on a resident ExpressionMatrix, dense or sparse; csrc/markers_kernels.hip).  A gene's ranks do not depend on the labelling: the device sorts every gene once and returns
 # exact integer rank sums, counts and the tie term; everything reported is a closed form of those, evaluated here in fp64.
 # ---------------------------------------------------------------------------------------------------------------------
 MARKERS_LDS_MAX_NONZEROS = 8192            # MI_MARKERS_LDS_MAX_NONZEROS (include/mi_metrics.h)
@@ -582,13 +582,59 @@ except ImportError:                        # the package does not need scipy
     _erfc = np.vectorize(math.erfc, otypes=[np.float64])
 
 
-def rank_sum_pass(X, L, K: int, device: int = 0, plain: bool = False, force_global: bool = False) -> dict:
-    """The device pass.  ``X``: cells x genes, finite; ``L``: (n,) or (B, n) labels in [0, K), K <= 64.  Returns, per
+def _resident(X, which):
+    """``(handle, which, owned)`` for an ``X`` that is ranked on the device where it lies -- an open
+    :class:`preprocess.ExpressionMatrix`, or a ``scipy.sparse`` matrix, which is uploaded through a temporary handle as the
+    values to rank -- and ``None`` for a dense array.  ``which`` of a handle defaults to ``"normalized"`` once it has been
+    normalised, else ``"counts"``.  The errors are raised before any library call."""
+    from . import preprocess                                      # (lazily: preprocess does not import metrics either)
+    if isinstance(X, preprocess.ExpressionMatrix):
+        if which is None:
+            which = "normalized" if X.normalized else "counts"
+        if which not in ("counts", "normalized"):
+            raise ValueError("which must be 'counts' or 'normalized'")
+        X._handle()                                               # ValueError for a closed handle
+        return X, which, False
+    if preprocess.is_sparse(X):
+        if which not in (None, "counts"):
+            raise ValueError("a sparse matrix holds the values to rank: which must be 'counts' (or None)")
+        if X.ndim != 2:
+            raise ValueError("X must be (cells, genes) (got shape %s)" % (X.shape,))
+        return None, "counts", True
+    if which is not None:
+        raise TypeError("which= applies to an ExpressionMatrix or a scipy.sparse matrix, not to a dense array")
+    return None
+
+
+def _check_labels_shape(L, n):
+    L = np.asarray(L)
+    if L.ndim == 1:
+        L = L[None, :]
+    if L.ndim != 2 or L.shape[1] != n:
+        raise ValueError("X must be (n, g) and L (n,) or (B, n) (got n = %d, %s)" % (n, L.shape))
+    return L
+
+
+def rank_sum_pass(X, L, K: int, device: int = 0, plain: bool = False, force_global: bool = False, which=None) -> dict:
+    """The device pass.  ``X``: cells x genes, finite; ``L``: (n,) or (B, n) labels in [0, K), K <= 64.  ``X`` may also be
+    an open :class:`preprocess.ExpressionMatrix` (``which``: its ``"counts"`` or ``"normalized"`` matrix, by default the
+    normalised one once it exists; ranked where it lies, ``device`` is the handle's) or a ``scipy.sparse`` matrix of the
+    values to rank, which must be non-negative (uploaded as CSR, never densified); both give the bits of the dense array.
+    Returns, per
     (labelling, gene, cluster), ``rank2`` (int64, twice the sum of the cluster's midranks among all n cells), ``npos``
     (int32, its cells with x > 0) and ``sum`` (fp64, the sum of ``expm1(x)`` over its cells in cell order; of ``x`` with
     ``plain``); ``tie`` (g,) int64, the sum of t^3 - t over each gene's tie groups; and ``kernel_ms``.
     ``force_global``: the ranking kernel's HBM form, which otherwise serves genes with more than
     ``MARKERS_LDS_MAX_NONZEROS`` non-zero cells."""
+    res = _resident(X, which)
+    if res is not None:
+        handle, which, owned = res
+        L = _check_labels_shape(L, X.n if handle is not None else X.shape[0])
+        if not owned:
+            return handle.rank_sum_pass(L, K, which=which, plain=plain, force_global=force_global)
+        from . import preprocess
+        with preprocess.ExpressionMatrix(X, device=device) as m:
+            return m.rank_sum_pass(L, K, which="counts", plain=plain, force_global=force_global)
     X = np.ascontiguousarray(X, dtype=np.float32)
     L = np.asarray(L)
     if L.ndim == 1:
@@ -660,29 +706,36 @@ def markers_passed(stats: dict, only_pos: bool = False, min_pct: float = 0.1, lo
 
 
 def find_all_markers(X, labels, only_pos: bool = False, min_pct: float = 0.1, logfc_threshold: float = 0.25, genes=None,
-                     device: int = 0, plain: bool = False) -> dict:
+                     device: int = 0, plain: bool = False, which=None) -> dict:
     """Seurat's ``FindAllMarkers`` (Wilcoxon rank-sum, every cluster against all other cells) for one labelling ((n,)) or
     many ((B, n)) in one device call.  ``X``: cells x genes, log-normalised (``plain``: scaled data or counts, whose mean is
-    the plain mean).  Cluster ids are any values, at most 64 distinct over all labellings.  Returns the fields of
+    the plain mean): a dense array; an open :class:`preprocess.ExpressionMatrix`, whose resident matrix is ranked without
+    an upload (``which``: ``"counts"`` or ``"normalized"``, by default the normalised matrix once the handle has one); or a
+    ``scipy.sparse`` matrix of the values to rank, e.g. what ``log_normalize(sparse)`` returns -- its values must be
+    non-negative, it is uploaded as CSR and no n x g buffer is made.  All three give the same bits.
+    Cluster ids are any values, at most 64 distinct over all labellings.  Returns the fields of
     :func:`markers_from_stats`, shaped (g, K) or (B, g, K), ``passed`` (:func:`markers_passed`), ``cluster_ids`` (K,),
     ``cluster_size`` ((K,) or (B, K); a labelling that does not use an id has size 0 and NaN statistics there),
     ``genes`` (the names, default 0 .. g - 1) and ``kernel_ms``."""
-    X = np.asarray(X)
+    res = _resident(X, which)
+    if res is None:
+        X = np.asarray(X)
     lab = np.asarray(labels)
     one = lab.ndim == 1
-    if lab.ndim not in (1, 2) or X.ndim != 2 or lab.shape[-1] != X.shape[0]:
+    shape = (X.n, X.g) if res is not None and res[0] is not None else X.shape
+    if lab.ndim not in (1, 2) or len(shape) != 2 or lab.shape[-1] != shape[0]:
         raise ValueError("labels must be (n,) or (B, n) for the n rows of X")
     uniq, inv = np.unique(lab, return_inverse=True)
     if len(uniq) > 64:
         raise ValueError("%d distinct cluster ids (at most 64)" % len(uniq))
     L = inv.reshape((1, -1) if one else lab.shape)
-    n, g = X.shape
+    n, g = (int(v) for v in shape)
     K = len(uniq)
     genes = np.arange(g) if genes is None else np.asarray(genes)
     if genes.shape != (g,):
         raise ValueError("genes must name the %d columns of X" % g)
     sizes = np.stack([np.bincount(row, minlength=K) for row in L]).astype(np.int64)
-    r = rank_sum_pass(X, L, K, device=device, plain=plain)
+    r = rank_sum_pass(X, L, K, device=device, plain=plain, which=None if res is None else res[1])
     out = markers_from_stats(r["rank2"], r["npos"], r["sum"], r["tie"], sizes, n, plain=plain)
     out["passed"] = markers_passed(out, only_pos, min_pct, logfc_threshold)
     out["cluster_size"] = sizes

@@ -26,7 +26,7 @@ agreement with R is UNPINNED.
 
 Out of scope: SCTransform's corrected counts and ``data`` slot, ``vst.flavor = "v2"``, ``batch_var``, latent variables other
 than ``log_umi``, glmGamPoi's Cox-Reid adjustment; more than ``MAX_FEATURES`` = 4096 features or ``MAX_COVARIATES`` = 8
-covariates, sparse input to :func:`metrics.find_all_markers` and to the ``--counts`` option of ``run``.
+covariates, sparse input to the ``--counts`` option of ``run``.
 
     qc = preprocess.cell_qc(counts, gene_names)
     keep = preprocess.qc_filter(qc)
@@ -105,6 +105,7 @@ class ExpressionMatrix:
         self.nnz = len(data) if self.sparse else self.n * self.g
         self.device = int(device)
         self.h = 0
+        self.normalized = False                                  # has normalize() run
         self.timing = {}
         self._stats = {}
         self.coef_q = self.resid_mean = self.resid_var = self.flat = self.regression = None     # of select_regressed
@@ -154,6 +155,7 @@ class ExpressionMatrix:
         ms = C.c_float(0.0)
         _lib.check(self._lib.mi_prep_normalize(self._handle(), float(scale_factor), C.byref(ms)))
         self._stats.pop(1, None)
+        self.normalized = True
         self.timing["normalize_ms"] = float(ms.value)
         return self
 
@@ -238,6 +240,38 @@ class ExpressionMatrix:
                                              C.byref(ms)))
         self.timing["qc_ms"] = float(ms.value)
         return n_count, n_feature, subset
+
+    def rank_sum_pass(self, L, K: int, which: str = "normalized", plain: bool = False, force_global: bool = False,
+                      gather: Optional[str] = None) -> dict:
+        """The device pass of :func:`metrics.rank_sum_pass` on the resident ``"counts"`` or ``"normalized"`` matrix, with no
+        upload and, on a sparse handle, no n x g buffer: the same dict (``rank2``, ``npos``, ``sum``, ``tie``,
+        ``kernel_ms``), bit for bit that of the dense entry point on the densified matrix.  ``gather`` (sparse handle only;
+        changes no result): ``"permute"`` copies the values into gene-major order first, ``"inplace"`` reads them through
+        the position map, ``None`` takes the library's default.  The handle is not modified."""
+        if which not in ("counts", "normalized"):
+            raise ValueError("which must be 'counts' or 'normalized'")
+        if gather not in (None, "permute", "inplace"):
+            raise ValueError("gather must be None, 'permute' or 'inplace'")
+        L = np.asarray(L)
+        if L.ndim == 1:
+            L = L[None, :]
+        if L.ndim != 2 or L.shape[1] != self.n:
+            raise ValueError("L must be (n,) or (B, n) for the %d cells of the handle (got %s)" % (self.n, L.shape))
+        if L.dtype.kind not in "iub" or (L.size and (L.min() < 0 or L.max() > 65535)):
+            raise ValueError("labels must be integers in [0, K)")
+        L = np.ascontiguousarray(L, dtype=np.uint16)
+        B, K = L.shape[0], int(K)
+        h = self._handle()
+        shape = (B, self.g, max(K, 0))
+        rank2, npos = np.empty(shape, dtype=np.int64), np.empty(shape, dtype=np.int32)
+        sums, tie = np.empty(shape, dtype=np.float64), np.empty(self.g, dtype=np.int64)
+        flags = (1 if plain else 0) | (2 if force_global else 0) | {None: 0, "inplace": 4, "permute": 8}[gather]
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_rank_sum_markers(h, int(which == "normalized"), _p(L, C.POINTER(C.c_uint16)), B, K, flags,
+                                                      _p(rank2, _i64p), _p(npos, _i32p), _p(sums, _f64p), _p(tie, _i64p),
+                                                      C.byref(ms)))
+        self.timing["markers_ms"] = float(ms.value)
+        return {"rank2": rank2, "npos": npos, "sum": sums, "tie": tie, "kernel_ms": float(ms.value)}
 
     def select_regressed(self, genes, Q, clip: float = 10.0):
         """:meth:`select` on the residuals of a linear model: with ``y`` the chosen column of the normalised matrix and
@@ -407,8 +441,9 @@ class Result(dict):
 
 
 def log_normalize(X, scale_factor: float = 1e4, device: int = 0):
-    """The log-normalised fp32 matrix (cells x genes) :func:`metrics.find_all_markers` takes; sparse in, sparse
-    (``csr_matrix``) out."""
+    """The log-normalised fp32 matrix (cells x genes) :func:`metrics.find_all_markers` takes, dense or sparse: sparse in,
+    sparse (``csr_matrix``) out.  To skip the download and the second upload, keep the handle instead:
+    ``find_all_markers(ExpressionMatrix(X).normalize(), labels)`` ranks the resident matrix."""
     with ExpressionMatrix(X, device=device) as m:
         return m.normalize(scale_factor).fetch_normalized()
 
