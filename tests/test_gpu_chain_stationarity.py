@@ -15,8 +15,12 @@ largest R there is 4096-8192).  Which cases do not, and why:
 * K1x / K1g exist for n > 4096 only: the 6-variable model is embedded in 4097 variables (the others uncoupled with a
   linear term of 64: beta * 64 > 23 ln 2, the largest -ln u of the chain, so once 0 they never move; asserted), 2^12
   replicas in one call -- 2^18 would be 1 GiB of states and 4e13 proposals for a 64-state model;
-* K2 keeps a 16-bit state cell per variable on every model below 4600 variables, and its byte / bit state forms and its
-  threshold wavefront exist beyond that only: K2 is covered in its 16-bit form (``k_anneal_csr_rank1<16, 2>``);
+* K2 keeps a 16-bit state cell per variable on every model up to 4608 variables; its byte / bit state forms, the library's
+  choice beyond, run here under ``MI_K2_STATE`` (read when the model is created; the cases named "byte" / "bit"):
+  ``k_anneal_csr_rank1<16, 1>`` and ``<16, 0>`` at 2^18 replicas, one of them with the weighted slot, and both beside their
+  threshold wavefront (``<16, 1, tw>``, ``<16, 0, tw>``) in calls of 1024 replicas.  D = 32 / 64 / the runtime width of K2
+  stay pinned by oracle parity alone (tests/test_gpu_k2_state_forms.py): a row of 17 neighbours needs n = 18, and 2^18
+  states cannot each expect 5 of 2^18 samples;
 * K3 / K3f with 32 adjacency entries need a variable with 17 neighbours, so n = 18: with K = 2 the 2^18 labelings can
   be enumerated but cannot each expect 5 samples, so 12 leaves are tied to the hub and move with it as one variable
   (chain_stats.hub_model says why the block's label is still exactly Boltzmann); K3f's 16-label form at that width
@@ -28,7 +32,7 @@ in which shape; and the single counted sweep of the scheduler case (variant 4) i
 K1w alone -- the 50 judged sweeps before it ran on both kernels, as the asserted name shows.
 
 The GPU is shared: every case is one or a few launches on register-sized models, nothing loops on a failure.
-Measured on an MI355X: 8 s for the file, 0.01 - 0.23 s per case (``pytest -s`` prints kernel, R per call, p, z, acceptance deviation and
+Measured on an MI355X: 8 s for the file (65 cases), 0.01 - 0.23 s per case (``pytest -s`` prints kernel, R per call, p, z, acceptance deviation and
 wall time per case; DESIGN.md section 6, "what pins the chain").
 """
 import time
@@ -124,6 +128,14 @@ def csr6():
     return rp, col, val, (np.random.RandomState(27).randn(6) * 0.5).astype(np.float32), 0.11
 
 
+def force_k2_state(monkeypatch, case):
+    """MI_K2_STATE (read when the model is created) for a case named "... byte ..." / "... bit ...", unset for the others."""
+    monkeypatch.delenv("MI_K2_STATE", raising=False)
+    for state in ("byte", "bit"):
+        if state in case.split():
+            monkeypatch.setenv("MI_K2_STATE", state)
+
+
 @pytest.mark.parametrize("case,kind,order,options,beta,kernel", [
     ("K2", "pair", None, (("k2_pair", 0),), 0.5, "k_anneal_csr_rank1<16, 2>"),
     ("K2", "pair", None, (("k2_pair", 0),), 2.0, "k_anneal_csr_rank1<16, 2>"),
@@ -136,8 +148,13 @@ def csr6():
     ("K2p tw weighted", "weighted", "padded", (), 2.0, "k_anneal_csr_rank1_pair<16, tw>"),
     ("K2p weighted", "weighted", "padded", (("k2_tw", 2),), 2.0, "k_anneal_csr_rank1_pair<16>"),
     ("K2 weighted", "weighted", "padded", (("k2_pair", 2),), 2.0, "k_anneal_csr_rank1<16, 2>"),
+    # K2's byte and bit state (MI_K2_STATE; without a threshold wavefront: more than 1024 replicas)
+    ("K2 byte", "pair", None, (("k2_pair", 0),), 0.5, "k_anneal_csr_rank1<16, 1>"),
+    ("K2 bit", "pair", None, (("k2_pair", 0),), 0.5, "k_anneal_csr_rank1<16, 0>"),
+    ("K2 bit weighted", "weighted", "padded", (("k2_pair", 2),), 2.0, "k_anneal_csr_rank1<16, 0>"),
 ])
-def test_structured_kernels(case, kind, order, options, beta, kernel):
+def test_structured_kernels(case, kind, order, options, beta, kernel, monkeypatch):
+    force_k2_state(monkeypatch, case)
     rp, col, val, lin, c, w = csr_model(kind)
     X, E = cs.enumerate_binary(rowptr=rp, col=col, val=val, lin=lin, c_pair=c, weights=w)
     pi = cs.reference(E, beta, R)
@@ -159,9 +176,13 @@ def test_structured_kernels(case, kind, order, options, beta, kernel):
     ("K2 few reads", 64, (("k2_split", 2), ("k2_pair", 2)), 512, "k_anneal_csr_rank1<16, 2>"),
     ("K2 three waves", 64, (("k2_split", 2), ("k2_pair", 2), ("k2_waves", 3)), 510, "k_anneal_csr_rank1<16, 2>"),
     ("K2p tw", 64, (("k2_pair", 1),), 2048, "k_anneal_csr_rank1_pair<16, tw>"),
+    # K2's byte and bit state beside a threshold wavefront (MI_K2_STATE; up to 1024 replicas a call)
+    ("K2 byte tw", 64, (("k2_split", 2), ("k2_pair", 2)), 1024, "k_anneal_csr_rank1<16, 1, tw>"),
+    ("K2 bit tw", 64, (("k2_split", 2), ("k2_pair", 2)), 1024, "k_anneal_csr_rank1<16, 0, tw>"),
 ])
-def test_few_replica_structured_kernels(case, block, options, r_call, kernel):
+def test_few_replica_structured_kernels(case, block, options, r_call, kernel, monkeypatch):
     """The forms the library picks by read count: 2^15 samples over calls of ``r_call`` replicas, 64-state model."""
+    force_k2_state(monkeypatch, case)
     rp, col, val, lin, c = csr6()
     beta = 0.5
     X, E = cs.enumerate_binary(rowptr=rp, col=col, val=val, lin=lin, c_pair=c)

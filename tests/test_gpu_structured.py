@@ -1,5 +1,6 @@
 """Parity of the structured kernels (K2: CSR + uniform pair term, K3: Potts / DQM) against the oracle,
-through the C ABI.  GPU only.  States / labels / accepted-move counts / edge cuts are bit-exact."""
+through the C ABI.  GPU only.  States / labels / accepted-move counts / edge cuts are bit-exact.
+Measured on an MI355X: 9 s for the file (164 tests)."""
 import numpy as np
 import pytest
 
@@ -69,10 +70,12 @@ def test_csr_rank1_sparse_only_model_and_ragged_n():
     assert np.allclose(en, oen, rtol=1e-9, atol=1e-9)
 
 
-def test_structured_kernels_beyond_4096_variables():
-    """n = 5000 (> 64 slots: several state masks in K2, > 4096 labels in K3): 3 replicas vs the oracle."""
-    from scrna_seq_qannealing_clustering_amd import graphs
+def test_structured_kernels_beyond_4096_variables(monkeypatch):
+    """n = 5000 (> 64 slots: several state masks in K2, > 4096 labels in K3): 3 replicas vs the oracle.  Beyond 4608
+    variables K2 keeps a byte of state per variable, and with 3 replicas a threshold wavefront beside each."""
+    from scrna_seq_qannealing_clustering_amd import engine, graphs
     from scrna_seq_qannealing_clustering_amd.sampler import default_potts_beta_range
+    monkeypatch.delenv("MI_K2_STATE", raising=False)
     nodes, eu, ev, w, _ = graphs.synthetic_snn(5000, 5, 15, 15, 12, seed=3)
     G = graphs.EdgeListGraph(nodes, eu, ev, w)
     m = models.build_bqm_qubo(G, 0.05)
@@ -82,6 +85,8 @@ def test_structured_kernels_beyond_4096_variables():
     with Problem.csr_rank1(*args) as p:
         p.anneal(3, betas, 21, resync_interval=4)
         st, en, info = p.fetch()
+        assert p.kernel_name() == engine.plan_anneal(_lib.KIND_CSR_RANK1, m.rowptr, m.col, 5000, 3)[0] \
+            == "k_anneal_csr_rank1<16, 1, tw>", p.kernel_name()
     assert np.array_equal(st, ost) and info["accepted"] == int(ostats[1])
     assert np.allclose(en, oen, rtol=1e-9, atol=1e-9)
     pm = models.build_dqm_potts(G, 15, 0.005)
@@ -91,6 +96,8 @@ def test_structured_kernels_beyond_4096_variables():
     with Problem.potts_csr(*pargs, lin_offset=pm.lin_offset) as p:
         p.anneal(3, pb, 22)
         lab, en, info = p.fetch()
+        assert p.kernel_name() == engine.plan_anneal(_lib.KIND_POTTS_CSR, pm.rowptr, pm.col, 5000, 3, num_cases=15)[0] \
+            == "k_anneal_potts<16>", p.kernel_name()
     assert np.array_equal(lab, olab) and info["accepted"] == int(ostats[1])
     assert np.allclose(en, oen, rtol=1e-9, atol=1e-9)
 
@@ -117,10 +124,12 @@ def _sparse_ring_model(n, seed):
 
 
 @pytest.mark.parametrize("n,R,sweeps", [(20000, 3, 3), (45003, 2, 2)])
-def test_csr_rank1_large_models(n, R, sweeps):
+def test_csr_rank1_large_models(n, R, sweeps, monkeypatch):
     """K2 at large n (BASELINE config 4 is n = 50000): the only per-replica memory is one state bit per
     variable in LDS, so the size is bounded by nothing else.  Bit-exact against the oracle (rows of up to 28
-    neighbours: the 32-wide adjacency layout)."""
+    neighbours: the 32-wide adjacency layout, the bit state beside a threshold wavefront)."""
+    from scrna_seq_qannealing_clustering_amd import engine
+    monkeypatch.delenv("MI_K2_STATE", raising=False)
     args = _sparse_ring_model(n, seed=n)
     assert int(np.diff(args[0]).max()) <= 64
     betas = np.geomspace(0.002, 0.5, sweeps)
@@ -128,7 +137,31 @@ def test_csr_rank1_large_models(n, R, sweeps):
     with Problem.csr_rank1(*args) as p:
         p.anneal(R, betas, 5, replica_offset=2, resync_interval=2)
         st, en, info = p.fetch()
+        assert p.kernel_name() == engine.plan_anneal(_lib.KIND_CSR_RANK1, args[0], args[1], n, R)[0] \
+            == "k_anneal_csr_rank1<32, 0, tw>", p.kernel_name()
     assert info["accepted"] == int(ostats[1]) and info["accepted"] > n // 4
+    assert np.array_equal(st, ost)
+    assert np.allclose(en, oen, rtol=1e-9, atol=1e-9)
+
+
+@pytest.mark.parametrize("n,state", [(4608, 2), (4609, 1), (9216, 1), (9217, 0)])
+def test_csr_rank1_state_form_switches_at_its_natural_sizes(n, state, monkeypatch):
+    """With MI_K2_STATE unset K2 keeps a half of state per variable while 16 replicas' states fit a CU's LDS (72 slots, n =
+    4608), a byte up to 144 slots (n = 9216), a bit beyond: the name switches exactly there -- the byte and bit forms, run
+    by few replicas, get a threshold wavefront -- and the run on either side of each switch equals the oracle's.  Measured
+    on an MI355X: 0.01 - 0.03 s a size."""
+    from scrna_seq_qannealing_clustering_amd import engine
+    monkeypatch.delenv("MI_K2_STATE", raising=False)
+    args = _sparse_ring_model(n, seed=n)
+    assert 16 < int(np.diff(args[0]).max()) <= 32
+    betas = np.geomspace(0.002, 0.5, 2)
+    ost, oen, ostats = so.sa_csr_rank1_philox(*args, 2, betas, 5, replica_offset=2)
+    with Problem.csr_rank1(*args) as p:
+        p.anneal(2, betas, 5, replica_offset=2)
+        st, en, info = p.fetch()
+        assert p.kernel_name() == engine.plan_anneal(_lib.KIND_CSR_RANK1, args[0], args[1], n, 2)[0] \
+            == "k_anneal_csr_rank1<32, %d%s>" % (state, "" if state == 2 else ", tw"), p.kernel_name()
+    assert info["accepted"] == int(ostats[1]) and info["accepted"] > n // 4 and info["proposals"] == 2 * 2 * n == int(ostats[0])
     assert np.array_equal(st, ost)
     assert np.allclose(en, oen, rtol=1e-9, atol=1e-9)
 
