@@ -542,7 +542,7 @@ template <int NT>
 int launch_dense_wg_any(const DenseLaunchCtx &p, const DenseArgs &a, hipStream_t st)
 {
     int gr = p.opt_unit_rows ? p.opt_unit_rows : 4;       // 4 rows per rendezvous measured fastest
-    if (gr == 4 && !WgCfg<NT, 4>::ok) gr = 2;
+    if (!p.opt_unit_rows && !WgCfg<NT, 4>::ok) gr = 2;    // (NT >= 56; a unit of 4 rows asked for by option is refused there)
     switch (gr) {
         case 2: return launch_dense_wg<NT, 2>(p, a, st);
         case 4: return launch_dense_wg<NT, 4>(p, a, st);

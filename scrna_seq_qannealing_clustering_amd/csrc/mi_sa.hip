@@ -240,7 +240,7 @@ struct mi_sa_problem {
         int mfma_permille = 600;                 // chunks that accept >= this share of their proposals hand the next one to K1m (0 = never)
         int chunk_sweeps = 32;                   // K1w/K1m: sweeps per launch of a chunked run (0 = one launch)
         int ondemand_permille = 40;              // K1w: on-demand sweeps below this acceptance (per mille); 0 = always stream
-        int unit_rows = 0;                       // K1w ring unit (rows per rendezvous): 0 auto, 2 or 4
+        int unit_rows = 0;                       // K1w ring unit (rows per rendezvous): 0 auto, 2 or 4 (4 is refused where its ring does not fit LDS: n > 3328)
         int debug = 0;                           // DenseArgs::debug (diagnostic timing only; results are wrong)
         int xl_batched = 0;                      // n > 4096: 0 auto (K1g for >= 256 replicas or n >= 16384), 1 always K1g, 2 always K1x
         int xl_chain = 0;                        // K1g, chain of a group of blocks: 0 auto (fused up to 512 replicas), 1 a DIAG and a small pass per block, 2 fused
