@@ -142,6 +142,12 @@ def _declare(lib):
         "mi_umap_fetch_graph": (C.c_int, [vp, C.POINTER(C.c_int64), i32p, f32p]),
         "mi_umap_layout_f32": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), i32p, f32p, f32p, C.c_float, C.c_float,
                                          C.c_float, C.c_int, C.c_int, C.c_uint64, C.c_int, f32p, f32p]),
+        # include/mi_annot.h
+        "mi_annot_create": (C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_int, C.POINTER(C.c_uint32), C.c_int, pp, f32p]),
+        "mi_annot_destroy": (C.c_int, [vp]),
+        "mi_annot_score": (C.c_int, [vp, f32p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), f64p,
+                                     i32p, f32p]),
+        "mi_annot_fine_tune": (C.c_int, [vp, i32p, f64p, f64p, i32p, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
@@ -167,6 +173,7 @@ EXPORTS = (
     "mi_prep_rank_sum_markers",
     "mi_umap_knn_f32", "mi_umap_destroy", "mi_umap_fetch_knn", "mi_umap_smooth", "mi_umap_fetch_smooth", "mi_umap_union",
     "mi_umap_info", "mi_umap_fetch_graph", "mi_umap_layout_f32",
+    "mi_annot_create", "mi_annot_destroy", "mi_annot_score", "mi_annot_fine_tune",
 )
 
 
