@@ -52,13 +52,15 @@ int mi_annot_destroy(mi_annot *h);
 /* X: n_c x m row-major f32, a chunk of test cells on the marker genes; it stays resident for mi_annot_fine_tune.  Outputs,
  * each nullable: out_sab n_c x S (sum a b, samples in the caller's order), out_sa2 n_c, out_sb2 S, out_scores n_c x L fp64,
  * out_first n_c (argmax of the scores, lowest label on ties); out_kernel_ms: 3 floats, the ranking, cross and score
- * kernels.  MI_EINVAL for NULL h or X, n_c < 1, a NaN or infinity in X; MI_EUNSUPPORTED for n_c > MI_ANNOT_MAX_CHUNK. */
+ * kernels.  MI_EINVAL for NULL h or X, n_c < 1, a NaN or infinity in X; MI_EUNSUPPORTED for n_c > MI_ANNOT_MAX_CHUNK.
+ * Every call with a handle first drops the chunk of the call before: after a call that was refused or that failed, no chunk
+ * is resident, and mi_annot_fine_tune returns MI_ESTATE until a later mi_annot_score succeeds. */
 int mi_annot_score(mi_annot *h, const float *X, int n_c, int64_t *out_sab, int64_t *out_sa2, int64_t *out_sb2,
                    double *out_scores, int32_t *out_first, float *out_kernel_ms);
 
 /* The fine-tuning loop on the resident chunk.  Outputs, n_c entries each, nullable: out_labels, out_best / out_next (the
- * largest and second-largest of the last scores computed; -inf for out_next when L = 1), out_iterations.  MI_ESTATE before
- * mi_annot_score. */
+ * largest and second-largest of the last scores computed; -inf for out_next when L = 1), out_iterations.  MI_ESTATE when
+ * no chunk is resident: before the first mi_annot_score, and after one that was refused or that failed. */
 int mi_annot_fine_tune(mi_annot *h, int32_t *out_labels, double *out_best, double *out_next, int32_t *out_iterations,
                        float *out_kernel_ms);
 

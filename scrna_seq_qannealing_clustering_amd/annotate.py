@@ -21,6 +21,7 @@ from . import _lib
 
 MAX_GENES, MAX_LABELS, MAX_SAMPLES, MAX_CHUNK = 8191, 64, 4096, 16384      # include/mi_annot.h
 QUANTILE, TUNE_THRESH, PRUNE_NMADS = 0.8, 0.05, 3.0
+MI_ESTATE = -6                                                             # include/mi_sa.h: a call out of order
 
 
 # ---- host steps -----------------------------------------------------------------------------------------------------------
@@ -229,7 +230,10 @@ class Annotator:
         return out
 
     def fine_tune(self) -> dict:
+        """the fine-tuning loop on the chunk of the last ``score`` call; after a ``score`` that raised there is none"""
         n = self.n_c
+        if n < 1:                                   # the outputs below are sized by n: never hand the library empty ones
+            raise _lib.MiSaError(MI_ESTATE, "score() has not run, or its last call was refused: no chunk is resident")
         labels, iters = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
         best, nxt = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
         ms = C.c_float(0.0)

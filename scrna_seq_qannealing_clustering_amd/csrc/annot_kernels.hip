@@ -590,7 +590,9 @@ int mi_annot_score(mi_annot *h, const float *X, int n_c, int64_t *out_sab, int64
                    double *out_scores, int32_t *out_first, float *out_kernel_ms)
 {
     if (out_kernel_ms) out_kernel_ms[0] = out_kernel_ms[1] = out_kernel_ms[2] = 0.0f;
-    if (!h || !X) return fail(MI_EINVAL, "NULL argument");
+    if (!h) return fail(MI_EINVAL, "NULL argument");
+    h->n_c = 0;                                // a refused or failed call leaves no resident chunk
+    if (!X) return fail(MI_EINVAL, "NULL argument");
     if (n_c < 1) return fail(MI_EINVAL, "n_c must be >= 1 (got %d)", n_c);
     if (n_c > MI_ANNOT_MAX_CHUNK) return fail(MI_EUNSUPPORTED, "%d cells exceed a chunk of %d", n_c, MI_ANNOT_MAX_CHUNK);
     const int S = h->S, m = h->m, L = h->L, mpad = h->mpad;
@@ -598,7 +600,6 @@ int mi_annot_score(mi_annot *h, const float *X, int n_c, int64_t *out_sab, int64
     if (!finite_bits(X, (size_t)n_c * m, &bad)) return fail(MI_EINVAL, "X[%zu, %zu] is not finite", bad / m, bad % m);
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(h->device));
-        h->n_c = 0;
         HIP_TRY(h->d_X.reserve((size_t)n_c * m));
         HIP_TRY(h->d_chi.reserve((size_t)n_c * mpad));
         HIP_TRY(h->d_clo.reserve((size_t)n_c * mpad));

@@ -50,10 +50,12 @@ def label_scores(m, sab_row, sa2, sb2, ids, labels):
     return out
 
 
-def scores(X, R, ids, L):
-    """step 3: (n, L) fp64 scores and the argmax (lowest id on ties)"""
+def scores(X, R, ids, L, row_of=None):
+    """step 3: (n, L) fp64 scores and the argmax (lowest id on ties).  ``row_of``: see :func:`annotate`."""
     ids = np.asarray(ids)
     sab, sa2, sb2 = integers(X, R)
+    if row_of is not None:
+        sab, sb2 = sab[:, row_of], sb2[row_of]
     m = np.shape(X)[1]
     sc = np.empty((sab.shape[0], L), dtype=np.float64)
     for i in range(sab.shape[0]):
@@ -67,21 +69,25 @@ def _top_two(values):
     return v[0], (v[1] if len(v) > 1 else -math.inf)
 
 
-def annotate(X, R, ids, L, pairs):
+def annotate(X, R, ids, L, pairs, trace=None, row_of=None):
     """Steps 3-5 on matrices restricted to the marker set M (n x m, S x m); ``pairs[(a, b)]``: positions in M.
-    -> dict: scores, first_labels, labels, tuned_best, tuned_next, iterations, margin (n,), delta, pruned."""
+    -> dict: scores, first_labels, labels, tuned_best, tuned_next, iterations, margin (n,), delta, pruned.
+    ``trace`` (a list) receives ``(cell, use, |G'|)`` for every pass of the fine-tuning loop.  ``row_of``: R holds only the
+    distinct sample rows and sample s is ``R[row_of[s]]`` (``ids`` has one entry per sample); a row's ranks depend on that
+    row alone, so the integers of the distinct rows, indexed, are the integers of all the samples."""
     X, R, ids = np.asarray(X), np.asarray(R), np.asarray(ids)
     n = X.shape[0]
-    sc, first = scores(X, R, ids, L)
+    sc, first = scores(X, R, ids, L, row_of)
     labels, iters = np.empty(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
     best, nxt, margin = np.empty(n), np.empty(n), np.full(n, np.inf)
-    ranked = {}                                    # use -> (G', the samples' doubled ranks over G', their sums of squares)
+    ranked = {}                                    # use -> (G', the rows' doubled ranks over G', the samples' sums of squares)
 
     def reference_side(use):
         if use not in ranked:
             genes = sorted(set(int(j) for a in use for b in use if a != b for j in pairs[(a, b)]))
             B = doubled_midranks(R[:, genes])
-            ranked[use] = (genes, B, (B * B).sum(axis=1))
+            sb2 = (B * B).sum(axis=1)
+            ranked[use] = (genes, B, sb2 if row_of is None else sb2[row_of])
         return ranked[use]
 
     def within(cur, i):
@@ -99,6 +105,10 @@ def annotate(X, R, ids, L, pairs):
             genes, B, sb2 = reference_side(use)
             a = doubled_midranks(X[i, genes])[0]
             sab, sa2 = B @ a, int((a * a).sum())
+            if row_of is not None:
+                sab = sab[row_of]
+            if trace is not None:
+                trace.append((i, use, len(genes)))
             cur = label_scores(len(genes), sab, sa2, sb2, ids, use)
             iters[i] += 1
             new = within(cur, i)
