@@ -138,6 +138,19 @@ int mi_sa_plan_anneal(int kind, const int32_t *rowptr, const int32_t *col, int n
                       int pair_weight_slot, int node_weights, int min_cluster_size, char *out_kernel, int len,
                       int *out_adjacency_bytes);
 
+/* Host-only planning of a dense model's anneal (touches no device, makes no HIP call): the kernel(s) mi_sa_anneal_ex would run
+ * for n <= 4096 variables (MI_EUNSUPPORTED above: the large-model kernels are still chosen by the anneal itself), R replicas,
+ * num_sweeps sweeps, resync_interval and flags (the MI_F_* of mi_sa_anneal_ex) on a device of `cus` compute units (0: 256)
+ * on which `resident_waves` wavefronts of the wave-per-replica kernel are co-resident (read only where that kernel serves the
+ * run; the library asks the device).  options: "key=value,..." with the dense keys of mi_sa_set_option -- pace, variant,
+ * unit_rows, ondemand_permille, chunk_sweeps, mfma_permille (NULL or "": the defaults).  Writes the name
+ * mi_sa_last_kernel_name reports after such a run,
+ * the launches mi_sa_last_launch_count reports and the bytes of cached fields the run keeps between its launches
+ * (both nullable); returns the code the anneal would fail with.  The plan depends on these arguments alone, never on what
+ * the handle ran before.  The one planning step of the library itself (csrc/mi_dense_plan.h). */
+int mi_sa_plan_dense(int n, int R, int num_sweeps, int resync_interval, uint32_t flags, int cus, int resident_waves,
+                     const char *options, char *out_kernel, int len, int *out_launches, uint64_t *out_field_bytes);
+
 /* The same planning with HOLES allowed: variable i gets the seat out_pos[i] = slot_index * slot + rank in a layout of
  * *out_slots slots (>= ceil(n / slot), at most max_slots), the fewest -- tried from the packed count upwards -- for which
  * the greedy pass leaves NO edge inside a slot; unused seats are holes.  Small or strongly clustered graphs (the

@@ -1,5 +1,5 @@
 // dense_kernels.hip -- the dense-QUBO anneal kernels (K1 wave-per-replica, K1w workgroup/LDS ring) and
-// their launcher for ONE field-register count NT = MI_NT (n <= 64*NT).  Compiled once per NT so that the
+// their thin launchers for ONE field-register count NT = MI_NT (n <= 64*NT).  Compiled once per NT so that the
 // sixteen sizes build in parallel (each is a fully unrolled ~10k-instruction kernel).
 //
 // Chain specification, layouts and the reference call sites served: see mi_sa.hip / DESIGN.md.
@@ -166,18 +166,14 @@ __global__ void __launch_bounds__(256, 4) k_anneal_dense(DenseArgs a)
 //         (U-2) units stay in flight across every barrier.
 //   lockstep: the 16 waves rendezvous once per unit (GR rows); inside a unit each wave runs its own
 //         accept/commit loop on the unit's rows.
-constexpr int kWgWaves = 16;
-constexpr int kLdsBytes = 160 * 1024 - 256;   // ring budget; the last 256 bytes hold the sweep-mode words
-
+// (kWgWaves = 16 and the ring arithmetic, dense_ring_units: csrc/mi_dense_plan.h, where the planner reads the same)
 template <int NT, int GR>
 struct WgCfg {
     static constexpr int ROWB = NT * 256;
     static constexpr int UNITB = GR * ROWB;
     static constexpr int G = NT / 4;                    // 1 KiB pieces per row (<= 16)
-    static constexpr int Ufit = kLdsBytes / UNITB;
-    static constexpr int Ucap = 2 + 60 / GR;            // keeps (U-2)*GR within the 6-bit vmcnt
-    static constexpr int U = Ufit < Ucap ? Ufit : Ucap;
-    static constexpr bool ok = U >= 3 && (64 % GR) == 0;
+    static constexpr int U = dense_ring_units(NT, GR);  // units in the ring: what fits, (U-2)*GR within the 6-bit vmcnt
+    static constexpr bool ok = U > 0;
 };
 
 
@@ -467,63 +463,12 @@ __global__ void __launch_bounds__(1024, 4) k_anneal_dense_wg(DenseArgs a)
 
 namespace {
 
-
-// Launches the anneal in chunks of at most `resident` replicas (= wavefronts), so that every wave of
-// a launch is co-resident and the sweep pacing rendezvous can complete; chunks run back to back on
-// the stream.  Each chunk gets its own zeroed pacing words.
-template <int NT>
-int launch_dense(const DenseLaunchCtx &p, DenseArgs a, hipStream_t st)
-{
-    if ((*p.resident_waves) == 0) {
-        int blocks_per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_anneal_dense<NT>, 256, 0));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p.device));
-        (*p.resident_waves) = blocks_per_cu * cus * 4;
-        if ((*p.resident_waves) < 4) return fail(MI_EHIP, "anneal kernel cannot be resident (occupancy 0)");
-    }
-    const int total = a.R;
-    const uint32_t base_offset = a.replica_offset;
-    const uint8_t *init0 = a.init;
-    uint8_t *states0 = a.states;
-    double *energy0 = a.energy;
-    const float *temps0 = a.temps;
-    int chunk = (*p.resident_waves);
-    if ((total + chunk - 1) / chunk > kMaxChunks) chunk = (total + kMaxChunks - 1) / kMaxChunks;
-    const bool pace = p.opt_pace && a.num_sweeps > 1;
-    if (pace)
-        HIP_TRY(hipMemsetAsync(p.d_pace, 0, kMaxChunks * kPaceWords * sizeof(unsigned int), st));
-    int c = 0;
-    for (int lo = 0; lo < total; lo += chunk, ++c) {
-        const int cnt = total - lo < chunk ? total - lo : chunk;
-        a.R = cnt;
-        a.replica_offset = base_offset + (uint32_t)lo;
-        a.init = init0 ? init0 + (size_t)lo * a.n : nullptr;
-        a.states = states0 + (size_t)lo * a.n;
-        a.energy = energy0 + lo;
-        a.temps = temps0 + (a.temps_per_replica ? lo : 0);          // one temperature per replica: the chunk's own
-        a.pace = (pace && cnt <= (*p.resident_waves)) ? p.d_pace + (size_t)c * kPaceWords : nullptr;
-        note_kernel("k_anneal_dense<%d>", NT);
-        hipLaunchKernelGGL(k_anneal_dense<NT>, dim3((cnt + 3) / 4), dim3(256), 0, st, a);
-        HIP_TRY(hipGetLastError());
-    }
-    *p.launches = c;
-    return MI_OK;
-}
-
+// The launchers: a switch from what the plan names (csrc/mi_dense_plan.h) to the instantiation, and its launch.  Which kernel
+// serves a run, on which replicas and sweeps, with which buffers and pacing words is the plan's to say (anneal_dense, mi_sa.hip).
 template <int NT, int GR>
-int launch_dense_wg(const DenseLaunchCtx &p, DenseArgs a, hipStream_t st)
+int launch_dense_wg(const DenseArgs &a, hipStream_t st)
 {
     if constexpr (WgCfg<NT, GR>::ok) {
-        int cus = 0;
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p.device));
-        const int blocks = (a.R + kWgWaves - 1) / kWgWaves;
-        a.ondemand_flips = (int)((long long)p.opt_ondemand_permille * a.n * kWgWaves / 1000);
-        a.pace = nullptr;
-        if (p.opt_pace && a.num_sweeps > 1 && blocks <= cus) {     // one 160 KB workgroup per CU
-            HIP_TRY(hipMemsetAsync(p.d_pace, 0, kPaceWords * sizeof(unsigned int), st));
-            a.pace = p.d_pace;
-        }
-        note_kernel("k_anneal_dense_wg<%d,%d>", NT, GR);
         hipLaunchKernelGGL((k_anneal_dense_wg<NT, GR>), dim3((a.R + kWgWaves - 1) / kWgWaves), dim3(1024), 0, st, a);
         HIP_TRY(hipGetLastError());
         return MI_OK;
@@ -532,130 +477,36 @@ int launch_dense_wg(const DenseLaunchCtx &p, DenseArgs a, hipStream_t st)
     }
 }
 
-// sweeps until the first field re-synchronisation of a launch that starts at sweep s0 of its run
-inline int resync_first_for(int resync, int s0)
+int launch_dense(const DenseArgs &a, int unit_rows, hipStream_t st)
 {
-    return resync > 0 ? ((resync - s0 % resync) % resync) + 1 : 0;
+    switch (unit_rows) {
+    case 0:
+        hipLaunchKernelGGL(k_anneal_dense<MI_NT>, dim3((a.R + 3) / 4), dim3(256), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        return MI_OK;
+    case 2: return launch_dense_wg<MI_NT, 2>(a, st);
+    case 4: return launch_dense_wg<MI_NT, 4>(a, st);
+    }
+    return fail(MI_EUNSUPPORTED, "LDS ring unit of %d rows is not built for NT=%d", unit_rows, MI_NT);
 }
 
-template <int NT>
-int launch_dense_wg_any(const DenseLaunchCtx &p, const DenseArgs &a, hipStream_t st)
+int k1_blocks_per_cu(int *out)
 {
-    int gr = p.opt_unit_rows ? p.opt_unit_rows : 4;       // 4 rows per rendezvous measured fastest
-    if (!p.opt_unit_rows && !WgCfg<NT, 4>::ok) gr = 2;    // (NT >= 56; a unit of 4 rows asked for by option is refused there)
-    switch (gr) {
-        case 2: return launch_dense_wg<NT, 2>(p, a, st);
-        case 4: return launch_dense_wg<NT, 4>(p, a, st);
-    }
-    return fail(MI_EUNSUPPORTED, "LDS ring unit of %d rows is not built for NT=%d", gr, NT);
-}
-
-// K1w over a long schedule: the run is cut into launches of `chunk` sweeps.  State (bits in
-// DenseArgs::states, cached fields in DenseArgs::fields) persists in HBM between launches, so the cut
-// points are invisible to the chain -- results are bit-identical to one launch -- and each launch can
-// be served by whichever kernel suits the acceptance rate the run has reached.
-template <int NT>
-int launch_dense_mfma(const DenseArgs &a, hipStream_t st)
-{
-#if MI_NT <= 44
-#define MI_CAT2(x, y) x##y
-#define MI_CAT(x, y) MI_CAT2(x, y)
-    return MI_CAT(mi_launch_dense_mfma_nt, MI_NT)(a, st);
-#undef MI_CAT
-#undef MI_CAT2
-#else
-    (void)a; (void)st;
-    return fail(MI_EUNSUPPORTED, "K1m is not built for NT=%d (n > %d)", NT, kMaxMfmaNT * 64);
-#endif
-}
-
-template <int NT>
-int launch_dense_chunked(const DenseLaunchCtx &p, const DenseArgs &a, hipStream_t st, int variant)
-{
-    const int chunk = p.opt_chunk_sweeps;
-    // variant 4 = scheduled: every chunk is offered to both kernels, the device-side mode word decides
-    const bool scheduled = (variant == 4);
-    if (variant == 3 && (chunk <= 0 || a.num_sweeps <= chunk || !p.d_fields)) {
-        DenseArgs b = a;
-        b.fields = nullptr; b.ctrl = nullptr; b.flags = 0; b.my_mode = 0; b.mode_up_flips = 0; b.chunk_index = 0;
-        b.resync_first = resync_first_for(a.resync, 0);
-        return launch_dense_mfma<NT>(b, st);
-    }
-    if (chunk <= 0 || a.num_sweeps <= chunk || !p.d_fields) {
-        DenseArgs b = a;
-        b.fields = nullptr; b.ctrl = nullptr; b.flags = 0; b.my_mode = 0; b.mode_up_flips = 0; b.chunk_index = 0;
-        b.resync_first = resync_first_for(a.resync, 0);
-        return launch_dense_wg_any<NT>(p, b, st);   // (variant 4 never gets here: it requires chunking)
-    }
-    if (scheduled) {
-        if ((a.num_sweeps + chunk - 1) / chunk + 2 > kCtrlWords - kCtrlModes)
-            return fail(MI_EINVAL, "too many chunks for the scheduler: raise chunk_sweeps");
-        HIP_TRY(hipMemsetAsync(p.d_ctrl, 0, kCtrlWords * sizeof(unsigned int), st));
-        const unsigned int start = kModeMfma;            // start hot; a short first chunk calibrates
-        HIP_TRY(hipMemcpyAsync(p.d_ctrl + kCtrlModes, &start, sizeof start, hipMemcpyHostToDevice, st));
-    }
-    int chunk_index = 0;
-    const int first_len = scheduled ? (chunk < 8 ? chunk : 8) : chunk;
-    for (int s0 = 0, len = first_len; s0 < a.num_sweeps; s0 += len, len = chunk) {
-        const bool first = (s0 == 0), last = (s0 + len >= a.num_sweeps);
-        DenseArgs b = a;
-        b.num_sweeps = last ? a.num_sweeps - s0 : len;
-        b.temps = a.temps_per_replica ? a.temps : a.temps + s0;
-        b.sweep_offset = a.sweep_offset + (uint32_t)s0;
-        b.init = first ? a.init : a.states;
-        b.fields = p.d_fields; b.ctrl = nullptr; b.my_mode = 0; b.mode_up_flips = 0;
-        b.flags = (first ? 0 : kDenseFieldsIn) | (last ? 0 : (kDenseFieldsOut | kDenseNoEnergy));
-        b.resync_first = resync_first_for(a.resync, s0);
-        b.chunk_index = chunk_index++;
-        int rc;
-        if (scheduled) {
-            // next chunk goes to K1m when this one accepted at least opt_mfma_permille of its proposals
-            b.ctrl = p.d_ctrl;
-            b.mode_up_flips = (unsigned int)((double)p.opt_mfma_permille * 1e-3 * (double)a.R * a.n * b.num_sweeps);
-            if (b.mode_up_flips == 0) b.mode_up_flips = 1;
-            b.my_mode = (int)kModeMfma;
-            rc = launch_dense_mfma<NT>(b, st);
-            if (rc) return rc;
-            b.my_mode = (int)kModeWg;
-            rc = launch_dense_wg_any<NT>(p, b, st);
-        } else {
-            rc = (variant == 3) ? launch_dense_mfma<NT>(b, st) : launch_dense_wg_any<NT>(p, b, st);
-        }
-        if (rc) return rc;
-    }
-    *p.launches = chunk_index;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k_anneal_dense<MI_NT>, 256, 0));
     return MI_OK;
-}
-
-template <int NT>
-int launch_dense_any(const DenseLaunchCtx &p, const DenseArgs &a, hipStream_t st)
-{
-    int variant = p.opt_variant;
-    if (variant == 0) {
-        variant = (a.R >= 2 * kWgWaves && a.num_sweeps > 0) ? 2 : 1;
-        // 128 .. 1024 replicas: a run is one chain's latency whatever serves it (85 ms per 200 sweeps at n = 2638 from 64 to
-        // 2048 replicas), and with at most one wavefront per SIMD the wave-per-replica kernel is the quicker one by 7-10 %
-        // (scripts/perf_dense_few.py); same chain, bit for bit
-        if (variant == 2 && a.R >= 128 && a.R <= 1024) variant = 1;
-        // long schedules on sizes K1m is built for: let the device alternate K1m (hot) and K1w (cold)
-        if (variant == 2 && NT <= kMaxMfmaNT && a.Qm && p.d_fields && p.opt_chunk_sweeps > 0 &&
-            a.num_sweeps > p.opt_chunk_sweeps && p.opt_mfma_permille > 0)
-            variant = 4;
-    }
-    if (variant >= 2) return launch_dense_chunked<NT>(p, a, st, variant);
-    DenseArgs b = a;
-    b.fields = nullptr; b.ctrl = nullptr; b.flags = 0; b.my_mode = 0; b.mode_up_flips = 0; b.chunk_index = 0;
-    b.resync_first = resync_first_for(a.resync, 0);
-    return launch_dense<NT>(p, b, st);
 }
 
 }  // namespace
 
 #define MI_CAT2(a, b) a##b
 #define MI_CAT(a, b) MI_CAT2(a, b)
-int MI_CAT(mi_launch_dense_nt, MI_NT)(const DenseLaunchCtx &ctx, const DenseArgs &a, hipStream_t st)
+DenseWidth MI_CAT(mi_dense_nt, MI_NT)()
 {
-    return launch_dense_any<MI_NT>(ctx, a, st);
+#if MI_NT <= 44
+    return DenseWidth{launch_dense, k1_blocks_per_cu, MI_CAT(mi_launch_dense_mfma_nt, MI_NT)};
+#else
+    return DenseWidth{launch_dense, k1_blocks_per_cu, nullptr};
+#endif
 }
 
 }  // namespace mi_sa_impl

@@ -167,9 +167,9 @@ struct mi_sa_problem {
         int NT = 0;
         DevArray<float> d_Qp;
         DevArray<float> d_Qm;                    // K1m: plain row-major Q2 + diagonal row (NT <= 44)
-        DevArray<float> d_fields;                // cached fields between the launches of a chunked run
-        DevArray<unsigned int> d_ctrl;           // kernel-scheduling words
-        int resident_waves = 0;                  // co-resident wavefronts of the anneal kernel on this device
+        DevArray<float> d_fields;                // cached fields between the launches of a run that is cut (DensePlan::field_floats)
+        DevArray<unsigned int> d_ctrl;           // kernel-scheduling words (the scheduled form)
+        int resident_waves = 0;                  // co-resident wavefronts of K1 on this device (0: not asked yet)
     } dense;
     struct DenseXl {                             // n > 4096: the model and the state of a run
         int chunks = 0;
@@ -235,12 +235,6 @@ struct mi_sa_problem {
         DevArray<unsigned int> d_pace;           // kPaceWords per launch chunk
     } run;
     struct Options {                             // mi_sa_set_option
-        int pace = 1;                            // sweep pacing on/off (speed only)
-        int variant = 0;                         // 0 auto, 1 wave-per-replica (K1), 2 workgroup/LDS ring (K1w), 3 MFMA (K1m)
-        int mfma_permille = 600;                 // chunks that accept >= this share of their proposals hand the next one to K1m (0 = never)
-        int chunk_sweeps = 32;                   // K1w/K1m: sweeps per launch of a chunked run (0 = one launch)
-        int ondemand_permille = 40;              // K1w: on-demand sweeps below this acceptance (per mille); 0 = always stream
-        int unit_rows = 0;                       // K1w ring unit (rows per rendezvous): 0 auto, 2 or 4 (4 is refused where its ring does not fit LDS: n > 3328)
         int debug = 0;                           // DenseArgs::debug (diagnostic timing only; results are wrong)
         int xl_batched = 0;                      // n > 4096: 0 auto (K1g for >= 256 replicas or n >= 16384), 1 always K1g, 2 always K1x
         int xl_chain = 0;                        // K1g, chain of a group of blocks: 0 auto (fused up to 512 replicas), 1 a DIAG and a small pass per block, 2 fused
@@ -249,6 +243,7 @@ struct mi_sa_problem {
         int xl_async = 1;                        // that cooling run is driven by a worker thread: mi_sa_anneal returns at once (0 = in the caller)
         int min_cluster_size = 0;                // K3: hard lower bound on every cluster's size (CQM_clustering.py:46-48)
         PlanOptions plan;                        // the k2_* / k3_* options: what the planner reads (csrc/mi_sa_plan.h)
+        DensePlanOptions dense;                  // pace, variant, unit_rows, *_permille, chunk_sweeps: what the dense planner reads (csrc/mi_dense_plan.h)
     } opt;
     struct Tempering {                           // mi_sa_tempering_*: ladder, rung of every replica of the run, exchange statistics
         int T = 0, chains = 0, lo = 0, R_local = 0;
@@ -275,7 +270,6 @@ struct mi_sa_problem {
 
 namespace {
 
-constexpr int kMaxDenseN = 64 * 64;        // register-per-wave kernels (K1, K1w, K1m)
 constexpr int kMaxDenseXlN = 16 * 4096;    // workgroup-per-replica kernel (K1x)
 
 // d_states, d_energy and d_init (where it exists) always hold the same number of replicas, d_energy.count: growing resets
@@ -295,27 +289,17 @@ int ensure_run_buffers(mi_sa_problem *p, int R, int num_sweeps, bool need_init)
     return MI_OK;
 }
 
-int dispatch_dense(mi_sa_problem *p, const DenseArgs &a, hipStream_t st)
+// what the translation unit of a register width exports (csrc/dense_kernels.hip)
+DenseWidth dense_width_unit(int NT)
 {
-    mi_sa_problem::Dense &d = p->dense;
-    const mi_sa_problem::Options &o = p->opt;
-    if (o.chunk_sweeps > 0 && a.num_sweeps > o.chunk_sweeps && o.variant != 1 && a.R >= 32)
-        HIP_TRY(d.d_fields.reserve((size_t)a.R * d.NT * 64));
-    if (!d.d_ctrl) {
-        HIP_TRY(d.d_ctrl.resize(kCtrlWords));
-        HIP_TRY(hipMemset(d.d_ctrl, 0, kCtrlWords * sizeof(unsigned int)));
-    }
-    DenseLaunchCtx ctx{p->device, o.pace, o.variant, o.unit_rows, o.ondemand_permille, o.chunk_sweeps, o.mfma_permille,
-                       d.d_fields, d.d_ctrl, p->run.d_pace, &d.resident_waves, &p->last.launches};
-    p->last.launches = 1;
-    switch (d.NT) {
-#define MI_CASE(N) case N: return mi_launch_dense_nt##N(ctx, a, st);
+    switch (NT) {
+#define MI_CASE(N) case N: return mi_dense_nt##N();
         MI_CASE(4) MI_CASE(8) MI_CASE(12) MI_CASE(16) MI_CASE(20) MI_CASE(24) MI_CASE(28)
         MI_CASE(32) MI_CASE(36) MI_CASE(40) MI_CASE(44) MI_CASE(48) MI_CASE(52) MI_CASE(56)
         MI_CASE(60) MI_CASE(64)
 #undef MI_CASE
     }
-    return fail(MI_EUNSUPPORTED, "dense kernel not built for NT=%d", d.NT);
+    return DenseWidth{nullptr, nullptr, nullptr};
 }
 
 // A cooling run on the batched large-model kernels decides its hand-over per chunk on the host (anneal_dense_xl), in a
@@ -539,6 +523,22 @@ int upload_linear_terms(mi_sa_problem *p, const float *lin)
     return MI_OK;
 }
 
+// "key=value,..." with the keys of mi_sa_set_option that `set` takes (the host-only planning entries)
+template <typename F>
+int parse_option_string(const char *options, F &&set)
+{
+    for (const char *s = options ? options : ""; *s;) {
+        const char *end = strchr(s, ','), *eq = strchr(s, '=');
+        if (!end) end = s + strlen(s);
+        const std::string key(s, eq && eq < end ? eq : end);
+        char *stop = nullptr;
+        const long value = eq && eq < end ? strtol(eq + 1, &stop, 10) : 0;
+        if (stop != end || stop == eq + 1 || !set(key.c_str(), value)) return fail(MI_EINVAL, "unknown option '%s'", key.c_str());
+        s = *end ? end + 1 : end;
+    }
+    return MI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -752,6 +752,37 @@ int mi_sa_plan_slot_order(const int32_t *rowptr, const int32_t *col, int n, int 
     return guarded([&]() -> int { return plan_slot_order_impl(rowptr, col, n, slot, out_perm); });
 }
 
+int mi_sa_plan_dense(int n, int R, int num_sweeps, int resync_interval, uint32_t flags, int cus, int resident_waves,
+                     const char *options, char *out_kernel, int len, int *out_launches, uint64_t *out_field_bytes)
+{
+    if (!out_kernel || len < 1) return fail(MI_EINVAL, "NULL argument");
+    if (flags & ~(uint32_t)(MI_F_CONTINUE | MI_F_BETA_PER_REPLICA | MI_F_TEMPS_RESIDENT | MI_F_BETA_PER_GROUP))
+        return fail(MI_EINVAL, "unknown flags 0x%x", flags);
+    if (n < 1) return fail(MI_EINVAL, "n must be >= 1 (got %d)", n);
+    if (R < 1) return fail(MI_EINVAL, "R must be >= 1 (got %d)", R);
+    if (num_sweeps < 0) return fail(MI_EINVAL, "num_sweeps must be >= 0");
+    if (resync_interval < 0) return fail(MI_EINVAL, "resync_interval must be >= 0");
+    return guarded([&]() -> int {
+        DensePlanOptions opts;
+        MI_TRY(parse_option_string(options, [&](const char *key, long value) { return dense_plan_option_set(opts, key, value); }));
+        DenseRun run;
+        run.n = n; run.R = R; run.num_sweeps = num_sweeps; run.resync = resync_interval;
+        run.temps_per_replica = (flags & (MI_F_BETA_PER_REPLICA | MI_F_TEMPS_RESIDENT)) != 0;
+        run.cus = cus; run.resident_waves = resident_waves;
+        std::string err;
+        int launches = 1;
+        uint64_t field_bytes = 0;
+        DensePlan plan;
+        if (const int rc = plan_dense(run, opts, &plan, &err)) return fail(rc, "%s", err.c_str());
+        dense_plan_kernel_name(plan, out_kernel, (size_t)len);
+        launches = plan.launches;
+        field_bytes = (uint64_t)plan.field_floats * sizeof(float);
+        if (out_launches) *out_launches = launches;
+        if (out_field_bytes) *out_field_bytes = field_bytes;
+        return MI_OK;
+    });
+}
+
 int mi_sa_plan_anneal(int kind, const int32_t *rowptr, const int32_t *col, int n, int K, int R, int cus, const char *options,
                       int pair_weight_slot, int node_weights, int min_cluster_size, char *out_kernel, int len,
                       int *out_adjacency_bytes)
@@ -766,15 +797,7 @@ int mi_sa_plan_anneal(int kind, const int32_t *rowptr, const int32_t *col, int n
         if (!rc) rc = slot_model_facts(kind, rowptr, col, n, kind == MI_KIND_CSR_RANK1 ? 2 : K, getenv("MI_K2_STATE"), &facts, &err);
         if (rc) return fail(rc, "%s", err.c_str());
         PlanOptions opts;
-        for (const char *s = options ? options : ""; *s;) {         // "key=value,..." with the keys of mi_sa_set_option
-            const char *end = strchr(s, ','), *eq = strchr(s, '=');
-            if (!end) end = s + strlen(s);
-            const std::string key(s, eq && eq < end ? eq : end);
-            char *stop = nullptr;
-            const long value = eq && eq < end ? strtol(eq + 1, &stop, 10) : 0;
-            if (stop != end || stop == eq + 1 || !plan_option_set(opts, key.c_str(), value)) return fail(MI_EINVAL, "unknown option '%s'", key.c_str());
-            s = *end ? end + 1 : end;
-        }
+        MI_TRY(parse_option_string(options, [&](const char *key, long value) { return plan_option_set(opts, key, value); }));
         RunFacts run;
         run.R = R; run.cus = cus; run.pair_weight_slot = kind == MI_KIND_CSR_RANK1 ? pair_weight_slot : -1;
         run.node_weights = node_weights != 0; run.min_cluster_size = min_cluster_size;
@@ -1041,15 +1064,12 @@ int mi_sa_set_option(mi_sa_problem *p, const char *key, long value)
 {
     return on_problem(p, key != nullptr, 0, [&]() -> int {
         mi_sa_problem::Options &o = p->opt;
-        if (!strcmp(key, "pace")) { o.pace = value != 0; return MI_OK; }
+        if (dense_plan_option_set(o.dense, key, value)) return MI_OK;      // (pace, variant, unit_rows, chunk_sweeps, *_permille: csrc/mi_dense_plan.h)
         if (!strcmp(key, "xl_batched") && value >= 0 && value <= 2) { o.xl_batched = (int)value; return MI_OK; }
         if (!strcmp(key, "xl_chunk") && value >= 1) { o.xl_chunk = (int)value; return MI_OK; }
         if (!strcmp(key, "xl_chain") && value >= 0 && value <= 2) { o.xl_chain = (int)value; return MI_OK; }
         if (!strcmp(key, "xl_cold_permille") && value >= 0 && value <= 1000) { o.xl_cold_permille = (int)value; return MI_OK; }
         if (!strcmp(key, "xl_async") && value >= 0 && value <= 1) { o.xl_async = (int)value; return MI_OK; }
-        if (!strcmp(key, "mfma_permille") && value >= 0 && value <= 1000) { o.mfma_permille = (int)value; return MI_OK; }
-        if (!strcmp(key, "chunk_sweeps") && value >= 0) { o.chunk_sweeps = (int)value; return MI_OK; }
-        if (!strcmp(key, "ondemand_permille") && value >= 0 && value <= 1000) { o.ondemand_permille = (int)value; return MI_OK; }
         if (!strcmp(key, "debug")) { o.debug = (int)value; return MI_OK; }
         if (plan_option_set(o.plan, key, value)) return MI_OK;             // (the k2_* / k3_* keys: csrc/mi_sa_plan.h)
         if (!strcmp(key, "min_cluster_size") && value >= 0) {
@@ -1059,8 +1079,6 @@ int mi_sa_set_option(mi_sa_problem *p, const char *key, long value)
             o.min_cluster_size = (int)value;
             return MI_OK;
         }
-        if (!strcmp(key, "variant") && value >= 0 && value <= 4) { o.variant = (int)value; return MI_OK; }
-        if (!strcmp(key, "unit_rows") && (value == 0 || value == 2 || value == 4)) { o.unit_rows = (int)value; return MI_OK; }
         return fail(MI_EINVAL, "unknown option '%s'", key);
     });
 }
@@ -1150,6 +1168,15 @@ int stage_anneal(mi_sa_problem *p, int R, uint32_t replica_offset, int num_sweep
     return MI_OK;
 }
 
+// the run of a dense anneal as the planners see it (csrc/mi_dense_plan.h)
+DenseRun dense_run_of(const mi_sa_problem *p, const AnnealCall &call)
+{
+    DenseRun run;
+    run.n = p->n; run.R = call.R; run.num_sweeps = call.num_sweeps; run.resync = call.resync;
+    run.temps_per_replica = call.per_replica; run.cus = p->cus; run.resident_waves = p->dense.resident_waves;
+    return run;
+}
+
 int anneal_dense_xl(mi_sa_problem *p, const AnnealCall &call)
 {
     const mi_sa_problem::Options &o = p->opt;
@@ -1224,15 +1251,102 @@ int anneal_dense_xl(mi_sa_problem *p, const AnnealCall &call)
     return MI_OK;
 }
 
+// sweeps until the first field re-synchronisation of a launch that starts at sweep s0 of its run
+inline int resync_first_for(int resync, int s0)
+{
+    return resync > 0 ? ((resync - s0 % resync) % resync) + 1 : 0;
+}
+
+// n <= 4096: the plan says which kernel(s), on which sweeps and replicas, with which buffers (csrc/mi_dense_plan.h); this
+// walks its launches.  A run that is cut keeps its state (DenseArgs::states) and cached fields (DenseArgs::fields) in HBM
+// between launches, so the cut points are invisible to the chain -- results are bit-identical to one launch.
 int anneal_dense(mi_sa_problem *p, const AnnealCall &call)
 {
+    mi_sa_problem::Dense &d = p->dense;
+    const DenseWidth unit = dense_width_unit(d.NT);
+    if (!unit.launch) return fail(MI_EUNSUPPORTED, "dense kernel not built for NT=%d", d.NT);
+    if (!d.resident_waves && dense_plan_is_k1(dense_run_of(p, call), p->opt.dense)) {     // K1's occupancy at this width: asked once, by the first run K1 serves
+        int blocks_per_cu = 0;
+        MI_TRY(unit.k1_blocks_per_cu(&blocks_per_cu));
+        d.resident_waves = blocks_per_cu * p->cus * 4;
+    }
+    DensePlan plan;
+    std::string plan_err;
+    if (const int rc_p = plan_dense(dense_run_of(p, call), p->opt.dense, &plan, &plan_err)) return fail(rc_p, "%s", plan_err.c_str());
+    if (plan.field_floats) HIP_TRY(d.d_fields.reserve(plan.field_floats));
+    if (plan.form == DENSE_SCHEDULED && !d.d_ctrl) HIP_TRY(d.d_ctrl.resize(kCtrlWords));
+    char name[128];
+    dense_plan_kernel_name(plan, name, sizeof name);
+    note_kernel("%s", name);
+    p->last.launches = plan.launches;
+
     DenseArgs a;
     fill_common(a, p, call);
-    a.Qp = p->dense.d_Qp; a.Qm = p->dense.d_Qm; a.pace = nullptr;
+    a.Qp = d.d_Qp; a.Qm = d.d_Qm; a.pace = nullptr;
     a.debug = p->opt.debug; a.ondemand_flips = 0;
-    HIP_TRY(hipEventRecord(p->ev.e[0], p->stream));
-    MI_TRY(dispatch_dense(p, a, p->stream));
-    HIP_TRY(hipEventRecord(p->ev.e[1], p->stream));
+    a.fields = nullptr; a.ctrl = nullptr; a.flags = 0; a.my_mode = 0; a.mode_up_flips = 0; a.chunk_index = 0;
+    a.resync_first = resync_first_for(a.resync, 0);
+    unsigned int *d_pace = p->run.d_pace;
+    hipStream_t st = p->stream;
+    HIP_TRY(hipEventRecord(p->ev.e[0], st));
+    if (plan.form == DENSE_K1) {
+        // launches of at most `resident` replicas (= wavefronts), so that every wave of a launch is co-resident and the sweep
+        // pacing rendezvous can complete; they run back to back on the stream, each with its own zeroed pacing words
+        if (plan.k1_pace) HIP_TRY(hipMemsetAsync(d_pace, 0, kMaxChunks * kPaceWords * sizeof(unsigned int), st));
+        for (int lo = 0, c = 0; lo < call.R; lo += plan.replicas_per_launch, ++c) {
+            DenseArgs b = a;
+            b.R = call.R - lo < plan.replicas_per_launch ? call.R - lo : plan.replicas_per_launch;
+            b.replica_offset = a.replica_offset + (uint32_t)lo;
+            b.init = a.init ? a.init + (size_t)lo * a.n : nullptr;
+            b.states = a.states + (size_t)lo * a.n;
+            b.energy = a.energy + lo;
+            b.temps = a.temps + (a.temps_per_replica ? lo : 0);          // one temperature per replica: the launch's own
+            b.pace = dense_k1_paced(plan, b.R) ? d_pace + (size_t)c * kPaceWords : nullptr;
+            MI_TRY(unit.launch(b, 0, st));
+        }
+    } else {
+        auto launch_k1w = [&](DenseArgs b) -> int {
+            b.ondemand_flips = plan.ondemand_flips;
+            if (plan.wg_pace && b.num_sweeps > 1) {
+                HIP_TRY(hipMemsetAsync(d_pace, 0, kPaceWords * sizeof(unsigned int), st));
+                b.pace = d_pace;
+            }
+            return unit.launch(b, plan.unit_rows, st);
+        };
+        if (plan.form == DENSE_SCHEDULED) {
+            // every launch is offered to both kernels, the device-side mode word decides
+            HIP_TRY(hipMemsetAsync(d.d_ctrl, 0, kCtrlWords * sizeof(unsigned int), st));
+            const unsigned int start = kModeMfma;            // start hot; a short first launch calibrates
+            HIP_TRY(hipMemcpyAsync(d.d_ctrl + kCtrlModes, &start, sizeof start, hipMemcpyHostToDevice, st));
+        }
+        for (int i = 0; i < plan.steps; ++i) {
+            const DenseStep step = dense_plan_step(plan, i);
+            DenseArgs b = a;
+            b.num_sweeps = step.len;
+            b.temps = a.temps_per_replica ? a.temps : a.temps + step.s0;
+            b.sweep_offset = a.sweep_offset + (uint32_t)step.s0;
+            b.init = step.first ? a.init : a.states;
+            b.resync_first = resync_first_for(a.resync, step.s0);
+            b.chunk_index = i;
+            if (plan.cut) {
+                b.fields = d.d_fields;
+                b.flags = (step.first ? 0 : kDenseFieldsIn) | (step.last ? 0 : (kDenseFieldsOut | kDenseNoEnergy));
+            }
+            if (plan.form == DENSE_SCHEDULED) {
+                // next launch goes to K1m when this one accepted at least mfma_permille of its proposals
+                b.ctrl = d.d_ctrl;
+                b.mode_up_flips = (unsigned int)((double)p->opt.dense.mfma_permille * 1e-3 * (double)a.R * a.n * b.num_sweeps);
+                if (b.mode_up_flips == 0) b.mode_up_flips = 1;
+                b.my_mode = (int)kModeMfma;
+                MI_TRY(unit.launch_mfma(b, st));
+                b.my_mode = (int)kModeWg;
+                MI_TRY(launch_k1w(b));
+            } else {
+                MI_TRY(plan.form == DENSE_K1M ? unit.launch_mfma(b, st) : launch_k1w(b));
+            }
+        }
+    }
+    HIP_TRY(hipEventRecord(p->ev.e[1], st));
     return MI_OK;
 }
 

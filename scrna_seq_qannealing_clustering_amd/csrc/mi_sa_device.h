@@ -9,6 +9,7 @@
 
 #include "mi_sa_host.h"
 #include "mi_sa_plan.h"
+#include "mi_dense_plan.h"
 
 namespace mi_sa_impl {
 
@@ -219,7 +220,7 @@ struct DenseArgs {
     uint32_t sweep_offset;  // added to the sweep index in the RNG counter (continuation of an earlier run)
     int temps_per_replica;  // 0: temps[s] per sweep; 1: temps[r], one constant temperature per replica
     float *fields;          // cached local fields between launches, canonical [R][64*NT] (nullable)
-    unsigned int *ctrl;     // kernel-scheduling words (see dense_mfma / launch_dense_chunked), nullable
+    unsigned int *ctrl;     // kernel-scheduling words (see sched_my_turn; anneal_dense in mi_sa.hip), nullable
     int flags;              // kDenseFieldsIn | kDenseFieldsOut | kDenseNoEnergy
     int resync_first;       // sweeps until the first field re-synchronisation of this launch (resync > 0)
     int my_mode;            // mode value for which this kernel serves its chunk (otherwise it exits at once)
@@ -543,8 +544,7 @@ __device__ __forceinline__ double dense_energy_f64(__amdgpu_buffer_rsrc_t rsrc, 
 // kernel that did run picks the mode of the NEXT chunk from the acceptance the run has reached (a word per
 // chunk, so the second kernel of the same chunk cannot see the update).  Results do not depend on the
 // choice: same chain, same state.
-constexpr unsigned int kModeWg = 0, kModeMfma = 1;
-constexpr int kCtrlModes = 8, kCtrlWords = 4096;
+constexpr unsigned int kModeWg = 0, kModeMfma = 1;      // (kCtrlModes, kCtrlWords: csrc/mi_dense_plan.h)
 
 __device__ __forceinline__ bool sched_my_turn(const DenseArgs &a)
 {
@@ -578,23 +578,14 @@ MI_DECLARE_MFMA(4) MI_DECLARE_MFMA(8) MI_DECLARE_MFMA(12) MI_DECLARE_MFMA(16) MI
 MI_DECLARE_MFMA(24) MI_DECLARE_MFMA(28) MI_DECLARE_MFMA(32) MI_DECLARE_MFMA(36) MI_DECLARE_MFMA(40)
 MI_DECLARE_MFMA(44)
 #undef MI_DECLARE_MFMA
-constexpr int kMaxMfmaNT = 44;
-
-// what a per-NT launcher needs to know about the problem handle
-struct DenseLaunchCtx {
-    int device;
-    int opt_pace, opt_variant, opt_unit_rows, opt_ondemand_permille, opt_chunk_sweeps, opt_mfma_permille;
-    float *d_fields;               // R x 64*NT floats or nullptr
-    unsigned int *d_ctrl;
-    unsigned int *d_pace;          // kMaxChunks * kPaceWords words
-    int *resident_waves;           // cached occupancy of the wave-per-replica kernel (0 = unknown)
-    int *launches;                 // out: kernel launches that serve this anneal (a chunked run has several)
+// What one per-NT translation unit (dense_kernels.hip compiled with -DMI_NT=<NT>) exports: switches from the coordinates of a
+// plan (csrc/mi_dense_plan.h, the only place that decides) to the instantiation they name, and K1's occupancy.
+struct DenseWidth {                                                 // (all null: a width that is not built)
+    int (*launch)(const DenseArgs &, int unit_rows, hipStream_t);   // unit_rows 0: K1 on a.R replicas; 2 / 4: K1w with that ring unit
+    int (*k1_blocks_per_cu)(int *out);                              // co-resident workgroups (4 replicas each) of K1 per CU
+    int (*launch_mfma)(const DenseArgs &, hipStream_t);             // K1m; null above kMaxMfmaNT
 };
-
-constexpr int kMaxChunks = 64;
-
-// one translation unit per NT (dense_kernels.hip compiled with -DMI_NT=<NT>) defines its launcher
-#define MI_DECLARE_DENSE(N) int mi_launch_dense_nt##N(const DenseLaunchCtx &, const DenseArgs &, hipStream_t);
+#define MI_DECLARE_DENSE(N) DenseWidth mi_dense_nt##N();
 MI_DECLARE_DENSE(4) MI_DECLARE_DENSE(8) MI_DECLARE_DENSE(12) MI_DECLARE_DENSE(16) MI_DECLARE_DENSE(20)
 MI_DECLARE_DENSE(24) MI_DECLARE_DENSE(28) MI_DECLARE_DENSE(32) MI_DECLARE_DENSE(36) MI_DECLARE_DENSE(40)
 MI_DECLARE_DENSE(44) MI_DECLARE_DENSE(48) MI_DECLARE_DENSE(52) MI_DECLARE_DENSE(56) MI_DECLARE_DENSE(60)

@@ -645,6 +645,23 @@ def plan_anneal(kind, rowptr, col, n, num_reads, num_cases=2, cus=0, options=Non
     return name.value.decode(), int(nbytes.value)
 
 
+def plan_dense(n, num_reads, num_sweeps, resync_interval=0, per_replica=False, cus=0, resident_waves=4096, options=None):
+    """Which kernel(s) an anneal of a dense model of ``n`` variables would run, and in how many launches, decided on the
+    host without touching a device (mi_sa_plan_dense).  ``per_replica``: one temperature per replica (``anneal`` with
+    ``num_sweeps``); ``cus``: compute units of the device (0: 256); ``resident_waves``: co-resident wavefronts of the
+    wave-per-replica kernel (read only where it serves the run); ``options``: ``{key: value}`` (or ``"key=value,..."``)
+    with the dense keys of ``Problem.set_option``.  Returns ``(kernel_name, launch_count, field_bytes)`` -- the name up to
+    the hand-over of a cooling run, which is measured; raises MiSaError with the code and message the anneal would."""
+    if isinstance(options, dict):
+        options = ",".join("%s=%d" % (k, int(v)) for k, v in sorted(options.items()))
+    name = C.create_string_buffer(256)
+    launches, nbytes = C.c_int(0), C.c_uint64(0)
+    _lib.check(_lib.load().mi_sa_plan_dense(
+        int(n), int(num_reads), int(num_sweeps), int(resync_interval), C.c_uint32(2 if per_replica else 0), int(cus),
+        int(resident_waves), (options or "").encode(), name, 256, C.byref(launches), C.byref(nbytes)))
+    return name.value.decode(), int(launches.value), int(nbytes.value)
+
+
 def energy_dense(Qs: np.ndarray, X: np.ndarray, offset: float = 0.0, device: int = 0, path: int = 0,
                  return_ms: bool = False):
     """Batched ``E_r = x_r^T Qs x_r + offset`` on the GPU (kernel K4).  ``path``: 0 auto (MFMA for

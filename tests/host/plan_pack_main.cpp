@@ -1,6 +1,7 @@
-// Stand-alone host program over the HIP-free headers of the engine (csrc/mi_sa_plan.h, csrc/mi_sa_pack.h): the model
-// facts, both planners and every packer at the edge shapes -- n = 1, 63, 64, 65, an empty graph, max degree 0, 13, 15, 16,
-// 17, 64, 65, 4096, and 4097, which must be refused -- with the sizes of what they return checked.  Built with
+// Stand-alone host program over the HIP-free headers of the engine (csrc/mi_sa_plan.h, csrc/mi_dense_plan.h,
+// csrc/mi_sa_pack.h): the model facts, both planners and every packer at the edge shapes -- n = 1, 63, 64, 65, an empty
+// graph, max degree 0, 13, 15, 16, 17, 64, 65, 4096, and 4097, which must be refused -- with the sizes of what they return
+// checked; the dense planner at every register width, ring unit and occupancy (check_dense).  Built with
 // -fsanitize=address,undefined by tests/test_plan_pack_host.py; prints "ok" and returns 0.
 #include <algorithm>
 #include <cstdio>
@@ -10,6 +11,7 @@
 
 #include "../../scrna_seq_qannealing_clustering_amd/csrc/mi_sa_pack.h"
 #include "../../scrna_seq_qannealing_clustering_amd/csrc/mi_sa_plan.h"
+#include "../../scrna_seq_qannealing_clustering_amd/csrc/mi_dense_plan.h"
 
 using namespace mi_sa_plan;
 
@@ -108,8 +110,93 @@ static void check_model(int kind, const Csr &g, int K, const char *forced_state,
                 }
 }
 
+// The dense planner at every width NT, ring unit and a synthetic occupancy: K1's launches cover the replicas exactly, within
+// kMaxChunks, and are paced only where they are co-resident; the steps of a plan tile [0, num_sweeps); the ring arithmetic
+// gives the refusals tests/golden/dense_plan_table.json recorded (4 rows from NT = 56, K1m above NT = 44).
+static void check_dense()
+{
+    for (int NT = 4; NT <= 64; NT += 4) {
+        CHECK(dense_ring_units(NT, 2) >= 3 && (dense_ring_units(NT, 4) >= 3) == (NT <= 52) && dense_ring_units(NT, 3) == 0);
+        for (int GR : {2, 4}) CHECK(dense_ring_units(NT, GR) * GR * NT * 256 <= kDenseRingBytes && (dense_ring_units(NT, GR) - 2) * GR < 64);
+    }
+    CHECK(dense_ring_units(4, 4) == 17 && dense_ring_units(4, 2) == 32 && dense_ring_units(48, 4) == 3 && dense_ring_units(64, 2) == 4);
+    for (int NT = 4; NT <= 64; NT += 4)
+        for (int n : {64 * NT - 255, 64 * NT})
+            for (int GR : {0, 2, 4})
+                for (int waves : {4, 8, 1000})
+                    for (int variant = 0; variant <= 4; ++variant)
+                        for (int chunk : {0, 1, 2, 32})
+                            for (int sweeps : {0, 1, 2, 3, 5, 32, 33, 4086, 4087})
+                                for (int R : {1, 4, 5, 19, 31, 32, 127, 128, 1000, 1024, 1025, 64 * 1000, 64 * 1000 + 1})
+                                    for (int pace : {0, 1}) {
+                                        DensePlanOptions o;
+                                        CHECK(dense_plan_option_set(o, "variant", variant) && dense_plan_option_set(o, "unit_rows", GR));
+                                        CHECK(dense_plan_option_set(o, "chunk_sweeps", chunk) && dense_plan_option_set(o, "pace", 7 * pace));
+                                        DenseRun run;
+                                        run.n = n; run.R = R; run.num_sweeps = sweeps; run.cus = 256; run.resident_waves = waves;
+                                        DensePlan p;
+                                        std::string err;
+                                        CHECK(dense_width(n) == NT);
+                                        const int rc = plan_dense(run, o, &p, &err);
+                                        ++plans_checked;
+                                        if (rc != MI_OK) {
+                                            // the refusals: K1m above NT = 44, a ring unit that does not fit, too many launches to schedule
+                                            CHECK(!err.empty() && variant != 1);
+                                            const bool k1m = NT > kMaxMfmaNT && (variant == 3 || variant == 4);
+                                            const bool ring = GR == 4 && NT >= 56 && variant != 3;
+                                            const bool sched = (variant == 4 || variant == 0) && chunk == 1 && sweeps == 4087 && R >= 32;
+                                            CHECK(k1m || ring || sched);
+                                            CHECK(rc == (err.find("too many chunks") != std::string::npos ? MI_EINVAL : MI_EUNSUPPORTED));
+                                            continue;
+                                        }
+                                        char name[128];
+                                        dense_plan_kernel_name(p, name, sizeof name);
+                                        CHECK(name[0] == 'k' && p.NT == NT && p.num_sweeps == sweeps);
+                                        CHECK((p.form == DENSE_K1) == dense_plan_is_k1(run, o));
+                                        if (p.form == DENSE_K1) {
+                                            CHECK(!p.cut && p.steps == 1 && p.field_floats == 0 && p.unit_rows == 0);
+                                            CHECK(p.launches >= 1 && p.launches <= kMaxChunks && p.replicas_per_launch >= 1);
+                                            int covered = 0, count = 0;
+                                            for (int lo = 0; lo < R; lo += p.replicas_per_launch, ++count) {
+                                                const int cnt = std::min(R - lo, p.replicas_per_launch);
+                                                CHECK(cnt >= 1 && (!dense_k1_paced(p, cnt) || (cnt <= waves && pace && sweeps > 1)));
+                                                covered += cnt;
+                                            }
+                                            CHECK(covered == R && count == p.launches);
+                                            CHECK(p.replicas_per_launch == waves || p.launches == kMaxChunks || (R + waves - 1) / waves > kMaxChunks);
+                                        } else {
+                                            CHECK(p.launches == p.steps && p.cut == (p.steps > 1) && (p.field_floats != 0) == p.cut);
+                                            CHECK(!p.cut || (p.field_floats == (size_t)R * NT * 64 && chunk > 0 && sweeps > chunk && R >= 32));
+                                            CHECK((p.form == DENSE_K1M) == (p.unit_rows == 0) && (p.unit_rows == 0 || dense_ring_units(NT, p.unit_rows) >= 3));
+                                            CHECK(p.form != DENSE_SCHEDULED || (p.cut && NT <= kMaxMfmaNT && p.steps + 2 <= kCtrlWords - kCtrlModes));
+                                            CHECK(!p.wg_pace || (pace && (R + kWgWaves - 1) / kWgWaves <= 256));
+                                        }
+                                        // the steps tile [0, num_sweeps) without gap or overlap
+                                        int at = 0;
+                                        for (int i = 0; i < p.steps; ++i) {
+                                            const DenseStep s = dense_plan_step(p, i);
+                                            CHECK(s.s0 == at && s.first == (i == 0) && s.last == (i == p.steps - 1) && (s.len >= 1 || sweeps == 0));
+                                            CHECK(!p.cut || s.len <= chunk);
+                                            at += s.len;
+                                        }
+                                        CHECK(at == sweeps);
+                                    }
+    DenseRun run;
+    DensePlan p;
+    std::string err;
+    run.n = 0;
+    CHECK(plan_dense(run, DensePlanOptions(), &p, &err) == MI_EINVAL);
+    run.n = 4097;
+    CHECK(plan_dense(run, DensePlanOptions(), &p, &err) == MI_EUNSUPPORTED);
+    DensePlanOptions o;
+    CHECK(!dense_plan_option_set(o, "unit_rows", 3) && !dense_plan_option_set(o, "unit_rows", -2) && !dense_plan_option_set(o, "variant", 5));
+    CHECK(!dense_plan_option_set(o, "xl_chunk", 2) && !dense_plan_option_set(o, "chunk_sweeps", -1) && !dense_plan_option_set(o, "k2_pair", 1));
+    CHECK(dense_plan_option_set(o, "pace", -3) && o.pace == 1 && dense_plan_option_set(o, "pace", 0) && o.pace == 0);
+}
+
 int main()
 {
+    check_dense();
     for (int n : {1, 63, 64, 65}) {
         for (int kind : {MI_KIND_CSR_RANK1, MI_KIND_POTTS_CSR}) check_model(kind, hub_graph(n, 0, 1), 4, nullptr);   // an empty graph
         check_model(MI_KIND_CSR_RANK1, hub_graph(n, n > 1 ? 1 : 0, 1), 2, "bit");

@@ -108,6 +108,32 @@ def test_problem_reused_across_sizes_equals_fresh_problems(kind, options, R):
     assert not np.array_equal(reused[0][0], reused[2][0])               # (the steps are different runs)
 
 
+def test_dense_plan_does_not_depend_on_what_the_handle_ran_before():
+    """Forced K1w at n = 64 with launches of 2 sweeps: 40 replicas x 5 sweeps are cut into 3 launches and leave the buffer of
+    cached fields allocated; 19 replicas on the same handle are then one launch of the same kernel, as on a fresh handle
+    (fewer than 32 replicas are never cut), and the states are the oracle's."""
+    from oracle import sa_oracle as so
+    Qs, betas, options = make_dense(64, 17), schedule(5), (("variant", 2), ("chunk_sweeps", 2))
+
+    def run(p, R):
+        p.anneal(R, betas, 31, replica_offset=3)
+        st, _, info = p.fetch()
+        return p.kernel_name(), p.launch_count(), st, info["accepted"]
+
+    with Problem.dense(Qs) as fresh:
+        for key, value in options:
+            fresh.set_option(key, value)
+        want = run(fresh, 19)
+    with Problem.dense(Qs) as p:
+        for key, value in options:
+            p.set_option(key, value)
+        assert run(p, 40)[:2] == ("k_anneal_dense_wg<4,4>", 3)
+        got = run(p, 19)
+    assert got[:2] == want[:2] == ("k_anneal_dense_wg<4,4>", 1)
+    ost, _, ostats = so.sa_dense_philox(Qs, 19, betas, 31, replica_offset=3)
+    assert np.array_equal(got[2], ost) and np.array_equal(want[2], ost) and got[3] == want[3] == int(ostats[1])
+
+
 # ---- 2. tempering set up twice ---------------------------------------------------------------------------------------
 
 def tempering_round(p, T, chains, seed):
