@@ -19,10 +19,12 @@
  *            element index 64-bit everywhere.
  *   k_prep_normalize    one wavefront per cell: the cell's total in fp64 (lane-strided, then a butterfly: a fixed order),
  *                       then y = (float) log1p((double) x * scale_factor / total).  No LDS.
- *   k_prep_col_partial  column reductions: a workgroup is 64 genes x 4 row lanes over a slice of MI_PREP_ROW_SLICE rows
- *                       (reads coalesce along the genes); the 4 lanes meet in 2 KB + 1 KB of LDS in lane order; one fp64
- *                       partial per (slice, gene).  k_prep_col_finish adds the slices in ascending order.  The slicing
- *                       depends on n alone, so every result is a pure function of the input.
+ *   k_prep_col_partial<Mode>  column reductions: a workgroup is 64 genes x 4 row lanes over a slice of MI_PREP_ROW_SLICE
+ *                       rows (reads coalesce along the genes); the 4 lanes meet in 2 KB (+ 1 KB for the counts) of LDS in
+ *                       lane order; one fp64 partial per (slice, gene).  k_prep_col_finish adds the slices in ascending
+ *                       order.  The slicing depends on n alone, so every result is a pure function of the input.  The mode
+ *                       is the term, written once for both kinds of handle: ColSum, ColLog1p, ColCentred, ColClipped,
+ *                       RegressMoment<0 / 1> and SctMoment<0 / 1> (the last two pairs: a residual, or its square about a mean).
  *   k_prep_select       one thread per element of Z: gathers the chosen columns of Y and scales them.  Z is n x ldz f32 with
  *                       ldz = h rounded up to 128, the padding columns zero.
  *   k_prep_gram         G = Z^T Z on v_mfma_f32_32x32x2_f32.  Work unit = (128 x 128 tile of the upper block triangle, chunk
@@ -48,12 +50,13 @@
  * matrix -- the kernels add in the dense kernels' order (csrc/prep_kernels.hip, DESIGN.md section 5c "Sparse input"):
  *   k_prep_csr_normalize    one wavefront per cell, 64 entries at a time, each broadcast (v_readlane) to the lane
  *                           `column & 63`, columns ascending; the same butterfly; y for the stored entries only.  No LDS.
- *   k_prep_csc_col_partial  the workgroup and slice of k_prep_col_partial on the transpose: a thread finds its gene's first
- *                           entry of the slice by a lower bound in the gene's row list.  SUM adds the stored entries; CENTRED
- *                           and CLIPPED walk every row of the slice and add the stored value's term or the per-gene constant
+ *   k_prep_csc_col_partial<Term>  the workgroup and slice of k_prep_col_partial on the transpose: a thread finds its gene's
+ *                           first entry of the slice by a lower bound in the gene's row list, and a zero's term is the dense
+ *                           mode's own term function of 0.0f.  SumTerm and Log1pTerm add the stored entries; CentredTerm and
+ *                           ClippedTerm walk every row of the slice and add the stored value's term or the per-gene constant
  *                           of a zero ((0 - mean)^2, min((0 - mean) / sd, clip)^2) at that row's place: sparse in memory,
  *                           n * g fp64 additions in arithmetic (the closed form (n - nnz) c gives other bits).
- *   k_prep_csr_select       one workgroup per cell builds its row of Z in LDS (ldz <= 4096 floats, 16 KB): every column's
+ *   k_prep_csr_select<Cols> one workgroup per cell builds its row of Z in LDS (ldz <= 4096 floats, 16 KB): every column's
  *                           value of y = 0, a barrier, the cell's stored entries of chosen genes (gene -> column map of g
  *                           int32) over their columns, a barrier, one coalesced store.  Z has the dense layout, so
  *                           mi_prep_fetch_scaled, k_prep_gram and k_prep_project run unchanged.
@@ -68,12 +71,12 @@
  * Regression (mi_prep_select_regressed): Z = the scaled residuals of y ~ design, for vars.to.regress.  Stage 1 gathers the
  * chosen columns of Y into Z unscaled, with the two select kernels (mu = 0, inv = 1, an infinite clip:
  * fminf((y - 0) * 1, inf) is y); every later stage reads the dense Z alone, so a sparse handle gives the bits of a dense
- * one.  Q: n x q row-major fp64, an orthonormal basis of the design.  The three kernels have k_prep_col_partial's shape and
- * order: a workgroup is 64 columns x 4 row lanes over a slice of MI_PREP_ROW_SLICE rows; lane ty (one wavefront, so its row
+ * one.  Q: n x q row-major fp64, an orthonormal basis of the design.  The kernels have k_prep_col_partial's shape and
+ * order (the moments are that kernel itself): a workgroup is 64 columns x 4 row lanes over a slice of MI_PREP_ROW_SLICE rows; lane ty (one wavefront, so its row
  * of Q is uniform) adds rows r0 + ty, r0 + ty + 4, ... ascending; the four lanes meet in LDS as ((s0 + s1) + s2) + s3;
  * k_prep_col_finish adds the slices in ascending order.  Every product is a separate multiply and add (no contraction).
  *   k_prep_regress_coef     c_kj = sum_i Q_ik (double) y_ij and S_j = sum_i (double) y_ij^2.
- *   k_prep_regress_moment   mean_j = (sum_i r_ij) / n, then ss_j = sum_i (r_ij - mean_j)^2, var_j = ss_j / (n - 1); r is
+ *   k_prep_col_partial<RegressMoment>  mean_j = (sum_i r_ij) / n, then ss_j = sum_i (r_ij - mean_j)^2, var_j = ss_j / (n - 1); r is
  *                           recomputed each time as (double) y - acc with acc = Q_i0 c_0, then acc = acc + Q_ik c_k for k
  *                           ascending: no n x h fp64 buffer exists.
  *   host, inside the entry  flat_j = ss_j <= 1e-16 S_j (a convention of this package: an all-zero gene, a constant gene and
@@ -84,7 +87,7 @@
  *
  * SCTransform (mi_prep_gene_log1p_sum, mi_prep_nb_fit, mi_prep_sct_residual_moments, mi_prep_sct_select; DESIGN.md section 5c
  * "SCTransform").  The chain is this package's specification, modelled on sctransform::vst; it is unpinned against R.
- *   k_prep_col_partial<LOG1P>  sum_i log1p((double) x_ij): the SUM mode's walk with another term, dense and sparse (a zero adds
+ *   k_prep_col_partial<ColLog1p>  sum_i log1p((double) x_ij): the SUM mode's walk with another term, dense and sparse (a zero adds
  *                           +0.0 either way), for sctransform's geometric mean.
  *   k_sct_gather            the counts of the fit cells x fit genes as a dense f32 block, gene-major (one thread per element);
  *   k_sct_csr_gather        the same from CSR: one workgroup per fit cell, its row in LDS (zeros, a barrier, the stored entries
@@ -112,12 +115,12 @@
  *                                stops, converged = 1; after 40 rounds it keeps its last iterate, converged = 0.
  *                             4. se_b0c = sqrt(I_11 / det I), se_b1 = sqrt(I_00 / det I), se_alpha = 1 / sqrt(-l2) of the last
  *                                round (NaN for a Poisson gene or while l2 >= 0).
- *   k_sct_col_partial       k_prep_col_partial's shape, slices and order on r = clip((x - mu) / sqrt(mu + alpha mu^2), +-clip),
- *                           mu = exp(b0 + b1 log_umi_i): the sum, then the squares about the mean;
- *   k_sct_csc_col_partial   the same on the transpose.  A zero's residual depends on the cell, so every row of the slice is
- *                           walked, as in the CENTRED mode, and the contract holds bit for bit.
+ *   k_prep_col_partial<SctMoment>  the column reduction on r = clip((x - mu) / sqrt(mu + alpha mu^2), +-clip), mu = exp(b0 +
+ *                           b1 log_umi_i): the sum, then the squares about the mean;
+ *   k_prep_csc_row_partial<SctMoment>  the same on the transpose.  A zero's residual depends on the cell, so every row of
+ *                           the slice is computed, and the contract holds bit for bit.
  *   k_sct_select            Z = (float) r for the chosen genes, k_prep_select's shape;
- *   k_sct_csr_select        k_prep_csr_select's: the zeros' residuals fill the cell's LDS row, the stored entries overwrite.
+ *   k_prep_csr_select<SctCols>  the zeros' residuals fill the cell's LDS row, the stored entries overwrite.
  */
 #ifndef MI_PREP_H
 #define MI_PREP_H

@@ -382,12 +382,8 @@ extern "C" int mi_label_agreement_u16(const uint16_t *A, int Ra, const uint16_t 
     uint16_t *d_A = nullptr, *d_B = nullptr;
     return guarded([&]() -> int {
         DevBufs bufs;
-        HIP_TRY(bufs.alloc(&d_A, (size_t)Ra * n));
-        HIP_TRY(hipMemcpy(d_A, A, (size_t)Ra * n * sizeof(uint16_t), hipMemcpyHostToDevice));
-        if (B) {
-            HIP_TRY(bufs.alloc(&d_B, (size_t)Rb * n));
-            HIP_TRY(hipMemcpy(d_B, B, (size_t)Rb * n * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
+        HIP_TRY(bufs.upload(&d_A, A, (size_t)Ra * n));
+        if (B) HIP_TRY(bufs.upload(&d_B, B, (size_t)Rb * n));
         AgreeArgs a;
         a.A = d_A; a.lda = (size_t)n; a.B = d_B; a.ldb = (size_t)n;
         a.Ra = Ra; a.Rb = Rb; a.cols = n; a.Ka = Ka; a.Kb = Kb; a.groups = groups; a.meta = nullptr; a.n_real = n;

@@ -439,8 +439,7 @@ extern "C" int mi_coassociation_u16(const uint16_t *L, int R, int n, int K, int 
     uint16_t *d_L = nullptr;
     return guarded([&]() -> int {
         DevBufs bufs;
-        HIP_TRY(bufs.alloc(&d_L, (size_t)R * n));
-        HIP_TRY(hipMemcpy(d_L, L, (size_t)R * n * sizeof(uint16_t), hipMemcpyHostToDevice));
+        HIP_TRY(bufs.upload(&d_L, L, (size_t)R * n));
         CoassocArgs a;
         a.L = d_L; a.ld = (size_t)n; a.R = R; a.cols = n; a.K = K; a.groups = groups; a.meta = nullptr;
         a.ref = ref; a.Kref = ref ? Kref : 1; a.eu = eu; a.ev = ev; a.m = out_edge ? m : 0;

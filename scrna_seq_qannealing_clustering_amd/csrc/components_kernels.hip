@@ -228,18 +228,10 @@ extern "C" int mi_graph_components(const int32_t *rowptr, const int32_t *col, in
     uint8_t *d_keep = nullptr;
     return guarded([&]() -> int {
         DevBufs bufs;
-        HIP_TRY(bufs.alloc(&d_rowptr, ((size_t)n + 1)));
-        HIP_TRY(hipMemcpy(d_rowptr, rowptr, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(bufs.alloc(&d_col, (size_t)(nnz > 0 ? nnz : 1)));
-        if (nnz > 0) HIP_TRY(hipMemcpy(d_col, col, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (L) {
-            HIP_TRY(bufs.alloc(&d_L, (size_t)B * n));
-            HIP_TRY(hipMemcpy(d_L, L, (size_t)B * n * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
-        if (keep && nnz > 0) {
-            HIP_TRY(bufs.alloc(&d_keep, (size_t)B * (size_t)nnz));
-            HIP_TRY(hipMemcpy(d_keep, keep, (size_t)B * (size_t)nnz, hipMemcpyHostToDevice));
-        }
+        HIP_TRY(bufs.upload(&d_rowptr, rowptr, (size_t)n + 1));
+        HIP_TRY(bufs.upload(&d_col, col, (size_t)nnz));           // (without edges: a pointer all the same, nothing copied)
+        if (L) HIP_TRY(bufs.upload(&d_L, L, (size_t)B * n));
+        if (keep && nnz > 0) HIP_TRY(bufs.upload(&d_keep, keep, (size_t)B * (size_t)nnz));
         ComponentsArgs a;
         a.rowptr = d_rowptr; a.col = d_col; a.n = n; a.nnz = nnz;
         a.L = d_L; a.ldl = (size_t)n; a.keep = d_keep;

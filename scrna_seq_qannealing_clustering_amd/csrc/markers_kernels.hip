@@ -408,8 +408,8 @@ struct MarkersRun {
         unsigned long long *d_slab = nullptr;
         uint32_t *d_slab_mid = nullptr;
         const size_t entries = c.entries();
-        HIP_TRY(bufs.alloc(&d_Lt, Lt.size()));
-        HIP_TRY(bufs.alloc(&d_sizes, sizes.size()));
+        HIP_TRY(bufs.upload(&d_Lt, Lt.data(), Lt.size()));
+        HIP_TRY(bufs.upload(&d_sizes, sizes.data(), sizes.size()));
         HIP_TRY(bufs.alloc(&d_rank2, entries));
         HIP_TRY(bufs.alloc(&d_npos, entries));
         HIP_TRY(bufs.alloc(&d_tie, (size_t)c.g));
@@ -418,8 +418,6 @@ struct MarkersRun {
             HIP_TRY(bufs.alloc(&d_slab, grid * slab_stride));
             HIP_TRY(bufs.alloc(&d_slab_mid, grid * slab_stride));
         }
-        HIP_TRY(hipMemcpy(d_Lt, Lt.data(), Lt.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_sizes, sizes.data(), sizes.size() * sizeof(int32_t), hipMemcpyHostToDevice));
 
         a.Lt = d_Lt; a.sizes = d_sizes;
         a.n = c.n; a.g = c.g; a.B = c.B; a.Bp = c.Bp(); a.K = c.K; a.lds_cap = lds_cap;
@@ -531,12 +529,10 @@ extern "C" int mi_rank_sum_markers_f32(const float *X, int n, int g, const uint1
         float *d_X = nullptr, *d_Xt = nullptr;
         int32_t *d_nnz = nullptr;
         const size_t cells = (size_t)n * g;
-        HIP_TRY(bufs.alloc(&d_X, cells));
+        HIP_TRY(bufs.upload(&d_X, X, cells));
         HIP_TRY(bufs.alloc(&d_Xt, cells));
-        HIP_TRY(bufs.alloc(&d_nnz, nnz.size()));
+        HIP_TRY(bufs.upload(&d_nnz, nnz.data(), nnz.size()));
         MI_TRY(run.prepare(bufs, c, sizes, Lt, nnz.data(), device));
-        HIP_TRY(hipMemcpy(d_X, X, cells * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_nnz, nnz.data(), nnz.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         Timer tm;
         MI_TRY(tm.start(0));
         MI_TRY(run.run_dense(c, d_X, d_Xt, d_nnz));
@@ -549,30 +545,27 @@ extern "C" int mi_prep_rank_sum_markers(mi_prep_matrix *m, int which, const uint
                                         int64_t *out_rank2, int32_t *out_npos, double *out_sum, int64_t *out_tie,
                                         float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m || !L || !out_rank2) return fail(MI_EINVAL, "NULL argument");
-    if (which != MI_PREP_MARKERS_COUNTS && which != MI_PREP_MARKERS_NORMALIZED)
-        return fail(MI_EINVAL, "which must be 0 (counts) or 1 (normalised), got %d", which);
-    MarkersCall c;
-    c.n = m->n; c.g = m->g; c.B = B; c.K = K; c.flags = flags; c.L = L;
-    c.out_rank2 = out_rank2; c.out_npos = out_npos; c.out_sum = out_sum; c.out_tie = out_tie;
-    const uint32_t gather = MI_PREP_MARKERS_GATHER_INPLACE | MI_PREP_MARKERS_GATHER_PERMUTE;
-    MI_TRY(check_call(c, MI_MARKERS_SUM_PLAIN | MI_MARKERS_GLOBAL | gather));
-    if ((flags & gather) == gather) return fail(MI_EINVAL, "flags 0x%x ask for both gather forms", flags);
-    for (int b = 0; b < B; ++b)
-        for (int i = 0; i < c.n; ++i)
-            if (L[(size_t)b * c.n + i] >= K)
-                return fail(MI_EINVAL, "label %d of labelling %d, cell %d is not below K = %d", (int)L[(size_t)b * c.n + i], b, i, K);
-    if (which == MI_PREP_MARKERS_NORMALIZED && !m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
-    MI_TRY(check_limits(c));
-    c.flags = flags & ~gather;
-    const bool permute = (flags & gather) ? (flags & MI_PREP_MARKERS_GATHER_PERMUTE) != 0 : kPermuteByDefault;
-    return guarded([&]() -> int {
+    return on_matrix(m, L && out_rank2, 0, out_kernel_ms, [&]() -> int {
+        if (which != MI_PREP_MARKERS_COUNTS && which != MI_PREP_MARKERS_NORMALIZED)
+            return fail(MI_EINVAL, "which must be 0 (counts) or 1 (normalised), got %d", which);
+        MarkersCall c;
+        c.n = m->n; c.g = m->g; c.B = B; c.K = K; c.flags = flags; c.L = L;
+        c.out_rank2 = out_rank2; c.out_npos = out_npos; c.out_sum = out_sum; c.out_tie = out_tie;
+        const uint32_t gather = MI_PREP_MARKERS_GATHER_INPLACE | MI_PREP_MARKERS_GATHER_PERMUTE;
+        MI_TRY(check_call(c, MI_MARKERS_SUM_PLAIN | MI_MARKERS_GLOBAL | gather));
+        if ((flags & gather) == gather) return fail(MI_EINVAL, "flags 0x%x ask for both gather forms", flags);
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < c.n; ++i)
+                if (L[(size_t)b * c.n + i] >= K)
+                    return fail(MI_EINVAL, "label %d of labelling %d, cell %d is not below K = %d", (int)L[(size_t)b * c.n + i], b, i, K);
+        MI_TRY(check_state(m, which == MI_PREP_MARKERS_NORMALIZED ? NEED_NORMALIZED : 0));
+        MI_TRY(check_limits(c));
+        c.flags = flags & ~gather;
+        const bool permute = (flags & gather) ? (flags & MI_PREP_MARKERS_GATHER_PERMUTE) != 0 : kPermuteByDefault;
         DevBufs bufs;
         std::vector<int32_t> sizes, counts((size_t)c.g, 0);
         std::vector<uint16_t> Lt;
         MI_TRY(scan_labels(c, sizes, Lt));
-        HIP_TRY(hipSetDevice(m->device));
         const float *M = which == MI_PREP_MARKERS_NORMALIZED ? m->d_Y : m->d_X;
         MarkersRun run;
         float ms_count = 0.0f, ms = 0.0f;

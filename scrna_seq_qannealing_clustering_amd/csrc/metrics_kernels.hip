@@ -171,33 +171,29 @@ extern "C" int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, 
     float *d_D = nullptr;
     return guarded([&]() -> int {
         DevBufs bufs;
-        HIP_TRY(bufs.alloc(&d_bits, (size_t)n * words));
-        HIP_TRY(bufs.alloc(&d_lab, (size_t)n));
         HIP_TRY(bufs.alloc(&d_rowsum, (size_t)n * K));
         HIP_TRY(bufs.alloc(&d_sqa, (size_t)n));
         HIP_TRY(bufs.alloc(&d_sqw, (size_t)n));
         HIP_TRY(bufs.alloc(&d_part, (size_t)S * per_plane));
         HIP_TRY(bufs.alloc(&d_diam, (size_t)K));
-        HIP_TRY(bufs.alloc(&d_sep, (size_t)K * K));
         if (out_D) HIP_TRY(bufs.alloc(&d_D, (size_t)n * n));
         // cells sorted by cluster (counting sort: stable, index order inside a cluster)
         std::vector<int> start((size_t)K + 1, 0), order((size_t)n), lab_s((size_t)n);
         for (int i = 0; i < n; ++i) start[labels[i] + 1]++;
         for (int c = 0; c < K; ++c) start[c + 1] += start[c];
         for (int i = 0; i < n; ++i) order[start[labels[i]]++] = i;
-        std::vector<uint64_t> bits_s((size_t)n * words);
+        std::vector<unsigned long long> bits_s((size_t)n * words);
         for (int p = 0; p < n; ++p) {
             lab_s[p] = labels[order[p]];
             memcpy(&bits_s[(size_t)p * words], &bits[(size_t)order[p] * words], (size_t)words * 8);
         }
-        HIP_TRY(bufs.alloc(&d_orig, (size_t)n));
-        HIP_TRY(hipMemcpy(d_bits, bits_s.data(), (size_t)n * words * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_lab, lab_s.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_orig, order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(bufs.upload(&d_bits, bits_s.data(), bits_s.size()));
+        HIP_TRY(bufs.upload(&d_lab, lab_s.data(), lab_s.size()));
+        HIP_TRY(bufs.upload(&d_orig, order.data(), order.size()));
         HIP_TRY(hipMemset(d_part, 0, (size_t)S * per_plane * 8));              // clusters absent from a slice stay 0
         HIP_TRY(hipMemset(d_diam, 0, (size_t)K * 8));
-        std::vector<double> inf((size_t)K * K, INFINITY);
-        HIP_TRY(hipMemcpy(d_sep, inf.data(), inf.size() * 8, hipMemcpyHostToDevice));
+        const std::vector<unsigned long long> inf((size_t)K * K, 0x7ff0000000000000ull);       // the bits of +inf (fp64)
+        HIP_TRY(bufs.upload(&d_sep, inf.data(), inf.size()));
         if (lds > 64 * 1024)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_jaccard_stats), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         Timer tm;

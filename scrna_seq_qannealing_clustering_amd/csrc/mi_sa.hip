@@ -1827,7 +1827,7 @@ int mi_energy_dense_f32_ex(const float *Qs, int n, const uint8_t *X, int R, doub
         const size_t ldq = path == 2 ? ((size_t)n + 127) / 128 * 128 : (size_t)n;
         const size_t rows = path == 2 ? ldq : (size_t)n;
         HIP_TRY(bufs.alloc(&dQ, rows * ldq));
-        HIP_TRY(bufs.alloc(&dX, (size_t)R * n));
+        HIP_TRY(bufs.upload(&dX, X, (size_t)R * n));
         HIP_TRY(bufs.alloc(&dE, (size_t)R));
         if (path == 2) {
             HIP_TRY(bufs.alloc(&dXt, mi_energy_dense_scratch_bytes(n, R)));
@@ -1835,7 +1835,6 @@ int mi_energy_dense_f32_ex(const float *Qs, int n, const uint8_t *X, int R, doub
         }
         HIP_TRY(hipMemcpy2D(dQ, ldq * sizeof(float), Qs, (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)n,
                             hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dX, X, (size_t)R * n, hipMemcpyHostToDevice));
         Timer tm;
         MI_TRY(tm.start(0));
         MI_TRY(mi_launch_energy_dense(dQ, n, (int)ldq, dX, R, offset, dE, dXt, path, 0));
@@ -1855,11 +1854,9 @@ int mi_energy_dense_f64(const double *Qs, int n, const uint8_t *X, int R, double
     return guarded([&]() -> int {
         DevBufs bufs;
         double *dQ = nullptr, *dE = nullptr; uint8_t *dX = nullptr;
-        HIP_TRY(bufs.alloc(&dQ, (size_t)n * n));
-        HIP_TRY(bufs.alloc(&dX, (size_t)R * n));
+        HIP_TRY(bufs.upload(&dQ, Qs, (size_t)n * n));
+        HIP_TRY(bufs.upload(&dX, X, (size_t)R * n));
         HIP_TRY(bufs.alloc(&dE, (size_t)R));
-        HIP_TRY(hipMemcpy(dQ, Qs, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dX, X, (size_t)R * n, hipMemcpyHostToDevice));
         MI_TRY(mi_launch_energy_dense_f64(dQ, n, dX, R, offset, dE, 0));
         HIP_TRY(hipMemcpy(out_energy, dE, (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
         return MI_OK;

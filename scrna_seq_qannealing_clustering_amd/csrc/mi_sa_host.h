@@ -83,6 +83,13 @@ struct DevBufs : NoCopy {
         *out = static_cast<T *>(p.back());
         return e;
     }
+    // alloc(), then the copy of `count` elements from the host (none for a count of 0)
+    template <typename T>
+    hipError_t upload(T **out, const T *host, size_t count)
+    {
+        const hipError_t e = alloc(out, count);
+        return e != hipSuccess || count == 0 ? e : hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice);
+    }
 };
 
 // One device array of T that outlives a call, with its element count: a member of a handle, freed when the handle is

@@ -2,21 +2,24 @@
 // C ABI, layouts and LDS plans: include/mi_prep.h; the loess curve and the eigen-solve are host fp64 in preprocess.py.
 //
 //   k_prep_normalize     one wavefront per cell: fp64 total, then y = (float) log1p((double) x * scale / total).
-//   k_prep_col_partial   per-gene reductions over a slice of kRowSlice rows, 64 genes x 4 row lanes per workgroup:
-//                        SUM (sum and non-zero count), CENTRED (squares about a given mean), CLIPPED (vst's clipped
-//                        standardised squares); k_prep_col_finish adds the slices in ascending order and divides.
-//   k_prep_select        z = fminf((y - mu) * inv, clip) for the chosen columns, into Z (n x ldz, zero padded columns).
+//   k_prep_col_partial<Mode>  per-column reductions over a slice of kRowSlice rows, 64 columns x 4 row lanes per workgroup.  The
+//                        mode is the term: ColSum (sum and non-zero count), ColLog1p, ColCentred (squares about a given
+//                        mean), ColClipped (vst's clipped standardised squares), RegressMoment and SctMoment (a residual, or
+//                        its square about a mean); k_prep_col_finish adds the slices in ascending order and divides.
+//   k_prep_select        z = fminf((y - mu) * inv, clip) for the chosen columns, into Z (n x ldz, zero padded columns);
+//                        k_sct_select: the clipped Pearson residual instead.
 //   k_prep_gram          one (upper-triangle 128 x 128 tile, chunk of kChunk cells) per workgroup on the f32-input MFMA,
 //                        f32 tile out; k_prep_gram_reduce adds the chunks in fp64 in chunk order and mirrors.
 //   k_prep_project       out = Z V, 64 cells x 128 columns per workgroup on the same MFMA.
 //   k_prep_cell_qc       per cell: the normaliser's fp64 total, the total of a gene subset, the count of x != 0.
-//   k_prep_regress_*     mi_prep_select_regressed on the gathered Z: c = Q^T y and sum y^2, the residuals' mean and centred
-//                        squares, the in-place scaling; the shape and order of k_prep_col_partial, fp64, no contraction.
-//   k_sct_*              SCTransform: the gather of the fit block, the per-gene negative-binomial fit (one workgroup per gene,
-//                        its counts in LDS), the residual moments and the residual selection, each dense and sparse.
+//   k_prep_regress_*     mi_prep_select_regressed on the gathered Z: c = Q^T y and sum y^2 (coef) and the in-place scaling
+//                        (scale), on the slices, lanes and LDS join of k_prep_col_partial, fp64, no contraction.
+//   k_sct_*              SCTransform: the gather of the fit block, dense and sparse, and the per-gene negative-binomial fit
+//                        (one workgroup per gene, its counts in LDS).
 // A sparse handle (mi_prep_create_csr_f32) keeps the counts as CSR and is served by k_prep_csr_normalize,
-// k_prep_csc_col_partial, k_prep_csr_select and k_prep_csr_cell_qc, which add in the order of their dense kernels: the same
-// bits come out.
+// k_prep_csc_col_partial<Term> (k_prep_csc_row_partial<Mode> for the SCT residuals), k_prep_csr_select<Cols> and
+// k_prep_csr_cell_qc, which add in the order of their dense kernels and call the same term functions, on 0.0f for a zero:
+// the same bits come out.
 // Operand maps of v_mfma_f32_32x32x2_f32 as in energy_kernels.hip: A: lane l holds A[i = l & 31][k = l >> 5]; B: lane l
 // holds B[k = l >> 5][j = l & 31]; C/D: register q of lane l is C[row = (q & 3) + 8 (q >> 2) + 4 (l >> 5)][col = l & 31].
 // No floating-point atomics; stores are ordinary vector stores.
@@ -39,7 +42,7 @@ constexpr int kChunk = MI_PREP_GRAM_CHUNK;
 constexpr int kTile = 128, kKC = 32;
 constexpr int kProjCells = 64, kProjCols = MI_PREP_MAX_PCS;
 constexpr size_t kGramWorkspace = (size_t)256 << 20;                    // bytes of f32 tiles in flight between the two Gram kernels
-enum { kColSum = 0, kColCentred = 1, kColClipped = 2, kColLog1p = 3 };
+constexpr int kMaxQ = MI_PREP_MAX_DESIGN_COLS;
 
 __global__ void __launch_bounds__(256) k_prep_normalize(const float *__restrict__ X, float *__restrict__ Y, int n, int g,
                                                         double scale)
@@ -55,45 +58,191 @@ __global__ void __launch_bounds__(256) k_prep_normalize(const float *__restrict_
     for (int j = lane; j < g; j += 64) y[j] = t > 0.0 ? (float)log1p((double)x[j] * scale / t) : 0.0f;
 }
 
+// ---- the column reductions: every term is written once, and so is the skeleton of each source form -------------------------
+// A workgroup is 64 columns x 4 row lanes over a slice of kRowSlice rows: lane ty adds the rows r0 + ty, r0 + ty + 4, ...
+// ascending, the four lanes meet in LDS as ((s0 + s1) + s2) + s3, and k_prep_col_finish adds the slices in ascending order
+// and divides once.  All of it is fp64 without contraction: every product is a multiply, then an add.
+//
+// A mode is the kernel argument that says what is added: `count` columns are reduced, bind(j) loads what column j needs and
+// returns its column in the source, and mode(v, r) is the term of value v in row r.  The dense kernel applies it to every
+// element; the transposed kernels apply the same term to the stored values and to 0.0f for a zero, at that row's place
+// in the order, so a sparse handle gives the bits of a dense one.  kWalk says which zeros a transposed kernel may skip.
+enum { kWalkStored,        // a zero's term is +0.0 (and the sum is never negative): the stored entries alone
+       kWalkZeroConstant,  // a zero's term is one constant per gene, hoisted and added for each run of zeros
+       kWalkEveryRow };    // a zero's term depends on the row: every row is computed
+
+// the tail of the moment modes: the value itself (MODE 0) or its square about a mean (MODE 1)
 template <int MODE>
-__global__ void __launch_bounds__(256) k_prep_col_partial(const float *__restrict__ M, int n, int g,
-                                                          const double *__restrict__ mean, const double *__restrict__ sd,
-                                                          double clip, double *__restrict__ psum, int32_t *__restrict__ pnnz)
+__device__ __forceinline__ double moment_tail(double x, double mean)
 {
-    __shared__ double s_sum[4][64];
-    __shared__ int32_t s_cnt[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    if (!MODE) return x;
+    const double d = x - mean;
+    return d * d;
+}
+
+// The four terms over the counts and the normalised values.  term(v, mj, sj, clip) is the arithmetic, written here alone.
+struct SumTerm {                                                  // the sum, and the count of v != 0
+    static constexpr int kWalk = kWalkStored;
+    static constexpr bool kCounts = true, kUsesMean = false, kUsesSd = false;
+    static __device__ __forceinline__ double term(float v, double, double, double) { return (double)v; }
+};
+
+struct Log1pTerm {                                                // (log1p(0) is +0.0, like the 0 of a sum)
+    static constexpr int kWalk = kWalkStored;
+    static constexpr bool kCounts = false, kUsesMean = false, kUsesSd = false;
+    static __device__ __forceinline__ double term(float v, double, double, double) { return log1p((double)v); }
+};
+
+struct CentredTerm {                                              // squares about a given mean
+    static constexpr int kWalk = kWalkZeroConstant;
+    static constexpr bool kCounts = false, kUsesMean = true, kUsesSd = false;
+    static __device__ __forceinline__ double term(float v, double mj, double, double) { return moment_tail<1>((double)v, mj); }
+};
+
+struct ClippedTerm {                                              // vst's clipped standardised squares (sj != 0)
+    static constexpr int kWalk = kWalkZeroConstant;
+    static constexpr bool kCounts = false, kUsesMean = true, kUsesSd = true;
+    static __device__ __forceinline__ double term(float v, double mj, double sj, double clip)
+    {
+        double d = ((double)v - mj) / sj;
+        d = d < clip ? d : clip;
+        return d * d;
+    }
+};
+
+// the mode of one of these terms: mean, sd and clip as far as the term uses them
+template <typename T>
+struct ColMode {
+    typedef T Term;
+    static constexpr int kWalk = T::kWalk;
+    static constexpr bool kCounts = T::kCounts;
+    int count;
+    const double *mean, *sd;
+    double clip, mj, sj;
+    __device__ int bind(int j)
+    {
+        if (T::kUsesMean) mj = mean[j];
+        if (T::kUsesSd) sj = sd[j];
+        return j;
+    }
+    // (a gene without spread adds +0.0 to a sum of squares)
+    __device__ double operator()(float v, int) const { return !T::kUsesSd || sj != 0.0 ? T::term(v, mj, sj, clip) : 0.0; }
+};
+typedef ColMode<SumTerm> ColSum;
+typedef ColMode<Log1pTerm> ColLog1p;
+typedef ColMode<CentredTerm> ColCentred;
+typedef ColMode<ClippedTerm> ColClipped;
+
+// One gathered column of mi_prep_select_regressed: r = y - sum_k Q_ik c_k, as acc = Q_i0 c_0, then acc = acc + Q_ik c_k for
+// k ascending.  Q: n x q row-major fp64 (q <= kMaxQ); the row lane is one wavefront, so its row of Q comes by scalar loads.
+struct RegressColumn {
+    const double *Q;
+    int q;
+    const double *coef;                                           // q x h
+    double c[kMaxQ];
+    __device__ void bind(int j, int h)
+    {
+#pragma unroll
+        for (int k = 0; k < kMaxQ; ++k) c[k] = k < q ? coef[(size_t)k * h + j] : 0.0;
+    }
+    __device__ double residual(float y, int r) const
+    {
+        const double *qr = Q + (size_t)r * q;
+        double acc = qr[0] * c[0];
+#pragma unroll
+        for (int k = 1; k < kMaxQ; ++k)
+            if (k < q) acc = acc + qr[k] * c[k];
+        return (double)y - acc;
+    }
+};
+
+template <int MODE>
+struct RegressMoment {                                            // the regression residuals' sum, or squares about their mean
+    static constexpr bool kCounts = false;
+    int count;
+    RegressColumn col;
+    const double *mean;
+    double mj;
+    __device__ int bind(int j)
+    {
+        col.bind(j, count);
+        mj = MODE ? mean[j] : 0.0;
+        return j;
+    }
+    __device__ double operator()(float v, int r) const { return moment_tail<MODE>(col.residual(v, r), mj); }
+};
+
+// the Pearson residual of count x under mu = exp(b0 + b1 log_umi), variance mu + alpha mu^2, clipped to +- clip
+__device__ __forceinline__ double sct_residual(float x, double b0, double b1, double alpha, double lu, double clip)
+{
+    const double mu = exp(b0 + b1 * lu);
+    const double r = ((double)x - mu) / sqrt(mu + alpha * (mu * mu));
+    return fmin(fmax(r, -clip), clip);
+}
+
+template <int MODE>
+struct SctMoment {                                                // the Pearson residuals' sum, or squares about their mean
+    static constexpr int kWalk = kWalkEveryRow;
+    static constexpr bool kCounts = false;
+    int count;
+    const int32_t *genes;
+    const double *par, *lu;                                       // par: b0, b1, alpha, `count` entries each; lu: per cell
+    double clip;
+    const double *mean;
+    double b0, b1, al, mj;
+    __device__ int bind(int jj)
+    {
+        b0 = par[jj];
+        b1 = par[count + jj];
+        al = par[2 * (size_t)count + jj];
+        mj = MODE ? mean[jj] : 0.0;
+        return genes[jj];
+    }
+    __device__ double operator()(float v, int r) const { return moment_tail<MODE>(sct_residual(v, b0, b1, al, lu[r], clip), mj); }
+};
+
+// this thread's place in the skeleton: column j (tx) of the reduction, row lane ty, the slice's rows [r0, r1)
+struct ColSlice {
+    const int tx = threadIdx.x & 63, ty = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int j = blockIdx.x * 64 + tx;
-    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
+    const int r0 = blockIdx.y * kRowSlice, r1;
+    __device__ explicit ColSlice(int n) : r1(r0 + kRowSlice < n ? r0 + kRowSlice : n) {}
+    // the four lanes' values of a column meet in LDS, joined left to right; lane 0 stores for the columns that exist
+    template <typename T>
+    __device__ void join(T v, bool live, T *out) const
+    {
+        __shared__ T s[4][64];
+        s[ty][tx] = v;
+        __syncthreads();
+        if (ty == 0 && live) *out = ((s[0][tx] + s[1][tx]) + s[2][tx]) + s[3][tx];
+    }
+    // the end of a reduction over `count` columns: the partial of (slice, column) at slice * count + j
+    template <typename Mode>
+    __device__ void store(const Mode &mode, double acc, int32_t cnt, double *psum, int32_t *pnnz) const
+    {
+        const size_t o = (size_t)blockIdx.y * mode.count + j;
+        join(acc, j < mode.count, psum + o);
+        if (Mode::kCounts) join(cnt, j < mode.count, pnnz + o);
+    }
+};
+
+// the dense source: M is n x ld row-major
+template <typename Mode>
+__global__ void __launch_bounds__(256) k_prep_col_partial(const float *__restrict__ M, int ld, int n, Mode mode,
+                                                          double *__restrict__ psum, int32_t *__restrict__ pnnz)
+{
+    const ColSlice s(n);
     double acc = 0.0;
     int32_t cnt = 0;
-    if (j < g) {
-        const double mj = MODE == kColSum || MODE == kColLog1p ? 0.0 : mean[j], sj = MODE == kColClipped ? sd[j] : 1.0;
-        for (int r = r0 + ty; r < r1; r += 4) {
-            const float v = M[(size_t)r * g + j];
-            if (MODE == kColSum) {
-                acc += (double)v;
-                cnt += v != 0.0f;
-            } else if (MODE == kColLog1p) {
-                acc += log1p((double)v);
-            } else if (MODE == kColCentred) {
-                const double d = (double)v - mj;
-                acc += d * d;
-            } else if (sj != 0.0) {
-                double d = ((double)v - mj) / sj;
-                d = d < clip ? d : clip;
-                acc += d * d;
-            }
+    if (s.j < mode.count) {
+        const float *col = M + mode.bind(s.j);
+        for (int r = s.r0 + s.ty; r < s.r1; r += 4) {
+            const float v = col[(size_t)r * ld];
+            acc += mode(v, r);
+            if (Mode::kCounts) cnt += v != 0.0f;
         }
     }
-    s_sum[ty][tx] = acc;
-    s_cnt[ty][tx] = cnt;
-    __syncthreads();
-    if (ty == 0 && j < g) {
-        const size_t o = (size_t)blockIdx.y * g + j;
-        psum[o] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
-        if (MODE == kColSum) pnnz[o] = s_cnt[0][tx] + s_cnt[1][tx] + s_cnt[2][tx] + s_cnt[3][tx];
-    }
+    s.store(mode, acc, cnt, psum, pnnz);
 }
 
 __global__ void __launch_bounds__(256) k_prep_col_finish(const double *__restrict__ psum, const int32_t *__restrict__ pnnz,
@@ -112,6 +261,41 @@ __global__ void __launch_bounds__(256) k_prep_col_finish(const double *__restric
     if (pnnz) out_nnz[j] = c;
 }
 
+// ---- the selections into Z (n x ldz, h chosen columns, zero padding) --------------------------------------------------------
+// `cols` says what column c of Z holds for input x; bind_row(row) loads what a cell needs: the argument of the CSR kernel
+// below, which applies it to 0.0f for what a cell does not store.  The two dense kernels take the same fields one by one
+// and call the same scaled_value / sct_residual.
+// mi_prep_select's scaling, as separate f32 operations
+__device__ __forceinline__ float scaled_value(float y, float mu, float inv, float clip)
+{
+    const float d = y - mu;
+    return fminf(d * inv, clip);
+}
+
+struct ScaledCols {                                               // mi_prep_select: z = fminf((y - mu) * inv, clip), 0 where flat
+    int h;
+    const float *mu, *inv;
+    const uint8_t *flat;
+    float clip;
+    __device__ void bind_row(size_t) {}
+    __device__ float operator()(int c, float y) const
+    {
+        return c < h && !flat[c] ? scaled_value(y, mu[c], inv[c], clip) : 0.0f;
+    }
+};
+
+struct SctCols {                                                  // stage 1 of mi_prep_sct_select: z = (float) the clipped residual
+    int h;
+    const double *par, *lu;                                       // par: b0, b1, alpha, h entries each; lu: per cell
+    double clip, l;
+    __device__ void bind_row(size_t row) { l = lu[row]; }
+    __device__ float operator()(int c, float x) const
+    {
+        return c < h ? (float)sct_residual(x, par[c], par[h + c], par[2 * (size_t)h + c], l, clip) : 0.0f;
+    }
+};
+
+// The dense kernels: one thread per element of Z, one cell per blockIdx.y.
 __global__ void __launch_bounds__(256) k_prep_select(const float *__restrict__ Y, int n, int g, const int32_t *__restrict__ genes,
                                                      int h, int ldz, const float *__restrict__ mu, const float *__restrict__ inv,
                                                      const uint8_t *__restrict__ flat, float clip, float *__restrict__ Z)
@@ -120,10 +304,19 @@ __global__ void __launch_bounds__(256) k_prep_select(const float *__restrict__ Y
     const size_t row = blockIdx.y;
     if (c >= ldz) return;
     float z = 0.0f;
-    if (c < h && !flat[c]) {
-        const float d = Y[row * g + genes[c]] - mu[c];
-        z = fminf(d * inv[c], clip);
-    }
+    if (c < h && !flat[c]) z = scaled_value(Y[row * g + genes[c]], mu[c], inv[c], clip);
+    Z[row * ldz + c] = z;
+}
+
+__global__ void __launch_bounds__(256) k_sct_select(const float *__restrict__ X, int g, const int32_t *__restrict__ genes, int h,
+                                                    int ldz, const double *__restrict__ par, const double *__restrict__ lu,
+                                                    double clip, float *__restrict__ Z)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const size_t row = blockIdx.y;
+    if (c >= ldz) return;
+    float z = 0.0f;
+    if (c < h) z = (float)sct_residual(X[row * g + genes[c]], par[c], par[h + c], par[2 * (size_t)h + c], lu[row], clip);
     Z[row * ldz + c] = z;
 }
 
@@ -155,10 +348,22 @@ __global__ void __launch_bounds__(256) k_prep_csr_normalize(const int64_t *__res
     for (int64_t e = e0 + lane; e < e1; e += 64) Y[e] = t > 0.0 ? (float)log1p((double)X[e] * scale / t) : 0.0f;
 }
 
-// k_prep_col_partial on the transpose: thread (tx, ty) owns gene j and the rows r = ty (mod 4) of the slice; `vals` is in
-// the caller's order and reached through pos.  SUM walks the stored entries of the slice; CENTRED and CLIPPED walk all its
-// rows and add the stored value's term or the constant of a zero.
-template <int MODE>
+// the first entry of a column's row list [k, end) at or below row r0
+__device__ __forceinline__ int64_t csc_first_entry(const int32_t *__restrict__ rows, int64_t k, int64_t end, int r0)
+{
+    while (k < end) {
+        const int64_t mid = k + ((end - k) >> 1);
+        if (rows[mid] < r0) k = mid + 1; else end = mid;
+    }
+    return k;
+}
+
+// k_prep_col_partial<ColMode<Term>> on the transpose: thread (tx, ty) owns gene j and the rows r = ty (mod 4) of the slice;
+// `vals` is in the caller's order and reached through pos.  The walk is the term's: the stored entries of the slice
+// (kWalkStored), or all its rows, adding the stored value's term or the gene's constant of a zero (kWalkZeroConstant).  This
+// kernel keeps its own prologue, LDS join and arguments: written over ColSlice and a mode argument it measured 1.5 - 2.4 %
+// slower at 70 000 x 65 536 (profiles/prep_refactor_ab.json).
+template <typename Term>
 __global__ void __launch_bounds__(256) k_prep_csc_col_partial(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rows,
                                                               const int32_t *__restrict__ pos, const float *__restrict__ vals,
                                                               int n, int g, const double *__restrict__ mean,
@@ -173,13 +378,8 @@ __global__ void __launch_bounds__(256) k_prep_csc_col_partial(const int64_t *__r
     double acc = 0.0;
     int32_t cnt = 0;
     if (j < g) {
-        int64_t lo = colptr[j], hi = colptr[j + 1];
-        while (lo < hi) {                                         // the column's first entry at or below row r0
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (rows[mid] < r0) lo = mid + 1; else hi = mid;
-        }
         const int64_t end = colptr[j + 1];
-        int64_t k = lo;
+        int64_t k = csc_first_entry(rows, colptr[j], end, r0);
         // the next stored row of this thread's row lane inside the slice, r1 when there is none
         auto seek = [&]() -> int {
             for (; k < end; ++k) {
@@ -190,39 +390,23 @@ __global__ void __launch_bounds__(256) k_prep_csc_col_partial(const int64_t *__r
             return r1;
         };
         int nr = seek();
-        if (MODE == kColSum || MODE == kColLog1p) {                 // (log1p(0) is +0.0, like the 0 of a sum)
+        if (Term::kWalk == kWalkStored) {
             while (nr < r1) {
                 const float v = vals[pos[k]];
-                acc += MODE == kColLog1p ? log1p((double)v) : (double)v;
+                acc += Term::term(v, 0.0, 1.0, clip);
                 cnt += v != 0.0f;
                 ++k;
                 nr = seek();
             }
         } else {
-            const double mj = mean[j], sj = MODE == kColClipped ? sd[j] : 1.0;
-            double zero;                                          // a zero's term, by the operations of the dense kernel
-            if (MODE == kColCentred) {
-                const double d = (double)0.0f - mj;
-                zero = d * d;
-            } else {
-                double d = ((double)0.0f - mj) / (sj != 0.0 ? sj : 1.0);
-                d = d < clip ? d : clip;
-                zero = d * d;
-            }
-            if (MODE == kColCentred || sj != 0.0) {
+            const double mj = mean[j], sj = Term::kUsesSd ? sd[j] : 1.0;
+            const double zero = Term::term(0.0f, mj, sj != 0.0 ? sj : 1.0, clip);
+            if (!Term::kUsesSd || sj != 0.0) {
                 int r = r0 + ty;
                 while (r < r1) {
                     for (; r < nr; r += 4) acc += zero;
                     if (r >= r1) break;
-                    const float v = vals[pos[k]];                 // (r == nr: both are = ty mod 4)
-                    if (MODE == kColCentred) {
-                        const double d = (double)v - mj;
-                        acc += d * d;
-                    } else {
-                        double d = ((double)v - mj) / sj;
-                        d = d < clip ? d : clip;
-                        acc += d * d;
-                    }
+                    acc += Term::term(vals[pos[k]], mj, sj, clip);    // (r == nr: both are = ty mod 4)
                     r += 4;
                     ++k;
                     nr = seek();
@@ -236,39 +420,60 @@ __global__ void __launch_bounds__(256) k_prep_csc_col_partial(const int64_t *__r
     if (ty == 0 && j < g) {
         const size_t o = (size_t)blockIdx.y * g + j;
         psum[o] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
-        if (MODE == kColSum) pnnz[o] = s_cnt[0][tx] + s_cnt[1][tx] + s_cnt[2][tx] + s_cnt[3][tx];
+        if (Term::kCounts) pnnz[o] = s_cnt[0][tx] + s_cnt[1][tx] + s_cnt[2][tx] + s_cnt[3][tx];
     }
 }
 
-// k_prep_select from CSR: one workgroup per cell builds its row of Z in LDS -- every column's value for y = 0 first, then,
-// past a barrier, the cell's stored entries of chosen genes over their columns (a gene is stored at most once per cell and
-// chosen at most once: no two lanes write one word) -- and stores it coalesced.  gmap: gene -> column of Z, -1 = not chosen.
-__global__ void __launch_bounds__(256) k_prep_csr_select(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                                         const float *__restrict__ Y, const int32_t *__restrict__ gmap, int h,
-                                                         int ldz, const float *__restrict__ mu, const float *__restrict__ inv,
-                                                         const uint8_t *__restrict__ flat, float clip, float *__restrict__ Z)
+// the transposed kernel of a mode whose zeros depend on the row (kWalkEveryRow): every row of the slice is computed, a
+// stored value's term or that of 0.0f, over ColSlice like the dense kernel
+template <typename Mode>
+__global__ void __launch_bounds__(256) k_prep_csc_row_partial(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rows,
+                                                              const int32_t *__restrict__ pos, const float *__restrict__ vals,
+                                                              int n, Mode mode, double *__restrict__ psum)
+{
+    const ColSlice s(n);
+    double acc = 0.0;
+    if (s.j < mode.count) {
+        const int j = mode.bind(s.j);
+        const int64_t end = colptr[j + 1];
+        int64_t k = csc_first_entry(rows, colptr[j], end, s.r0);
+        for (int r = s.r0 + s.ty; r < s.r1; r += 4) {
+            while (k < end && rows[k] < r) ++k;
+            acc += mode(k < end && rows[k] == r ? vals[pos[k]] : 0.0f, r);
+        }
+    }
+    s.store(mode, acc, 0, psum, nullptr);
+}
+
+// One workgroup per cell builds a row of `count` floats in LDS -- at(c, 0.0f) in every column first, then, past a barrier,
+// at(c, x) over the columns of the cell's stored entries of chosen genes (a gene is stored at most once per cell and chosen
+// at most once: no two lanes write one word) -- and stores it as out[c * stride].  gmap: gene -> column, -1 = not chosen.
+template <typename At>
+__device__ __forceinline__ void csr_row_scatter(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                const float *__restrict__ vals, const int32_t *__restrict__ gmap, size_t row,
+                                                int count, const At &at, float *__restrict__ out, size_t stride)
 {
     __shared__ float s_row[MI_PREP_MAX_FEATURES];
-    const size_t row = blockIdx.x;
-    for (int c = threadIdx.x; c < ldz; c += 256) {
-        float z = 0.0f;
-        if (c < h && !flat[c]) {
-            const float d = 0.0f - mu[c];
-            z = fminf(d * inv[c], clip);
-        }
-        s_row[c] = z;
-    }
+    for (int c = threadIdx.x; c < count; c += 256) s_row[c] = at(c, 0.0f);
     __syncthreads();
     const int64_t e1 = indptr[row + 1];
     for (int64_t e = indptr[row] + threadIdx.x; e < e1; e += 256) {
         const int c = gmap[indices[e]];
-        if (c >= 0 && !flat[c]) {
-            const float d = Y[e] - mu[c];
-            s_row[c] = fminf(d * inv[c], clip);
-        }
+        if (c >= 0) s_row[c] = at(c, vals[e]);
     }
     __syncthreads();
-    for (int c = threadIdx.x; c < ldz; c += 256) Z[row * ldz + c] = s_row[c];
+    for (int c = threadIdx.x; c < count; c += 256) out[c * stride] = s_row[c];
+}
+
+// k_prep_select from CSR, the row stored coalesced
+template <typename Cols>
+__global__ void __launch_bounds__(256) k_prep_csr_select(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                         const float *__restrict__ vals, const int32_t *__restrict__ gmap,
+                                                         int ldz, Cols cols, float *__restrict__ Z)
+{
+    const size_t row = blockIdx.x;
+    cols.bind_row(row);
+    csr_row_scatter(indptr, indices, vals, gmap, row, ldz, cols, Z + row * ldz, 1);
 }
 
 // tile s of the row-major list of the upper block triangle: row I holds the tiles J = I .. T - 1
@@ -512,37 +717,20 @@ __global__ void __launch_bounds__(256) k_prep_csr_cell_qc(const int64_t *__restr
 }
 
 // ---- regression of covariates out of the gathered columns (mi_prep_select_regressed) --------------------------------------
-// Z holds the h chosen columns of Y, unscaled; Q is the n x q orthonormal basis of the design (fp64, q <= kMaxQ).  The three
-// kernels below share k_prep_col_partial's shape and order: a workgroup is 64 columns x 4 row lanes over a slice of kRowSlice
-// rows, lane ty (one wavefront: its row of Q is uniform, fetched by scalar loads) adds rows r0 + ty, r0 + ty + 4, ...
-// ascending, the four lanes meet in LDS as ((s0 + s1) + s2) + s3, and k_prep_col_finish adds the slices in ascending order.
-// They read Z alone, so a sparse handle gives the bits of a dense one.  Every product is a multiply, then an add.
-constexpr int kMaxQ = MI_PREP_MAX_DESIGN_COLS;
-
-// r = y - sum_k Q_ik c_k: acc = Q_i0 c_0, then acc = acc + Q_ik c_k for k ascending
-__device__ __forceinline__ double regress_residual(float y, const double *__restrict__ qr, const double (&c)[kMaxQ], int q)
-{
-    double acc = qr[0] * c[0];
-#pragma unroll
-    for (int k = 1; k < kMaxQ; ++k)
-        if (k < q) acc = acc + qr[k] * c[k];
-    return (double)y - acc;
-}
+// Z holds the h chosen columns of Y, unscaled.  The residuals' moments are k_prep_col_partial<RegressMoment>; the two kernels
+// below stand on the same slices and lanes.  They read Z alone, so a sparse handle gives the bits of a dense one.
 
 // psum[(slice * (q + 1) + k) * h + j]: k < q: sum_i Q_ik y_ij; k = q: sum_i y_ij^2
 __global__ void __launch_bounds__(256) k_prep_regress_coef(const float *__restrict__ Z, int n, int h, int ldz,
                                                            const double *__restrict__ Q, int q, double *__restrict__ psum)
 {
-    __shared__ double s_sum[4][64];
-    const int tx = threadIdx.x & 63, ty = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int j = blockIdx.x * 64 + tx;
-    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
+    const ColSlice s(n);
     double acc[kMaxQ + 1];
 #pragma unroll
     for (int k = 0; k <= kMaxQ; ++k) acc[k] = 0.0;
-    if (j < h) {
-        for (int r = r0 + ty; r < r1; r += 4) {
-            const double y = (double)Z[(size_t)r * ldz + j];
+    if (s.j < h) {
+        for (int r = s.r0 + s.ty; r < s.r1; r += 4) {
+            const double y = (double)Z[(size_t)r * ldz + s.j];
             const double *qr = Q + (size_t)r * q;
 #pragma unroll
             for (int k = 0; k < kMaxQ; ++k)
@@ -553,68 +741,25 @@ __global__ void __launch_bounds__(256) k_prep_regress_coef(const float *__restri
 #pragma unroll
     for (int k = 0; k <= kMaxQ; ++k) {
         if (k >= q && k < kMaxQ) continue;                        // (uniform)
-        s_sum[ty][tx] = acc[k];
-        __syncthreads();
-        if (ty == 0 && j < h)
-            psum[((size_t)blockIdx.y * (q + 1) + (k < q ? k : q)) * h + j] =
-                ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
-        __syncthreads();
+        s.join(acc[k], s.j < h, psum + ((size_t)blockIdx.y * (q + 1) + (k < q ? k : q)) * h + s.j);
+        __syncthreads();                                          // (the next sum goes into the same words)
     }
-}
-
-// MODE 0: psum[slice * h + j] = sum_i r_ij;  MODE 1: sum_i (r_ij - mean_j)^2.  coef: q x h.
-template <int MODE>
-__global__ void __launch_bounds__(256) k_prep_regress_moment(const float *__restrict__ Z, int n, int h, int ldz,
-                                                             const double *__restrict__ Q, int q,
-                                                             const double *__restrict__ coef, const double *__restrict__ mean,
-                                                             double *__restrict__ psum)
-{
-    __shared__ double s_sum[4][64];
-    const int tx = threadIdx.x & 63, ty = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int j = blockIdx.x * 64 + tx;
-    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
-    double acc = 0.0;
-    if (j < h) {
-        double c[kMaxQ];
-#pragma unroll
-        for (int k = 0; k < kMaxQ; ++k) c[k] = k < q ? coef[(size_t)k * h + j] : 0.0;
-        const double mj = MODE ? mean[j] : 0.0;
-        for (int r = r0 + ty; r < r1; r += 4) {
-            const double res = regress_residual(Z[(size_t)r * ldz + j], Q + (size_t)r * q, c, q);
-            if (MODE) {
-                const double d = res - mj;
-                acc += d * d;
-            } else {
-                acc += res;
-            }
-        }
-    }
-    s_sum[ty][tx] = acc;
-    __syncthreads();
-    if (ty == 0 && j < h)
-        psum[(size_t)blockIdx.y * h + j] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
 }
 
 // in place: z = flat ? 0 : (float) fmin((r - mean) * inv, clip), fp64 with one rounding to f32 (the padding columns keep
 // the zeros of the gather)
-__global__ void __launch_bounds__(256) k_prep_regress_scale(float *__restrict__ Z, int n, int h, int ldz,
-                                                            const double *__restrict__ Q, int q, const double *__restrict__ coef,
+__global__ void __launch_bounds__(256) k_prep_regress_scale(float *__restrict__ Z, int n, int h, int ldz, RegressColumn col,
                                                             const double *__restrict__ mean, const double *__restrict__ inv,
                                                             const uint8_t *__restrict__ flat, double clip)
 {
-    const int tx = threadIdx.x & 63, ty = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int j = blockIdx.x * 64 + tx;
-    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
-    if (j >= h) return;
-    double c[kMaxQ];
-#pragma unroll
-    for (int k = 0; k < kMaxQ; ++k) c[k] = k < q ? coef[(size_t)k * h + j] : 0.0;
-    const double mj = mean[j], ij = inv[j];
-    const bool fj = flat[j] != 0;
-    for (int r = r0 + ty; r < r1; r += 4) {
-        float *z = Z + (size_t)r * ldz + j;
-        const double res = regress_residual(*z, Q + (size_t)r * q, c, q);
-        *z = fj ? 0.0f : (float)fmin((res - mj) * ij, clip);
+    const ColSlice s(n);
+    if (s.j >= h) return;
+    col.bind(s.j, h);
+    const double mj = mean[s.j], ij = inv[s.j];
+    const bool fj = flat[s.j] != 0;
+    for (int r = s.r0 + s.ty; r < s.r1; r += 4) {
+        float *z = Z + (size_t)r * ldz + s.j;
+        *z = fj ? 0.0f : (float)fmin((col.residual(*z, r) - mj) * ij, clip);
     }
 }
 
@@ -634,23 +779,13 @@ __global__ void __launch_bounds__(256) k_sct_gather(const float *__restrict__ X,
     B[(size_t)jj * mc + ii] = X[(size_t)cells[ii] * g + genes[jj]];
 }
 
-// the same from CSR: one workgroup per fit cell, its row of the block in LDS (zeros, then the stored entries of fit genes)
+// the same from CSR: one workgroup per fit cell scatters its row of the block (the counts as they are) and stores it gene-major
 __global__ void __launch_bounds__(256) k_sct_csr_gather(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                         const float *__restrict__ X, const int32_t *__restrict__ gmap,
                                                         const int32_t *__restrict__ cells, int mc, int g1, float *__restrict__ B)
 {
-    __shared__ float s_row[MI_PREP_MAX_FEATURES];
     const int ii = blockIdx.x;
-    const size_t row = (size_t)cells[ii];
-    for (int c = threadIdx.x; c < g1; c += 256) s_row[c] = 0.0f;
-    __syncthreads();
-    const int64_t e1 = indptr[row + 1];
-    for (int64_t e = indptr[row] + threadIdx.x; e < e1; e += 256) {
-        const int c = gmap[indices[e]];
-        if (c >= 0) s_row[c] = X[e];
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < g1; c += 256) B[(size_t)c * mc + ii] = s_row[c];
+    csr_row_scatter(indptr, indices, X, gmap, (size_t)cells[ii], g1, [](int, float x) { return x; }, B + ii, (size_t)mc);
 }
 
 // K sums of a workgroup of 256: the wave butterfly, then the four waves in LDS as ((s0 + s1) + s2) + s3; every thread
@@ -793,175 +928,95 @@ __global__ void __launch_bounds__(256) k_sct_nb_fit(const float *__restrict__ B,
     }
 }
 
-// the Pearson residual of count x under mu = exp(b0 + b1 log_umi), variance mu + alpha mu^2, clipped to +- clip
-__device__ __forceinline__ double sct_residual(float x, double b0, double b1, double alpha, double lu, double clip)
-{
-    const double mu = exp(b0 + b1 * lu);
-    const double r = ((double)x - mu) / sqrt(mu + alpha * (mu * mu));
-    return fmin(fmax(r, -clip), clip);
-}
-
-// k_prep_col_partial's shape, slices and order on the residuals of the chosen genes.  MODE 0: psum[slice * gp + jj] =
-// sum_i r;  MODE 1: sum_i (r - mean_jj)^2.  par: b0, b1, alpha, gp entries each.
-template <int MODE>
-__global__ void __launch_bounds__(256) k_sct_col_partial(const float *__restrict__ X, int n, int g,
-                                                         const int32_t *__restrict__ genes, int gp,
-                                                         const double *__restrict__ par, const double *__restrict__ lu, double clip,
-                                                         const double *__restrict__ mean, double *__restrict__ psum)
-{
-    __shared__ double s_sum[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int jj = blockIdx.x * 64 + tx;
-    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
-    double acc = 0.0;
-    if (jj < gp) {
-        const int j = genes[jj];
-        const double b0 = par[jj], b1 = par[gp + jj], al = par[2 * (size_t)gp + jj], mj = MODE ? mean[jj] : 0.0;
-        for (int r = r0 + ty; r < r1; r += 4) {
-            const double res = sct_residual(X[(size_t)r * g + j], b0, b1, al, lu[r], clip);
-            if (MODE) {
-                const double d = res - mj;
-                acc += d * d;
-            } else {
-                acc += res;
-            }
-        }
-    }
-    s_sum[ty][tx] = acc;
-    __syncthreads();
-    if (ty == 0 && jj < gp)
-        psum[(size_t)blockIdx.y * gp + jj] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
-}
-
-// the same on the transpose of a sparse handle.  The residual of a zero depends on the cell, so every row of the slice is
-// walked (as in k_prep_csc_col_partial's CENTRED mode) and each adds its own term at its place in the order.
-template <int MODE>
-__global__ void __launch_bounds__(256) k_sct_csc_col_partial(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rows,
-                                                             const int32_t *__restrict__ pos, const float *__restrict__ vals, int n,
-                                                             const int32_t *__restrict__ genes, int gp,
-                                                             const double *__restrict__ par, const double *__restrict__ lu,
-                                                             double clip, const double *__restrict__ mean,
-                                                             double *__restrict__ psum)
-{
-    __shared__ double s_sum[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int jj = blockIdx.x * 64 + tx;
-    const int r0 = blockIdx.y * kRowSlice, r1 = r0 + kRowSlice < n ? r0 + kRowSlice : n;
-    double acc = 0.0;
-    if (jj < gp) {
-        const int j = genes[jj];
-        const double b0 = par[jj], b1 = par[gp + jj], al = par[2 * (size_t)gp + jj], mj = MODE ? mean[jj] : 0.0;
-        int64_t lo = colptr[j], hi = colptr[j + 1];
-        while (lo < hi) {                                         // the column's first entry at or below row r0
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (rows[mid] < r0) lo = mid + 1; else hi = mid;
-        }
-        const int64_t end = colptr[j + 1];
-        int64_t k = lo;
-        for (int r = r0 + ty; r < r1; r += 4) {
-            while (k < end && rows[k] < r) ++k;
-            const float x = k < end && rows[k] == r ? vals[pos[k]] : 0.0f;
-            const double res = sct_residual(x, b0, b1, al, lu[r], clip);
-            if (MODE) {
-                const double d = res - mj;
-                acc += d * d;
-            } else {
-                acc += res;
-            }
-        }
-    }
-    s_sum[ty][tx] = acc;
-    __syncthreads();
-    if (ty == 0 && jj < gp)
-        psum[(size_t)blockIdx.y * gp + jj] = ((s_sum[0][tx] + s_sum[1][tx]) + s_sum[2][tx]) + s_sum[3][tx];
-}
-
-// stage 1 of mi_prep_sct_select: Z = (float) the clipped residual of the chosen genes, k_prep_select's two forms
-__global__ void __launch_bounds__(256) k_sct_select(const float *__restrict__ X, int g, const int32_t *__restrict__ genes, int h,
-                                                    int ldz, const double *__restrict__ par, const double *__restrict__ lu,
-                                                    double clip, float *__restrict__ Z)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    const size_t row = blockIdx.y;
-    if (c >= ldz) return;
-    float z = 0.0f;
-    if (c < h) z = (float)sct_residual(X[row * g + genes[c]], par[c], par[h + c], par[2 * (size_t)h + c], lu[row], clip);
-    Z[row * ldz + c] = z;
-}
-
-__global__ void __launch_bounds__(256) k_sct_csr_select(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                                        const float *__restrict__ X, const int32_t *__restrict__ gmap, int h, int ldz,
-                                                        const double *__restrict__ par, const double *__restrict__ lu, double clip,
-                                                        float *__restrict__ Z)
-{
-    __shared__ float s_row[MI_PREP_MAX_FEATURES];
-    const size_t row = blockIdx.x;
-    const double l = lu[row];
-    for (int c = threadIdx.x; c < ldz; c += 256)
-        s_row[c] = c < h ? (float)sct_residual(0.0f, par[c], par[h + c], par[2 * (size_t)h + c], l, clip) : 0.0f;
-    __syncthreads();
-    const int64_t e1 = indptr[row + 1];
-    for (int64_t e = indptr[row] + threadIdx.x; e < e1; e += 256) {
-        const int c = gmap[indices[e]];
-        if (c >= 0) s_row[c] = (float)sct_residual(X[e], par[c], par[h + c], par[2 * (size_t)h + c], l, clip);
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < ldz; c += 256) Z[row * ldz + c] = s_row[c];
-}
-
 }  // namespace
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
 
-// (mi_prep_matrix: mi_prep_handle.h)
+// (mi_prep_matrix and on_matrix, the way into every entry below: mi_prep_handle.h)
 
 namespace {
 
-// one column reduction over M: partials per slice, then the ordered sum divided by denom (device pointers in and out)
-template <int MODE>
-int col_reduce(const mi_prep_matrix *m, const float *M, const double *d_mean, const double *d_sd, double clip, double denom,
-               double *d_psum, int32_t *d_pnnz, double *d_out, int32_t *d_out_nnz)
+int slices(const mi_prep_matrix *m) { return (m->n + kRowSlice - 1) / kRowSlice; }
+
+// out[e] = (sum over the slices, ascending, of psum[slice * count + e]) / denom; with d_pnnz, out_nnz[e] = the counts' sum
+int finish_slices(const double *d_psum, const int32_t *d_pnnz, int nslices, size_t count, double denom, double *d_out,
+                  int32_t *d_out_nnz)
 {
-    const int slices = (m->n + kRowSlice - 1) / kRowSlice;
-    const dim3 grid((unsigned)((m->g + 63) / 64), (unsigned)slices);
-    if (m->sparse)
-        hipLaunchKernelGGL(k_prep_csc_col_partial<MODE>, grid, dim3(256), 0, 0, m->d_colptr, m->d_rows, m->d_pos, M, m->n, m->g,
-                           d_mean, d_sd, clip, d_psum, d_pnnz);
-    else
-        hipLaunchKernelGGL(k_prep_col_partial<MODE>, grid, dim3(256), 0, 0, M, m->n, m->g, d_mean, d_sd, clip, d_psum, d_pnnz);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_prep_col_finish, dim3((unsigned)((m->g + 255) / 256)), dim3(256), 0, 0, d_psum,
-                       MODE == kColSum ? d_pnnz : nullptr, slices, m->g, denom, d_out, d_out_nnz);
+    hipLaunchKernelGGL(k_prep_col_finish, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, d_psum, d_pnnz, nslices,
+                       (int)count, denom, d_out, d_out_nnz);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
 
-// Z (n x ldz) = the scaled chosen columns of Y, by the select kernel of the handle's kind (device pointers; d_gmap: sparse only)
-int launch_select(const mi_prep_matrix *m, const int32_t *d_genes, const int32_t *d_gmap, int h, int ldz, const float *d_mu,
-                  const float *d_inv, const uint8_t *d_flat, float clip)
+// the partials of `mode` per slice of the dense M (n x ld)
+template <typename Mode>
+int col_partials_dense(const float *M, int ld, int n, const Mode &mode, double *d_psum, int32_t *d_pnnz)
+{
+    const dim3 grid((unsigned)((mode.count + 63) / 64), (unsigned)((n + kRowSlice - 1) / kRowSlice));
+    hipLaunchKernelGGL(k_prep_col_partial<Mode>, grid, dim3(256), 0, 0, M, ld, n, mode, d_psum, d_pnnz);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+// One column reduction over M, the handle's counts or normalised values: the partials by the kernel of the handle's kind,
+// then the ordered sum divided by denom (device pointers in and out; d_pnnz and d_out_nnz: the modes that count).
+template <typename Mode>
+int col_reduce(const mi_prep_matrix *m, const float *M, const Mode &mode, double denom, double *d_psum, int32_t *d_pnnz,
+               double *d_out, int32_t *d_out_nnz)
 {
     if (m->sparse) {
-        hipLaunchKernelGGL(k_prep_csr_select, dim3((unsigned)m->n), dim3(256), 0, 0, m->d_indptr, m->d_indices, m->d_Y, d_gmap,
-                           h, ldz, d_mu, d_inv, d_flat, clip, m->d_Z);
+        const dim3 grid((unsigned)((mode.count + 63) / 64), (unsigned)slices(m));
+        if constexpr (Mode::kWalk == kWalkEveryRow)
+            hipLaunchKernelGGL(k_prep_csc_row_partial<Mode>, grid, dim3(256), 0, 0, m->d_colptr, m->d_rows, m->d_pos, M, m->n, mode,
+                               d_psum);
+        else
+            hipLaunchKernelGGL(k_prep_csc_col_partial<typename Mode::Term>, grid, dim3(256), 0, 0, m->d_colptr, m->d_rows,
+                               m->d_pos, M, m->n, mode.count, mode.mean, mode.sd, mode.clip, d_psum, d_pnnz);
         HIP_TRY(hipGetLastError());
+    } else {
+        MI_TRY(col_partials_dense(M, m->g, m->n, mode, d_psum, d_pnnz));
     }
-    // dense: (one cell per grid.y, whose limit is 65535: slabs of 32768 cells)
-    for (int r0 = 0; r0 < m->n && !m->sparse; r0 += 32768) {
-        const int rows = m->n - r0 < 32768 ? m->n - r0 : 32768;
-        hipLaunchKernelGGL(k_prep_select, dim3((unsigned)(ldz / 256 + (ldz % 256 != 0)), (unsigned)rows), dim3(256), 0, 0,
-                           m->d_Y + (size_t)r0 * m->g, rows, m->g, d_genes, h, ldz, d_mu, d_inv, d_flat, clip,
-                           m->d_Z + (size_t)r0 * ldz);
-        HIP_TRY(hipGetLastError());
-    }
+    return finish_slices(d_psum, Mode::kCounts ? d_pnnz : nullptr, slices(m), (size_t)mode.count, denom, d_out, d_out_nnz);
+}
+
+// Z sized for h columns (ldz: h rounded up to the Gram tile); a failure leaves it empty
+int size_Z(mi_prep_matrix *m, int h)
+{
+    const int ldz = (h + kTile - 1) / kTile * kTile;
+    HIP_TRY(m->d_Z.resize((size_t)m->n * ldz));
+    m->ldz = ldz;
     return MI_OK;
 }
 
-// out[e] = (sum over the slices, ascending, of psum[slice * count + e]) / denom
-int finish_slices(const double *d_psum, int slices, size_t count, double denom, double *d_out)
+// one slab of the dense selection: `rows` cells from cell r0 on, M and Z already at that cell
+void launch_dense_select(dim3 grid, const float *M, int rows, int g, const int32_t *d_genes, int ldz, const ScaledCols &c, int,
+                         float *Z)
 {
-    hipLaunchKernelGGL(k_prep_col_finish, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, d_psum, nullptr, slices,
-                       (int)count, denom, d_out, nullptr);
-    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_prep_select, grid, dim3(256), 0, 0, M, rows, g, d_genes, c.h, ldz, c.mu, c.inv, c.flat, c.clip, Z);
+}
+
+void launch_dense_select(dim3 grid, const float *M, int, int g, const int32_t *d_genes, int ldz, const SctCols &c, int r0, float *Z)
+{
+    hipLaunchKernelGGL(k_sct_select, grid, dim3(256), 0, 0, M, g, d_genes, c.h, ldz, c.par, c.lu + r0, c.clip, Z);
+}
+
+// Z (n x ldz) = `cols` of the chosen columns of M, by the select kernel of the handle's kind (device pointers; d_gmap: sparse only)
+template <typename Cols>
+int launch_select(const mi_prep_matrix *m, const float *M, const int32_t *d_genes, const int32_t *d_gmap, const Cols &cols)
+{
+    const int ldz = m->ldz;
+    if (m->sparse) {
+        hipLaunchKernelGGL(k_prep_csr_select<Cols>, dim3((unsigned)m->n), dim3(256), 0, 0, m->d_indptr, m->d_indices, M, d_gmap,
+                           ldz, cols, m->d_Z);
+        HIP_TRY(hipGetLastError());
+        return MI_OK;
+    }
+    for (int r0 = 0; r0 < m->n; r0 += 32768) {                    // (one cell per grid.y, whose limit is 65535: slabs of 32768 cells)
+        const int rows = m->n - r0 < 32768 ? m->n - r0 : 32768;
+        launch_dense_select(dim3((unsigned)(ldz / 256 + (ldz % 256 != 0)), (unsigned)rows), M + (size_t)r0 * m->g, rows, m->g,
+                            d_genes, ldz, cols, r0, m->d_Z + (size_t)r0 * ldz);
+        HIP_TRY(hipGetLastError());
+    }
     return MI_OK;
 }
 
@@ -971,36 +1026,31 @@ int regress_stages(mi_prep_matrix *m, int h, const double *d_Q, int q, double cl
                    double *out_mean, double *out_var, uint8_t *out_flat, float *out_ms)
 {
     const size_t hs = (size_t)h, qs = (size_t)q;
-    const int ldz = m->ldz, slices = (m->n + kRowSlice - 1) / kRowSlice;
+    const int ldz = m->ldz, ns = slices(m);
     std::vector<uint8_t> flat(hs, 0);
     std::vector<double> S(hs), ss(hs), inv(hs), var(hs);
     DevBufs bufs;
     uint8_t *d_flat;
     double *d_psum, *d_coef, *d_mean, *d_ss, *d_inv;
-    HIP_TRY(bufs.alloc(&d_flat, hs));
-    HIP_TRY(bufs.alloc(&d_psum, (size_t)slices * (qs + 1) * hs));
+    HIP_TRY(bufs.alloc(&d_psum, (size_t)ns * (qs + 1) * hs));
     HIP_TRY(bufs.alloc(&d_coef, (qs + 1) * hs));                  // q rows of coefficients, then S
     HIP_TRY(bufs.alloc(&d_mean, hs));
     HIP_TRY(bufs.alloc(&d_ss, hs));
-    HIP_TRY(bufs.alloc(&d_inv, hs));
-    const dim3 grid((unsigned)((h + 63) / 64), (unsigned)slices);
+    const RegressColumn col{d_Q, q, d_coef};
     float ms1 = 0.0f, ms2 = 0.0f;
     {
         Timer t;
         MI_TRY(t.start(0));
         // 2. c = Q^T y and S = sum y^2
-        hipLaunchKernelGGL(k_prep_regress_coef, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_psum);
+        hipLaunchKernelGGL(k_prep_regress_coef, dim3((unsigned)((h + 63) / 64), (unsigned)ns), dim3(256), 0, 0, m->d_Z, m->n, h,
+                           ldz, d_Q, q, d_psum);
         HIP_TRY(hipGetLastError());
-        MI_TRY(finish_slices(d_psum, slices, (qs + 1) * hs, 1.0, d_coef));
+        MI_TRY(finish_slices(d_psum, nullptr, ns, (qs + 1) * hs, 1.0, d_coef, nullptr));
         // 3. the mean of the residuals, then their squares about it
-        hipLaunchKernelGGL(k_prep_regress_moment<0>, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, nullptr,
-                           d_psum);
-        HIP_TRY(hipGetLastError());
-        MI_TRY(finish_slices(d_psum, slices, hs, (double)m->n, d_mean));
-        hipLaunchKernelGGL(k_prep_regress_moment<1>, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, d_mean,
-                           d_psum);
-        HIP_TRY(hipGetLastError());
-        MI_TRY(finish_slices(d_psum, slices, hs, 1.0, d_ss));
+        MI_TRY(col_partials_dense(m->d_Z, ldz, m->n, RegressMoment<0>{h, col, nullptr}, d_psum, nullptr));
+        MI_TRY(finish_slices(d_psum, nullptr, ns, hs, (double)m->n, d_mean, nullptr));
+        MI_TRY(col_partials_dense(m->d_Z, ldz, m->n, RegressMoment<1>{h, col, d_mean}, d_psum, nullptr));
+        MI_TRY(finish_slices(d_psum, nullptr, ns, hs, 1.0, d_ss, nullptr));
         MI_TRY(t.stop(0, &ms1));
     }
     // 4. the flat rule and the inverse standard deviation, in host fp64
@@ -1011,14 +1061,14 @@ int regress_stages(mi_prep_matrix *m, int h, const double *d_Q, int q, double cl
         flat[c] = ss[c] <= 1e-16 * S[c];
         inv[c] = flat[c] ? 0.0 : (unit_scale ? 1.0 : 1.0 / std::sqrt(var[c]));
     }
-    HIP_TRY(hipMemcpy(d_flat, flat.data(), hs, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_inv, inv.data(), hs * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(bufs.upload(&d_flat, flat.data(), hs));
+    HIP_TRY(bufs.upload(&d_inv, inv.data(), hs));
     {
         Timer t;
         MI_TRY(t.start(0));
         // 5. scale in place
-        hipLaunchKernelGGL(k_prep_regress_scale, grid, dim3(256), 0, 0, m->d_Z, m->n, h, ldz, d_Q, q, d_coef, d_mean, d_inv,
-                           d_flat, clip);
+        hipLaunchKernelGGL(k_prep_regress_scale, dim3((unsigned)((h + 63) / 64), (unsigned)ns), dim3(256), 0, 0, m->d_Z, m->n, h,
+                           ldz, col, d_mean, d_inv, d_flat, clip);
         MI_TRY(t.stop(0, &ms2));
     }
     if (out_ms) *out_ms = ms1 + ms2;
@@ -1029,16 +1079,44 @@ int regress_stages(mi_prep_matrix *m, int h, const double *d_Q, int q, double cl
     return MI_OK;
 }
 
-// MI_EINVAL unless the `count` indices are distinct and inside [0, limit)
-int check_indices(const int32_t *idx, int count, int limit, const char *what)
+// MI_EINVAL unless the `count` indices are distinct and inside [0, limit); `what` names the array, `one` an element
+int check_indices(const int32_t *idx, int count, int limit, const char *what, const char *one)
 {
     std::vector<uint8_t> seen((size_t)limit, 0);
     for (int c = 0; c < count; ++c) {
         const int32_t j = idx[c];
         if (j < 0 || j >= limit) return fail(MI_EINVAL, "%s[%d] = %d is outside [0, %d)", what, c, (int)j, limit);
-        if (seen[j]) return fail(MI_EINVAL, "%s %d is chosen twice", what, (int)j);
+        if (seen[j]) return fail(MI_EINVAL, "%s %d is chosen twice", one, (int)j);
         seen[j] = 1;
     }
+    return MI_OK;
+}
+
+// the map gene -> its place among the `count` chosen genes, -1 = not chosen (what the CSR kernels scatter through)
+std::vector<int32_t> gene_map(const mi_prep_matrix *m, const int32_t *genes, int count)
+{
+    std::vector<int32_t> gmap((size_t)m->g, -1);
+    for (int c = 0; c < count; ++c) gmap[genes[c]] = c;
+    return gmap;
+}
+
+// the chosen genes on the device and, for a sparse handle, their gene_map (null for a dense one)
+int upload_genes(DevBufs &bufs, const mi_prep_matrix *m, const int32_t *genes, int count, int32_t **d_genes, int32_t **d_gmap)
+{
+    HIP_TRY(bufs.upload(d_genes, genes, (size_t)count));
+    *d_gmap = nullptr;
+    if (m->sparse) {
+        const std::vector<int32_t> gmap = gene_map(m, genes, count);
+        HIP_TRY(bufs.upload(d_gmap, gmap.data(), gmap.size()));
+    }
+    return MI_OK;
+}
+
+// Q: n x q row-major
+int check_Q(const double *Q, size_t n, size_t q)
+{
+    for (size_t e = 0; e < n * q; ++e)
+        if (!std::isfinite(Q[e])) return fail(MI_EINVAL, "Q[%lld, %lld] is not finite", (long long)(e / q), (long long)(e % q));
     return MI_OK;
 }
 
@@ -1088,20 +1166,21 @@ int mi_prep_create_f32(const float *X, int n, int g, int device, mi_prep_matrix 
     for (size_t e = 0; e < cells; ++e)
         if (!(X[e] >= 0.0f) || std::isinf(X[e]))
             return fail(MI_EINVAL, "X[%lld, %lld] is NaN, infinite or negative", (long long)(e / g), (long long)(e % g));
-    MI_TRY(pick_device(device));
-    mi_prep_matrix *m = new (std::nothrow) mi_prep_matrix();
-    if (!m) return fail(MI_ENOMEM, "out of host memory");
-    m->n = n; m->g = g; m->device = device;
-    const int rc = [&]() -> int {
-        HIP_TRY(m->d_X.upload(X, cells));
+    return guarded([&]() -> int {
+        MI_TRY(pick_device(device));
+        mi_prep_matrix *m = new mi_prep_matrix();
+        m->n = n; m->g = g; m->device = device;
+        const int rc = [&]() -> int {
+            HIP_TRY(m->d_X.upload(X, cells));
+            return MI_OK;
+        }();
+        if (rc != MI_OK) {
+            mi_prep_destroy(m);
+            return rc;
+        }
+        *out = m;
         return MI_OK;
-    }();
-    if (rc != MI_OK) {
-        mi_prep_destroy(m);
-        return rc;
-    }
-    *out = m;
-    return MI_OK;
+    });
 }
 
 int mi_prep_create_csr_f32(const int64_t *indptr, const int32_t *indices, const float *data, int n, int g, int device,
@@ -1154,67 +1233,63 @@ int mi_prep_info(const mi_prep_matrix *m, int *n, int *g, int64_t *nnz, int *spa
 
 int mi_prep_normalize(mi_prep_matrix *m, double scale_factor, float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m) return fail(MI_EINVAL, "NULL argument");
-    if (!(scale_factor > 0.0) || std::isinf(scale_factor)) return fail(MI_EINVAL, "scale_factor must be finite and > 0");
-    HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(m->d_Y.reserve(m->sparse ? (size_t)m->nnz : (size_t)m->n * m->g));
-    m->normalized = false;
-    Timer t;
-    MI_TRY(t.start(0));
-    if (m->sparse)
-        hipLaunchKernelGGL(k_prep_csr_normalize, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_indptr, m->d_indices,
-                           m->d_X, m->d_Y, m->n, scale_factor);
-    else
-        hipLaunchKernelGGL(k_prep_normalize, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_X, m->d_Y, m->n, m->g,
-                           scale_factor);
-    MI_TRY(t.stop(0, out_kernel_ms));
-    m->normalized = true;
-    return MI_OK;
+    return on_matrix(m, true, 0, out_kernel_ms, [&]() -> int {
+        if (!(scale_factor > 0.0) || std::isinf(scale_factor)) return fail(MI_EINVAL, "scale_factor must be finite and > 0");
+        HIP_TRY(m->d_Y.reserve(m->sparse ? (size_t)m->nnz : (size_t)m->n * m->g));
+        m->normalized = false;
+        Timer t;
+        MI_TRY(t.start(0));
+        if (m->sparse)
+            hipLaunchKernelGGL(k_prep_csr_normalize, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_indptr, m->d_indices,
+                               m->d_X, m->d_Y, m->n, scale_factor);
+        else
+            hipLaunchKernelGGL(k_prep_normalize, dim3((unsigned)((m->n + 3) / 4)), dim3(256), 0, 0, m->d_X, m->d_Y, m->n, m->g,
+                               scale_factor);
+        MI_TRY(t.stop(0, out_kernel_ms));
+        m->normalized = true;
+        return MI_OK;
+    });
 }
 
 int mi_prep_fetch_normalized(mi_prep_matrix *m, float *out)
 {
-    if (!m || !out) return fail(MI_EINVAL, "NULL argument");
-    if (m->sparse) return fail(MI_EUNSUPPORTED, "a sparse handle has no dense normalised matrix: mi_prep_fetch_normalized_csr");
-    if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
-    HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpy(out, m->d_Y, (size_t)m->n * m->g * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return on_matrix(m, out != nullptr, 0, nullptr, [&]() -> int {
+        if (m->sparse) return fail(MI_EUNSUPPORTED, "a sparse handle has no dense normalised matrix: mi_prep_fetch_normalized_csr");
+        MI_TRY(check_state(m, NEED_NORMALIZED));
+        HIP_TRY(hipMemcpy(out, m->d_Y, (size_t)m->n * m->g * sizeof(float), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
 }
 
 int mi_prep_fetch_normalized_csr(mi_prep_matrix *m, float *out_data)
 {
-    if (!m || !out_data) return fail(MI_EINVAL, "NULL argument");
-    if (!m->sparse) return fail(MI_EINVAL, "the handle is dense: mi_prep_fetch_normalized");
-    if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
-    HIP_TRY(hipSetDevice(m->device));
-    if (m->nnz) HIP_TRY(hipMemcpy(out_data, m->d_Y, (size_t)m->nnz * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return on_matrix(m, out_data != nullptr, 0, nullptr, [&]() -> int {
+        if (!m->sparse) return fail(MI_EINVAL, "the handle is dense: mi_prep_fetch_normalized");
+        MI_TRY(check_state(m, NEED_NORMALIZED));
+        if (m->nnz) HIP_TRY(hipMemcpy(out_data, m->d_Y, (size_t)m->nnz * sizeof(float), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
 }
 
 int mi_prep_gene_stats(mi_prep_matrix *m, int which, double *mean, double *var, int32_t *nnz, float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m) return fail(MI_EINVAL, "NULL argument");
-    if (which != 0 && which != 1) return fail(MI_EINVAL, "which must be 0 (counts) or 1 (normalised), got %d", which);
-    if (which == 1 && !m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
-    HIP_TRY(hipSetDevice(m->device));
-    const size_t g = (size_t)m->g, slices = (size_t)(m->n + kRowSlice - 1) / kRowSlice;
-    return guarded([&]() -> int {                             // (the scratch owner holds a vector)
+    return on_matrix(m, true, 0, out_kernel_ms, [&]() -> int {
+        if (which != 0 && which != 1) return fail(MI_EINVAL, "which must be 0 (counts) or 1 (normalised), got %d", which);
+        MI_TRY(check_state(m, which ? NEED_NORMALIZED : 0));
+        const size_t g = (size_t)m->g, ns = (size_t)slices(m);
         DevBufs bufs;
         double *d_psum, *d_mean, *d_var;
         int32_t *d_pnnz, *d_nnz;
-        HIP_TRY(bufs.alloc(&d_psum, slices * g));
-        HIP_TRY(bufs.alloc(&d_pnnz, slices * g));
+        HIP_TRY(bufs.alloc(&d_psum, ns * g));
+        HIP_TRY(bufs.alloc(&d_pnnz, ns * g));
         HIP_TRY(bufs.alloc(&d_mean, g));
         HIP_TRY(bufs.alloc(&d_var, g));
         HIP_TRY(bufs.alloc(&d_nnz, g));
         const float *M = which ? m->d_Y : m->d_X;
         Timer t;
         MI_TRY(t.start(0));
-        MI_TRY(col_reduce<kColSum>(m, M, nullptr, nullptr, 0.0, (double)m->n, d_psum, d_pnnz, d_mean, d_nnz));
-        MI_TRY(col_reduce<kColCentred>(m, M, d_mean, nullptr, 0.0, (double)(m->n - 1), d_psum, nullptr, d_var, nullptr));
+        MI_TRY(col_reduce(m, M, ColSum{m->g}, (double)m->n, d_psum, d_pnnz, d_mean, d_nnz));
+        MI_TRY(col_reduce(m, M, ColCentred{m->g, d_mean}, (double)(m->n - 1), d_psum, nullptr, d_var, nullptr));
         MI_TRY(t.stop(0, out_kernel_ms));
         if (mean) HIP_TRY(hipMemcpy(mean, d_mean, g * sizeof(double), hipMemcpyDeviceToHost));
         if (var) HIP_TRY(hipMemcpy(var, d_var, g * sizeof(double), hipMemcpyDeviceToHost));
@@ -1226,27 +1301,22 @@ int mi_prep_gene_stats(mi_prep_matrix *m, int which, double *mean, double *var, 
 int mi_prep_clipped_variance(mi_prep_matrix *m, const double *mean, const double *sd, double clip, double *out,
                              float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m || !mean || !sd || !out) return fail(MI_EINVAL, "NULL argument");
-    if (std::isnan(clip)) return fail(MI_EINVAL, "clip is NaN");
-    for (int j = 0; j < m->g; ++j) {
-        if (!std::isfinite(mean[j])) return fail(MI_EINVAL, "mean[%d] is not finite", j);
-        if (!(sd[j] >= 0.0) || std::isinf(sd[j])) return fail(MI_EINVAL, "sd[%d] must be finite and >= 0", j);
-    }
-    HIP_TRY(hipSetDevice(m->device));
-    const size_t g = (size_t)m->g, slices = (size_t)(m->n + kRowSlice - 1) / kRowSlice;
-    return guarded([&]() -> int {
+    return on_matrix(m, mean && sd && out, 0, out_kernel_ms, [&]() -> int {
+        if (std::isnan(clip)) return fail(MI_EINVAL, "clip is NaN");
+        for (int j = 0; j < m->g; ++j) {
+            if (!std::isfinite(mean[j])) return fail(MI_EINVAL, "mean[%d] is not finite", j);
+            if (!(sd[j] >= 0.0) || std::isinf(sd[j])) return fail(MI_EINVAL, "sd[%d] must be finite and >= 0", j);
+        }
+        const size_t g = (size_t)m->g;
         DevBufs bufs;
         double *d_psum, *d_mean, *d_sd, *d_out;
-        HIP_TRY(bufs.alloc(&d_psum, slices * g));
-        HIP_TRY(bufs.alloc(&d_mean, g));
-        HIP_TRY(bufs.alloc(&d_sd, g));
+        HIP_TRY(bufs.alloc(&d_psum, (size_t)slices(m) * g));
+        HIP_TRY(bufs.upload(&d_mean, mean, g));
+        HIP_TRY(bufs.upload(&d_sd, sd, g));
         HIP_TRY(bufs.alloc(&d_out, g));
-        HIP_TRY(hipMemcpy(d_mean, mean, g * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_sd, sd, g * sizeof(double), hipMemcpyHostToDevice));
         Timer t;
         MI_TRY(t.start(0));
-        MI_TRY(col_reduce<kColClipped>(m, m->d_X, d_mean, d_sd, clip, (double)(m->n - 1), d_psum, nullptr, d_out, nullptr));
+        MI_TRY(col_reduce(m, m->d_X, ColClipped{m->g, d_mean, d_sd, clip}, (double)(m->n - 1), d_psum, nullptr, d_out, nullptr));
         MI_TRY(t.stop(0, out_kernel_ms));
         HIP_TRY(hipMemcpy(out, d_out, g * sizeof(double), hipMemcpyDeviceToHost));
         return MI_OK;
@@ -1256,56 +1326,34 @@ int mi_prep_clipped_variance(mi_prep_matrix *m, const double *mean, const double
 int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double *mu, const double *sigma, double clip,
                    float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m || !genes || !mu || !sigma) return fail(MI_EINVAL, "NULL argument");
-    if (h < 1) return fail(MI_EINVAL, "h must be >= 1 (got %d)", h);
-    if (h > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d features exceed %d", h, MI_PREP_MAX_FEATURES);
-    if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
-    return guarded([&]() -> int {
-        std::vector<uint8_t> seen((size_t)m->g, 0), flat((size_t)h, 0);
-        std::vector<int32_t> gmap;                                // sparse: gene -> column of Z
+    return on_matrix(m, genes && mu && sigma, 0, out_kernel_ms, [&]() -> int {
+        if (h < 1) return fail(MI_EINVAL, "h must be >= 1 (got %d)", h);
+        if (h > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d features exceed %d", h, MI_PREP_MAX_FEATURES);
+        if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
+        MI_TRY(check_indices(genes, h, m->g, "genes", "gene"));
+        std::vector<uint8_t> flat((size_t)h, 0);
         std::vector<float> muf((size_t)h), inv((size_t)h);
         for (int c = 0; c < h; ++c) {
-            const int32_t j = genes[c];
-            if (j < 0 || j >= m->g) return fail(MI_EINVAL, "genes[%d] = %d is outside [0, %d)", c, (int)j, m->g);
-            if (seen[j]) return fail(MI_EINVAL, "gene %d is chosen twice", (int)j);
-            seen[j] = 1;
             if (!std::isfinite(mu[c])) return fail(MI_EINVAL, "mu[%d] is not finite", c);
             if (!(sigma[c] >= 0.0) || std::isinf(sigma[c])) return fail(MI_EINVAL, "sigma[%d] must be finite and >= 0", c);
             flat[c] = sigma[c] == 0.0;
             muf[c] = (float)mu[c];
             inv[c] = flat[c] ? 0.0f : (float)(1.0 / sigma[c]);
         }
-        if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
-        if (m->sparse) {
-            gmap.assign((size_t)m->g, -1);
-            for (int c = 0; c < h; ++c) gmap[genes[c]] = c;
-        }
-        HIP_TRY(hipSetDevice(m->device));
-        const int ldz = (h + kTile - 1) / kTile * kTile;
+        MI_TRY(check_state(m, NEED_NORMALIZED));
         m->h = 0;
-        HIP_TRY(m->d_Z.resize((size_t)m->n * ldz));      // (a failure leaves it empty, with h = 0: mi_prep_select has not run)
-        m->ldz = ldz;
+        MI_TRY(size_Z(m, h));                            // (a failure leaves it empty, with h = 0: mi_prep_select has not run)
         DevBufs bufs;
-        int32_t *d_genes;
+        int32_t *d_genes, *d_gmap;
         float *d_mu, *d_inv;
         uint8_t *d_flat;
-        HIP_TRY(bufs.alloc(&d_genes, (size_t)h));
-        HIP_TRY(bufs.alloc(&d_mu, (size_t)h));
-        HIP_TRY(bufs.alloc(&d_inv, (size_t)h));
-        HIP_TRY(bufs.alloc(&d_flat, (size_t)h));
-        HIP_TRY(hipMemcpy(d_genes, genes, (size_t)h * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_mu, muf.data(), (size_t)h * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_inv, inv.data(), (size_t)h * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_flat, flat.data(), (size_t)h, hipMemcpyHostToDevice));
-        int32_t *d_gmap = nullptr;
-        if (m->sparse) {
-            HIP_TRY(bufs.alloc(&d_gmap, gmap.size()));
-            HIP_TRY(hipMemcpy(d_gmap, gmap.data(), gmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        MI_TRY(upload_genes(bufs, m, genes, h, &d_genes, &d_gmap));
+        HIP_TRY(bufs.upload(&d_mu, muf.data(), muf.size()));
+        HIP_TRY(bufs.upload(&d_inv, inv.data(), inv.size()));
+        HIP_TRY(bufs.upload(&d_flat, flat.data(), flat.size()));
         Timer t;
         MI_TRY(t.start(0));
-        MI_TRY(launch_select(m, d_genes, d_gmap, h, ldz, d_mu, d_inv, d_flat, (float)clip));
+        MI_TRY(launch_select(m, m->d_Y, d_genes, d_gmap, ScaledCols{h, d_mu, d_inv, d_flat, (float)clip}));
         MI_TRY(t.stop(0, out_kernel_ms));
         m->h = h;
         return MI_OK;
@@ -1315,22 +1363,16 @@ int mi_prep_select(mi_prep_matrix *m, const int32_t *genes, int h, const double 
 int mi_prep_cell_qc(mi_prep_matrix *m, const uint8_t *gene_mask, double *n_count, int32_t *n_feature, double *subset_count,
                     float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m) return fail(MI_EINVAL, "NULL argument");
-    if (subset_count && !gene_mask) return fail(MI_EINVAL, "subset_count needs a gene_mask");
-    for (int j = 0; gene_mask && j < m->g; ++j)
-        if (gene_mask[j] > 1) return fail(MI_EINVAL, "gene_mask[%d] = %d is neither 0 nor 1", j, (int)gene_mask[j]);
-    HIP_TRY(hipSetDevice(m->device));
-    const size_t n = (size_t)m->n;
-    return guarded([&]() -> int {
+    return on_matrix(m, true, 0, out_kernel_ms, [&]() -> int {
+        if (subset_count && !gene_mask) return fail(MI_EINVAL, "subset_count needs a gene_mask");
+        for (int j = 0; gene_mask && j < m->g; ++j)
+            if (gene_mask[j] > 1) return fail(MI_EINVAL, "gene_mask[%d] = %d is neither 0 nor 1", j, (int)gene_mask[j]);
+        const size_t n = (size_t)m->n;
         DevBufs bufs;
         uint8_t *d_mask = nullptr;
         double *d_count, *d_subset;
         int32_t *d_feature;
-        if (gene_mask) {
-            HIP_TRY(bufs.alloc(&d_mask, (size_t)m->g));
-            HIP_TRY(hipMemcpy(d_mask, gene_mask, (size_t)m->g, hipMemcpyHostToDevice));
-        }
+        if (gene_mask) HIP_TRY(bufs.upload(&d_mask, gene_mask, (size_t)m->g));
         HIP_TRY(bufs.alloc(&d_count, n));
         HIP_TRY(bufs.alloc(&d_subset, n));
         HIP_TRY(bufs.alloc(&d_feature, n));
@@ -1353,63 +1395,37 @@ int mi_prep_cell_qc(mi_prep_matrix *m, const uint8_t *gene_mask, double *n_count
 int mi_prep_select_regressed(mi_prep_matrix *m, const int32_t *genes, int h, const double *Q, int q, double clip,
                              double *out_coef, double *out_mean, double *out_var, uint8_t *out_flat, float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m) return fail(MI_EINVAL, "NULL argument");
-    m->h = 0;                                                     // (whatever fails below, nothing is selected)
-    if (!genes || !Q) return fail(MI_EINVAL, "NULL argument");
-    if (h < 1) return fail(MI_EINVAL, "h must be >= 1 (got %d)", h);
-    if (q < 1) return fail(MI_EINVAL, "q must be >= 1 (got %d)", q);
-    if (h > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d features exceed %d", h, MI_PREP_MAX_FEATURES);
-    if (q > MI_PREP_MAX_DESIGN_COLS) return fail(MI_EUNSUPPORTED, "%d design columns exceed %d", q, MI_PREP_MAX_DESIGN_COLS);
-    if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
-    return guarded([&]() -> int {
+    return on_matrix(m, true, 0, out_kernel_ms, [&]() -> int {
+        m->h = 0;                                                 // (whatever fails below, nothing is selected)
+        if (!genes || !Q) return fail(MI_EINVAL, "NULL argument");
+        if (h < 1) return fail(MI_EINVAL, "h must be >= 1 (got %d)", h);
+        if (q < 1) return fail(MI_EINVAL, "q must be >= 1 (got %d)", q);
+        if (h > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d features exceed %d", h, MI_PREP_MAX_FEATURES);
+        if (q > MI_PREP_MAX_DESIGN_COLS) return fail(MI_EUNSUPPORTED, "%d design columns exceed %d", q, MI_PREP_MAX_DESIGN_COLS);
+        if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
         const size_t n = (size_t)m->n, hs = (size_t)h, qs = (size_t)q;
-        std::vector<uint8_t> seen((size_t)m->g, 0);
-        for (int c = 0; c < h; ++c) {
-            const int32_t j = genes[c];
-            if (j < 0 || j >= m->g) return fail(MI_EINVAL, "genes[%d] = %d is outside [0, %d)", c, (int)j, m->g);
-            if (seen[j]) return fail(MI_EINVAL, "gene %d is chosen twice", (int)j);
-            seen[j] = 1;
-        }
-        for (size_t e = 0; e < n * qs; ++e)
-            if (!std::isfinite(Q[e])) return fail(MI_EINVAL, "Q[%lld, %lld] is not finite", (long long)(e / qs), (long long)(e % qs));
-        if (!m->normalized) return fail(MI_ESTATE, "mi_prep_normalize has not run");
-        std::vector<int32_t> gmap;                                // sparse: gene -> column of Z
-        if (m->sparse) {
-            gmap.assign((size_t)m->g, -1);
-            for (int c = 0; c < h; ++c) gmap[genes[c]] = c;
-        }
+        MI_TRY(check_indices(genes, h, m->g, "genes", "gene"));
+        MI_TRY(check_Q(Q, n, qs));
+        MI_TRY(check_state(m, NEED_NORMALIZED));
         const std::vector<float> zero(hs, 0.0f), one(hs, 1.0f);
         const std::vector<uint8_t> none(hs, 0);
-        HIP_TRY(hipSetDevice(m->device));
-        const int ldz = (h + kTile - 1) / kTile * kTile;
-        HIP_TRY(m->d_Z.resize(n * ldz));                 // (a failure leaves it empty, with h = 0)
-        m->ldz = ldz;
+        MI_TRY(size_Z(m, h));                            // (a failure leaves it empty, with h = 0)
         DevBufs bufs;
-        int32_t *d_genes, *d_gmap = nullptr;
+        int32_t *d_genes, *d_gmap;
         float *d_mu, *d_one;
         uint8_t *d_none;
         double *d_Q;
-        HIP_TRY(bufs.alloc(&d_genes, hs));
-        HIP_TRY(bufs.alloc(&d_mu, hs));
-        HIP_TRY(bufs.alloc(&d_one, hs));
-        HIP_TRY(bufs.alloc(&d_none, hs));
-        HIP_TRY(bufs.alloc(&d_Q, n * qs));
-        HIP_TRY(hipMemcpy(d_genes, genes, hs * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_mu, zero.data(), hs * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_one, one.data(), hs * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_none, none.data(), hs, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_Q, Q, n * qs * sizeof(double), hipMemcpyHostToDevice));
-        if (m->sparse) {
-            HIP_TRY(bufs.alloc(&d_gmap, gmap.size()));
-            HIP_TRY(hipMemcpy(d_gmap, gmap.data(), gmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        MI_TRY(upload_genes(bufs, m, genes, h, &d_genes, &d_gmap));
+        HIP_TRY(bufs.upload(&d_mu, zero.data(), hs));
+        HIP_TRY(bufs.upload(&d_one, one.data(), hs));
+        HIP_TRY(bufs.upload(&d_none, none.data(), hs));
+        HIP_TRY(bufs.upload(&d_Q, Q, n * qs));
         float ms1 = 0.0f, ms2 = 0.0f;
         {
             Timer t;
             MI_TRY(t.start(0));
             // 1. the gather: fminf((y - 0) * 1, inf) is y
-            MI_TRY(launch_select(m, d_genes, d_gmap, h, ldz, d_mu, d_one, d_none, HUGE_VALF));
+            MI_TRY(launch_select(m, m->d_Y, d_genes, d_gmap, ScaledCols{h, d_mu, d_one, d_none, HUGE_VALF}));
             MI_TRY(t.stop(0, &ms1));
         }
         MI_TRY(regress_stages(m, h, d_Q, q, clip, false, out_coef, out_mean, out_var, out_flat, &ms2));
@@ -1421,26 +1437,21 @@ int mi_prep_select_regressed(mi_prep_matrix *m, const int32_t *genes, int h, con
 
 int mi_prep_fetch_scaled(mi_prep_matrix *m, float *out)
 {
-    if (!m || !out) return fail(MI_EINVAL, "NULL argument");
-    if (m->h < 1) return fail(MI_ESTATE, "mi_prep_select has not run");
-    HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpy2D(out, (size_t)m->h * sizeof(float), m->d_Z, (size_t)m->ldz * sizeof(float), (size_t)m->h * sizeof(float),
-                        (size_t)m->n, hipMemcpyDeviceToHost));
-    return MI_OK;
+    return on_matrix(m, out != nullptr, NEED_SELECTED, nullptr, [&]() -> int {
+        HIP_TRY(hipMemcpy2D(out, (size_t)m->h * sizeof(float), m->d_Z, (size_t)m->ldz * sizeof(float), (size_t)m->h * sizeof(float),
+                            (size_t)m->n, hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
 }
 
 int mi_prep_gram(mi_prep_matrix *m, double *out_G, float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m || !out_G) return fail(MI_EINVAL, "NULL argument");
-    if (m->h < 1) return fail(MI_ESTATE, "mi_prep_select has not run");
-    HIP_TRY(hipSetDevice(m->device));
-    const int T = m->ldz / kTile, tiles = T * (T + 1) / 2;
-    const int chunks = (m->n + kChunk - 1) / kChunk;
-    const size_t tile_bytes = (size_t)kTile * kTile * sizeof(float), ldg = (size_t)T * kTile;
-    int batch = (int)(kGramWorkspace / (tile_bytes * tiles));
-    batch = batch < 1 ? 1 : (batch > chunks ? chunks : batch);
-    return guarded([&]() -> int {
+    return on_matrix(m, out_G != nullptr, NEED_SELECTED, out_kernel_ms, [&]() -> int {
+        const int T = m->ldz / kTile, tiles = T * (T + 1) / 2;
+        const int chunks = (m->n + kChunk - 1) / kChunk;
+        const size_t tile_bytes = (size_t)kTile * kTile * sizeof(float), ldg = (size_t)T * kTile;
+        int batch = (int)(kGramWorkspace / (tile_bytes * tiles));
+        batch = batch < 1 ? 1 : (batch > chunks ? chunks : batch);
         DevBufs bufs;
         float *d_P;
         double *d_G;
@@ -1465,12 +1476,10 @@ int mi_prep_gram(mi_prep_matrix *m, double *out_G, float *out_kernel_ms)
 
 int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m || !V || !out) return fail(MI_EINVAL, "NULL argument");
-    if (p < 1) return fail(MI_EINVAL, "p must be >= 1 (got %d)", p);
-    if (p > MI_PREP_MAX_PCS) return fail(MI_EUNSUPPORTED, "%d output columns exceed %d", p, MI_PREP_MAX_PCS);
-    if (m->h < 1) return fail(MI_ESTATE, "mi_prep_select has not run");
-    return guarded([&]() -> int {
+    return on_matrix(m, V && out, 0, out_kernel_ms, [&]() -> int {
+        if (p < 1) return fail(MI_EINVAL, "p must be >= 1 (got %d)", p);
+        if (p > MI_PREP_MAX_PCS) return fail(MI_EUNSUPPORTED, "%d output columns exceed %d", p, MI_PREP_MAX_PCS);
+        MI_TRY(check_state(m, NEED_SELECTED));
         std::vector<float> Vp((size_t)m->ldz * kProjCols, 0.0f);
         for (int k = 0; k < m->h; ++k)
             for (int c = 0; c < p; ++c) {
@@ -1478,12 +1487,10 @@ int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float 
                 if (!std::isfinite(v)) return fail(MI_EINVAL, "V[%d, %d] is not finite", k, c);
                 Vp[(size_t)k * kProjCols + c] = v;
             }
-        HIP_TRY(hipSetDevice(m->device));
         DevBufs bufs;
         float *d_V, *d_out;
-        HIP_TRY(bufs.alloc(&d_V, Vp.size()));
+        HIP_TRY(bufs.upload(&d_V, Vp.data(), Vp.size()));
         HIP_TRY(bufs.alloc(&d_out, (size_t)m->n * p));
-        HIP_TRY(hipMemcpy(d_V, Vp.data(), Vp.size() * sizeof(float), hipMemcpyHostToDevice));
         Timer t;
         MI_TRY(t.start(0));
         hipLaunchKernelGGL(k_prep_project, dim3((unsigned)((m->n + kProjCells - 1) / kProjCells)), dim3(256), 0, 0, m->d_Z, m->ldz,
@@ -1496,18 +1503,15 @@ int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float 
 
 int mi_prep_gene_log1p_sum(mi_prep_matrix *m, double *out, float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m || !out) return fail(MI_EINVAL, "NULL argument");
-    HIP_TRY(hipSetDevice(m->device));
-    const size_t g = (size_t)m->g, slices = (size_t)(m->n + kRowSlice - 1) / kRowSlice;
-    return guarded([&]() -> int {
+    return on_matrix(m, out != nullptr, 0, out_kernel_ms, [&]() -> int {
+        const size_t g = (size_t)m->g;
         DevBufs bufs;
         double *d_psum, *d_out;
-        HIP_TRY(bufs.alloc(&d_psum, slices * g));
+        HIP_TRY(bufs.alloc(&d_psum, (size_t)slices(m) * g));
         HIP_TRY(bufs.alloc(&d_out, g));
         Timer t;
         MI_TRY(t.start(0));
-        MI_TRY(col_reduce<kColLog1p>(m, m->d_X, nullptr, nullptr, 0.0, 1.0, d_psum, nullptr, d_out, nullptr));
+        MI_TRY(col_reduce(m, m->d_X, ColLog1p{m->g}, 1.0, d_psum, nullptr, d_out, nullptr));
         MI_TRY(t.stop(0, out_kernel_ms));
         HIP_TRY(hipMemcpy(out, d_out, g * sizeof(double), hipMemcpyDeviceToHost));
         return MI_OK;
@@ -1519,17 +1523,15 @@ int mi_prep_nb_fit(mi_prep_matrix *m, const int32_t *cells, int mc, const int32_
                    double *out_se_alpha, int32_t *out_iterations, uint8_t *out_converged, uint8_t *out_poisson,
                    float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m || !cells || !genes || !log_umi || !out_b0 || !out_b1 || !out_alpha || !out_se_b0c || !out_se_b1 || !out_se_alpha ||
-        !out_iterations || !out_converged || !out_poisson)
-        return fail(MI_EINVAL, "NULL argument");
-    if (mc < 3) return fail(MI_EINVAL, "at least 3 fit cells are needed (got %d)", mc);
-    if (g1 < 1) return fail(MI_EINVAL, "at least 1 fit gene is needed (got %d)", g1);
-    if (mc > MI_PREP_SCT_MAX_FIT_CELLS) return fail(MI_EUNSUPPORTED, "%d fit cells exceed %d", mc, MI_PREP_SCT_MAX_FIT_CELLS);
-    if (g1 > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d fit genes exceed %d", g1, MI_PREP_MAX_FEATURES);
-    return guarded([&]() -> int {
-        MI_TRY(check_indices(cells, mc, m->n, "cells"));
-        MI_TRY(check_indices(genes, g1, m->g, "genes"));
+    const bool args_ok = cells && genes && log_umi && out_b0 && out_b1 && out_alpha && out_se_b0c && out_se_b1 && out_se_alpha &&
+                         out_iterations && out_converged && out_poisson;
+    return on_matrix(m, args_ok, 0, out_kernel_ms, [&]() -> int {
+        if (mc < 3) return fail(MI_EINVAL, "at least 3 fit cells are needed (got %d)", mc);
+        if (g1 < 1) return fail(MI_EINVAL, "at least 1 fit gene is needed (got %d)", g1);
+        if (mc > MI_PREP_SCT_MAX_FIT_CELLS) return fail(MI_EUNSUPPORTED, "%d fit cells exceed %d", mc, MI_PREP_SCT_MAX_FIT_CELLS);
+        if (g1 > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d fit genes exceed %d", g1, MI_PREP_MAX_FEATURES);
+        MI_TRY(check_indices(cells, mc, m->n, "cells", "cells"));
+        MI_TRY(check_indices(genes, g1, m->g, "genes", "genes"));
         MI_TRY(check_log_umi(log_umi, mc));
         const size_t ms = (size_t)mc, gs = (size_t)g1;
         // the centred covariate, in host fp64: the mean is the sum in the order of `cells`, divided by their number
@@ -1543,31 +1545,18 @@ int mi_prep_nb_fit(mi_prep_matrix *m, const int32_t *cells, int mc, const int32_
             constant = constant && log_umi[i] == log_umi[0];
         }
         if (constant) return fail(MI_EINVAL, "log_umi is the same in every fit cell: the slope is not identified");
-        std::vector<int32_t> gmap;                                // sparse: gene -> row of the block
-        if (m->sparse) {
-            gmap.assign((size_t)m->g, -1);
-            for (int c = 0; c < g1; ++c) gmap[genes[c]] = c;
-        }
-        HIP_TRY(hipSetDevice(m->device));
         DevBufs bufs;
-        int32_t *d_cells, *d_genes, *d_gmap = nullptr, *d_iter;
+        int32_t *d_cells, *d_genes, *d_gmap, *d_iter;             // (d_gmap: gene -> row of the block)
         float *d_B;
         double *d_xc, *d_out;
         uint8_t *d_flags;
-        HIP_TRY(bufs.alloc(&d_cells, ms));
-        HIP_TRY(bufs.alloc(&d_genes, gs));
+        HIP_TRY(bufs.upload(&d_cells, cells, ms));
+        MI_TRY(upload_genes(bufs, m, genes, g1, &d_genes, &d_gmap));
         HIP_TRY(bufs.alloc(&d_B, ms * gs));
-        HIP_TRY(bufs.alloc(&d_xc, ms));
+        HIP_TRY(bufs.upload(&d_xc, xc.data(), ms));
         HIP_TRY(bufs.alloc(&d_out, 6 * gs));
         HIP_TRY(bufs.alloc(&d_iter, gs));
         HIP_TRY(bufs.alloc(&d_flags, 2 * gs));
-        HIP_TRY(hipMemcpy(d_cells, cells, ms * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_genes, genes, gs * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_xc, xc.data(), ms * sizeof(double), hipMemcpyHostToDevice));
-        if (m->sparse) {
-            HIP_TRY(bufs.alloc(&d_gmap, gmap.size()));
-            HIP_TRY(hipMemcpy(d_gmap, gmap.data(), gmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
         Timer t;
         MI_TRY(t.start(0));
         if (m->sparse)
@@ -1593,50 +1582,30 @@ int mi_prep_sct_residual_moments(mi_prep_matrix *m, const int32_t *genes, int gp
                                  const double *alpha, const double *log_umi, double clip, double *out_mean, double *out_var,
                                  float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m || !genes || !b0 || !b1 || !alpha || !log_umi || !out_mean || !out_var) return fail(MI_EINVAL, "NULL argument");
-    if (gp < 1) return fail(MI_EINVAL, "at least 1 gene is needed (got %d)", gp);
-    if (gp > m->g) return fail(MI_EINVAL, "%d genes are chosen of %d", gp, m->g);
-    if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
-    return guarded([&]() -> int {
+    return on_matrix(m, genes && b0 && b1 && alpha && log_umi && out_mean && out_var, 0, out_kernel_ms, [&]() -> int {
+        if (gp < 1) return fail(MI_EINVAL, "at least 1 gene is needed (got %d)", gp);
+        if (gp > m->g) return fail(MI_EINVAL, "%d genes are chosen of %d", gp, m->g);
+        if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
         std::vector<double> par;
-        MI_TRY(check_indices(genes, gp, m->g, "genes"));
+        MI_TRY(check_indices(genes, gp, m->g, "genes", "genes"));
         MI_TRY(pack_nb_parameters(b0, b1, alpha, gp, par));
         MI_TRY(check_log_umi(log_umi, m->n));
-        HIP_TRY(hipSetDevice(m->device));
-        const size_t gs = (size_t)gp, n = (size_t)m->n;
-        const int slices = (m->n + kRowSlice - 1) / kRowSlice;
+        const size_t gs = (size_t)gp;
         DevBufs bufs;
         int32_t *d_genes;
         double *d_par, *d_lu, *d_psum, *d_mean, *d_var;
-        HIP_TRY(bufs.alloc(&d_genes, gs));
-        HIP_TRY(bufs.alloc(&d_par, 3 * gs));
-        HIP_TRY(bufs.alloc(&d_lu, n));
-        HIP_TRY(bufs.alloc(&d_psum, (size_t)slices * gs));
+        HIP_TRY(bufs.upload(&d_genes, genes, gs));
+        HIP_TRY(bufs.upload(&d_par, par.data(), par.size()));
+        HIP_TRY(bufs.upload(&d_lu, log_umi, (size_t)m->n));
+        HIP_TRY(bufs.alloc(&d_psum, (size_t)slices(m) * gs));
         HIP_TRY(bufs.alloc(&d_mean, gs));
         HIP_TRY(bufs.alloc(&d_var, gs));
-        HIP_TRY(hipMemcpy(d_genes, genes, gs * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_par, par.data(), 3 * gs * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_lu, log_umi, n * sizeof(double), hipMemcpyHostToDevice));
-        const dim3 grid((unsigned)((gp + 63) / 64), (unsigned)slices);
         Timer t;
         MI_TRY(t.start(0));
-        if (m->sparse)
-            hipLaunchKernelGGL(k_sct_csc_col_partial<0>, grid, dim3(256), 0, 0, m->d_colptr, m->d_rows, m->d_pos, m->d_X, m->n,
-                               d_genes, gp, d_par, d_lu, clip, nullptr, d_psum);
-        else
-            hipLaunchKernelGGL(k_sct_col_partial<0>, grid, dim3(256), 0, 0, m->d_X, m->n, m->g, d_genes, gp, d_par, d_lu, clip,
-                               nullptr, d_psum);
-        HIP_TRY(hipGetLastError());
-        MI_TRY(finish_slices(d_psum, slices, gs, (double)m->n, d_mean));
-        if (m->sparse)
-            hipLaunchKernelGGL(k_sct_csc_col_partial<1>, grid, dim3(256), 0, 0, m->d_colptr, m->d_rows, m->d_pos, m->d_X, m->n,
-                               d_genes, gp, d_par, d_lu, clip, d_mean, d_psum);
-        else
-            hipLaunchKernelGGL(k_sct_col_partial<1>, grid, dim3(256), 0, 0, m->d_X, m->n, m->g, d_genes, gp, d_par, d_lu, clip,
-                               d_mean, d_psum);
-        HIP_TRY(hipGetLastError());
-        MI_TRY(finish_slices(d_psum, slices, gs, (double)(m->n - 1), d_var));
+        MI_TRY(col_reduce(m, m->d_X, SctMoment<0>{gp, d_genes, d_par, d_lu, clip, nullptr}, (double)m->n, d_psum, nullptr, d_mean,
+                          nullptr));
+        MI_TRY(col_reduce(m, m->d_X, SctMoment<1>{gp, d_genes, d_par, d_lu, clip, d_mean}, (double)(m->n - 1), d_psum, nullptr,
+                          d_var, nullptr));
         MI_TRY(t.stop(0, out_kernel_ms));
         HIP_TRY(hipMemcpy(out_mean, d_mean, gs * sizeof(double), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(out_var, d_var, gs * sizeof(double), hipMemcpyDeviceToHost));
@@ -1648,65 +1617,35 @@ int mi_prep_sct_select(mi_prep_matrix *m, const int32_t *genes, int h, const dou
                        const double *log_umi, double clip, const double *Q, int q, double *out_coef, double *out_mean,
                        double *out_var, uint8_t *out_flat, float *out_kernel_ms)
 {
-    if (out_kernel_ms) *out_kernel_ms = 0.0f;
-    if (!m) return fail(MI_EINVAL, "NULL argument");
-    m->h = 0;                                                     // (whatever fails below, nothing is selected)
-    const bool raw = !Q && q == 0;                                // stage 1 alone: the residuals as they are
-    if (!genes || !b0 || !b1 || !alpha || !log_umi || (!Q && !raw)) return fail(MI_EINVAL, "NULL argument");
-    if (h < 1) return fail(MI_EINVAL, "h must be >= 1 (got %d)", h);
-    if (q < 1 && !raw) return fail(MI_EINVAL, "q must be >= 1, or 0 without Q (got %d)", q);
-    if (h > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d features exceed %d", h, MI_PREP_MAX_FEATURES);
-    if (q > MI_PREP_MAX_DESIGN_COLS) return fail(MI_EUNSUPPORTED, "%d design columns exceed %d", q, MI_PREP_MAX_DESIGN_COLS);
-    if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
-    return guarded([&]() -> int {
-        const size_t n = (size_t)m->n, hs = (size_t)h, qs = (size_t)q;
+    return on_matrix(m, true, 0, out_kernel_ms, [&]() -> int {
+        m->h = 0;                                                 // (whatever fails below, nothing is selected)
+        const bool raw = !Q && q == 0;                            // stage 1 alone: the residuals as they are
+        if (!genes || !b0 || !b1 || !alpha || !log_umi || (!Q && !raw)) return fail(MI_EINVAL, "NULL argument");
+        if (h < 1) return fail(MI_EINVAL, "h must be >= 1 (got %d)", h);
+        if (q < 1 && !raw) return fail(MI_EINVAL, "q must be >= 1, or 0 without Q (got %d)", q);
+        if (h > MI_PREP_MAX_FEATURES) return fail(MI_EUNSUPPORTED, "%d features exceed %d", h, MI_PREP_MAX_FEATURES);
+        if (q > MI_PREP_MAX_DESIGN_COLS) return fail(MI_EUNSUPPORTED, "%d design columns exceed %d", q, MI_PREP_MAX_DESIGN_COLS);
+        if (!(clip > 0.0)) return fail(MI_EINVAL, "clip must be > 0");
+        const size_t n = (size_t)m->n, qs = (size_t)q;
         std::vector<double> par;
-        MI_TRY(check_indices(genes, h, m->g, "genes"));
+        MI_TRY(check_indices(genes, h, m->g, "genes", "genes"));
         MI_TRY(pack_nb_parameters(b0, b1, alpha, h, par));
         MI_TRY(check_log_umi(log_umi, m->n));
-        for (size_t e = 0; e < n * qs; ++e)
-            if (!std::isfinite(Q[e])) return fail(MI_EINVAL, "Q[%lld, %lld] is not finite", (long long)(e / qs), (long long)(e % qs));
-        std::vector<int32_t> gmap;                                // sparse: gene -> column of Z
-        if (m->sparse) {
-            gmap.assign((size_t)m->g, -1);
-            for (int c = 0; c < h; ++c) gmap[genes[c]] = c;
-        }
-        HIP_TRY(hipSetDevice(m->device));
-        const int ldz = (h + kTile - 1) / kTile * kTile;
-        HIP_TRY(m->d_Z.resize(n * ldz));                 // (a failure leaves it empty, with h = 0)
-        m->ldz = ldz;
+        MI_TRY(check_Q(Q, n, qs));
+        MI_TRY(size_Z(m, h));                            // (a failure leaves it empty, with h = 0)
         DevBufs bufs;
-        int32_t *d_genes, *d_gmap = nullptr;
+        int32_t *d_genes, *d_gmap;
         double *d_par, *d_lu, *d_Q;
-        HIP_TRY(bufs.alloc(&d_genes, hs));
-        HIP_TRY(bufs.alloc(&d_par, 3 * hs));
-        HIP_TRY(bufs.alloc(&d_lu, n));
-        HIP_TRY(bufs.alloc(&d_Q, n * qs));
-        HIP_TRY(hipMemcpy(d_genes, genes, hs * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_par, par.data(), 3 * hs * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_lu, log_umi, n * sizeof(double), hipMemcpyHostToDevice));
-        if (!raw) HIP_TRY(hipMemcpy(d_Q, Q, n * qs * sizeof(double), hipMemcpyHostToDevice));
-        if (m->sparse) {
-            HIP_TRY(bufs.alloc(&d_gmap, gmap.size()));
-            HIP_TRY(hipMemcpy(d_gmap, gmap.data(), gmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        MI_TRY(upload_genes(bufs, m, genes, h, &d_genes, &d_gmap));
+        HIP_TRY(bufs.upload(&d_par, par.data(), par.size()));
+        HIP_TRY(bufs.upload(&d_lu, log_umi, n));
+        HIP_TRY(bufs.upload(&d_Q, Q, n * qs));                    // (raw: no columns, nothing is copied)
         float ms1 = 0.0f, ms2 = 0.0f;
         {
             Timer t;
             MI_TRY(t.start(0));
             // 1. Z = (float) the clipped residual
-            if (m->sparse) {
-                hipLaunchKernelGGL(k_sct_csr_select, dim3((unsigned)m->n), dim3(256), 0, 0, m->d_indptr, m->d_indices, m->d_X,
-                                   d_gmap, h, ldz, d_par, d_lu, clip, m->d_Z);
-                HIP_TRY(hipGetLastError());
-            }
-            for (int r0 = 0; r0 < m->n && !m->sparse; r0 += 32768) {  // (one cell per grid.y: slabs, as launch_select)
-                const int rows = m->n - r0 < 32768 ? m->n - r0 : 32768;
-                hipLaunchKernelGGL(k_sct_select, dim3((unsigned)(ldz / 256 + (ldz % 256 != 0)), (unsigned)rows), dim3(256), 0, 0,
-                                   m->d_X + (size_t)r0 * m->g, m->g, d_genes, h, ldz, d_par, d_lu + r0, clip,
-                                   m->d_Z + (size_t)r0 * ldz);
-                HIP_TRY(hipGetLastError());
-            }
+            MI_TRY(launch_select(m, m->d_X, d_genes, d_gmap, SctCols{h, d_par, d_lu, clip}));
             MI_TRY(t.stop(0, &ms1));
         }
         // 2 - 5. centring (and regression) by the projection off Q, unit scale, no further clip

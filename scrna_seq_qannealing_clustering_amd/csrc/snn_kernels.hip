@@ -641,8 +641,7 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
         int32_t *d_rn_idx = nullptr, *d_col0 = nullptr, *d_sh0 = nullptr;
         unsigned char *d_alive = nullptr, *d_alive2 = nullptr, *d_code0 = nullptr;
         int32_t *d_key = nullptr, *d_table = nullptr;
-        HIP_TRY(bufs.alloc(&dX, (size_t)n * dim));
-        HIP_TRY(hipMemcpy(dX, X, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(bufs.upload(&dX, X, (size_t)n * dim));
         HIP_TRY(g->d_nn.resize((size_t)n * k));
         HIP_TRY(bufs.alloc(&d_cnt, (size_t)(n + 1)));
         HIP_TRY(bufs.alloc(&d_rn_ptr, (size_t)(n + 1)));

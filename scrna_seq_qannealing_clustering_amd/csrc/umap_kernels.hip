@@ -349,10 +349,9 @@ int mi_umap_knn_f32(const float *X, int n, int dim, int k, int metric, int devic
         g->n = n; g->dim = dim; g->k = k; g->metric = metric; g->device = device;
         DevBufs tmp;
         float *dX = nullptr;
-        HIP_TRY(tmp.alloc(&dX, cells));
+        HIP_TRY(tmp.upload(&dX, src, cells));
         HIP_TRY(g->d_nn.resize((size_t)n * k));
         HIP_TRY(g->d_dist.resize((size_t)n * k));
-        HIP_TRY(hipMemcpy(dX, src, cells * sizeof(float), hipMemcpyHostToDevice));
         Timer tm;
         MI_TRY(tm.start(0));
         MI_TRY(mi_snn_knn_dev(dX, n, dim, k, g->d_nn, 0));
@@ -551,17 +550,11 @@ int mi_umap_layout_f32(int n, int c, const int64_t *rowptr, const int32_t *col, 
         uint32_t *d_ptr = nullptr;
         int32_t *d_col = nullptr;
         float *d_prob = nullptr, *d_Y[2] = {nullptr, nullptr};
-        HIP_TRY(tmp.alloc(&d_ptr, (size_t)n + 1));
-        HIP_TRY(tmp.alloc(&d_col, (size_t)nnz));
-        HIP_TRY(tmp.alloc(&d_prob, (size_t)nnz));
-        HIP_TRY(tmp.alloc(&d_Y[0], cells));
+        HIP_TRY(tmp.upload(&d_ptr, ptr32.data(), ptr32.size()));
+        HIP_TRY(tmp.upload(&d_col, col, (size_t)nnz));
+        HIP_TRY(tmp.upload(&d_prob, prob.data(), (size_t)nnz));
+        HIP_TRY(tmp.upload(&d_Y[0], Y0, cells));
         HIP_TRY(tmp.alloc(&d_Y[1], cells));
-        HIP_TRY(hipMemcpy(d_ptr, ptr32.data(), ptr32.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (nnz) {
-            HIP_TRY(hipMemcpy(d_col, col, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_prob, prob.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
-        }
-        HIP_TRY(hipMemcpy(d_Y[0], Y0, cells * sizeof(float), hipMemcpyHostToDevice));
         // lanes per vertex: the smallest of 16, 32, 64 that holds the mean row length (a function of the graph alone)
         const double mean_deg = (double)nnz / (double)n;
         const int G = mean_deg > 32.0 ? 64 : (mean_deg > 16.0 ? 32 : 16);

@@ -120,8 +120,8 @@ int mi_sa_impl::fail(int code, const char *fmt, ...)
 }
 
 // ---- a call shaped like the library's -----------------------------------------------------------------------------------
-// the device check, a scratch stream, four marks, scratch (one buffer of count 0), a timed span, a nested owner that
-// releases early (the symmetric trim of the SNN build), then success
+// the device check, a scratch stream, four marks, scratch (one buffer of count 0, two uploads), a timed span, a nested
+// owner that releases early (the symmetric trim of the SNN build), then success
 static int handle_life();
 
 static int entry(int device, float *out_ms)
@@ -142,6 +142,20 @@ static int entry(int device, float *out_ms)
         HIP_TRY(bufs.alloc(&d_none, 0));
         CHECK(d_none != nullptr);
         d_a[99] = 1.0f; d_b[6] = 1; d_none[0] = 1.0;              // (each at least as large as asked: the sanitizer checks)
+        // upload: the allocation, then the copy; none for a count of 0 (the fake copy refuses 0 bytes), though a pointer
+        // all the same.  A failed copy leaves the buffer with its owner: released once, where the scope ends.
+        const int h_up[7] = {1, 2, 3, 4, 5, 6, 7};
+        int *d_up = nullptr, *d_empty = nullptr;
+        const size_t held = g_live.size();
+        const hipError_t up = bufs.upload(&d_up, h_up, 7);
+        CHECK(g_live.size() == held + (up != hipSuccess && g_malloc_failed ? 0 : 1));
+        CHECK((d_up == nullptr) == (up != hipSuccess && g_malloc_failed));
+        HIP_TRY(up);
+        CHECK(d_up[0] == 1 && d_up[6] == 7);
+        const int calls = g_calls;
+        HIP_TRY(bufs.upload(&d_empty, static_cast<const int *>(nullptr), 0));
+        CHECK(d_empty != nullptr && g_calls == calls + 1);        // (the hipMalloc alone)
+        d_empty[0] = 1;
         HIP_TRY(hipEventRecord(ev.e[0], st));
         Timer t;
         MI_TRY(t.start(st));
@@ -246,7 +260,7 @@ int main()
     float ms = 0.0f;
     CHECK(run(0, 1, &ms) == MI_OK && ms == 1.5f && g_current == 1);
     const int total = g_calls;
-    CHECK(total >= 38);
+    CHECK(total >= 41);
     CHECK(run(0, 0, nullptr) == MI_OK && g_calls == total);       // out_ms may be null
     for (int k = 1; k <= total; ++k) {
         const int rc = run(k, 0, &ms);

@@ -33,6 +33,85 @@ def clipped_variance(X, mean, sd, clip):
     return out
 
 
+# ---- the column reductions restated in their own order: equal bit for bit, not within a tolerance ---------------------------
+# include/mi_prep.h: inside a slice of ROW_SLICE rows, row lane ty adds the rows r0 + ty, r0 + ty + ROW_LANES, ... ascending;
+# the lanes join as ((s0 + s1) + s2) + s3; the slices add in ascending order; one division.  All IEEE fp64, no contraction,
+# so numpy's elementwise fp64 gives the same bits.
+ROW_SLICE, ROW_LANES = 256, 4
+
+
+def ordered_column_sum(T, denom=1.0):
+    """the device's sum over the rows of the fp64 terms T (n x columns), divided once"""
+    T = np.asarray(T, dtype=np.float64)
+    total = np.zeros(T.shape[1])
+    for r0 in range(0, T.shape[0], ROW_SLICE):
+        r1 = min(r0 + ROW_SLICE, T.shape[0])
+        lanes = []
+        for ty in range(ROW_LANES):
+            acc = np.zeros(T.shape[1])
+            for r in range(r0 + ty, r1, ROW_LANES):
+                acc = acc + T[r]
+            lanes.append(acc)
+        total = total + (((lanes[0] + lanes[1]) + lanes[2]) + lanes[3])
+    return total / denom
+
+
+def plain_column_sum(T, denom=1.0):
+    """the rows added in ascending order into one accumulator: what the device does not do (the tests' control)"""
+    T = np.asarray(T, dtype=np.float64)
+    total = np.zeros(T.shape[1])
+    for row in T:
+        total = total + row
+    return total / denom
+
+
+def ordered_gene_stats(M, column_sum=ordered_column_sum):
+    """gene_stats in the device's order -> mean, variance, nnz"""
+    M64 = np.asarray(M, dtype=np.float32).astype(np.float64)
+    n = M64.shape[0]
+    mean = column_sum(M64, n)
+    d = M64 - mean
+    return mean, column_sum(d * d, n - 1), (M64 != 0).sum(axis=0).astype(np.int32)
+
+
+def ordered_clipped_variance(X, mean, sd, clip):
+    """clipped_variance in the device's order and operations: d = (x - mean) / sd, d < clip ? d : clip, d * d"""
+    X64 = np.asarray(X, dtype=np.float32).astype(np.float64)
+    mean, sd = np.asarray(mean, dtype=np.float64), np.asarray(sd, dtype=np.float64)
+    ok = sd != 0
+    d = (X64 - mean) / np.where(ok, sd, 1.0)
+    d = np.where(d < clip, d, clip)
+    return ordered_column_sum(np.where(ok, d * d, 0.0), X64.shape[0] - 1)
+
+
+def ordered_regression(Yg, Q, column_sum=ordered_column_sum):
+    """select_regressed's fp64 outputs from the gathered float32 columns Yg (n x h) and the basis Q (n x q), in the device's
+    order: c_k = sum_i Q_ik y_i; r = y - acc with acc = Q_i0 c_0, then acc = acc + Q_ik c_k; the mean of r; the squares about
+    it over n - 1  ->  coef_q (q x h), resid_mean, resid_var"""
+    Y64 = np.asarray(Yg, dtype=np.float32).astype(np.float64)
+    Q = np.asarray(Q, dtype=np.float64)
+    n, q = Q.shape
+    coef = np.stack([column_sum(Q[:, k:k + 1] * Y64) for k in range(q)])
+    acc = Q[:, 0:1] * coef[0]
+    for k in range(1, q):
+        acc = acc + Q[:, k:k + 1] * coef[k]
+    r = Y64 - acc
+    mean = column_sum(r, n)
+    d = r - mean
+    return coef, mean, column_sum(d * d) / (n - 1)
+
+
+def fractional_counts(rng, n, g):
+    """non-negative float32 "counts" that are no integers, about 70 % zeros: a gamma draw times a power of two between
+    2^-24 and 2^24 (integer counts, and float32 values of one magnitude, add exactly in fp64 and would pin no order); from
+    three columns on, the last is all zero and the one before it constant"""
+    X = (rng.gamma(2.0, 1.5, (n, g)) * 2.0 ** rng.integers(-24, 25, (n, g)) * (rng.random((n, g)) < 0.3)).astype(np.float32)
+    if g >= 3:
+        X[:, -1] = 0.0
+        X[:, -2] = 0.3
+    return X
+
+
 def scaled(Y, genes, mu, sigma, clip):
     """the kernel's float32 expression: z = min((y - f32(mu)) * f32(1 / sigma), f32(clip)), 0 where sigma == 0"""
     Y = np.asarray(Y, dtype=np.float32)

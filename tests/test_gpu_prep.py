@@ -11,6 +11,7 @@ Each chunk of GRAM_CHUNK = C cells is one fmaf chain of at most C terms per entr
 bound + Cauchy-Schwarz); likewise |out - Z64 V64|_ic <= (h + 2) 2^-24 |z_i| |v_c| for the projection."""
 import numpy as np
 import pytest
+import scipy.sparse as sp
 
 import prep_reference as ref
 from scrna_seq_qannealing_clustering_amd import _lib, metrics, preprocess, snn
@@ -65,6 +66,41 @@ def check_passes(X):
 def test_edges(n, g):
     rng = np.random.default_rng(1000 * n + g)
     check_passes(ref.sparse_counts(rng, n, g))
+
+
+# ---- 1b. the order of the reductions, bit for bit ---------------------------------------------------------------------------
+# n: lanes without a row (2), a lane with two rows (5), a second slice of one row (257), a last slice that fills three lanes
+# (1027); g: a partial workgroup of genes (1, 63), two and three workgroups (65, 130).
+
+def same_bits(got, want):
+    assert len(got) == len(want)
+    for a, b in zip(got, want):
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("g", [1, 63, 65, 130])
+@pytest.mark.parametrize("n", [2, 5, 257, 1027])
+def test_reduction_order_bit_for_bit(n, g):
+    """mean, variance and nnz of both matrices and the clipped variance, on a dense and on a CSR handle, are the bits of the
+    documented order restated in numpy (prep_reference.ordered_*); from two slices on, adding the rows in plain ascending
+    order gives other bits, so the comparison does pin the order"""
+    X = ref.fractional_counts(np.random.default_rng(7000 * n + g), n, g)
+    want = ref.ordered_gene_stats(X)
+    if n >= 257:
+        plain = ref.ordered_gene_stats(X, ref.plain_column_sum)
+        assert (plain[0] != want[0]).any() or (plain[1] != want[1]).any()
+    Y = None
+    for M in (X, sp.csr_matrix(X)):
+        with ExpressionMatrix(M) as m:
+            m.normalize(1e4)
+            if Y is None:
+                Y = m.fetch_normalized()                         # (the device's: log1p is not restated)
+            got, ygot = m.gene_stats("counts"), m.gene_stats("normalized")
+            sd = np.sqrt(got[1])
+            vs = m.clipped_variance(got[0], sd, np.sqrt(n))
+        same_bits(got, want)
+        same_bits(ygot, ref.ordered_gene_stats(Y))
+        same_bits([vs], [ref.ordered_clipped_variance(X, got[0], sd, np.sqrt(n))])
 
 
 # ---- 2. special rows and columns ------------------------------------------------------------------------------------------

@@ -156,6 +156,34 @@ def test_intercept_only_is_scale_data(n, h):
     assert np.all(np.abs(Z - want) <= 2.0 ** -24 * np.abs(want) + 1e-12 * (np.abs(Y) + np.abs(mu)) / sd)
 
 
+# ---- 6b. the order of the reductions, bit for bit ---------------------------------------------------------------------------
+
+ORDER_SHAPES = ([(n, 65, 2) for n in (2, 5, 257, 1027)] + [(257, h, 2) for h in (1, 63, 130)] + [(257, 65, q) for q in (1, 9)])
+
+
+@pytest.mark.parametrize("n,h,q", ORDER_SHAPES)
+def test_regression_order_bit_for_bit(n, h, q):
+    """coef_q, resid_mean and resid_var of a dense handle are the bits of the documented order restated in numpy on the
+    gathered columns of the device's Y (prep_reference.ordered_regression); from two slices on, plain ascending sums give
+    other coefficients, means and variances"""
+    rng = np.random.default_rng(9000 * q + 70 * n + h)
+    X = ref.fractional_counts(rng, n, G)
+    genes = rng.permutation(G - 2)[:h]
+    if h >= 3:
+        genes[-2:] = [G - 1, G - 2]                              # (the all-zero and the constant column)
+    Q = cases.intercept_basis(n) if q == 1 else preprocess.design_basis(cases.covariates(rng, X, q - 1))[0]
+    with ExpressionMatrix(X) as m:
+        Yg = m.normalize().fetch_normalized()[:, genes]
+        m.select_regressed(genes, Q, 10.0)
+        got = (m.coef_q, m.resid_mean, m.resid_var)
+    want = ref.ordered_regression(Yg, Q)
+    if n >= 257:
+        for plain, ordered in zip(ref.ordered_regression(Yg, Q, ref.plain_column_sum), want):
+            assert (plain != ordered).any()                      # (coefficients, means and variances alike)
+    for a, b in zip(got, want):
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+
+
 # ---- 7. sparse equals dense, run equals run -----------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("n,h,q", [(257, 65, 2), (1027, 65, 2), (257, 129, 9), (255, 1, 1)])
