@@ -268,7 +268,7 @@ int mi_prep_project(mi_prep_matrix *m, const float *V, int p, float *out, float 
  *                  values V[pos[k]]).  A stored zero is a zero: the compaction skips it, it joins the zero block, and
  *                  zeros = n - (true non-zeros).  The launch (LDS capacity, slab stride, LDS or HBM form per gene) is
  *                  planned from the stored counts, an upper bound read from colptr; the true non-zero count comes out of the
- *                  compaction and the sort is padded to the planned power of two.  The sums walk the stored entries in
+ *                  compaction and the sort is padded to its power of two.  The sums walk the stored entries in
  *                  ascending cell order, one thread per (gene, labelling): the dense kernel's additions in its order.
  *                  The two GATHER flags pick how the values are read (neither: the form kept by measurement, DESIGN.md
  *                  section 5c; they change no result and a dense handle ignores them).

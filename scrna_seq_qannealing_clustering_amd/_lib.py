@@ -26,7 +26,8 @@ class MiSaError(RuntimeError):
         self.message = message
 
 
-def _declare(lib):
+def _signatures():
+    """Every export of libmi_sa.so, written once: name -> (result type, argument types)."""
     u8p, u16p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)
     i32p, f32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)
     u64p, ip, vp = C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_void_p
@@ -151,32 +152,18 @@ def _declare(lib):
                                      i32p, f32p]),
         "mi_annot_fine_tune": (C.c_int, [vp, i32p, f64p, f64p, i32p, f32p]),
     }
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
     return sig
 
 
-EXPORTS = (
-    "mi_last_error", "mi_abi_version", "mi_device_count", "mi_device_info",
-    "mi_sa_problem_create_dense_f32", "mi_sa_problem_create_csr_rank1_f32",
-    "mi_sa_problem_create_potts_csr_f32", "mi_sa_problem_destroy", "mi_sa_problem_info",
-    "mi_sa_last_adjacency_bytes_per_slot", "mi_sa_set_option", "mi_sa_plan_slot_order", "mi_sa_plan_anneal", "mi_sa_plan_dense", "mi_sa_plan_slot_layout", "mi_sa_problem_set_absent", "mi_sa_problem_set_pair_weights", "mi_sa_problem_set_node_weights", "mi_sa_problem_set_node_weight_groups", "mi_sa_problem_set_merge_moves", "mi_sa_problem_set_energy_model_f64", "mi_sa_debug_pace", "mi_sa_debug_stats", "mi_sa_anneal", "mi_sa_anneal_ex", "mi_sa_tempering_begin", "mi_sa_tempering_exchange", "mi_sa_tempering_exchange_dev", "mi_sa_device_results", "mi_sa_tempering_state", "mi_sa_sync", "mi_sa_last_kernel_ms", "mi_sa_last_launch_count", "mi_sa_last_kernel_name", "mi_sa_fetch", "mi_sa_best",
-    "mi_multi_gpu_anneal", "mi_multi_gpu_best", "mi_multi_gpu_fetch", "mi_sa_qubo_dense_f32", "mi_energy_dense_f32", "mi_energy_dense_f64", "mi_energy_dense_f32_ex",
-    "mi_snn_build_f32", "mi_snn_build_ex_f32", "mi_snn_build_rounded_f32", "mi_snn_fetch_codes", "mi_snn_info", "mi_snn_fetch", "mi_snn_kernel_ms", "mi_snn_destroy",
-    "mi_jaccard_cluster_stats", "mi_label_agreement_u16", "mi_sa_problem_label_agreement",
-    "mi_coassociation_u16", "mi_sa_problem_coassociation",
-    "mi_graph_components", "mi_sa_problem_components",
-    "mi_rank_sum_markers_f32",
-    "mi_prep_create_f32", "mi_prep_create_csr_f32", "mi_prep_info", "mi_prep_fetch_normalized_csr", "mi_prep_destroy", "mi_prep_normalize", "mi_prep_fetch_normalized", "mi_prep_gene_stats",
-    "mi_prep_clipped_variance", "mi_prep_select", "mi_prep_fetch_scaled", "mi_prep_cell_qc", "mi_prep_select_regressed", "mi_prep_gram", "mi_prep_project",
-    "mi_prep_gene_log1p_sum", "mi_prep_nb_fit", "mi_prep_sct_residual_moments", "mi_prep_sct_select",
-    "mi_prep_rank_sum_markers",
-    "mi_umap_knn_f32", "mi_umap_destroy", "mi_umap_fetch_knn", "mi_umap_smooth", "mi_umap_fetch_smooth", "mi_umap_union",
-    "mi_umap_info", "mi_umap_fetch_graph", "mi_umap_layout_f32",
-    "mi_annot_create", "mi_annot_destroy", "mi_annot_score", "mi_annot_fine_tune",
-)
+_SIG = _signatures()
+EXPORTS = tuple(_SIG)
+
+
+def _declare(lib):
+    for name, (res, args) in _SIG.items():
+        fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
+        fn.restype = res
+        fn.argtypes = args
 
 
 def load():

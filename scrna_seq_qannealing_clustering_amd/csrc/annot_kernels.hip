@@ -2,13 +2,9 @@
 // (gfx950).  C ABI: include/mi_annot.h; the specification is DESIGN.md section 5c ("chain A"); markers and pruning are host
 // fp64 in annotate.py.
 //
-// A row (a reference sample or a test cell) is ranked over a set of genes with midranks, kept doubled: r2 = lo + 1 + hi for a
-// sorted position inside the tie run [lo, hi).  The zeros of a row (both signs) are one tie block whose rank needs no sort:
-// with `neg` negative and `zeros` zero entries it is 2 neg + zeros + 1.  rank_row is the scheme of rank_gene in
-// markers_kernels.hip applied to rows: the non-zeros are compacted as (order-preserving u32 key << 32 | position) -- unique
-// 64-bit words, so the sorted array does not depend on the order the compaction wrote them in -- padded with ~0 to a power
-// of two, sorted by a bitonic network in LDS, and every sorted position finds its tie run by its neighbours and, inside a
-// run, by binary search.
+// A row (a reference sample or a test cell) is ranked over a set of genes with midranks, kept doubled (r2), by the scheme of
+// mi_midrank.h (wg_midranks, the sort array in LDS): the non-zeros get their r2 from a sort, the zeros of a row (both signs)
+// are one tie block with a closed-form r2.
 //
 //   k_annot_rank       one workgroup per row over the m marker genes: r2 as two base-128 digits (2 <= r2 <= 2 m <= 16382 <
 //                      128^2) in two i8 planes of mpad = 64 ceil(m / 64) bytes per row (padding 0), and sum r2^2.
@@ -34,6 +30,7 @@
 #include <vector>
 
 #include "../../include/mi_annot.h"
+#include "mi_midrank.h"
 #include "mi_sa_device.h"
 
 namespace mi_sa_impl {
@@ -47,94 +44,19 @@ constexpr int kCrossCols = 4;                  // 16-sample tiles per wavefront 
 constexpr double kTuneThresh = 0.05;
 constexpr double kQuantile = 0.8;
 
-__device__ __forceinline__ bool zero_bits(uint32_t u) { return (u & 0x7fffffffu) == 0u; }
+using mi_midrank::pow2_at_least;
 
-// ascending u32 order == ascending float order over the finite non-zero values (equal floats <=> equal keys)
-__device__ __forceinline__ uint32_t order_key(uint32_t u) { return (u >> 31) ? ~u : (u | 0x80000000u); }
-
-__host__ __device__ inline int pow2_at_least(int v)
-{
-    int p = 0;
-    if (v > 0)
-        for (p = 1; p < v; p <<= 1) {}
-    return p;
-}
-
-// Whole workgroup.  Candidate k of `count` has the value bits val(k).  emit(k, r2) is called once for every non-zero
-// candidate, by the thread that owns its sorted position.  zeros / zr2: the size and the doubled midrank of the zero block.
-// S: pow2_at_least(count) entries of LDS; cnt: 2 words of LDS.  Ends with a barrier: S and cnt are free again.
+// Whole workgroup: mi_midrank::wg_midranks on a row whose entry k of `count` has the value bits val(k).  emit(k, r2) is
+// called once for every non-zero entry, by the thread that owns its sorted position.  S: pow2_at_least(count) entries of
+// LDS; cnt: 2 words of LDS.  Ends with a barrier: S and cnt are free again.
 template <class Val, class Emit>
-__device__ __forceinline__ void rank_row(int count, Val val, unsigned long long *S, uint32_t *cnt, Emit emit, int &zeros, uint32_t &zr2)
+__device__ __forceinline__ mi_midrank::Ranked rank_row(int count, Val val, unsigned long long *S, uint32_t *cnt, Emit emit)
 {
-    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
-    const int cap = pow2_at_least(count);
-    if (tid == 0) {
-        cnt[0] = 0u;
-        cnt[1] = 0u;
-    }
+    const mi_midrank::Ranked rk = mi_midrank::wg_midranks(
+        count, val, [](int k) { return k; }, count, pow2_at_least(count), S, cnt,
+        [&](int, unsigned long long e, int, int, uint32_t r2) { emit((int)(uint32_t)e, r2); });
     __syncthreads();
-    for (int i0 = 0; i0 < count; i0 += nt) {
-        const int i = i0 + tid;
-        const uint32_t u = i < count ? val(i) : 0u;
-        const bool nz = !zero_bits(u), ng = nz && (u >> 31);
-        const unsigned long long mk = __ballot(nz), mn = __ballot(ng);
-        if (mk) {
-            uint32_t base = 0u;
-            if (lane == 0) {
-                base = atomicAdd(&cnt[0], (uint32_t)__popcll(mk));
-                if (mn) atomicAdd(&cnt[1], (uint32_t)__popcll(mn));
-            }
-            base = __shfl(base, 0);
-            const uint32_t at = base + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull));
-            if (nz && at < (uint32_t)cap) S[at] = ((unsigned long long)order_key(u) << 32) | (uint32_t)i;
-        }
-    }
-    __syncthreads();
-    const int nnz = cnt[0] < (uint32_t)cap ? (int)cnt[0] : cap;                          // (<= count <= cap always)
-    const uint32_t neg = cnt[1];
-    const int P = pow2_at_least(nnz);                                                    // the sort covers the non-zeros only
-    for (int p = nnz + tid; p < P; p += nt) S[p] = ~0ull;                                // (sorts last: no finite key is ~0)
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += nt) {
-                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-                const unsigned long long x = S[lo], y = S[hi];
-                if ((x > y) == ((lo & k) == 0)) {
-                    S[lo] = y;
-                    S[hi] = x;
-                }
-            }
-            __syncthreads();
-        }
-    zeros = count - nnz;
-    zr2 = 2u * neg + (uint32_t)zeros + 1u;
-    for (int p = tid; p < nnz; p += nt) {
-        const unsigned long long e = S[p];
-        const uint32_t key = (uint32_t)(e >> 32);
-        int lo = p, hi = p + 1;
-        if (p > 0 && (uint32_t)(S[p - 1] >> 32) == key) {                                // first position with this key, in [0, p - 1]
-            int l = 0, r = p - 1;
-            while (l < r) {
-                const int md = (l + r) >> 1;
-                if ((uint32_t)(S[md] >> 32) < key) l = md + 1;
-                else r = md;
-            }
-            lo = l;
-        }
-        if (p + 1 < nnz && (uint32_t)(S[p + 1] >> 32) == key) {                          // first position past this key, in [p + 2, nnz]
-            int l = p + 2, r = nnz;
-            while (l < r) {
-                const int md = (l + r) >> 1;
-                if ((uint32_t)(S[md] >> 32) <= key) l = md + 1;
-                else r = md;
-            }
-            hi = l;
-        }
-        const bool isneg = key < 0x80000000u;
-        emit((int)(uint32_t)e, (uint32_t)(lo + 1 + hi) + (isneg ? 0u : 2u * (uint32_t)zeros));
-    }
-    __syncthreads();
+    return rk;
 }
 
 // the sum of N integers per thread over the workgroup; ws: N * kAnnotWaves words of LDS.  Ends with a barrier.
@@ -215,10 +137,8 @@ __global__ void __launch_bounds__(kAnnotThreads) k_annot_rank(RankArgs a)
     for (int row = blockIdx.x; row < a.rows; row += gridDim.x) {
         const float *x = a.X + (size_t)row * a.m;
         for (int j = tid; j < a.mpad; j += nt) r[j] = 0;                                  // (0 is no rank: filled in below)
-        int zeros;
-        uint32_t zr2;
-        rank_row(a.m, [&](int k) { return __float_as_uint(x[k]); }, S, cnt,
-                 [&](int k, uint32_t r2) { r[k] = (uint16_t)r2; }, zeros, zr2);
+        const uint32_t zr2 = rank_row(a.m, [&](int k) { return __float_as_uint(x[k]); }, S, cnt,
+                                      [&](int k, uint32_t r2) { r[k] = (uint16_t)r2; }).zero_r2;
         long long part[1] = {0};
         for (int j = tid * 4; j < a.mpad; j += nt * 4) {
             uint32_t wh = 0u, wl = 0u;
@@ -403,10 +323,8 @@ __global__ void __launch_bounds__(kAnnotThreads) k_annot_fine_tune(TuneArgs a)
             for (int k = tid; k < mp; k += nt) ar[k] = 0;
             __syncthreads();
 
-            int zeros;
-            uint32_t zr2;
-            rank_row(mp, [&](int k) { return __float_as_uint(x[gidx[k]]); }, Sx, cnt,
-                     [&](int k, uint32_t r2) { ar[k] = (uint16_t)r2; }, zeros, zr2);
+            const uint32_t zr2 = rank_row(mp, [&](int k) { return __float_as_uint(x[gidx[k]]); }, Sx, cnt,
+                                          [&](int k, uint32_t r2) { ar[k] = (uint16_t)r2; }).zero_r2;
             long long pa[1] = {0};
             for (int k = tid; k < mp; k += nt) {
                 uint32_t v = ar[k];
@@ -424,18 +342,17 @@ __global__ void __launch_bounds__(kAnnotThreads) k_annot_fine_tune(TuneArgs a)
                 for (int s = a.off[l]; s < a.off[l + 1]; ++s) {
                     const float *rr = a.R + (size_t)s * a.m;
                     long long pv[3] = {0, 0, 0};                                         // sum a b, sum b^2, sum a over the sample's non-zeros
-                    rank_row(mp, [&](int k) { return __float_as_uint(rr[gidx[k]]); }, Sx, cnt,
-                             [&](int k, uint32_t r2) {
-                                 const long long av = ar[k];
-                                 pv[0] += av * (long long)r2;
-                                 pv[1] += (long long)r2 * r2;
-                                 pv[2] += av;
-                             },
-                             zeros, zr2);
+                    const mi_midrank::Ranked rk = rank_row(mp, [&](int k) { return __float_as_uint(rr[gidx[k]]); }, Sx, cnt,
+                                                           [&](int k, uint32_t r2) {
+                                                               const long long av = ar[k];
+                                                               pv[0] += av * (long long)r2;
+                                                               pv[1] += (long long)r2 * r2;
+                                                               pv[2] += av;
+                                                           });
                     block_sums<3>(pv, ws);
                     if (tid == 0) {
-                        const long long sab = pv[0] + (sum - pv[2]) * (long long)zr2;
-                        const long long sb2 = pv[1] + (long long)zeros * zr2 * zr2;
+                        const long long sab = pv[0] + (sum - pv[2]) * (long long)rk.zero_r2;
+                        const long long sb2 = pv[1] + (long long)rk.zeros * rk.zero_r2 * rk.zero_r2;
                         rho[s] = spearman(mp, sab, sa2, sb2);
                     }
                 }
@@ -462,14 +379,6 @@ __global__ void __launch_bounds__(kAnnotThreads) k_annot_fine_tune(TuneArgs a)
         }
         __syncthreads();
     }
-}
-
-template <class K>
-int allow_lds(K kernel, size_t bytes)
-{
-    if (bytes > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return MI_OK;
 }
 
 // entries of the LDS sort array for rows of m genes (at least 2: the arrays carved after it stay 16-byte aligned)

@@ -291,8 +291,7 @@ __global__ void __launch_bounds__(256) k_coassoc_edges(const uint8_t *__restrict
 template <int KB>
 int launch_coassoc(const CoDev &g, int wgs, int G, size_t lds, hipStream_t st)
 {
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_coassoc_mfma<KB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    MI_TRY(allow_lds(k_coassoc_mfma<KB>, lds));
     hipLaunchKernelGGL((k_coassoc_mfma<KB>), dim3((unsigned)wgs, (unsigned)G), dim3(256), lds, st, g);
     return MI_OK;
 }

@@ -189,8 +189,7 @@ int mi_components_dev(const ComponentsArgs &a, int B, bool force_global, hipStre
         Timer tm;
         MI_TRY(tm.start(st));
         if (use_lds) {
-            if (lds > 64 * 1024)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_components<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            MI_TRY(allow_lds(k_components<true>, lds));
             hipLaunchKernelGGL(k_components<true>, dim3((unsigned)B), dim3((unsigned)threads), lds, st, a, d_out, d_count);
         } else {
             hipLaunchKernelGGL(k_components<false>, dim3((unsigned)B), dim3((unsigned)threads), 0, st, a, d_out, d_count);

@@ -6,11 +6,8 @@
 // sort: with `neg` negative and `zeros` zero cells the block holds the ranks neg + 1 .. neg + zeros.
 //
 //   k_markers_transpose  64 x 64 tiles through LDS (row padded by one float): X -> gene-major Xt, coalesced on both sides.
-//   k_markers_rank       one workgroup per gene, grid-stride.  The gene's non-zeros are compacted as
-//                        (order-preserving u32 key << 32 | cell) -- unique 64-bit words, so the sorted array does not depend
-//                        on the order the compaction wrote them in -- padded with ~0 to a power of two and sorted by a
-//                        bitonic network.  A sorted position finds its tie run [lo, hi) by its neighbours and, inside a
-//                        run, by binary search; its doubled midrank is lo + 1 + hi, plus 2 * zeros for a positive value.
+//   k_markers_rank       one workgroup per gene, grid-stride.  The gene's non-zeros are sorted as (key << 32 | cell) and
+//                        every sorted position gets its doubled midrank and its tie run by mi_midrank.h (wg_midranks).
 //                        The labellings are then scored kMarkersChunk at a time: per (labelling, cluster) one 64-bit LDS
 //                        word takes the doubled midranks (bits 0 .. 41: the sum over all n cells is n (n + 1) < 2^42 for
 //                        n <= 2^20) and the number of non-zero cells (bits 42 .. 62) in ONE integer atomic per (entry,
@@ -29,7 +26,7 @@
 // n x g buffer.  rank_gene is one body for both: it is a template on how a gene's candidates are enumerated (DenseGenes:
 // the n cells of Xt's row; CscGenes: the stored entries, cell = rows[k], value = V[pos[k]]).  The launch is planned from
 // an upper bound of each gene's non-zeros (the stored count; exact for a dense matrix); the compaction skips stored zeros
-// and yields the true count, which everything after it uses, and the sort is padded to the planned power of two.
+// and yields the true count, which everything after it uses, the sort's power of two included.
 //   k_markers_permute    Vg[k] = V[pos[k]]: the values in gene-major order, nnz floats of scratch (one of the two gather forms)
 //   k_markers_sums_csc   k_markers_sums on the stored entries: the same additions in the same (ascending cell) order, so the
 //                        sums are bit for bit the dense kernel's.
@@ -39,6 +36,7 @@
 #include "../../include/mi_metrics.h"
 #include "../../include/mi_prep.h"
 #include "mi_markers_plan.h"
+#include "mi_midrank.h"
 #include "mi_prep_handle.h"
 #include "mi_sa_device.h"
 
@@ -66,10 +64,7 @@ struct MarkersArgs {
     long long *tie = nullptr;              // g
 };
 
-__device__ __forceinline__ bool zero_bits(uint32_t u) { return (u & 0x7fffffffu) == 0u; }
-
-// ascending u32 order == ascending float order over the finite non-zero values (equal floats <=> equal keys)
-__device__ __forceinline__ uint32_t order_key(uint32_t u) { return (u >> 31) ? ~u : (u | 0x80000000u); }
+using mi_midrank::zero_bits;
 
 __global__ void __launch_bounds__(256) k_markers_transpose(const float *__restrict__ X, float *__restrict__ Xt, int n, int g)
 {
@@ -124,100 +119,38 @@ struct CscGenes {                          // the stored entries colptr[gene] ..
     __device__ __forceinline__ int planned(int j) const { return (int)(colptr[j + 1] - colptr[j]); }
 };
 
-// One gene, whole workgroup.  `planned` >= the gene's non-zeros; S (P entries, P = next power of two of planned) and mid
-// (as many entries as there are non-zeros) are in LDS or in HBM.
+// One gene, whole workgroup.  S (`cap` entries, a power of two >= the gene's planned count) and mid (as many entries as
+// there are non-zeros) are in LDS or in HBM.
 template <class Src>
-__device__ __forceinline__ void rank_gene(const MarkersArgs &a, const Src &src, int gene, int planned, unsigned long long *S,
+__device__ __forceinline__ void rank_gene(const MarkersArgs &a, const Src &src, int gene, int cap, unsigned long long *S,
                                           uint32_t *mid, unsigned long long *acc, uint32_t *negc, unsigned long long *s_tie,
                                           uint32_t *s_cnt)
 {
-    const int n = a.n, K = a.K, tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
-    int P = 0;
-    if (planned > 0)
-        for (P = 1; P < planned; P <<= 1) {}
-    if (tid == 0) {
-        s_cnt[0] = 0u;
-        s_cnt[1] = 0u;
-        *s_tie = 0ull;
-    }
-    __syncthreads();
+    const int K = a.K, tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
+    if (tid == 0) *s_tie = 0ull;                                                         // (published by wg_midranks' first barrier)
 
-    // compaction of the non-zeros (any order: the 64-bit words are unique), count of the negatives
+    // doubled midrank of every sorted position, with the sign of its value; tie term of the non-zero runs
     const typename Src::Gene cand = src.gene(gene);
-    for (int i0 = 0; i0 < cand.count; i0 += nt) {
-        const int i = i0 + tid;
-        const uint32_t u = i < cand.count ? cand.bits(i) : 0u;
-        const bool nz = !zero_bits(u), ng = nz && (u >> 31);
-        const unsigned long long m = __ballot(nz), mn = __ballot(ng);
-        if (m) {
-            uint32_t base = 0u;
-            if (lane == 0) {
-                base = atomicAdd(&s_cnt[0], (uint32_t)__popcll(m));
-                if (mn) atomicAdd(&s_cnt[1], (uint32_t)__popcll(mn));
-            }
-            base = __shfl(base, 0);
-            const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (nz && at < (uint32_t)P) S[at] = ((unsigned long long)order_key(u) << 32) | cand.cell(i);
-        }
-    }
-    __syncthreads();
-    const int nnz = s_cnt[0] < (uint32_t)P ? (int)s_cnt[0] : P;                          // the true count (<= planned <= P): a stored zero is a zero
-    for (int p = nnz + tid; p < P; p += nt) S[p] = ~0ull;                                // (sorts last: no finite key is ~0)
-    __syncthreads();
-
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += nt) {
-                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-                const unsigned long long x = S[lo], y = S[hi];
-                if ((x > y) == ((lo & k) == 0)) {
-                    S[lo] = y;
-                    S[hi] = x;
-                }
-            }
-            __syncthreads();
-        }
-
-    // doubled midrank of every sorted position; tie term of the non-zero runs
-    const uint32_t neg = s_cnt[1], zeros = (uint32_t)(n - nnz);
     long long tie = 0;
-    for (int p = tid; p < nnz; p += nt) {
-        const uint32_t key = (uint32_t)(S[p] >> 32);
-        int lo = p, hi = p + 1;
-        if (p > 0 && (uint32_t)(S[p - 1] >> 32) == key) {                                // first position with this key, in [0, p - 1]
-            int l = 0, r = p - 1;
-            while (l < r) {
-                const int m = (l + r) >> 1;
-                if ((uint32_t)(S[m] >> 32) < key) l = m + 1;
-                else r = m;
+    const mi_midrank::Ranked rk = mi_midrank::wg_midranks(
+        cand.count, [&](int i) { return cand.bits(i); }, [&](int i) { return cand.cell(i); }, a.n, cap, S, s_cnt,
+        [&](int p, unsigned long long e, int lo, int hi, uint32_t r2) {
+            mid[p] = r2 | ((e >> 63) ? 0u : 0x80000000u);
+            if (lo == p) {
+                const long long t = hi - lo;
+                tie += t * t * t - t;
             }
-            lo = l;
-        }
-        if (p + 1 < nnz && (uint32_t)(S[p + 1] >> 32) == key) {                          // first position past this key, in [p + 2, nnz]
-            int l = p + 2, r = nnz;
-            while (l < r) {
-                const int m = (l + r) >> 1;
-                if ((uint32_t)(S[m] >> 32) <= key) l = m + 1;
-                else r = m;
-            }
-            hi = l;
-        }
-        const bool isneg = key < 0x80000000u;
-        mid[p] = ((uint32_t)(lo + 1 + hi) + (isneg ? 0u : 2u * zeros)) | (isneg ? 0x80000000u : 0u);
-        if (lo == p) {
-            const long long t = hi - lo;
-            tie += t * t * t - t;
-        }
-    }
+        });
+    const int nnz = rk.nnz;
     for (int off = 32; off > 0; off >>= 1) tie += __shfl_xor(tie, off);
     if (lane == 0 && tie) atomicAdd(s_tie, (unsigned long long)tie);
     __syncthreads();
     if (tid == 0 && a.tie) {
-        const long long z = zeros;
+        const long long z = rk.zeros;
         a.tie[gene] = (long long)*s_tie + z * z * z - z;
     }
 
-    const long long zmid2 = 2ll * neg + zeros + 1;
+    const long long zmid2 = rk.zero_r2;
     for (int b0 = 0; b0 < a.B; b0 += kMarkersChunk) {
         const int nb = a.B - b0 < kMarkersChunk ? a.B - b0 : kMarkersChunk;
         for (int t = tid; t < nb * K; t += nt) {
@@ -259,9 +192,8 @@ __global__ void __launch_bounds__(1024) k_markers_rank(MarkersArgs a, Src src)
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(lds + (size_t)a.lds_cap * 12);
     uint32_t *negc = reinterpret_cast<uint32_t *>(acc + kMarkersChunk * a.K);
     for (int gene = blockIdx.x; gene < a.g; gene += gridDim.x) {
-        const int planned = src.planned(gene);
-        if (planned <= a.lds_cap) rank_gene(a, src, gene, planned, S, mid, acc, negc, &s_tie, s_cnt);
-        else rank_gene(a, src, gene, planned, a.slab + blockIdx.x * a.slab_stride, a.slab_mid + blockIdx.x * a.slab_stride, acc, negc, &s_tie, s_cnt);
+        if (src.planned(gene) <= a.lds_cap) rank_gene(a, src, gene, a.lds_cap, S, mid, acc, negc, &s_tie, s_cnt);
+        else rank_gene(a, src, gene, (int)a.slab_stride, a.slab + blockIdx.x * a.slab_stride, a.slab_mid + blockIdx.x * a.slab_stride, acc, negc, &s_tie, s_cnt);
     }
 }
 
@@ -429,8 +361,7 @@ struct MarkersRun {
     template <class Src>
     int rank(const Src &src)
     {
-        if (lds_bytes > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_markers_rank<Src>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        MI_TRY(allow_lds(k_markers_rank<Src>, lds_bytes));
         hipLaunchKernelGGL(k_markers_rank<Src>, dim3((unsigned)grid), dim3((unsigned)threads), lds_bytes, 0, a, src);
         HIP_TRY(hipGetLastError());
         return MI_OK;

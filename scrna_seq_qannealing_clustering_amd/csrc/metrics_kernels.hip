@@ -194,8 +194,7 @@ extern "C" int mi_jaccard_cluster_stats(const uint64_t *bits, int n, int words, 
         HIP_TRY(hipMemset(d_diam, 0, (size_t)K * 8));
         const std::vector<unsigned long long> inf((size_t)K * K, 0x7ff0000000000000ull);       // the bits of +inf (fp64)
         HIP_TRY(bufs.upload(&d_sep, inf.data(), inf.size()));
-        if (lds > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_jaccard_stats), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MI_TRY(allow_lds(k_jaccard_stats, lds));
         Timer tm;
         MI_TRY(tm.start(0));
         // planes: [S][n][K] distance sums, then [S][n] squared sums (all), then [S][n] squared sums (within)

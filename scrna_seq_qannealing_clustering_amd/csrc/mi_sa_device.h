@@ -369,12 +369,20 @@ int mi_launch_csr_rank1_pair(const EllArgs &, const AnnealPlan &, hipStream_t); 
 int mi_launch_csr_rank1_split(const EllArgs &, const AnnealPlan &, hipStream_t);   // sparse_split_kernels.hip: K2w, K2s
 int mi_launch_potts_fast(const EllArgs &, const AnnealPlan &, hipStream_t);        // potts_fast_kernels.hip: K3f
 
+// a launch with more than 64 KiB of dynamic LDS has to be allowed per kernel first
+template <typename KernelT>
+int allow_lds(KernelT kernel, size_t bytes)
+{
+    if (bytes > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return MI_OK;
+}
+
 // ... and what each does once it has found the kernel: LDS size, the kernel's name, the launch
 template <typename KernelT>
 int launch_planned(KernelT kernel, const EllArgs &a, const AnnealPlan &plan, hipStream_t st)
 {
-    if (plan.lds_bytes > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+    MI_TRY(allow_lds(kernel, plan.lds_bytes));
     char name[128];
     plan_kernel_name(plan, name, sizeof name);
     note_kernel("%s", name);

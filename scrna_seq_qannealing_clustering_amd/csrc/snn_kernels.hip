@@ -14,7 +14,7 @@
 //   S3 k_snn_rows<P>   one workgroup per row i, persistent: shared counts s_ij accumulated in byte counters in
 //                      LDS (one per point) by walking RN(m) for m in N(i); a second walk reads-and-clears
 //                      them (atomic AND: the first visitor of a duplicate candidate wins).  Pass 0 counts the
-//                      row, pass 1 emits it, bitonic-sorted by column.  Integer / LDS-atomic bound.
+//                      row, pass 1 emits it, sorted by column (mi_midrank.h: wg_sort_u64).  Integer / LDS-atomic bound.
 //   S4 k_trim_par      the reference's trim loop is sequential and in place (what column i sees depends on
 //                      what columns < i deleted); column i only depends on its smaller NEIGHBOURS, so many
 //                      columns are in flight, each waiting for those (k_trim = the one-workgroup fallback).
@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "mi_midrank.h"
 #include "mi_sa_device.h"
 
 namespace mi_sa_impl {
@@ -198,22 +199,10 @@ __global__ void __launch_bounds__(256) k_snn_rows(const int32_t *__restrict__ nn
                 if (cntrow > kRowCap) atomicExch(err, 1);
             }
         } else if (cntrow <= kRowCap) {
-            int m2 = 1;
-            while (m2 < cntrow) m2 <<= 1;
+            const int m2 = mi_midrank::pow2_at_least(cntrow);
             for (int e = cntrow + (int)threadIdx.x; e < m2; e += 256) rowbuf[e] = ~0ull;
             __syncthreads();
-            for (int size = 2; size <= m2; size <<= 1)
-                for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                    for (int e = threadIdx.x; e < m2; e += 256) {
-                        const int partner = e ^ stride;
-                        if (partner > e) {
-                            const bool up = (e & size) == 0;
-                            const unsigned long long a = rowbuf[e], b = rowbuf[partner];
-                            if ((a > b) == up) { rowbuf[e] = b; rowbuf[partner] = a; }
-                        }
-                    }
-                    __syncthreads();
-                }
+            mi_midrank::wg_sort_u64(rowbuf, m2);                                // (column << 32 | shared): unique words
             const int base = rowptr[i];
             for (int e = threadIdx.x; e < cntrow; e += 256) {
                 col[base + e] = (int32_t)(rowbuf[e] >> 32);
@@ -665,8 +654,8 @@ static int snn_build_impl(const float *X, int n, int dim, int k, double prune, i
 
         // S3: shared-neighbour rows (count, scan, emit)
         const size_t lds = (size_t)(((n + 3) / 4 * 4 + 15) / 16) * 16 + (size_t)kRowCap * 8;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_snn_rows<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_snn_rows<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MI_TRY(allow_lds(k_snn_rows<0>, lds));
+        MI_TRY(allow_lds(k_snn_rows<1>, lds));
         const int rblocks = n < cus * 2 ? n : cus * 2;
         hipLaunchKernelGGL(k_snn_rows<0>, dim3(rblocks), dim3(256), lds, st, g->d_nn, n, k, prune, d_rn_ptr, d_rn_idx, d_deg,
                            (const int *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, d_err);

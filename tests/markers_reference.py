@@ -32,6 +32,27 @@ def reference_stats(X, L, K, plain=False):
     return rank2, npos, sums, tie, sizes
 
 
+TIE_BLOCKS = (1, 2, 3, 64, 65, 257)
+
+
+def tie_block_vectors(rng):
+    """(3, 800) float32 vectors made of tie blocks only: every length of TIE_BLOCKS once among the negatives and once
+    among the positives, one block of 16 zeros of both signs, the entries shuffled by position.  In ascending order of
+    value vector 0 begins with the block of 1 and ends with the block of 257, vector 1 the other way round, vector 2
+    begins and ends with a block of 2: tie runs that touch sorted position 0 and the last one, one longer than a workgroup
+    of 256 that straddles position 256.  -> the vectors and, per vector, the run lengths of its non-zeros in sorted order"""
+    out, runs = [], []
+    for first, last in ((1, 257), (257, 1), (2, 2)):
+        neg = [first] + [int(t) for t in rng.permutation([t for t in TIE_BLOCKS if t != first])]
+        pos = [int(t) for t in rng.permutation([t for t in TIE_BLOCKS if t != last])] + [last]
+        v = [np.full(t, -0.5 * (len(neg) - b)) for b, t in enumerate(neg)]
+        v += [np.zeros(8), -np.zeros(8)]
+        v += [np.full(t, 0.5 * (b + 1)) for b, t in enumerate(pos)]
+        out.append(rng.permutation(np.concatenate(v)))
+        runs.append(neg + pos)
+    return np.stack(out).astype(np.float32), runs
+
+
 def sparse_matrix(rng, n, g, rate=0.3):
     """scRNA-like columns: a Poisson(rate) mask (about 26 % non-zero at 0.3) times uniform values"""
     return ((rng.poisson(rate, (n, g)) > 0) * rng.uniform(0.1, 4.0, (n, g))).astype(np.float32)

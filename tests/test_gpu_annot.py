@@ -12,6 +12,7 @@ import scipy.sparse as sp
 
 import annot_cases
 import annot_reference as ar
+from markers_reference import tie_block_vectors
 from scrna_seq_qannealing_clustering_amd import _lib, annotate, metrics
 
 pytestmark = pytest.mark.gpu
@@ -108,6 +109,24 @@ def test_special_rows():
         assert not r["scores"][i].any()
     one = annotate.score_pass(X, X[[names.index("all_zero")]])
     assert not one["scores"].any()
+
+
+def test_tie_blocks_at_both_ends():
+    """rows whose tie runs touch sorted position 0 and the last one, cross position 256 and outgrow a workgroup
+    (markers_reference.tie_block_vectors): as cells and, reversed, as samples; then as the samples of two labels whose
+    pair markers are all the genes, so that the fine-tuning loop ranks every one of them again over G' = all genes"""
+    rng = np.random.default_rng(18)                                  # (a seed at which every cell enters the loop: asserted below)
+    X = tie_block_vectors(rng)[0]
+    m = X.shape[1]
+    check_integers(X, np.ascontiguousarray(X[::-1]))
+    R, ids = tie_block_vectors(rng)[0], np.array([0, 1, 0], dtype=np.int32)      # the same blocks, other positions
+    pairs = {(0, 1): np.arange(m), (1, 0): np.arange(m)}
+    trace = []
+    e = ar.annotate(X, R, ids, 2, pairs, trace=trace)
+    assert sorted(t[0] for t in trace) == [0, 1, 2] and all(t[1:] == ((0, 1), m) for t in trace) and e["margin"].min() > 1e-6
+    r = annotate.score_pass(X, R, labels=ids, masks=annotate.pair_masks(pairs, np.arange(m), 2), fine_tune=True)
+    for key in ("scores", "first_labels", "iterations", "labels", "tuned_best", "tuned_next"):
+        assert np.array_equal(r[key], e[key]), key
 
 
 def test_limits_are_refused():

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 from scipy.stats import mannwhitneyu
 
-from markers_reference import reference_stats, sparse_matrix
+from markers_reference import TIE_BLOCKS, reference_stats, sparse_matrix, tie_block_vectors
 from test_gpu_modularity import graph
 from scrna_seq_qannealing_clustering_amd import metrics
 from scrna_seq_qannealing_clustering_amd.clustering import clustering_modularity_sweep
@@ -83,6 +83,19 @@ def test_special_columns():
     assert r["tie"][names.index("all_distinct")] == 0
     # every gene's doubled ranks add up to n (n + 1), whatever the labelling
     assert (r["rank2"].sum(axis=2) == n * (n + 1)).all()
+
+
+def test_tie_blocks_at_both_ends():
+    """tie runs at sorted position 0 and at the last one, across position 256 and longer than a workgroup, in both forms"""
+    rng = np.random.default_rng(11)
+    V, runs = tie_block_vectors(rng)
+    n = V.shape[1]
+    for v, want in zip(V, runs):
+        assert np.unique(v[v != 0], return_counts=True)[1].tolist() == want and sorted(want) == sorted(2 * TIE_BLOCKS)
+        assert (v == 0).sum() == 16 and np.signbit(v[v == 0]).sum() == 8
+    assert [(r[0], r[-1]) for r in runs] == [(1, 257), (257, 1), (2, 2)]
+    r = check_integers(np.ascontiguousarray(V.T), rng.integers(0, 4, (2, n)), 4)
+    assert r["tie"].tolist() == [2 * sum(t ** 3 - t for t in TIE_BLOCKS) + 16 ** 3 - 16] * 3
 
 
 # ---- 3. labellings -------------------------------------------------------------------------------------------------------
