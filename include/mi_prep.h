@@ -244,6 +244,49 @@ int mi_prep_sct_select(mi_prep_matrix *m, const int32_t *genes, int h, const dou
                        const double *log_umi, double clip, const double *Q, int q, double *out_coef, double *out_mean,
                        double *out_var, uint8_t *out_flat, float *out_kernel_ms);
 
+/* SCTransform's corrected counts and its `data` slot as a second handle (modelled on sctransform::correct_counts; unpinned
+ * against R).  For a listed gene with (b0, b1, alpha), a cell with lu = log_umi[i] and the stored count x, all in fp64:
+ *     mu   = exp(b0 + b1 lu)              s   = sqrt(mu + alpha (mu mu))
+ *     mu_r = exp(b0 + b1 log_umi_ref)     s_r = sqrt(mu_r + alpha (mu_r mu_r))
+ *     r = ((double) x - mu) / s (not clipped)       c = fmax(rint(mu_r + r s_r), 0.0)   (a multiply, an add, half to even)
+ *     corrected = (float) c               data = (float) log1p(c)
+ * (mi_sct::corrected_count, csrc/mi_sct_math.h: the one text every kernel form calls).  A gene that is not listed gives all
+ * zeros: the output keeps the g columns of `m`, so gene names stay aligned (a convention of this package).  The caller
+ * passes log10 of the median of the cells' totals as log_umi_ref.
+ * *out: a new, independent handle on m's device, of m's kind and shape: its counts are the corrected counts, its normalised
+ * matrix is the data slot (every `which = 1` pass works at once; mi_prep_normalize would replace it).  m is not modified
+ * (its device_bytes is the same before and after), may be destroyed first, and all scratch is freed on return.
+ *   dense handle   k_sct_correct writes both matrices element by element; mu_r and s_r are computed once per gene
+ *                  (k_sct_gene_table).
+ *   sparse handle  a corrected zero need not stay zero, so the output has its own structure, built on the device with no
+ *                  n x g buffer.  It holds exactly the entries with c != 0 (a stored zero or an absent entry of m is x = 0; a
+ *                  stored entry whose c is 0 is dropped).  k_sct_csr_rows, one workgroup per cell: by chunk of 4096 genes the
+ *                  zeros' values fill the cell's LDS row (32 KB of fp64) and the stored entries overwrite; a count launch,
+ *                  k_prep_scan_counts into indptr, then a fill launch that evaluates again and writes columns (ascending),
+ *                  counts and data by an ordered compaction (ballot and lane prefix inside a wavefront, the four wavefronts'
+ *                  counts through LDS).  The transpose is a two-level counting sort of that CSR, which evaluates nothing:
+ *                  k_csr_block_hist counts the entries per (block of R rows, gene) (integer atomics: any order gives the same
+ *                  counts; blocks x genes int32 of scratch, at most 2^26), k_csr_block_offsets makes each gene's counts the
+ *                  prefix over the blocks, k_prep_scan_counts gives colptr, and k_csr_block_transpose, one workgroup per
+ *                  block, walks its rows one after another (a row's columns are distinct; a barrier parts the rows), so a
+ *                  gene's cells ascend and the position map is the entry's place in the CSR.  The other form -- a second
+ *                  evaluation gene-major over m's transpose -- measured twice as slow (profiles/prep_sct_correct_transpose_ab.json).
+ *                  Integer counts and ordered stores only: two runs are bit-identical and the result is that of the dense
+ *                  handle on the densified input.
+ * All checks before any device work, those of mi_prep_sct_residual_moments on the parameters: MI_EINVAL for a NULL argument,
+ * gp < 1 or > g, a gene outside [0, g) or repeated, a non-finite b0, b1, log_umi or log_umi_ref, alpha negative or not
+ * finite.  Found on the device, with no handle created: MI_EINVAL for a c that is not finite (an overflowed or vanished mu;
+ * a flag the kernels raise), MI_EUNSUPPORTED for more than MI_PREP_MAX_NNZ output entries on a sparse handle (the scanned
+ * total).  Needs no mi_prep_normalize. */
+int mi_prep_sct_correct(mi_prep_matrix *m, const int32_t *genes, int gp, const double *b0, const double *b1,
+                        const double *alpha, const double *log_umi, double log_umi_ref, mi_prep_matrix **out,
+                        float *out_kernel_ms);
+/* out: the counts of a dense handle, n x g.  MI_EUNSUPPORTED on a sparse handle. */
+int mi_prep_fetch_counts(mi_prep_matrix *m, float *out);
+/* The structure of a sparse handle and its counts: indptr n + 1 entries, indices and data `nnz` of mi_prep_info; each output
+ * is nullable.  MI_EINVAL on a dense handle. */
+int mi_prep_fetch_csr(mi_prep_matrix *m, int64_t *indptr, int32_t *indices, float *data);
+
 /* out_G: h x h fp64, G = Z^T Z (not divided by n - 1).  Every entry is the fp64 sum, in chunk order, of the f32 fmaf chains
  * over the cells of each chunk of MI_PREP_GRAM_CHUNK cells.  MI_ESTATE before mi_prep_select. */
 int mi_prep_gram(mi_prep_matrix *m, double *out_G, float *out_kernel_ms);

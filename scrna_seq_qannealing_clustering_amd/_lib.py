@@ -130,6 +130,9 @@ def _signatures():
         "mi_prep_sct_residual_moments": (C.c_int, [vp, i32p, C.c_int, f64p, f64p, f64p, f64p, C.c_double, f64p, f64p, f32p]),
         "mi_prep_sct_select": (C.c_int, [vp, i32p, C.c_int, f64p, f64p, f64p, f64p, C.c_double, f64p, C.c_int, f64p, f64p, f64p,
                                          u8p, f32p]),
+        "mi_prep_sct_correct": (C.c_int, [vp, i32p, C.c_int, f64p, f64p, f64p, f64p, C.c_double, pp, f32p]),
+        "mi_prep_fetch_counts": (C.c_int, [vp, f32p]),
+        "mi_prep_fetch_csr": (C.c_int, [vp, C.POINTER(C.c_int64), i32p, f32p]),
         "mi_prep_gram": (C.c_int, [vp, f64p, f32p]),
         "mi_prep_project": (C.c_int, [vp, f32p, C.c_int, f32p, f32p]),
         "mi_prep_rank_sum_markers": (C.c_int, [vp, C.c_int, u16p, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int64), i32p, f64p,

@@ -1,5 +1,7 @@
-// mi_sct_math.h -- the digamma and trigamma functions of the negative-binomial fit (k_sct_nb_fit, csrc/prep_kernels.hip),
-// for x > 0 in fp64: the recurrence psi(x) = psi(x + 1) - 1 / x (psi'(x) = psi'(x + 1) + 1 / x^2) up to an argument >= 8,
+// mi_sct_math.h -- the scalar functions of SCTransform in fp64.  The corrected count of mi_prep_sct_correct (every kernel
+// form of csrc/prep_kernels.hip, dense or sparse, stored entry or zero, calls corrected_count below; the host program is
+// tests/host/sct_correct_main.cpp).  The digamma and trigamma functions of the negative-binomial fit (k_sct_nb_fit),
+// for x > 0: the recurrence psi(x) = psi(x + 1) - 1 / x (psi'(x) = psi'(x + 1) + 1 / x^2) up to an argument >= 8,
 // then the asymptotic series with the Bernoulli numbers through B16 (psi) and B18 (psi'), whose first omitted term is below
 // 2e-16 of the value at 8.  Plain C++: the device code and a host program (tests/host/sct_psi_main.cpp) compile the same
 // text; every operation is a separate multiply, add or divide.
@@ -54,6 +56,21 @@ MI_SCT_FN double trigamma(double x)
     s = -1.0 / 30.0 + i2 * s;
     s = 1.0 / 6.0 + i2 * s;
     return r + (i + i2 * (0.5 + i * s));
+}
+
+// the standard deviation of the negative-binomial model at mean mu: sqrt(mu + alpha mu^2)
+MI_SCT_FN double nb_sd(double mu, double alpha) { return sqrt(mu + alpha * (mu * mu)); }
+
+// The corrected count of x: its Pearson residual under (mu, alpha), unclipped, carried to the reference depth's mean mu_r
+// and standard deviation s_r = nb_sd(mu_r, alpha), rounded half to even, not below 0 (a separate multiply and add).
+// *finite: is mu_r + r s_r finite -- an overflowed or vanished mu gives an infinity or a NaN, which the maximum would hide.
+MI_SCT_FN double corrected_count(double x, double mu, double alpha, double mu_r, double s_r, bool *finite)
+{
+    const double r = (x - mu) / nb_sd(mu, alpha);
+    const double v = mu_r + r * s_r;
+    *finite = v - v == 0.0;
+    const double c = rint(v);
+    return c > 0.0 ? c : 0.0;                                     // fmax(c, 0.0), with +0.0 for -0.0 (and for a NaN)
 }
 
 }  // namespace mi_sct

@@ -15,7 +15,8 @@
 //   k_prep_regress_*     mi_prep_select_regressed on the gathered Z: c = Q^T y and sum y^2 (coef) and the in-place scaling
 //                        (scale), on the slices, lanes and LDS join of k_prep_col_partial, fp64, no contraction.
 //   k_sct_*              SCTransform: the gather of the fit block, dense and sparse, and the per-gene negative-binomial fit
-//                        (one workgroup per gene, its counts in LDS).
+//                        (one workgroup per gene, its counts in LDS); the corrected counts and the data slot as a second
+//                        handle (k_sct_correct, k_sct_csr_rows), whose sparse structure is built on the device.
 // A sparse handle (mi_prep_create_csr_f32) keeps the counts as CSR and is served by k_prep_csr_normalize,
 // k_prep_csc_col_partial<Term> (k_prep_csc_row_partial<Mode> for the SCT residuals), k_prep_csr_select<Cols> and
 // k_prep_csr_cell_qc, which add in the order of their dense kernels and call the same term functions, on 0.0f for a zero:
@@ -24,6 +25,7 @@
 // holds B[k = l >> 5][j = l & 31]; C/D: register q of lane l is C[row = (q & 3) + 8 (q >> 2) + 4 (l >> 5)][col = l & 31].
 // No floating-point atomics; stores are ordinary vector stores.
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "../../include/mi_prep.h"
@@ -928,6 +930,230 @@ __global__ void __launch_bounds__(256) k_sct_nb_fit(const float *__restrict__ B,
     }
 }
 
+// ---- SCTransform's corrected counts (mi_prep_sct_correct): a second matrix from (counts, regularised model) ------------------
+// c = mi_sct::corrected_count(x, exp(b0 + b1 log_umi_i), alpha, mu_r, s_r) and the data slot (float) log1p(c).  The table
+// `tab` holds, per gene of the handle, b0, b1, alpha and the two values at the reference depth, mu_r and s_r, computed once
+// per gene (5 rows of g); listed[j] = 0 marks a gene that is not listed, whose column is all zero.  Every kernel below
+// evaluates through SctGene alone, on the stored value or on 0.0f for a zero, so the sparse form gives the dense form's bits.
+// A sparse result has its own structure: the row pass (k_sct_csr_rows: count, k_prep_scan_counts, fill) builds its CSR in
+// order, and its transpose is a counting sort of that CSR (k_csr_block_*), which evaluates nothing.
+constexpr int kCorrChunk = 4096;                                  // genes of a cell (cells of a gene) in LDS at a time: 32 KB of fp64
+
+__global__ void __launch_bounds__(256) k_sct_gene_table(const int32_t *__restrict__ genes, const double *__restrict__ par, int gp,
+                                                        double lu_ref, int g, double *__restrict__ tab,
+                                                        uint8_t *__restrict__ listed)
+{
+    const int jj = blockIdx.x * 256 + threadIdx.x;
+    if (jj >= gp) return;
+    const size_t j = (size_t)genes[jj], gs = (size_t)g;
+    const double b0 = par[jj], b1 = par[gp + jj], al = par[2 * (size_t)gp + jj];
+    const double mur = exp(b0 + b1 * lu_ref);
+    tab[j] = b0;
+    tab[gs + j] = b1;
+    tab[2 * gs + j] = al;
+    tab[3 * gs + j] = mur;
+    tab[4 * gs + j] = mi_sct::nb_sd(mur, al);
+    listed[j] = 1;
+}
+
+struct SctGene {                                                  // one gene's column of the table
+    double b0, b1, al, mur, sr;
+    __device__ __forceinline__ SctGene(const double *__restrict__ tab, int g, int j)
+        : b0(tab[j]), b1(tab[(size_t)g + j]), al(tab[2 * (size_t)g + j]), mur(tab[3 * (size_t)g + j]), sr(tab[4 * (size_t)g + j])
+    {
+    }
+    // the corrected count of x in a cell of log_umi l; a value that is not finite raises *bad (every writer stores 1)
+    __device__ __forceinline__ double operator()(float x, double l, int *__restrict__ bad) const
+    {
+        bool finite;
+        const double c = mi_sct::corrected_count((double)x, exp(b0 + b1 * l), al, mur, sr, &finite);
+        if (!finite) *bad = 1;
+        return c;
+    }
+};
+
+// the dense form, on the slices and lanes of k_prep_col_partial (a thread keeps its gene's column of the table over its rows):
+// C = (float) c and D = (float) log1p(c), n x g each
+__global__ void __launch_bounds__(256) k_sct_correct(const float *__restrict__ X, int n, int g, const double *__restrict__ tab,
+                                                     const uint8_t *__restrict__ listed, const double *__restrict__ lu,
+                                                     float *__restrict__ Cm, float *__restrict__ Dm, int *__restrict__ bad)
+{
+    const ColSlice s(n);
+    if (s.j >= g) return;
+    const bool on = listed[s.j] != 0;
+    const SctGene gene(tab, g, on ? s.j : 0);
+    for (int r = s.r0 + s.ty; r < s.r1; r += 4) {
+        const size_t e = (size_t)r * g + s.j;
+        const double c = on ? gene(X[e], lu[r], bad) : 0.0;
+        Cm[e] = (float)c;
+        Dm[e] = (float)log1p(c);
+    }
+}
+
+__device__ __forceinline__ int lanes_below(unsigned long long mask)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// the sum of v over the workgroup of 256 (integers: any order gives the same value), in every thread
+__device__ __forceinline__ int block_sum_i32(int v, int *s_w)
+{
+    v = wave_sum_i32(v);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// Ordered compaction of a chunk in LDS: emit(i, o) for every i < len with s[i] != 0, o counting up from `base` in ascending
+// i.  Wavefront w owns the quarter [w kCorrChunk / 4, ...): it counts its non-zeros by ballots, the four counts meet in LDS,
+// and it walks its quarter again with the prefix of the wavefronts before it; inside a ballot the place is the count of
+// the lanes below.  -> base + the chunk's non-zeros.  Ends on a barrier: s and s_w are free again.
+template <typename Emit>
+__device__ __forceinline__ int64_t chunk_compact(const double *s, int len, int64_t base, int *s_w, const Emit &emit)
+{
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i0 = w * (kCorrChunk / 4), i1 = i0 + kCorrChunk / 4 < len ? i0 + kCorrChunk / 4 : len;
+    int cnt = 0;
+    for (int i = i0; i < i1; i += 64) cnt += __popcll(__ballot(i + lane < i1 && s[i + lane] != 0.0));
+    if (lane == 0) s_w[w] = cnt;
+    __syncthreads();
+    int64_t o = base;
+    for (int k = 0; k < w; ++k) o += s_w[k];
+    const int total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    for (int i = i0; i < i1; i += 64) {
+        const bool nz = i + lane < i1 && s[i + lane] != 0.0;
+        const unsigned long long b = __ballot(nz);
+        if (nz) emit(i + lane, o + lanes_below(b));
+        o += __popcll(b);
+    }
+    __syncthreads();
+    return base + total;
+}
+
+// The row pass of the sparse form, one workgroup per cell: by chunk of genes the zeros' corrected counts fill the cell's LDS
+// row, the stored entries of listed genes overwrite theirs (a gene is stored at most once per cell).  PASS 0 counts the
+// non-zeros of the row; PASS 1, given the scanned counts as new_indptr, evaluates again and writes columns (ascending), counts
+// and data slot.
+template <int PASS>
+__global__ void __launch_bounds__(256) k_sct_csr_rows(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                      const float *__restrict__ X, int g, const double *__restrict__ tab,
+                                                      const uint8_t *__restrict__ listed, const double *__restrict__ lu,
+                                                      int32_t *__restrict__ row_count, const int64_t *__restrict__ new_indptr,
+                                                      int32_t *__restrict__ new_indices, float *__restrict__ Cv,
+                                                      float *__restrict__ Dv, int *__restrict__ bad)
+{
+    __shared__ double s_c[kCorrChunk];
+    __shared__ int s_w[4];
+    const size_t row = blockIdx.x;
+    const double l = lu[row];
+    const int64_t e0 = indptr[row], e1 = indptr[row + 1];
+    int64_t out = PASS ? new_indptr[row] : 0;
+    const int64_t end = PASS ? new_indptr[row + 1] : 0;          // (the count pass gave this row's room: nothing is written past it)
+    int cnt = 0;
+    for (int c0 = 0; c0 < g; c0 += kCorrChunk) {
+        const int len = g - c0 < kCorrChunk ? g - c0 : kCorrChunk;
+        for (int i = threadIdx.x; i < len; i += 256) s_c[i] = listed[c0 + i] ? SctGene(tab, g, c0 + i)(0.0f, l, bad) : 0.0;
+        __syncthreads();
+        const int64_t a = csc_first_entry(indices, e0, e1, c0), b = csc_first_entry(indices, a, e1, c0 + len);
+        for (int64_t e = a + threadIdx.x; e < b; e += 256) {
+            const int j = indices[e];
+            if (listed[j]) s_c[j - c0] = SctGene(tab, g, j)(X[e], l, bad);
+        }
+        __syncthreads();
+        if (PASS == 0) {
+            for (int i = threadIdx.x; i < len; i += 256) cnt += s_c[i] != 0.0;
+            __syncthreads();
+        } else {
+            out = chunk_compact(s_c, len, out, s_w, [&](int i, int64_t o) {
+                const double c = s_c[i];
+                if (o >= end) return;
+                new_indices[o] = c0 + i;
+                Cv[o] = (float)c;
+                Dv[o] = (float)log1p(c);
+            });
+        }
+    }
+    if (PASS == 0) {
+        cnt = block_sum_i32(cnt, s_w);
+        if (threadIdx.x == 0) row_count[row] = cnt;
+    }
+}
+
+// The transpose of a CSR structure built on the device, by a two-level counting sort that evaluates nothing: the rows are cut
+// into blocks of R, hist[b g + j] counts the entries of gene j in block b (integer atomics: any order gives the same
+// counts), k_csr_block_offsets turns each gene's counts into the exclusive prefix over the blocks (and the gene's total),
+// and k_csr_block_transpose, one workgroup per block, walks its rows one after another -- a row's columns are distinct, so
+// its entries take their places side by side; a barrier parts the rows -- which leaves every gene's cells ascending.
+__global__ void __launch_bounds__(256) k_csr_block_hist(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                        int n, int g, int R, int32_t *__restrict__ hist)
+{
+    const int r0 = blockIdx.x * R, r1 = r0 + R < n ? r0 + R : n;
+    int32_t *h = hist + (size_t)blockIdx.x * g;
+    const int64_t e1 = indptr[r1];
+    for (int64_t e = indptr[r0] + threadIdx.x; e < e1; e += 256) atomicAdd(&h[indices[e]], 1);
+}
+
+__global__ void __launch_bounds__(256) k_csr_block_offsets(int32_t *__restrict__ hist, int nb, int g, int32_t *__restrict__ count)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= g) return;
+    int32_t run = 0;
+    for (int b = 0; b < nb; ++b) {
+        const size_t o = (size_t)b * g + j;
+        const int32_t c = hist[o];
+        hist[o] = run;
+        run += c;
+    }
+    count[j] = run;
+}
+
+__global__ void __launch_bounds__(256) k_csr_block_transpose(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                             int n, int g, int R, const int64_t *__restrict__ colptr,
+                                                             int32_t *hist, int32_t *__restrict__ rows, int32_t *__restrict__ pos)
+{
+    const int r0 = blockIdx.x * R, r1 = r0 + R < n ? r0 + R : n;
+    int32_t *h = hist + (size_t)blockIdx.x * g;
+    for (int r = r0; r < r1; ++r) {
+        const int64_t e1 = indptr[r + 1];
+        for (int64_t e = indptr[r] + threadIdx.x; e < e1; e += 256) {
+            const int j = indices[e];
+            const int32_t k = h[j];
+            h[j] = k + 1;
+            const int64_t o = colptr[j] + k;
+            rows[o] = r;
+            pos[o] = (int32_t)e;
+        }
+        __syncthreads();                                          // (the next row reads the cursors this one moved)
+    }
+}
+
+// out[0] = 0, out[i + 1] = in[0] + ... + in[i] in 64 bits.  One workgroup, 1024 counts at a time: an inclusive scan inside
+// each wavefront by shuffles, the sixteen totals through LDS, the tiles before as a carry every thread keeps.
+__global__ void __launch_bounds__(1024) k_prep_scan_counts(const int32_t *__restrict__ in, int64_t *__restrict__ out, int n)
+{
+    __shared__ long long s_w[16];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    long long carry = 0;
+    if (threadIdx.x == 0) out[0] = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + (int)threadIdx.x;
+        long long v = i < n ? (long long)in[i] : 0;
+        for (int off = 1; off < 64; off <<= 1) {
+            const long long u = __shfl_up(v, off, 64);
+            if (lane >= off) v += u;
+        }
+        if (lane == 63) s_w[w] = v;
+        __syncthreads();
+        long long before = carry;
+        for (int k = 0; k < 16; ++k) {
+            if (k < w) before += s_w[k];
+            carry += s_w[k];
+        }
+        if (i < n) out[i + 1] = before + v;
+        __syncthreads();
+    }
+}
+
 }  // namespace
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
@@ -1652,6 +1878,143 @@ int mi_prep_sct_select(mi_prep_matrix *m, const int32_t *genes, int h, const dou
         if (!raw) MI_TRY(regress_stages(m, h, d_Q, q, HUGE_VAL, true, out_coef, out_mean, out_var, out_flat, &ms2));
         if (out_kernel_ms) *out_kernel_ms = ms1 + ms2;
         m->h = h;
+        return MI_OK;
+    });
+}
+
+int mi_prep_sct_correct(mi_prep_matrix *m, const int32_t *genes, int gp, const double *b0, const double *b1,
+                        const double *alpha, const double *log_umi, double log_umi_ref, mi_prep_matrix **out,
+                        float *out_kernel_ms)
+{
+    if (out) *out = nullptr;
+    return on_matrix(m, genes && b0 && b1 && alpha && log_umi && out, 0, out_kernel_ms, [&]() -> int {
+        if (gp < 1) return fail(MI_EINVAL, "at least 1 gene is needed (got %d)", gp);
+        if (gp > m->g) return fail(MI_EINVAL, "%d genes are chosen of %d", gp, m->g);
+        std::vector<double> par;
+        MI_TRY(check_indices(genes, gp, m->g, "genes", "genes"));
+        MI_TRY(pack_nb_parameters(b0, b1, alpha, gp, par));
+        MI_TRY(check_log_umi(log_umi, m->n));
+        if (!std::isfinite(log_umi_ref)) return fail(MI_EINVAL, "log_umi_ref is not finite");
+        const int n = m->n, g = m->g;
+        const size_t ns = (size_t)n, gs = (size_t)g;
+        DevBufs bufs;
+        int32_t *d_genes, *d_count;
+        double *d_par, *d_lu, *d_tab;
+        uint8_t *d_listed;
+        int *d_bad;
+        HIP_TRY(bufs.upload(&d_genes, genes, (size_t)gp));
+        HIP_TRY(bufs.upload(&d_par, par.data(), par.size()));
+        HIP_TRY(bufs.upload(&d_lu, log_umi, ns));
+        HIP_TRY(bufs.alloc(&d_tab, 5 * gs));
+        HIP_TRY(bufs.alloc(&d_listed, gs));
+        HIP_TRY(bufs.alloc(&d_bad, 1));
+        HIP_TRY(bufs.alloc(&d_count, (ns > gs ? ns : gs)));       // the rows' counts, then the genes'
+        HIP_TRY(hipMemset(d_tab, 0, 5 * gs * sizeof(double)));
+        HIP_TRY(hipMemset(d_listed, 0, gs));
+        HIP_TRY(hipMemset(d_bad, 0, sizeof(int)));
+        std::unique_ptr<mi_prep_matrix> o(new mi_prep_matrix());  // (deleted on every way out but the last: the device is current)
+        o->n = n; o->g = g; o->device = m->device; o->sparse = m->sparse;
+        int bad = 0;
+        const auto overflowed = [&]() -> int {
+            HIP_TRY(hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost));
+            if (bad) return fail(MI_EINVAL, "a corrected count is not finite: exp(b0 + b1 log_umi) overflows or vanishes");
+            return MI_OK;
+        };
+        const auto table = [&]() -> int {
+            hipLaunchKernelGGL(k_sct_gene_table, dim3((unsigned)((gp + 255) / 256)), dim3(256), 0, 0, d_genes, d_par, gp,
+                               log_umi_ref, g, d_tab, d_listed);
+            HIP_TRY(hipGetLastError());
+            return MI_OK;
+        };
+        if (!m->sparse) {
+            HIP_TRY(o->d_X.resize(ns * gs));
+            HIP_TRY(o->d_Y.resize(ns * gs));
+            Timer t;
+            MI_TRY(t.start(0));
+            MI_TRY(table());
+            hipLaunchKernelGGL(k_sct_correct, dim3((unsigned)((g + 63) / 64), (unsigned)slices(m)), dim3(256), 0, 0, m->d_X, n, g,
+                               d_tab, d_listed, d_lu, o->d_X, o->d_Y, d_bad);
+            MI_TRY(t.stop(0, out_kernel_ms));
+            MI_TRY(overflowed());
+        } else {
+            // the row pass: count, scan into the new indptr, fill
+            float ms1 = 0.0f, ms2 = 0.0f;
+            int64_t total = 0, total_t = 0;
+            HIP_TRY(o->d_indptr.resize(ns + 1));
+            HIP_TRY(o->d_colptr.resize(gs + 1));
+            {
+                Timer t;
+                MI_TRY(t.start(0));
+                MI_TRY(table());
+                hipLaunchKernelGGL(k_sct_csr_rows<0>, dim3((unsigned)n), dim3(256), 0, 0, m->d_indptr, m->d_indices, m->d_X, g, d_tab,
+                                   d_listed, d_lu, d_count, nullptr, nullptr, nullptr, nullptr, d_bad);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(k_prep_scan_counts, dim3(1), dim3(1024), 0, 0, d_count, o->d_indptr, n);
+                MI_TRY(t.stop(0, &ms1));
+            }
+            MI_TRY(overflowed());
+            HIP_TRY(hipMemcpy(&total, o->d_indptr + ns, sizeof(int64_t), hipMemcpyDeviceToHost));
+            if (total > MI_PREP_MAX_NNZ)
+                return fail(MI_EUNSUPPORTED, "%lld corrected entries exceed %lld", (long long)total, (long long)MI_PREP_MAX_NNZ);
+            const size_t nz = (size_t)total;
+            HIP_TRY(o->d_indices.resize(nz));
+            HIP_TRY(o->d_X.resize(nz));
+            HIP_TRY(o->d_Y.resize(nz));
+            HIP_TRY(o->d_rows.resize(nz));
+            HIP_TRY(o->d_pos.resize(nz));
+            // the transpose, by counting sort of what the row pass wrote.  Blocks of R rows: about a thousand workgroups, at
+            // least 32 rows each, the histogram (blocks x genes, scratch) within 2^26 counts
+            const long long nb_max = std::max(1ll, (1ll << 26) / (long long)g);
+            const int R = (int)std::max({32ll, ((long long)n + 1023) / 1024, ((long long)n + nb_max - 1) / nb_max});
+            const int nb = (n + R - 1) / R;
+            int32_t *d_hist;
+            HIP_TRY(bufs.alloc(&d_hist, (size_t)nb * gs));
+            {
+                Timer t;
+                MI_TRY(t.start(0));
+                hipLaunchKernelGGL(k_sct_csr_rows<1>, dim3((unsigned)n), dim3(256), 0, 0, m->d_indptr, m->d_indices, m->d_X, g, d_tab,
+                                   d_listed, d_lu, nullptr, o->d_indptr, o->d_indices, o->d_X, o->d_Y, d_bad);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)nb * gs * sizeof(int32_t), 0));
+                hipLaunchKernelGGL(k_csr_block_hist, dim3((unsigned)nb), dim3(256), 0, 0, o->d_indptr, o->d_indices, n, g, R, d_hist);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(k_csr_block_offsets, dim3((unsigned)((g + 255) / 256)), dim3(256), 0, 0, d_hist, nb, g, d_count);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(k_prep_scan_counts, dim3(1), dim3(1024), 0, 0, d_count, o->d_colptr, g);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(k_csr_block_transpose, dim3((unsigned)nb), dim3(256), 0, 0, o->d_indptr, o->d_indices, n, g, R,
+                                   o->d_colptr, d_hist, o->d_rows, o->d_pos);
+                MI_TRY(t.stop(0, &ms2));
+            }
+            HIP_TRY(hipMemcpy(&total_t, o->d_colptr + gs, sizeof(int64_t), hipMemcpyDeviceToHost));
+            if (total_t != total)
+                return fail(MI_EHIP, "the transpose holds %lld entries, the rows %lld", (long long)total_t, (long long)total);
+            o->nnz = total;
+            if (out_kernel_ms) *out_kernel_ms = ms1 + ms2;
+        }
+        o->normalized = true;
+        *out = o.release();
+        return MI_OK;
+    });
+}
+
+int mi_prep_fetch_counts(mi_prep_matrix *m, float *out)
+{
+    return on_matrix(m, out != nullptr, 0, nullptr, [&]() -> int {
+        if (m->sparse) return fail(MI_EUNSUPPORTED, "a sparse handle has no dense matrix of counts: mi_prep_fetch_csr");
+        HIP_TRY(hipMemcpy(out, m->d_X, (size_t)m->n * m->g * sizeof(float), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
+}
+
+int mi_prep_fetch_csr(mi_prep_matrix *m, int64_t *indptr, int32_t *indices, float *data)
+{
+    return on_matrix(m, true, 0, nullptr, [&]() -> int {
+        if (!m->sparse) return fail(MI_EINVAL, "the handle is dense: mi_prep_fetch_counts");
+        const size_t nz = (size_t)m->nnz;
+        if (indptr) HIP_TRY(hipMemcpy(indptr, m->d_indptr, ((size_t)m->n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (indices && nz) HIP_TRY(hipMemcpy(indices, m->d_indices, nz * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (data && nz) HIP_TRY(hipMemcpy(data, m->d_X, nz * sizeof(float), hipMemcpyDeviceToHost));
         return MI_OK;
     });
 }

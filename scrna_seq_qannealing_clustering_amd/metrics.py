@@ -17,9 +17,30 @@ import numpy as np
 from . import _lib
 
 
-def pack_expression(X: np.ndarray) -> np.ndarray:
+def _pack_expression_csr(X) -> np.ndarray:
+    """:func:`pack_expression` of a ``scipy.sparse`` matrix from its CSR structure, never densified"""
+    from . import preprocess
+    indptr, indices, data, (n, g) = preprocess.canonical_csr(X)
+    W = (g + 63) // 64
+    bits = np.zeros((n, W), dtype=np.uint64)
+    keep = data != 0                                             # (a stored zero is a zero)
+    cols = indices[keep].astype(np.int64)
+    word = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))[keep] * W + (cols >> 6)
+    if len(word):
+        # rows and, inside a row, columns ascend: the entries of one word are adjacent and their bits distinct, so their sum
+        # is their union
+        first = np.flatnonzero(np.concatenate([[True], word[1:] != word[:-1]]))
+        bits.reshape(-1)[word[first]] = np.add.reduceat(np.uint64(1) << (cols & 63).astype(np.uint64), first)
+    return bits
+
+
+def pack_expression(X) -> np.ndarray:
     """(n cells x g genes) -> (n, ceil(g / 64)) uint64 bit rows of the non-zero pattern (bit b of word w =
-    gene 64 w + b), the input of the device pass."""
+    gene 64 w + b), the input of the device pass.  ``X``: a dense array, or a ``scipy.sparse`` matrix, which is packed
+    from its CSR structure without densifying (a stored zero is a zero)."""
+    from . import preprocess                                      # (lazily: preprocess does not import metrics either)
+    if preprocess.is_sparse(X):
+        return _pack_expression_csr(X)
     B = (np.asarray(X) != 0)
     n, g = B.shape
     W = (g + 63) // 64
@@ -48,13 +69,18 @@ def jaccard_pass(bits: np.ndarray, labels: np.ndarray, K: int, device: int = 0, 
             "distances": D, "kernel_ms": float(ms.value)}
 
 
-def cluster_stats(X: np.ndarray, labels, device: int = 0, return_distances: bool = False) -> dict:
+def cluster_stats(X, labels, device: int = 0, return_distances: bool = False) -> dict:
     """``X``: cells x genes expression (any dtype; only the zero / non-zero pattern enters the binary Jaccard
-    distance) or pre-packed uint64 bit rows; ``labels``: one non-negative cluster id per cell.  Returns the
+    distance), dense or ``scipy.sparse`` (e.g. ``fetch_normalized()`` of a sparse handle), or pre-packed uint64 bit rows;
+    ``labels``: one non-negative cluster id per cell.  Returns the
     distance-based fields of ``fpc::cluster.stats`` under fpc's names, ``sil.widths`` (``cluster::silhouette``)
     and ``within.average.distance`` (the per-cluster mean the notebook computes at :36)."""
-    X = np.asarray(X)
-    bits = X if X.dtype == np.uint64 else pack_expression(X)
+    from . import preprocess
+    if preprocess.is_sparse(X):
+        bits = pack_expression(X)
+    else:
+        X = np.asarray(X)
+        bits = X if X.dtype == np.uint64 else pack_expression(X)
     labels = np.asarray(labels)
     if labels.ndim != 1 or len(labels) != bits.shape[0]:
         raise ValueError("labels must have one entry per cell")

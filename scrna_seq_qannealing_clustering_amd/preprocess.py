@@ -24,8 +24,11 @@ its regularisation over the genes (host fp64), Pearson residuals and their varia
 into the same Gram / eigen / project path.  The chain is this package's specification, modelled on ``sctransform::vst``;
 agreement with R is UNPINNED.
 
-Out of scope: SCTransform's corrected counts and ``data`` slot, ``vst.flavor = "v2"``, ``batch_var``, latent variables other
-than ``log_umi``, glmGamPoi's Cox-Reid adjustment; more than ``MAX_FEATURES`` = 4096 features or ``MAX_COVARIATES`` = 8
+``sctransform(..., return_corrected=True)`` also returns SCTransform's corrected counts and its ``data`` slot (the matrix
+the reference's benchmarks measure on) as a second device handle (:meth:`ExpressionMatrix.sct_correct`).
+
+Out of scope: ``vst.flavor = "v2"``, ``batch_var``, a corrected matrix restricted to Seurat's gene subset, latent variables
+other than ``log_umi``, glmGamPoi's Cox-Reid adjustment; more than ``MAX_FEATURES`` = 4096 features or ``MAX_COVARIATES`` = 8
 covariates, sparse input to the ``--counts`` option of ``run``.
 
     qc = preprocess.cell_qc(counts, gene_names)
@@ -121,6 +124,26 @@ class ExpressionMatrix:
             _lib.check(self._lib.mi_prep_create_f32(_p(X, _f32p), self.n, self.g, self.device, C.byref(h)))
         self._h = h
 
+    @classmethod
+    def _adopt(cls, lib, h, device: int) -> "ExpressionMatrix":
+        """An open handle around a ``mi_prep_matrix *`` the library has created (``mi_prep_sct_correct``): shape and kind
+        come from ``mi_prep_info``, a sparse handle's structure from ``mi_prep_fetch_csr``.  Closes it if that fails."""
+        m = cls.__new__(cls)
+        m._lib, m._h, m.device = lib, h, int(device)
+        m.h, m.normalized, m.timing, m._stats = 0, True, {}, {}
+        m.coef_q = m.resid_mean = m.resid_var = m.flat = m.regression = None
+        try:
+            n, g, sparse, nnz = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+            _lib.check(lib.mi_prep_info(h, C.byref(n), C.byref(g), C.byref(nnz), C.byref(sparse), None))
+            m.n, m.g, m.nnz, m.sparse = int(n.value), int(g.value), int(nnz.value), bool(sparse.value)
+            if m.sparse:
+                m._indptr, m._indices = np.empty(m.n + 1, dtype=np.int64), np.empty(m.nnz, dtype=np.int32)
+                _lib.check(lib.mi_prep_fetch_csr(h, _p(m._indptr, _i64p), _p(m._indices, _i32p), None))
+        except Exception:
+            m.close()
+            raise
+        return m
+
     def device_bytes(self) -> int:
         """Bytes the handle holds resident on the device now."""
         out = C.c_int64(0)
@@ -169,6 +192,18 @@ class ExpressionMatrix:
             return csr_matrix((data, self._indices, self._indptr), shape=(self.n, self.g))
         out = np.empty((self.n, self.g), dtype=np.float32)
         _lib.check(self._lib.mi_prep_fetch_normalized(self._handle(), _p(out, _f32p)))
+        return out
+
+    def fetch_counts(self):
+        """The counts the handle holds: an ndarray (n x g, fp32), or for a sparse handle a ``csr_matrix`` with the handle's
+        structure and fp32 data."""
+        if self.sparse:
+            from scipy.sparse import csr_matrix
+            data = np.empty(self.nnz, dtype=np.float32)
+            _lib.check(self._lib.mi_prep_fetch_csr(self._handle(), None, None, _p(data, _f32p)))
+            return csr_matrix((data, self._indices, self._indptr), shape=(self.n, self.g))
+        out = np.empty((self.n, self.g), dtype=np.float32)
+        _lib.check(self._lib.mi_prep_fetch_counts(self._handle(), _p(out, _f32p)))
         return out
 
     def gene_stats(self, which: str = "counts"):
@@ -368,6 +403,23 @@ class ExpressionMatrix:
                                                           _p(mean, _f64p), _p(var, _f64p), C.byref(ms)))
         self.timing["sct_moments_ms"] = float(ms.value)
         return mean, var
+
+    def sct_correct(self, genes, b0, b1, alpha, log_umi, log_umi_ref: float) -> "ExpressionMatrix":
+        """SCTransform's corrected counts and ``data`` slot as a second open handle of this kind and shape, made on the
+        device (``mi_prep_sct_correct``, where the formula stands): per listed gene the unclipped Pearson residual of each
+        count under ``mu = exp(b0 + b1 log_umi)`` is carried to the depth ``log_umi_ref`` and rounded,
+        ``c = max(rint(mu_ref + r sd_ref), 0)``; the result's counts are ``c``, its normalised matrix is ``log1p(c)``
+        (``normalized`` is set: :func:`metrics.find_all_markers` ranks it where it lies).  A gene that is not listed gives
+        all zeros -- the g columns stay, so gene names stay aligned.  A corrected zero need not stay zero: a sparse result
+        has its own structure.  This handle is not modified and may be closed first; the caller closes the result.
+        Records ``timing["sct_correct_ms"]`` here."""
+        genes, par, log_umi = self._nb_parameters(genes, b0, b1, alpha, log_umi)
+        out, ms = C.c_void_p(), C.c_float(0.0)
+        _lib.check(self._lib.mi_prep_sct_correct(self._handle(), _p(genes, _i32p), len(genes), _p(par[0], _f64p),
+                                                 _p(par[1], _f64p), _p(par[2], _f64p), _p(log_umi, _f64p), float(log_umi_ref),
+                                                 C.byref(out), C.byref(ms)))
+        self.timing["sct_correct_ms"] = float(ms.value)
+        return ExpressionMatrix._adopt(self._lib, out, self.device)
 
     def select_pearson(self, genes, b0, b1, alpha, log_umi, Q=None, clip: Optional[float] = None, center: bool = True):
         """SCTransform's ``scale.data`` as ``Z``: the Pearson residuals of the chosen genes clipped to ``+-clip`` (default
@@ -903,7 +955,7 @@ def _detected_in(X, cells) -> np.ndarray:
 
 def sctransform(X, variable_features_n: int = 3000, npcs: int = 50, vars_to_regress=None, ncells: int = 5000,
                 n_genes: int = 2000, min_cells: int = 5, seed: int = 0, clip: Optional[float] = None, device: int = 0,
-                cells=None, genes=None) -> Result:
+                cells=None, genes=None, return_corrected: bool = False) -> Result:
     """Seurat's ``SCTransform(vars.to.regress = ...)`` + ``RunPCA(features = VariableFeatures)`` on one upload, as this
     package specifies it (unpinned against R): per-cell ``log_umi = log10(total)`` and per-gene ``detected`` and
     ``log_gmean`` (device); the step-1 sub-samples (:func:`sct_cell_subsample`, :func:`sct_gene_subsample`; ``cells=`` and
@@ -916,9 +968,19 @@ def sctransform(X, variable_features_n: int = 3000, npcs: int = 50, vars_to_regr
     Returns the fields of :func:`pca` plus ``genes`` (rank order), ``gene_attr`` (per gene of ``X``: ``detected``,
     ``log_gmean``, ``passing``, the regularised ``b0``, ``b1``, ``alpha`` and ``residual_mean`` / ``residual_variance``,
     NaN where not passing), ``model`` (the step-1 table: ``genes``, ``cells``, the fields of ``nb_fit``, ``outlier``),
-    ``log_umi`` and ``timing``.  ``ValueError`` for a cell without counts: run :func:`qc_filter` first.  Not built:
-    corrected counts and the ``data`` slot, ``vst.flavor = "v2"``, ``batch_var``, latent variables other than ``log_umi``,
-    glmGamPoi's Cox-Reid adjustment, more than ``MAX_FEATURES`` features."""
+    ``log_umi`` and ``timing``.  ``ValueError`` for a cell without counts: run :func:`qc_filter` first.
+
+    ``return_corrected=True`` adds ``corrected``, an OPEN :class:`ExpressionMatrix` of the kind and shape of ``X`` that the
+    caller closes: the corrected counts (``fetch_counts()``) and the ``data`` slot ``log1p`` of them (``fetch_normalized()``;
+    the matrix ``find_all_markers(r.corrected, labels)`` ranks and ``cluster_stats(r.corrected.fetch_normalized(), labels)``
+    takes) of the ``passing`` genes under their regularised parameters at the depth ``log10(median(n_count))``
+    (:meth:`ExpressionMatrix.sct_correct`), and ``median_umi``.  Every gene of ``X`` keeps its column, all zero where it is
+    not passing -- a convention of this package: Seurat keeps the passing genes alone.  Without the flag the call is what
+    it was: the same outputs, passes and timing keys.
+
+    Not built: ``vst.flavor = "v2"``, ``batch_var``, a corrected matrix restricted to Seurat's gene subset, agreement with R
+    (unpinned throughout), latent variables other than ``log_umi``, glmGamPoi's Cox-Reid adjustment, more than
+    ``MAX_FEATURES`` features."""
     with ExpressionMatrix(X, device=device) as m:
         n = m.n
         n_count, _, _ = m.cell_qc()
@@ -962,6 +1024,10 @@ def sctransform(X, variable_features_n: int = 3000, npcs: int = 50, vars_to_regr
         if R is not None:
             r["regression"] = Result(betas=regression_betas(R, m.coef_q), resid_mean=m.resid_mean, resid_var=m.resid_var,
                                      flat=m.flat)
+        if return_corrected:
+            median_umi = float(np.median(n_count))
+            r["corrected"] = m.sct_correct(passing, reg.b0, reg.b1, reg.alpha, log_umi, math.log10(median_umi))
+            r["median_umi"] = median_umi
         r["timing"] = dict(m.timing)
     attr = Result(detected=detected, log_gmean=log_gmean, passing=np.isin(np.arange(len(detected)), passing))
     for name, values in (("b0", reg.b0), ("b1", reg.b1), ("alpha", reg.alpha), ("residual_mean", rmean),
