@@ -166,9 +166,10 @@ class Reference:
 
 # ---- the device handle ----------------------------------------------------------------------------------------------------
 
-class Annotator:
+class Annotator(_lib.Handle):
     """mi_annot: a reference restricted to m marker genes (``R`` S x m), its label ids in [0, L) and the pair masks,
     resident and ranked on the device.  ``score`` takes a chunk of cells (n_c x m), ``fine_tune`` works on that chunk."""
+    _destroy = "mi_annot_destroy"
 
     def __init__(self, R, label_ids, L: int, masks=None, device: int = 0):
         R = np.ascontiguousarray(R, dtype=np.float32)
@@ -182,30 +183,10 @@ class Annotator:
         masks = np.ascontiguousarray(masks, dtype=np.uint32)
         if masks.shape != (max(self.L, 0) ** 2, W):
             raise ValueError("masks must be (L * L, ceil(m / 32)) = (%d, %d) (got %s)" % (self.L ** 2, W, masks.shape))
-        self._h = C.c_void_p()
-        ms = C.c_float(0.0)
-        _lib.check(_lib.load().mi_annot_create(
-            R.ctypes.data_as(C.POINTER(C.c_float)), self.S, self.m, ids.ctypes.data_as(C.POINTER(C.c_int32)), self.L,
-            masks.ctypes.data_as(C.POINTER(C.c_uint32)), int(device), C.byref(self._h), C.byref(ms)))
-        self.rank_ref_ms = float(ms.value)
+        h = C.c_void_p()
+        self.rank_ref_ms = _lib.call_ms("mi_annot_create", R, self.S, self.m, ids, self.L, masks, int(device), h)
+        self._h = h
         self.n_c = 0
-
-    def close(self):
-        if self._h:
-            _lib.load().mi_annot_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def score(self, X, integers: bool = False) -> dict:
         X = np.ascontiguousarray(X, dtype=np.float32)
@@ -217,12 +198,8 @@ class Annotator:
         sa2 = np.empty(n, dtype=np.int64) if integers else None
         sb2 = np.empty(self.S, dtype=np.int64) if integers else None
         ms = (C.c_float * 3)()
-        i64p = C.POINTER(C.c_int64)
-        ptr = lambda a: a.ctypes.data_as(i64p) if a is not None else None
         self.n_c = 0
-        _lib.check(_lib.load().mi_annot_score(
-            self._h, X.ctypes.data_as(C.POINTER(C.c_float)), n, ptr(sab), ptr(sa2), ptr(sb2),
-            scores.ctypes.data_as(C.POINTER(C.c_double)), first.ctypes.data_as(C.POINTER(C.c_int32)), ms))
+        _lib.call("mi_annot_score", self._handle(), X, n, sab, sa2, sb2, scores, first, ms)
         self.n_c = n
         out = {"scores": scores, "first_labels": first, "kernel_ms": {"rank": float(ms[0]), "cross": float(ms[1]), "scores": float(ms[2])}}
         if integers:
@@ -236,12 +213,9 @@ class Annotator:
             raise _lib.MiSaError(MI_ESTATE, "score() has not run, or its last call was refused: no chunk is resident")
         labels, iters = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
         best, nxt = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
-        ms = C.c_float(0.0)
-        f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        _lib.check(_lib.load().mi_annot_fine_tune(self._h, labels.ctypes.data_as(i32p), best.ctypes.data_as(f64p),
-                                                  nxt.ctypes.data_as(f64p), iters.ctypes.data_as(i32p), C.byref(ms)))
+        ms = _lib.call_ms("mi_annot_fine_tune", self._handle(), labels, best, nxt, iters)
         return {"labels": labels, "tuned_best": best, "tuned_next": nxt, "iterations": iters,
-                "kernel_ms": {"fine_tune": float(ms.value)}}
+                "kernel_ms": {"fine_tune": ms}}
 
 
 def _chunks(n: int, chunk: int):

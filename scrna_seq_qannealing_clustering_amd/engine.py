@@ -32,12 +32,9 @@ def layout_block_for(n: int, num_reads: int, max_degree: int = 16):
 _WIDE_STEP_RATIO = 439.0 / 236.0
 
 
-def _ptr(a, ctype):
-    return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
-
-
-class Problem:
+class Problem(_lib.Handle):
     """A model uploaded to one MI355X.  ``anneal`` is asynchronous; ``fetch``/``best`` wait."""
+    _destroy = "mi_sa_problem_destroy"
 
     def __init__(self, handle, kind, n, num_cases, device, perm=None, seats=None, n_dev=None):
         self._h = handle
@@ -64,10 +61,8 @@ class Problem:
             raise ValueError("Qs must be a square matrix")
         if not np.array_equal(Qs, Qs.T):
             raise ValueError("Qs must be symmetric (use (Q + Q.T)/2 with the diagonal kept)")
-        lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(lib.mi_sa_problem_create_dense_f32(_ptr(Qs, C.c_float), Qs.shape[0],
-                                                      float(offset), int(device), C.byref(h)))
+        _lib.call("mi_sa_problem_create_dense_f32", Qs, Qs.shape[0], float(offset), int(device), h)
         return cls(h, _lib.KIND_DENSE, Qs.shape[0], 2, device)
 
     @classmethod
@@ -158,11 +153,8 @@ class Problem:
         val = np.ascontiguousarray(val, dtype=np.float32)
         lin = np.ascontiguousarray(lin, dtype=np.float32)
         n = len(lin)
-        lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(lib.mi_sa_problem_create_csr_rank1_f32(
-            _ptr(rowptr, C.c_int32), _ptr(col, C.c_int32), _ptr(val, C.c_float),
-            _ptr(lin, C.c_float), float(c_pair), n, float(offset), int(device), C.byref(h)))
+        _lib.call("mi_sa_problem_create_csr_rank1_f32", rowptr, col, val, lin, float(c_pair), n, float(offset), int(device), h)
         if order == "padded":
             prob = cls(h, _lib.KIND_CSR_RANK1, n_caller, 2, device, seats=seats, n_dev=n_dev)
         else:
@@ -179,16 +171,14 @@ class Problem:
             raise ValueError("a model with pair-term weights needs order='padded'")
         n_caller = len(lin)
         rp, cc, vv, lpad, wdev, seats, n_dev, val64, lin64 = weighted_layout_csr(rowptr, col, val, lin, weights, energy_model)
-        lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(lib.mi_sa_problem_create_csr_rank1_f32(
-            _ptr(rp, C.c_int32), _ptr(cc, C.c_int32), _ptr(vv, C.c_float),
-            _ptr(lpad, C.c_float), float(c_pair), n_dev, float(offset), int(device), C.byref(h)))
+        _lib.call("mi_sa_problem_create_csr_rank1_f32", rp, cc, vv, lpad, float(c_pair), n_dev, float(offset), int(device), h)
         prob = cls(h, _lib.KIND_CSR_RANK1, n_caller, 2, device, seats=seats, n_dev=n_dev)
-        rc = lib.mi_sa_problem_set_pair_weights(h, _ptr(wdev, C.c_int32))
-        if rc:
+        try:
+            _lib.call("mi_sa_problem_set_pair_weights", h, wdev)
+        except Exception:
             prob.close()
-            _lib.check(rc)
+            raise
         if val64 is not None:
             prob._set_energy_model(val64, lin64, float(energy_model[2]), len(vv))
         return prob
@@ -228,19 +218,18 @@ class Problem:
         rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
         col = np.ascontiguousarray(col, dtype=np.int32)
         val = np.ascontiguousarray(val, dtype=np.float32)
-        lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(lib.mi_sa_problem_create_potts_csr_f32(
-            _ptr(rowptr, C.c_int32), _ptr(col, C.c_int32), _ptr(val, C.c_float), float(c_pair),
-            int(n), int(num_cases), float(lin_offset), int(device), C.byref(h)))
+        _lib.call("mi_sa_problem_create_potts_csr_f32", rowptr, col, val, float(c_pair), int(n), int(num_cases),
+                  float(lin_offset), int(device), h)
         if order == "padded":
             prob = cls(h, _lib.KIND_POTTS_CSR, n_caller, int(num_cases), device, seats=seats, n_dev=n)
             absent = np.ones(n, dtype=np.uint8)
             absent[seats] = 0
-            rc = lib.mi_sa_problem_set_absent(h, absent.ctypes.data_as(C.POINTER(C.c_uint8)))
-            if rc:
+            try:
+                _lib.call("mi_sa_problem_set_absent", h, absent)
+            except Exception:
                 prob.close()
-                _lib.check(rc)
+                raise
         else:
             prob = cls(h, _lib.KIND_POTTS_CSR, int(n), int(num_cases), device, perm=perm)
         if val64 is not None:
@@ -272,8 +261,7 @@ class Problem:
         dq[cols] = wq.astype(np.int32)
         dc[cols] = cw
         dw[cols] = wq.astype(np.float64) if w64 is None else w64
-        _lib.check(_lib.load().mi_sa_problem_set_node_weights(self._h, _ptr(dq, C.c_int32), _ptr(dc, C.c_float),
-                                                               _ptr(dw, C.c_double)))
+        _lib.call("mi_sa_problem_set_node_weights", self._handle(), dq, dc, dw)
 
     def set_node_weight_groups(self, cw, c64, offset):
         """Resolution groups of a problem with node weights (include/mi_sa.h mi_sa_problem_set_node_weight_groups):
@@ -293,8 +281,7 @@ class Problem:
         cols = np.arange(self.n) if self._inv is None else self._inv
         dc = np.zeros((G, self.n_dev), dtype=np.float32)
         dc[:, cols] = cw
-        _lib.check(_lib.load().mi_sa_problem_set_node_weight_groups(self._h, int(G), _ptr(dc, C.c_float),
-                                                                    _ptr(c64, C.c_double), _ptr(offset, C.c_double)))
+        _lib.call("mi_sa_problem_set_node_weight_groups", self._handle(), int(G), dc, c64, offset)
         self.groups = int(G)
 
     def set_merge_moves(self, interval: int, proposals: Optional[int] = None, cq=None):
@@ -310,8 +297,7 @@ class Problem:
             cq_arr = np.ascontiguousarray(np.atleast_1d(np.asarray(cq, dtype=np.float64)))
             if cq_arr.shape != (self.groups,):
                 raise ValueError("cq needs one value per resolution group (%d)" % self.groups)
-        _lib.check(_lib.load().mi_sa_problem_set_merge_moves(self._h, int(interval), int(proposals),
-                                                             _ptr(cq_arr, C.c_double)))
+        _lib.call("mi_sa_problem_set_merge_moves", self._handle(), int(interval), int(proposals), cq_arr)
 
     def merges_accepted(self) -> int:
         """Merges the merge phases of the last anneal accepted (mi_sa_debug_stats word 4)."""
@@ -324,41 +310,22 @@ class Problem:
         val64 = np.ascontiguousarray(val64, dtype=np.float64)
         lin64 = None if lin64 is None else np.ascontiguousarray(lin64, dtype=np.float64)
         try:
-            _lib.check(_lib.load().mi_sa_problem_set_energy_model_f64(
-                self._h, _ptr(val64, C.c_double), None if lin64 is None else _ptr(lin64, C.c_double), float(c_pair64)))
+            _lib.call("mi_sa_problem_set_energy_model_f64", self._handle(), val64, lin64, float(c_pair64))
         except Exception:
             self.close()
             raise
 
-    # -- lifetime -------------------------------------------------------------------------------
-    def close(self):
-        if self._h is not None and self._h.value:
-            _lib.load().mi_sa_problem_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def set_option(self, key: str, value: int):
-        _lib.check(_lib.load().mi_sa_set_option(self._h, key.encode(), int(value)))
+        _lib.call("mi_sa_set_option", self._handle(), key.encode(), int(value))
 
     def debug_pace(self, words: int = 288):
         out = np.zeros(words, dtype=np.uint32)
-        _lib.check(_lib.load().mi_sa_debug_pace(self._h, _ptr(out, C.c_uint32), words))
+        _lib.call("mi_sa_debug_pace", self._handle(), out, words)
         return out
 
     def debug_stats(self, words: int = 16):
         out = np.zeros(words, dtype=np.uint64)
-        _lib.check(_lib.load().mi_sa_debug_stats(self._h, _ptr(out, C.c_uint64), words))
+        _lib.call("mi_sa_debug_stats", self._handle(), out, words)
         return out
 
     # -- the anneal -----------------------------------------------------------------------------
@@ -397,19 +364,17 @@ class Problem:
                 dev = np.zeros((num_reads, self.n_dev), dtype=self.state_dtype)
                 dev[:, self._inv] = init
                 init = dev
-        _lib.check(_lib.load().mi_sa_anneal_ex(
-            self._h, int(num_reads), C.c_uint32(int(replica_offset) & 0xFFFFFFFF), sweeps,
-            _ptr(betas, C.c_double), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            init.ctypes.data_as(C.c_void_p) if init is not None else None, int(resync_interval),
-            C.c_uint32(int(sweep_offset) & 0xFFFFFFFF), C.c_uint32(flags)))
+        _lib.call("mi_sa_anneal_ex", self._handle(), int(num_reads), C.c_uint32(int(replica_offset) & 0xFFFFFFFF), sweeps,
+                  betas, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), init, int(resync_interval),
+                  C.c_uint32(int(sweep_offset) & 0xFFFFFFFF), C.c_uint32(flags))
         self._last = (int(num_reads), sweeps)
 
     # -- parallel tempering: exchange step on the device (K6) ----------------------------------------
     def tempering_begin(self, ladder_betas, chains: int, first_replica: int, num_local: int):
         lad = np.ascontiguousarray(ladder_betas, dtype=np.float64)
         self._pt_total = len(lad) * int(chains)
-        _lib.check(_lib.load().mi_sa_tempering_begin(self._h, _ptr(lad, C.c_double), len(lad), int(chains),
-                                                     C.c_uint32(int(first_replica)), int(num_local)))
+        _lib.call("mi_sa_tempering_begin", self._handle(), lad, len(lad), int(chains), C.c_uint32(int(first_replica)),
+                  int(num_local))
 
     def tempering_exchange(self, rnd: int, seed: int, all_energies: Optional[np.ndarray] = None):
         """Neighbouring rungs of every chain exchange (Metropolis on a counter-based stream of (seed, round)).
@@ -418,24 +383,23 @@ class Problem:
         en = None if all_energies is None else np.ascontiguousarray(all_energies, dtype=np.float64)
         if en is not None and len(en) != self._pt_total:
             raise ValueError("all_energies must hold the %d energies of the run" % self._pt_total)
-        _lib.check(_lib.load().mi_sa_tempering_exchange(self._h, C.c_uint32(int(rnd) & 0xFFFFFFFF),
-                                                        C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(en, C.c_double)))
+        _lib.call("mi_sa_tempering_exchange", self._handle(), C.c_uint32(int(rnd) & 0xFFFFFFFF),
+                  C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), en)
 
     def tempering_exchange_device(self, rnd: int, seed: int, all_energies_dev):
         """The same exchange with the all-gathered energies already in HBM: ``all_energies_dev`` = a contiguous float64
         torch tensor on this problem's GPU (the output of the RCCL all-gather), read in place."""
         if all_energies_dev.numel() != self._pt_total or not all_energies_dev.is_contiguous():
             raise ValueError("all_energies_dev must hold the %d energies of the run, contiguous" % self._pt_total)
-        _lib.check(_lib.load().mi_sa_tempering_exchange_dev(self._h, C.c_uint32(int(rnd) & 0xFFFFFFFF),
-                                                            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                                            C.c_void_p(all_energies_dev.data_ptr())))
+        _lib.call("mi_sa_tempering_exchange_dev", self._handle(), C.c_uint32(int(rnd) & 0xFFFFFFFF),
+                  C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), all_energies_dev.data_ptr())
 
     def device_energies(self):
         """The energies of the last run as a float64 torch tensor that ALIASES the library's HBM buffer (no copy;
         waits for the run; valid until the next anneal on this handle): the send buffer of a GPU-to-GPU collective."""
         import torch
         d_en, R = C.c_void_p(), C.c_int(0)
-        _lib.check(_lib.load().mi_sa_device_results(self._h, None, C.byref(d_en), C.byref(R)))
+        _lib.call("mi_sa_device_results", self._handle(), None, d_en, R)
 
         class _Alias:                     # the array-interface protocol torch.as_tensor understands for device memory
             __cuda_array_interface__ = {"shape": (int(R.value),), "typestr": "<f8", "data": (int(d_en.value), False),
@@ -446,16 +410,14 @@ class Problem:
         """``(rung of every replica of the run, exchanges proposed, exchanges accepted)``."""
         rung = np.empty(self._pt_total, dtype=np.int32)
         prop, acc = C.c_uint64(0), C.c_uint64(0)
-        _lib.check(_lib.load().mi_sa_tempering_state(self._h, _ptr(rung, C.c_int32), C.byref(prop), C.byref(acc)))
+        _lib.call("mi_sa_tempering_state", self._handle(), rung, prop, acc)
         return rung.astype(np.int64), int(prop.value), int(acc.value)
 
     def sync(self):
-        _lib.check(_lib.load().mi_sa_sync(self._h))
+        _lib.call("mi_sa_sync", self._handle())
 
     def kernel_ms(self) -> float:
-        ms = C.c_float(0.0)
-        _lib.check(_lib.load().mi_sa_last_kernel_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _lib.call_ms("mi_sa_last_kernel_ms", self._handle())
 
     def label_agreement(self, groups: Optional[int] = None) -> dict:
         """ARI and NMI of every pair r < s of the last run's replicas inside each group of consecutive replicas (``groups``
@@ -471,10 +433,8 @@ class Problem:
         P = (R // G) * (R // G - 1) // 2
         ari, nmi = np.empty((G, P)), np.empty((G, P))
         S = np.empty((G, P), dtype=np.int64)
-        ms = C.c_float(0.0)
-        _lib.check(_lib.load().mi_sa_problem_label_agreement(self._h, G, _ptr(ari, C.c_double), _ptr(nmi, C.c_double),
-                                                             _ptr(S, C.c_int64), C.byref(ms)))
-        return {"ari": ari, "nmi": nmi, "pair_sum": S, "kernel_ms": float(ms.value)}
+        ms = _lib.call_ms("mi_sa_problem_label_agreement", self._handle(), G, ari, nmi, S)
+        return {"ari": ari, "nmi": nmi, "pair_sum": S, "kernel_ms": ms}
 
     def coassociation(self, groups: Optional[int] = None, ref=None, edges=None, matrix: bool = False,
                       hist: bool = True) -> dict:
@@ -506,15 +466,12 @@ class Problem:
             eu = np.ascontiguousarray(cols[eu], dtype=np.int32)
             ev = np.ascontiguousarray(cols[ev], dtype=np.int32)
         hist, rowsum, edge, counts = _coassoc_outputs(G, Rg, nd, Kref, None if eu is None else len(eu), matrix, hist)
-        ms = C.c_float(0.0)
-        _lib.check(_lib.load().mi_sa_problem_coassociation(
-            self._h, G, _ptr(dref, C.c_uint16), int(Kref or 1), _ptr(eu, C.c_int32), _ptr(ev, C.c_int32),
-            0 if eu is None else len(eu), _ptr(hist, C.c_int64), _ptr(rowsum, C.c_int64), _ptr(edge, C.c_int32),
-            _ptr(counts, C.c_int32), C.byref(ms)))
+        ms = _lib.call_ms("mi_sa_problem_coassociation", self._handle(), G, dref, int(Kref or 1), eu, ev,
+                          0 if eu is None else len(eu), hist, rowsum, edge, counts)
         if nd != n or self._inv is not None:             # device columns -> the caller's variables
             rowsum = None if rowsum is None else np.ascontiguousarray(rowsum[:, cols])
             counts = None if counts is None else np.ascontiguousarray(counts[:, cols][:, :, cols])
-        return _coassoc_result(G, Rg, hist, rowsum, edge, counts, ms.value)
+        return _coassoc_result(G, Rg, hist, rowsum, edge, counts, ms)
 
     def components(self):
         """Every cluster of every replica of the last run split into its connected components in the model's graph (the
@@ -528,7 +485,7 @@ class Problem:
         R = self._last[0]
         out = np.empty((R, self.n_dev), dtype=np.int32)
         cnt = np.empty(R, dtype=np.int32)
-        _lib.check(_lib.load().mi_sa_problem_components(self._h, _ptr(out, C.c_int32), _ptr(cnt, C.c_int32), None))
+        _lib.call("mi_sa_problem_components", self._handle(), out, cnt, None)
         if self._inv is not None:                        # device columns -> the caller's variables, numbered in their order
             out = renumber_by_first_cell(np.take(out, self._inv, axis=1))
         return out, cnt
@@ -536,20 +493,20 @@ class Problem:
     def launch_count(self) -> int:
         """Kernel launches that served the last anneal (kernel_ms() / launch_count() = mean launch time)."""
         k = C.c_int(0)
-        _lib.check(_lib.load().mi_sa_last_launch_count(self._h, C.byref(k)))
+        _lib.call("mi_sa_last_launch_count", self._handle(), k)
         return int(k.value)
 
     def kernel_name(self) -> str:
         """The kernel(s) that served the last anneal, as a profiler names them."""
         buf = C.create_string_buffer(256)
-        _lib.check(_lib.load().mi_sa_last_kernel_name(self._h, buf, 256))
+        _lib.call("mi_sa_last_kernel_name", self._handle(), buf, 256)
         return buf.value.decode()
 
     def adjacency_bytes_per_slot(self) -> int:
         """Packed adjacency bytes one wavefront fetched per 64-variable slot in the last anneal (which packing the pair
         kernel read: 6144 / 6400 / 12544 with 16-bit neighbour words, 7936 / 8448 / 16640 without); 0 for other kernels."""
         k = C.c_int(0)
-        _lib.check(_lib.load().mi_sa_last_adjacency_bytes_per_slot(self._h, C.byref(k)))
+        _lib.call("mi_sa_last_adjacency_bytes_per_slot", self._handle(), k)
         return int(k.value)
 
     def fetch(self, states: bool = True, energies: bool = True):
@@ -559,9 +516,7 @@ class Problem:
         st = np.empty((R, self.n_dev), dtype=self.state_dtype) if states else None
         en = np.empty(R, dtype=np.float64) if energies else None
         stats = np.zeros(3, dtype=np.uint64)
-        _lib.check(_lib.load().mi_sa_fetch(
-            self._h, st.ctypes.data_as(C.c_void_p) if st is not None else None,
-            _ptr(en, C.c_double), _ptr(stats, C.c_uint64)))
+        _lib.call("mi_sa_fetch", self._handle(), st, en, stats)
         info = {"proposals": int(R) * int(self._last[1]) * int(self.n),
                 "accepted": int(stats[1]), "row_bytes": int(stats[2])}
         if st is not None and self._inv is not None:
@@ -574,9 +529,7 @@ class Problem:
         en = C.c_double(0.0)
         key = C.c_uint64(0)
         st = np.empty(self.n_dev, dtype=self.state_dtype) if want_state else None
-        _lib.check(_lib.load().mi_sa_best(
-            self._h, C.byref(idx), C.byref(en), C.byref(key),
-            st.ctypes.data_as(C.c_void_p) if st is not None else None))
+        _lib.call("mi_sa_best", self._handle(), idx, en, key, st)
         if st is not None and self._inv is not None:
             st = st[self._inv]
         return int(idx.value), float(en.value), int(key.value), st
@@ -638,10 +591,9 @@ def plan_anneal(kind, rowptr, col, n, num_reads, num_cases=2, cus=0, options=Non
     col = np.ascontiguousarray(col, dtype=np.int32)
     name = C.create_string_buffer(256)
     nbytes = C.c_int(0)
-    _lib.check(_lib.load().mi_sa_plan_anneal(
-        int(kind), _ptr(rowptr, C.c_int32), _ptr(col, C.c_int32), int(n), int(num_cases), int(num_reads), int(cus),
-        (options or "").encode(), int(pair_weight_slot), int(bool(node_weights)), int(min_cluster_size), name, 256,
-        C.byref(nbytes)))
+    _lib.call("mi_sa_plan_anneal", int(kind), rowptr, col, int(n), int(num_cases), int(num_reads), int(cus),
+              (options or "").encode(), int(pair_weight_slot), int(bool(node_weights)), int(min_cluster_size), name, 256,
+              nbytes)
     return name.value.decode(), int(nbytes.value)
 
 
@@ -656,9 +608,9 @@ def plan_dense(n, num_reads, num_sweeps, resync_interval=0, per_replica=False, c
         options = ",".join("%s=%d" % (k, int(v)) for k, v in sorted(options.items()))
     name = C.create_string_buffer(256)
     launches, nbytes = C.c_int(0), C.c_uint64(0)
-    _lib.check(_lib.load().mi_sa_plan_dense(
-        int(n), int(num_reads), int(num_sweeps), int(resync_interval), C.c_uint32(2 if per_replica else 0), int(cus),
-        int(resident_waves), (options or "").encode(), name, 256, C.byref(launches), C.byref(nbytes)))
+    _lib.call("mi_sa_plan_dense", int(n), int(num_reads), int(num_sweeps), int(resync_interval),
+              C.c_uint32(2 if per_replica else 0), int(cus), int(resident_waves), (options or "").encode(), name, 256, launches,
+              nbytes)
     return name.value.decode(), int(launches.value), int(nbytes.value)
 
 
@@ -672,11 +624,8 @@ def energy_dense(Qs: np.ndarray, X: np.ndarray, offset: float = 0.0, device: int
     if X.ndim != 2 or X.shape[1] != Qs.shape[0]:
         raise ValueError("X must have shape (R, n)")
     out = np.empty(X.shape[0], dtype=np.float64)
-    ms = C.c_float(0.0)
-    _lib.check(_lib.load().mi_energy_dense_f32_ex(_ptr(Qs, C.c_float), Qs.shape[0], _ptr(X, C.c_uint8),
-                                                  X.shape[0], float(offset), _ptr(out, C.c_double),
-                                                  int(device), int(path), C.byref(ms)))
-    return (out, float(ms.value)) if return_ms else out
+    ms = _lib.call_ms("mi_energy_dense_f32_ex", Qs, Qs.shape[0], X, X.shape[0], float(offset), out, int(device), int(path))
+    return (out, ms) if return_ms else out
 
 
 def energy_dense_f64(Qs: np.ndarray, X: np.ndarray, offset: float = 0.0, device: int = 0) -> np.ndarray:
@@ -687,6 +636,5 @@ def energy_dense_f64(Qs: np.ndarray, X: np.ndarray, offset: float = 0.0, device:
     if X.ndim != 2 or Qs.ndim != 2 or Qs.shape[0] != Qs.shape[1] or X.shape[1] != Qs.shape[0]:
         raise ValueError("Qs must be n x n and X must have shape (R, n)")
     out = np.empty(X.shape[0], dtype=np.float64)
-    _lib.check(_lib.load().mi_energy_dense_f64(_ptr(Qs, C.c_double), Qs.shape[0], _ptr(X, C.c_uint8), X.shape[0],
-                                               float(offset), _ptr(out, C.c_double), int(device)))
+    _lib.call("mi_energy_dense_f64", Qs, Qs.shape[0], X, X.shape[0], float(offset), out, int(device))
     return out

@@ -10,8 +10,6 @@ is a closed form of those, evaluated here in fp64.  No n x n matrix is built unl
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -58,15 +56,9 @@ def jaccard_pass(bits: np.ndarray, labels: np.ndarray, K: int, device: int = 0, 
     sq_all, sq_in = np.empty(n), np.empty(n)
     diam, sep = np.empty(K), np.empty((K, K))
     D = np.empty((n, n), dtype=np.float32) if return_distances else None
-    ms = C.c_float(0.0)
-    f64p, f32p = C.POINTER(C.c_double), C.POINTER(C.c_float)
-    _lib.check(_lib.load().mi_jaccard_cluster_stats(
-        bits.ctypes.data_as(C.POINTER(C.c_uint64)), n, W, labels.ctypes.data_as(C.POINTER(C.c_int32)), int(K),
-        int(device), rowsum.ctypes.data_as(f64p), sq_all.ctypes.data_as(f64p), sq_in.ctypes.data_as(f64p),
-        diam.ctypes.data_as(f64p), sep.ctypes.data_as(f64p), D.ctypes.data_as(f32p) if D is not None else None,
-        C.byref(ms)))
+    ms = _lib.call_ms("mi_jaccard_cluster_stats", bits, n, W, labels, int(K), int(device), rowsum, sq_all, sq_in, diam, sep, D)
     return {"rowsum": rowsum, "sq_all": sq_all, "sq_within": sq_in, "diameter": diam, "separation.matrix": sep,
-            "distances": D, "kernel_ms": float(ms.value)}
+            "distances": D, "kernel_ms": ms}
 
 
 def cluster_stats(X, labels, device: int = 0, return_distances: bool = False) -> dict:
@@ -237,14 +229,8 @@ def label_agreement(A, B=None, groups: int = 1, device: int = 0, tables: bool = 
     ari, nmi = np.empty(shape), np.empty(shape)
     S = np.empty(shape, dtype=np.int64)
     T = np.empty(shape + (Ka, Kb), dtype=np.int32) if tables else None
-    ms = C.c_float(0.0)
-    f64p, u16p = C.POINTER(C.c_double), C.POINTER(C.c_uint16)
-    _lib.check(_lib.load().mi_label_agreement_u16(
-        La.ctypes.data_as(u16p), Ra, Lb.ctypes.data_as(u16p) if Lb is not None else None, Rb, n, Ka, Kb, mode,
-        int(groups), int(device), ari.ctypes.data_as(f64p), nmi.ctypes.data_as(f64p),
-        S.ctypes.data_as(C.POINTER(C.c_int64)), T.ctypes.data_as(C.POINTER(C.c_int32)) if T is not None else None,
-        C.byref(ms)))
-    return {"ari": ari, "nmi": nmi, "pair_sum": S, "tables": T, "kernel_ms": float(ms.value)}
+    ms = _lib.call_ms("mi_label_agreement_u16", La, Ra, Lb, Rb, n, Ka, Kb, mode, int(groups), int(device), ari, nmi, S, T)
+    return {"ari": ari, "nmi": nmi, "pair_sum": S, "tables": T, "kernel_ms": ms}
 
 
 def _against(a, b, key: str, device: int):
@@ -386,14 +372,9 @@ def coassociation(L, groups: int = 1, ref=None, edges=None, matrix: bool = False
     if edges is not None:
         eu, ev = _edge_arrays(edges, n)
     hist, rowsum, edge, counts = _coassoc_outputs(G, Rg, n, Kref, None if eu is None else len(eu), matrix, hist)
-    ms = C.c_float(0.0)
-    u16p, i32p, i64p = C.POINTER(C.c_uint16), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-    ptr = (lambda a, t: None if a is None else a.ctypes.data_as(t))
-    _lib.check(_lib.load().mi_coassociation_u16(
-        La.ctypes.data_as(u16p), R, n, K, G, ptr(Lr, u16p), int(Kref or 1), ptr(eu, i32p), ptr(ev, i32p),
-        0 if eu is None else len(eu), int(device), ptr(hist, i64p), ptr(rowsum, i64p), ptr(edge, i32p),
-        ptr(counts, i32p), C.byref(ms)))
-    return _coassoc_result(G, Rg, hist, rowsum, edge, counts, ms.value)
+    ms = _lib.call_ms("mi_coassociation_u16", La, R, n, K, G, Lr, int(Kref or 1), eu, ev, 0 if eu is None else len(eu),
+                      int(device), hist, rowsum, edge, counts)
+    return _coassoc_result(G, Rg, hist, rowsum, edge, counts, ms)
 
 
 def consensus_cdf(hist) -> np.ndarray:
@@ -533,12 +514,7 @@ def connected_components(edges_or_csr, n: int, labels=None, keep=None, device: i
     B = L.shape[0] if L is not None else (K.shape[0] if K is not None else 1)
     out = np.empty((B, n), dtype=np.int32)
     cnt = np.empty(B, dtype=np.int32)
-    i32p = C.POINTER(C.c_int32)
-    ptr = (lambda a, t: None if a is None else a.ctypes.data_as(t))
-    _lib.check(_lib.load().mi_graph_components(
-        rowptr.ctypes.data_as(i32p), col.ctypes.data_as(i32p), n, ptr(L, C.POINTER(C.c_uint16)),
-        ptr(K, C.POINTER(C.c_uint8)), int(B), int(device), 1 if force_global else 0, out.ctypes.data_as(i32p),
-        cnt.ctypes.data_as(i32p), None))
+    _lib.call("mi_graph_components", rowptr, col, n, L, K, int(B), int(device), 1 if force_global else 0, out, cnt, None)
     return out, cnt
 
 
@@ -674,14 +650,9 @@ def rank_sum_pass(X, L, K: int, device: int = 0, plain: bool = False, force_glob
     shape = (B, g, max(K, 0))
     rank2, npos = np.empty(shape, dtype=np.int64), np.empty(shape, dtype=np.int32)
     sums, tie = np.empty(shape, dtype=np.float64), np.empty(g, dtype=np.int64)
-    ms = C.c_float(0.0)
-    i64p = C.POINTER(C.c_int64)
-    _lib.check(_lib.load().mi_rank_sum_markers_f32(
-        X.ctypes.data_as(C.POINTER(C.c_float)), n, g, L.ctypes.data_as(C.POINTER(C.c_uint16)), B, K, int(device),
-        (MARKERS_SUM_PLAIN if plain else 0) | (MARKERS_GLOBAL if force_global else 0), rank2.ctypes.data_as(i64p),
-        npos.ctypes.data_as(C.POINTER(C.c_int32)), sums.ctypes.data_as(C.POINTER(C.c_double)), tie.ctypes.data_as(i64p),
-        C.byref(ms)))
-    return {"rank2": rank2, "npos": npos, "sum": sums, "tie": tie, "kernel_ms": float(ms.value)}
+    ms = _lib.call_ms("mi_rank_sum_markers_f32", X, n, g, L, B, K, int(device),
+                      (MARKERS_SUM_PLAIN if plain else 0) | (MARKERS_GLOBAL if force_global else 0), rank2, npos, sums, tie)
+    return {"rank2": rank2, "npos": npos, "sum": sums, "tie": tie, "kernel_ms": ms}
 
 
 def markers_from_stats(rank2, npos, sums, tie, sizes, n: int, plain: bool = False) -> dict:

@@ -763,9 +763,7 @@ def slot_independent_order(rowptr: np.ndarray, col: np.ndarray, slot: int = 64) 
     col = np.ascontiguousarray(col, dtype=np.int32)
     n = len(rowptr) - 1
     perm = np.empty(n, dtype=np.int64)
-    _lib.check(_lib.load().mi_sa_plan_slot_order(
-        rowptr.ctypes.data_as(C.POINTER(C.c_int32)), col.ctypes.data_as(C.POINTER(C.c_int32)), int(n), int(slot),
-        perm.ctypes.data_as(C.POINTER(C.c_int64))))
+    _lib.call("mi_sa_plan_slot_order", rowptr, col, int(n), int(slot), perm)
     return perm
 
 
@@ -785,9 +783,7 @@ def padded_slot_layout(rowptr: np.ndarray, col: np.ndarray, slot: int = 64, max_
         max_slots = 3 * s0 + 4
     pos = np.empty(n, dtype=np.int64)
     slots, clashes = C.c_int(0), C.c_int(0)
-    _lib.check(_lib.load().mi_sa_plan_slot_layout(
-        rowptr.ctypes.data_as(C.POINTER(C.c_int32)), col.ctypes.data_as(C.POINTER(C.c_int32)), int(n), int(slot),
-        int(max_slots), pos.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(slots), C.byref(clashes)))
+    _lib.call("mi_sa_plan_slot_layout", rowptr, col, int(n), int(slot), int(max_slots), pos, slots, clashes)
     return pos, int(slots.value), int(clashes.value)
 
 

@@ -57,14 +57,6 @@ MAX_COVARIATES = 8         # MI_PREP_MAX_DESIGN_COLS - 1 (the intercept)
 
 MAX_NNZ = 2 ** 31 - 1      # MI_PREP_MAX_NNZ
 
-_f32p, _f64p, _i32p, _i64p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-_u8p = C.POINTER(C.c_uint8)
-
-
-def _p(a, t):
-    return a.ctypes.data_as(t)
-
-
 def is_sparse(X) -> bool:
     """Is ``X`` a ``scipy.sparse`` matrix or array (scipy is imported only if the caller has done so)"""
     sp = sys.modules.get("scipy.sparse")
@@ -90,10 +82,11 @@ def canonical_csr(X):
             np.ascontiguousarray(A.data, dtype=np.float32), (n, g))
 
 
-class ExpressionMatrix:
+class ExpressionMatrix(_lib.Handle):
     """A cells x genes count matrix resident on the GPU (uploaded once), with one method per pass of include/mi_prep.h.
     ``X`` is a dense array or a ``scipy.sparse`` matrix / array (``sparse`` tells which; ``nnz``: its stored entries, ``n * g``
     for a dense one).  A context manager; ``timing`` collects the device milliseconds of every pass that has run."""
+    _destroy = "mi_prep_destroy"
 
     def __init__(self, X, device: int = 0):
         self.sparse = is_sparse(X)
@@ -112,16 +105,14 @@ class ExpressionMatrix:
         self.timing = {}
         self._stats = {}
         self.coef_q = self.resid_mean = self.resid_var = self.flat = self.regression = None     # of select_regressed
-        self._h = None
         self._lib = _lib.load()
         h = C.c_void_p()
         if self.sparse:
             t0 = time.perf_counter()
-            _lib.check(self._lib.mi_prep_create_csr_f32(_p(self._indptr, _i64p), _p(self._indices, _i32p), _p(data, _f32p),
-                                                        self.n, self.g, self.device, C.byref(h)))
+            _lib.call("mi_prep_create_csr_f32", self._indptr, self._indices, data, self.n, self.g, self.device, h)
             self.timing["create_s"] = time.perf_counter() - t0   # the checks, the transpose (host) and the upload
         else:
-            _lib.check(self._lib.mi_prep_create_f32(_p(X, _f32p), self.n, self.g, self.device, C.byref(h)))
+            _lib.call("mi_prep_create_f32", X, self.n, self.g, self.device, h)
         self._h = h
 
     @classmethod
@@ -134,11 +125,11 @@ class ExpressionMatrix:
         m.coef_q = m.resid_mean = m.resid_var = m.flat = m.regression = None
         try:
             n, g, sparse, nnz = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
-            _lib.check(lib.mi_prep_info(h, C.byref(n), C.byref(g), C.byref(nnz), C.byref(sparse), None))
+            _lib.call("mi_prep_info", h, n, g, nnz, sparse, None)
             m.n, m.g, m.nnz, m.sparse = int(n.value), int(g.value), int(nnz.value), bool(sparse.value)
             if m.sparse:
                 m._indptr, m._indices = np.empty(m.n + 1, dtype=np.int64), np.empty(m.nnz, dtype=np.int32)
-                _lib.check(lib.mi_prep_fetch_csr(h, _p(m._indptr, _i64p), _p(m._indices, _i32p), None))
+                _lib.call("mi_prep_fetch_csr", h, m._indptr, m._indices, None)
         except Exception:
             m.close()
             raise
@@ -147,39 +138,16 @@ class ExpressionMatrix:
     def device_bytes(self) -> int:
         """Bytes the handle holds resident on the device now."""
         out = C.c_int64(0)
-        _lib.check(self._lib.mi_prep_info(self._handle(), None, None, None, None, C.byref(out)))
+        _lib.call("mi_prep_info", self._handle(), None, None, None, None, out)
         return int(out.value)
-
-    def close(self):
-        if self._h is not None:
-            self._lib.mi_prep_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if self._h is None:
-            raise ValueError("the ExpressionMatrix is closed")
-        return self._h
 
     def normalize(self, scale_factor: float = 1e4):
         """Seurat's ``LogNormalize``: ``log1p(x * scale_factor / total of the cell)``, kept on the device.  A cell without
         counts keeps zeros (Seurat returns NaN there)."""
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_normalize(self._handle(), float(scale_factor), C.byref(ms)))
+        ms = _lib.call_ms("mi_prep_normalize", self._handle(), float(scale_factor))
         self._stats.pop(1, None)
         self.normalized = True
-        self.timing["normalize_ms"] = float(ms.value)
+        self.timing["normalize_ms"] = ms
         return self
 
     def fetch_normalized(self):
@@ -188,10 +156,10 @@ class ExpressionMatrix:
         if self.sparse:
             from scipy.sparse import csr_matrix
             data = np.empty(self.nnz, dtype=np.float32)
-            _lib.check(self._lib.mi_prep_fetch_normalized_csr(self._handle(), _p(data, _f32p)))
+            _lib.call("mi_prep_fetch_normalized_csr", self._handle(), data)
             return csr_matrix((data, self._indices, self._indptr), shape=(self.n, self.g))
         out = np.empty((self.n, self.g), dtype=np.float32)
-        _lib.check(self._lib.mi_prep_fetch_normalized(self._handle(), _p(out, _f32p)))
+        _lib.call("mi_prep_fetch_normalized", self._handle(), out)
         return out
 
     def fetch_counts(self):
@@ -200,10 +168,10 @@ class ExpressionMatrix:
         if self.sparse:
             from scipy.sparse import csr_matrix
             data = np.empty(self.nnz, dtype=np.float32)
-            _lib.check(self._lib.mi_prep_fetch_csr(self._handle(), None, None, _p(data, _f32p)))
+            _lib.call("mi_prep_fetch_csr", self._handle(), None, None, data)
             return csr_matrix((data, self._indices, self._indptr), shape=(self.n, self.g))
         out = np.empty((self.n, self.g), dtype=np.float32)
-        _lib.check(self._lib.mi_prep_fetch_counts(self._handle(), _p(out, _f32p)))
+        _lib.call("mi_prep_fetch_counts", self._handle(), out)
         return out
 
     def gene_stats(self, which: str = "counts"):
@@ -215,10 +183,7 @@ class ExpressionMatrix:
         if w not in self._stats:
             mean, var = np.empty(self.g), np.empty(self.g)
             nnz = np.empty(self.g, dtype=np.int32)
-            ms = C.c_float(0.0)
-            _lib.check(self._lib.mi_prep_gene_stats(self._handle(), w, _p(mean, _f64p), _p(var, _f64p), _p(nnz, _i32p),
-                                                    C.byref(ms)))
-            self.timing["gene_stats_%s_ms" % which] = float(ms.value)
+            self.timing["gene_stats_%s_ms" % which] = _lib.call_ms("mi_prep_gene_stats", self._handle(), w, mean, var, nnz)
             self._stats[w] = (mean, var, nnz)
         return self._stats[w]
 
@@ -230,31 +195,22 @@ class ExpressionMatrix:
         if mean.shape != (self.g,) or sd.shape != (self.g,):
             raise ValueError("mean and sd must have one entry per gene (%d)" % self.g)
         out = np.empty(self.g)
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_clipped_variance(self._handle(), _p(mean, _f64p), _p(sd, _f64p), float(clip),
-                                                      _p(out, _f64p), C.byref(ms)))
-        self.timing["clipped_variance_ms"] = float(ms.value)
+        self.timing["clipped_variance_ms"] = _lib.call_ms("mi_prep_clipped_variance", self._handle(), mean, sd, float(clip),
+                                                          out)
         return out
 
     def select(self, genes, mu, sigma, clip: float = 10.0):
         """Materialises ``Z[:, c] = fminf((y[:, genes[c]] - f32(mu[c])) * f32(1 / sigma[c]), f32(clip))`` (0 where
         ``sigma[c] == 0``) on the device; :meth:`fetch_scaled`, :meth:`gram` and :meth:`project` read it."""
-        genes = np.asarray(genes)
-        if genes.ndim != 1 or genes.dtype.kind not in "iu":
-            raise ValueError("genes must be a 1-d integer array")
-        if len(genes) and (genes.min() < -2 ** 31 or genes.max() >= 2 ** 31):
-            raise ValueError("gene index out of range")
-        genes = np.ascontiguousarray(genes, dtype=np.int32)
+        genes = self._index_array(genes, "genes", "gene index out of range")
         mu = np.ascontiguousarray(mu, dtype=np.float64)
         sigma = np.ascontiguousarray(sigma, dtype=np.float64)
         if mu.shape != genes.shape or sigma.shape != genes.shape:
             raise ValueError("mu and sigma must have one entry per chosen gene")
-        ms = C.c_float(0.0)
         self.h = 0
-        _lib.check(self._lib.mi_prep_select(self._handle(), _p(genes, _i32p), len(genes), _p(mu, _f64p), _p(sigma, _f64p),
-                                            float(clip), C.byref(ms)))
+        ms = _lib.call_ms("mi_prep_select", self._handle(), genes, len(genes), mu, sigma, float(clip))
         self.h = len(genes)
-        self.timing["select_ms"] = float(ms.value)
+        self.timing["select_ms"] = ms
         return self
 
     def cell_qc(self, gene_mask=None):
@@ -269,11 +225,7 @@ class ExpressionMatrix:
             mask = np.ascontiguousarray(mask, dtype=np.uint8)
         n_count, n_feature = np.empty(self.n), np.empty(self.n, dtype=np.int32)
         subset = None if mask is None else np.empty(self.n)
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_cell_qc(self._handle(), None if mask is None else _p(mask, _u8p), _p(n_count, _f64p),
-                                             _p(n_feature, _i32p), None if mask is None else _p(subset, _f64p),
-                                             C.byref(ms)))
-        self.timing["qc_ms"] = float(ms.value)
+        self.timing["qc_ms"] = _lib.call_ms("mi_prep_cell_qc", self._handle(), mask, n_count, n_feature, subset)
         return n_count, n_feature, subset
 
     def rank_sum_pass(self, L, K: int, which: str = "normalized", plain: bool = False, force_global: bool = False,
@@ -301,12 +253,9 @@ class ExpressionMatrix:
         rank2, npos = np.empty(shape, dtype=np.int64), np.empty(shape, dtype=np.int32)
         sums, tie = np.empty(shape, dtype=np.float64), np.empty(self.g, dtype=np.int64)
         flags = (1 if plain else 0) | (2 if force_global else 0) | {None: 0, "inplace": 4, "permute": 8}[gather]
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_rank_sum_markers(h, int(which == "normalized"), _p(L, C.POINTER(C.c_uint16)), B, K, flags,
-                                                      _p(rank2, _i64p), _p(npos, _i32p), _p(sums, _f64p), _p(tie, _i64p),
-                                                      C.byref(ms)))
-        self.timing["markers_ms"] = float(ms.value)
-        return {"rank2": rank2, "npos": npos, "sum": sums, "tie": tie, "kernel_ms": float(ms.value)}
+        ms = _lib.call_ms("mi_prep_rank_sum_markers", h, int(which == "normalized"), L, B, K, flags, rank2, npos, sums, tie)
+        self.timing["markers_ms"] = ms
+        return {"rank2": rank2, "npos": npos, "sum": sums, "tie": tie, "kernel_ms": ms}
 
     def select_regressed(self, genes, Q, clip: float = 10.0):
         """:meth:`select` on the residuals of a linear model: with ``y`` the chosen column of the normalised matrix and
@@ -314,43 +263,33 @@ class ExpressionMatrix:
         ``Z[:, c] = f32(min((r - mean(r)) / sd(r), clip))`` in fp64 with one rounding, 0 for a flat column
         (``sum (r - mean)^2 <= 1e-16 sum y^2``: an all-zero gene, a constant gene, a gene in the span of the design).
         Stores ``coef_q`` (q, h: ``Q^T y``), ``resid_mean``, ``resid_var`` and ``flat`` (h each) on the handle."""
-        genes = np.asarray(genes)
-        if genes.ndim != 1 or genes.dtype.kind not in "iu":
-            raise ValueError("genes must be a 1-d integer array")
-        if len(genes) and (genes.min() < -2 ** 31 or genes.max() >= 2 ** 31):
-            raise ValueError("gene index out of range")
-        genes = np.ascontiguousarray(genes, dtype=np.int32)
+        genes = self._index_array(genes, "genes", "gene index out of range")
         Q = np.ascontiguousarray(Q, dtype=np.float64)
         if Q.ndim != 2 or Q.shape[0] != self.n:
             raise ValueError("Q must be (n, q) with n = %d (got shape %s)" % (self.n, Q.shape))
         h, q = len(genes), Q.shape[1]
         coef, mean, var = np.empty((max(q, 1), max(h, 1))), np.empty(max(h, 1)), np.empty(max(h, 1))
         flat = np.empty(max(h, 1), dtype=np.uint8)
-        ms = C.c_float(0.0)
         self.h = 0
-        _lib.check(self._lib.mi_prep_select_regressed(self._handle(), _p(genes, _i32p), h, _p(Q, _f64p), q, float(clip),
-                                                      _p(coef, _f64p), _p(mean, _f64p), _p(var, _f64p), _p(flat, _u8p),
-                                                      C.byref(ms)))
+        ms = _lib.call_ms("mi_prep_select_regressed", self._handle(), genes, h, Q, q, float(clip), coef, mean, var, flat)
         self.h = h
         self.coef_q, self.resid_mean, self.resid_var, self.flat = coef, mean, var, flat.astype(bool)
-        self.timing["regress_ms"] = float(ms.value)
+        self.timing["regress_ms"] = ms
         return self
 
     def gene_log1p_sum(self) -> np.ndarray:
         """``sum_i log1p(x_ij)`` per gene of the counts, fp64 (``expm1`` of it over n is sctransform's geometric mean)."""
         out = np.empty(self.g)
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_gene_log1p_sum(self._handle(), _p(out, _f64p), C.byref(ms)))
-        self.timing["gene_log1p_ms"] = float(ms.value)
+        self.timing["gene_log1p_ms"] = _lib.call_ms("mi_prep_gene_log1p_sum", self._handle(), out)
         return out
 
     @staticmethod
-    def _index_array(idx, what):
+    def _index_array(idx, what, out_of_range=None):
         idx = np.asarray(idx)
         if idx.ndim != 1 or idx.dtype.kind not in "iu":
             raise ValueError("%s must be a 1-d integer array" % what)
         if len(idx) and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
-            raise ValueError("%s: index out of range" % what)
+            raise ValueError(out_of_range or "%s: index out of range" % what)
         return np.ascontiguousarray(idx, dtype=np.int32)
 
     def nb_fit(self, cells, genes, log_umi) -> "Result":
@@ -367,11 +306,8 @@ class ExpressionMatrix:
         k = max(len(genes), 1)
         f = [np.empty(k) for _ in range(6)]
         it, conv, pois = np.empty(k, dtype=np.int32), np.empty(k, dtype=np.uint8), np.empty(k, dtype=np.uint8)
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_nb_fit(self._handle(), _p(cells, _i32p), len(cells), _p(genes, _i32p), len(genes),
-                                            _p(log_umi, _f64p), *[_p(a, _f64p) for a in f], _p(it, _i32p), _p(conv, _u8p),
-                                            _p(pois, _u8p), C.byref(ms)))
-        self.timing["nb_fit_ms"] = float(ms.value)
+        self.timing["nb_fit_ms"] = _lib.call_ms("mi_prep_nb_fit", self._handle(), cells, len(cells), genes, len(genes), log_umi,
+                                                *f, it, conv, pois)
         total = 0.0
         for v in log_umi.tolist():                               # (the entry's mean: the sum in this order)
             total += v
@@ -397,11 +333,8 @@ class ExpressionMatrix:
         clip = math.sqrt(self.n) if clip is None else float(clip)
         k = max(len(genes), 1)
         mean, var = np.empty(k), np.empty(k)
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_sct_residual_moments(self._handle(), _p(genes, _i32p), len(genes), _p(par[0], _f64p),
-                                                          _p(par[1], _f64p), _p(par[2], _f64p), _p(log_umi, _f64p), clip,
-                                                          _p(mean, _f64p), _p(var, _f64p), C.byref(ms)))
-        self.timing["sct_moments_ms"] = float(ms.value)
+        self.timing["sct_moments_ms"] = _lib.call_ms("mi_prep_sct_residual_moments", self._handle(), genes, len(genes), par[0],
+                                                     par[1], par[2], log_umi, clip, mean, var)
         return mean, var
 
     def sct_correct(self, genes, b0, b1, alpha, log_umi, log_umi_ref: float) -> "ExpressionMatrix":
@@ -414,11 +347,9 @@ class ExpressionMatrix:
         has its own structure.  This handle is not modified and may be closed first; the caller closes the result.
         Records ``timing["sct_correct_ms"]`` here."""
         genes, par, log_umi = self._nb_parameters(genes, b0, b1, alpha, log_umi)
-        out, ms = C.c_void_p(), C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_sct_correct(self._handle(), _p(genes, _i32p), len(genes), _p(par[0], _f64p),
-                                                 _p(par[1], _f64p), _p(par[2], _f64p), _p(log_umi, _f64p), float(log_umi_ref),
-                                                 C.byref(out), C.byref(ms)))
-        self.timing["sct_correct_ms"] = float(ms.value)
+        out = C.c_void_p()
+        self.timing["sct_correct_ms"] = _lib.call_ms("mi_prep_sct_correct", self._handle(), genes, len(genes), par[0], par[1],
+                                                     par[2], log_umi, float(log_umi_ref), out)
         return ExpressionMatrix._adopt(self._lib, out, self.device)
 
     def select_pearson(self, genes, b0, b1, alpha, log_umi, Q=None, clip: Optional[float] = None, center: bool = True):
@@ -432,14 +363,12 @@ class ExpressionMatrix:
         if not center:
             if Q is not None:
                 raise ValueError("center=False takes no Q")
-            ms = C.c_float(0.0)
             self.h = 0
-            _lib.check(self._lib.mi_prep_sct_select(self._handle(), _p(genes, _i32p), len(genes), _p(par[0], _f64p),
-                                                    _p(par[1], _f64p), _p(par[2], _f64p), _p(log_umi, _f64p), clip, None, 0,
-                                                    None, None, None, None, C.byref(ms)))
+            ms = _lib.call_ms("mi_prep_sct_select", self._handle(), genes, len(genes), par[0], par[1], par[2], log_umi, clip,
+                              None, 0, None, None, None, None)
             self.h = len(genes)
             self.coef_q = self.resid_mean = self.resid_var = self.flat = None
-            self.timing["sct_select_ms"] = float(ms.value)
+            self.timing["sct_select_ms"] = ms
             return self
         Q = np.full((self.n, 1), 1.0 / math.sqrt(self.n)) if Q is None else np.ascontiguousarray(Q, dtype=np.float64)
         if Q.ndim != 2 or Q.shape[0] != self.n:
@@ -447,27 +376,23 @@ class ExpressionMatrix:
         h, q = len(genes), Q.shape[1]
         coef, mean, var = np.empty((max(q, 1), max(h, 1))), np.empty(max(h, 1)), np.empty(max(h, 1))
         flat = np.empty(max(h, 1), dtype=np.uint8)
-        ms = C.c_float(0.0)
         self.h = 0
-        _lib.check(self._lib.mi_prep_sct_select(self._handle(), _p(genes, _i32p), h, _p(par[0], _f64p), _p(par[1], _f64p),
-                                                _p(par[2], _f64p), _p(log_umi, _f64p), clip, _p(Q, _f64p), q,
-                                                _p(coef, _f64p), _p(mean, _f64p), _p(var, _f64p), _p(flat, _u8p), C.byref(ms)))
+        ms = _lib.call_ms("mi_prep_sct_select", self._handle(), genes, h, par[0], par[1], par[2], log_umi, clip, Q, q, coef,
+                          mean, var, flat)
         self.h = h
         self.coef_q, self.resid_mean, self.resid_var, self.flat = coef, mean, var, flat.astype(bool)
-        self.timing["sct_select_ms"] = float(ms.value)
+        self.timing["sct_select_ms"] = ms
         return self
 
     def fetch_scaled(self) -> np.ndarray:
         out = np.empty((self.n, max(self.h, 1)), dtype=np.float32)
-        _lib.check(self._lib.mi_prep_fetch_scaled(self._handle(), _p(out, _f32p)))
+        _lib.call("mi_prep_fetch_scaled", self._handle(), out)
         return out
 
     def gram(self) -> np.ndarray:
         """``Z^T Z`` (h x h, fp64; not divided by n - 1): exactly symmetric and identical between runs."""
         out = np.empty((max(self.h, 1),) * 2)
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_gram(self._handle(), _p(out, _f64p), C.byref(ms)))
-        self.timing["gram_ms"] = float(ms.value)
+        self.timing["gram_ms"] = _lib.call_ms("mi_prep_gram", self._handle(), out)
         return out
 
     def project(self, V) -> np.ndarray:
@@ -476,9 +401,7 @@ class ExpressionMatrix:
         if V.ndim != 2 or (self.h and V.shape[0] != self.h):
             raise ValueError("V must be (h, p) with h = %d (got shape %s)" % (self.h, V.shape))
         out = np.empty((self.n, V.shape[1]), dtype=np.float32)
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_prep_project(self._handle(), _p(V, _f32p), V.shape[1], _p(out, _f32p), C.byref(ms)))
-        self.timing["project_ms"] = float(ms.value)
+        self.timing["project_ms"] = _lib.call_ms("mi_prep_project", self._handle(), V, V.shape[1], out)
         return out
 
 

@@ -104,7 +104,6 @@ def build_snn(X: np.ndarray, k: int, prune: float = 0.0, ord: Optional[int] = No
     if X.ndim != 2:
         raise ValueError("X must be (n, dim)")
     n, dim = X.shape
-    lib = _lib.load()
     h = C.c_void_p()
     if enhance not in (None, "mutual", "sum"):
         raise ValueError("enhance must be None, 'mutual' or 'sum'")
@@ -114,29 +113,23 @@ def build_snn(X: np.ndarray, k: int, prune: float = 0.0, ord: Optional[int] = No
     if round_digits is not None:
         if flags or ord2:
             raise ValueError("the rounding variant is the notebook's plain pipeline: symmetric trim, no enhancement")
-        _lib.check(lib.mi_snn_build_rounded_f32(X.ctypes.data_as(C.POINTER(C.c_float)), n, dim, int(k), float(prune),
-                                                int(ord or 0), int(round_digits), float(negative_below or 0.0),
-                                                int(device), C.byref(h)))
+        _lib.call("mi_snn_build_rounded_f32", X, n, dim, int(k), float(prune), int(ord or 0), int(round_digits),
+                  float(negative_below or 0.0), int(device), h)
     else:
-        _lib.check(lib.mi_snn_build_ex_f32(X.ctypes.data_as(C.POINTER(C.c_float)), n, dim, int(k), float(prune),
-                                           int(ord or 0), C.c_uint32(flags), float(mutual_bonus), int(ord2 or 0),
-                                           int(device), C.byref(h)))
-    try:
+        _lib.call("mi_snn_build_ex_f32", X, n, dim, int(k), float(prune), int(ord or 0), C.c_uint32(flags), float(mutual_bonus),
+                  int(ord2 or 0), int(device), h)
+    with _lib.Handle(h, "mi_snn_destroy"):
         nnz = C.c_int64(0)
-        _lib.check(lib.mi_snn_info(h, None, None, C.byref(nnz), None))
+        _lib.call("mi_snn_info", h, None, None, nnz, None)
         nn = np.empty((n, int(k)), dtype=np.int32)
         rowptr = np.empty(n + 1, dtype=np.int64)
         col = np.empty(int(nnz.value), dtype=np.int32)
         shared = np.empty(int(nnz.value), dtype=np.int32)
         code = np.zeros(int(nnz.value), dtype=np.uint8)
-        i32p = C.POINTER(C.c_int32)
-        _lib.check(lib.mi_snn_fetch(h, nn.ctypes.data_as(i32p), rowptr.ctypes.data_as(C.POINTER(C.c_int64)),
-                                    col.ctypes.data_as(i32p), shared.ctypes.data_as(i32p)))
-        _lib.check(lib.mi_snn_fetch_codes(h, code.ctypes.data_as(C.POINTER(C.c_uint8))))
+        _lib.call("mi_snn_fetch", h, nn, rowptr, col, shared)
+        _lib.call("mi_snn_fetch_codes", h, code)
         t = [C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)]
-        _lib.check(lib.mi_snn_kernel_ms(h, C.byref(t[0]), C.byref(t[1]), C.byref(t[2])))
-    finally:
-        lib.mi_snn_destroy(h)
+        _lib.call("mi_snn_kernel_ms", h, t[0], t[1], t[2])
     return SnnGraph(n, k, nn, rowptr, col, shared,
                     {"knn_ms": t[0].value, "snn_ms": t[1].value, "trim_ms": t[2].value}, code=code, bonus=mutual_bonus,
                     symmetric=bool(symmetric) or enhance == "sum", round_digits=round_digits, negative_value=negative_value)

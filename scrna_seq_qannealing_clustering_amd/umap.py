@@ -30,16 +30,9 @@ METRICS = {"euclidean": 0, "cosine": 1}                      # MI_UMAP_EUCLIDEAN
 MAX_EPOCHS = 10000                                           # MI_UMAP_MAX_EPOCHS
 MAX_NEGATIVE = 16                                            # MI_UMAP_MAX_NEGATIVE
 
-_f32p, _f64p, _i32p, _i64p = (C.POINTER(t) for t in (C.c_float, C.c_double, C.c_int32, C.c_int64))
-
-
 class UmapResult(Result):
     """``coords`` (n x c f32), ``nn``, ``dist``, ``rho``, ``sigma``, the fuzzy graph as ``rowptr`` / ``col`` / ``weights``,
     ``a``, ``b``, ``n_epochs`` and ``timing`` (kernel ms per stage, host ms)."""
-
-
-def _p(a, t):
-    return a.ctypes.data_as(t)
 
 
 # ---- host side, fp64 ----------------------------------------------------------------------------------------------------------
@@ -181,82 +174,53 @@ def _check_init(init, X, n, c):
 
 # ---- device passes -------------------------------------------------------------------------------------------------------------
 
-class FuzzyGraph:
+class FuzzyGraph(_lib.Handle):
     """The handle of include/mi_umap.h: U1 on construction, then :meth:`smooth` and :meth:`union`.  A context manager;
     ``timing`` collects the device milliseconds of every pass that has run."""
+    _destroy = "mi_umap_destroy"
 
     def __init__(self, X, n_neighbors: int, metric: str = "euclidean", device: int = 0):
         X, k = _check_points(X, n_neighbors, metric)
         self.n, self.dim, self.k = X.shape[0], X.shape[1], k
         self.metric, self.device = metric, int(device)
         self.timing = {}
-        self._lib = _lib.load()
-        self._h = None
-        h, ms = C.c_void_p(), C.c_float(0.0)
-        _lib.check(self._lib.mi_umap_knn_f32(_p(X, _f32p), self.n, self.dim, k, METRICS[metric], self.device, C.byref(h),
-                                             C.byref(ms)))
+        h = C.c_void_p()
+        self.timing["knn_ms"] = _lib.call_ms("mi_umap_knn_f32", X, self.n, self.dim, k, METRICS[metric], self.device, h)
         self._h = h
-        self.timing["knn_ms"] = float(ms.value)
-
-    def close(self):
-        if self._h is not None:
-            self._lib.mi_umap_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if self._h is None:
-            raise ValueError("the FuzzyGraph is closed")
-        return self._h
 
     def fetch_knn(self):
         """``(nn, dist)``: n x k int32 indices as :func:`snn.build_snn` returns them, n x k f32 distances."""
         nn = np.empty((self.n, self.k), dtype=np.int32)
         dist = np.empty((self.n, self.k), dtype=np.float32)
-        _lib.check(self._lib.mi_umap_fetch_knn(self._handle(), _p(nn, _i32p), _p(dist, _f32p)))
+        _lib.call("mi_umap_fetch_knn", self._handle(), nn, dist)
         return nn, dist
 
     def smooth(self):
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_umap_smooth(self._handle(), C.byref(ms)))
-        self.timing["smooth_ms"] = float(ms.value)
+        self.timing["smooth_ms"] = _lib.call_ms("mi_umap_smooth", self._handle())
         return self
 
     def fetch_smooth(self):
         """``(rho, sigma)``, fp64."""
         rho, sigma = np.empty(self.n), np.empty(self.n)
-        _lib.check(self._lib.mi_umap_fetch_smooth(self._handle(), _p(rho, _f64p), _p(sigma, _f64p)))
+        _lib.call("mi_umap_fetch_smooth", self._handle(), rho, sigma)
         return rho, sigma
 
     def union(self):
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.mi_umap_union(self._handle(), C.byref(ms)))
-        self.timing["union_ms"] = float(ms.value)
+        self.timing["union_ms"] = _lib.call_ms("mi_umap_union", self._handle())
         return self
 
     def info(self) -> dict:
         nnz, deg, wmax = C.c_int64(0), C.c_int(0), C.c_float(0.0)
-        _lib.check(self._lib.mi_umap_info(self._handle(), None, None, C.byref(nnz), C.byref(deg), C.byref(wmax)))
+        _lib.call("mi_umap_info", self._handle(), None, None, nnz, deg, wmax)
         return {"nnz": int(nnz.value), "max_degree": int(deg.value), "w_max": float(wmax.value)}
 
     def fetch_graph(self):
         """``(rowptr, col, weights)``: the symmetric CSR (int64, int32, f32), rows ascending by column."""
         rowptr = np.empty(self.n + 1, dtype=np.int64)
-        _lib.check(self._lib.mi_umap_fetch_graph(self._handle(), _p(rowptr, _i64p), None, None))
+        _lib.call("mi_umap_fetch_graph", self._handle(), rowptr, None, None)
         col = np.empty(int(rowptr[-1]), dtype=np.int32)
         w = np.empty(int(rowptr[-1]), dtype=np.float32)
-        _lib.check(self._lib.mi_umap_fetch_graph(self._handle(), None, _p(col, _i32p), _p(w, _f32p)))
+        _lib.call("mi_umap_fetch_graph", self._handle(), None, col, w)
         return rowptr, col, w
 
 
@@ -307,11 +271,9 @@ def layout(rowptr, col, w, init, a: float, b: float, n_epochs: int = 500, learni
         raise ValueError("a and b must be finite")
     T, lr, neg, seed = _check_layout_args(n_epochs, learning_rate, negative_sample_rate, seed)
     out = np.empty_like(Y0)
-    ms = C.c_float(0.0)
-    _lib.check(_lib.load().mi_umap_layout_f32(n, Y0.shape[1], _p(rowptr, _i64p), _p(col, _i32p), _p(w, _f32p),
-                                              _p(Y0, _f32p), a, b, lr, T, neg, C.c_uint64(seed), int(device),
-                                              _p(out, _f32p), C.byref(ms)))
-    return (out, float(ms.value)) if return_ms else out
+    ms = _lib.call_ms("mi_umap_layout_f32", n, Y0.shape[1], rowptr, col, w, Y0, a, b, lr, T, neg, C.c_uint64(seed), int(device),
+                      out)
+    return (out, ms) if return_ms else out
 
 
 def run_umap(X, n_neighbors: int = 30, n_components: int = 2, metric: str = "cosine", min_dist: float = 0.3,
