@@ -21,12 +21,25 @@
  *                      combined as 16384 hh + 128 (hl + lh) + ll in int64.  Exact.
  *   k_annot_scores     one workgroup per cell: rho per sample in fp64 from the integers, the 0.8 quantile per label, the argmax.
  *   k_annot_fine_tune  one workgroup per cell: the loop of DESIGN.md section 5c on the genes G' of the labels still in use.
+ *
+ * The test cells may also come from a resident mi_prep_matrix (include/mi_prep.h), dense or sparse, with no n x g host
+ * traffic: mi_annot_score_matrix gathers a row range of the handle on the marker genes into the chunk, and
+ * mi_annot_score_clusters (SingleR's clusters = mode) fills the chunk with one averaged profile per cluster.
+ *   k_annot_gather_dense  chunk[i][s] = V[(row0 + i) g + cols[s]], 64-bit element indices.
+ *   k_annot_gather_csr    one workgroup per cell: m zeros in LDS, the cell's stored entries whose gene has a slot written
+ *                         over their slot, one coalesced store of the row.
+ *   k_annot_means<Src>    one wavefront per (marker gene, block of 64 clusters), lane = cluster: the gene's entries in
+ *                         ascending cell order (a dense column, or the stored entries of the transpose), each added in fp64 by
+ *                         the lane whose cluster owns the cell; mean = (float)(sum / size).
+ * Everything after the gather is the chain above on the chunk.
  * No floating-point atomics; two calls return identical bits.
  */
 #ifndef MI_ANNOT_H
 #define MI_ANNOT_H
 
 #include <stdint.h>
+
+#include "mi_prep.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -54,15 +67,45 @@ int mi_annot_destroy(mi_annot *h);
  * out_first n_c (argmax of the scores, lowest label on ties); out_kernel_ms: 3 floats, the ranking, cross and score
  * kernels.  MI_EINVAL for NULL h or X, n_c < 1, a NaN or infinity in X; MI_EUNSUPPORTED for n_c > MI_ANNOT_MAX_CHUNK.
  * Every call with a handle first drops the chunk of the call before: after a call that was refused or that failed, no chunk
- * is resident, and mi_annot_fine_tune returns MI_ESTATE until a later mi_annot_score succeeds. */
+ * is resident, and mi_annot_fine_tune returns MI_ESTATE until a later mi_annot_score* call succeeds. */
 int mi_annot_score(mi_annot *h, const float *X, int n_c, int64_t *out_sab, int64_t *out_sa2, int64_t *out_sb2,
                    double *out_scores, int32_t *out_first, float *out_kernel_ms);
 
 /* The fine-tuning loop on the resident chunk.  Outputs, n_c entries each, nullable: out_labels, out_best / out_next (the
  * largest and second-largest of the last scores computed; -inf for out_next when L = 1), out_iterations.  MI_ESTATE when
- * no chunk is resident: before the first mi_annot_score, and after one that was refused or that failed. */
+ * no chunk is resident: before the first mi_annot_score* call, and after one that was refused or that failed. */
 int mi_annot_fine_tune(mi_annot *h, int32_t *out_labels, double *out_best, double *out_next, int32_t *out_iterations,
                        float *out_kernel_ms);
+
+/* mi_annot_score on rows [row0, row0 + n_c) of a resident expression handle, restricted to the genes `cols` (m indices in
+ * [0, g), any order, no repeats: the handle's positions of the annotator's m marker genes); which: 0 the uploaded values,
+ * 1 the output of mi_prep_normalize (MI_PREP_MARKERS_COUNTS / _NORMALIZED).  The chunk is gathered on the device and stays
+ * resident for mi_annot_fine_tune; the outputs are those of mi_annot_score on the densified slice, bit for bit (a stored
+ * zero of a sparse handle is a zero).  out_kernel_ms: 4 floats, the gather, ranking, cross and score kernels.
+ * The checks, all before any device work and in this order: NULL h (MI_EINVAL; from here on no chunk is resident until a
+ * call succeeds); NULL M or cols; which outside {0, 1}; M on another device than h; row0 < 0, n_c < 1 or row0 + n_c > n
+ * (all MI_EINVAL); n_c > MI_ANNOT_MAX_CHUNK (MI_EUNSUPPORTED); a column outside [0, g) or repeated (MI_EINVAL); which = 1
+ * before mi_prep_normalize (MI_ESTATE).  M is not modified and all scratch outside the annotator is freed on return:
+ * mi_prep_info's device_bytes is the same before and after. */
+int mi_annot_score_matrix(mi_annot *h, mi_prep_matrix *M, int which, const int32_t *cols, int row0, int n_c, int64_t *out_sab,
+                          int64_t *out_sa2, int64_t *out_sb2, double *out_scores, int32_t *out_first, float *out_kernel_ms);
+
+/* SingleR's clusters = mode: the chunk becomes K rows, row c the mean profile of the cells i with cluster_of[i] == c (n
+ * entries in [0, K), every cluster used) on the genes `cols`, and the chain runs on it with n_c = K.  The specification of
+ * a mean: sum = the fp64 sum of (double)x[i][cols[s]] over the cluster's cells in ascending cell index, one addition after
+ * another; mean = (float)(sum / (double)size).  A sparse handle walks only the stored entries of the gene (zeros add +0.0
+ * to a non-negative sum) and returns the dense handle's bits.  out_sizes (K, nullable): the cells per cluster; the five
+ * outputs as mi_annot_score with n_c = K; out_kernel_ms: 4 floats, the means, ranking, cross and score kernels.
+ * The checks, in this order: those of mi_annot_score_matrix up to the device; NULL cluster_of, K < 1 (MI_EINVAL); K >
+ * MI_ANNOT_MAX_CHUNK (MI_EUNSUPPORTED); the columns; a cluster_of entry outside [0, K), a cluster without cells
+ * (MI_EINVAL); the state.  M is not modified, as above. */
+int mi_annot_score_clusters(mi_annot *h, mi_prep_matrix *M, int which, const int32_t *cols, const int32_t *cluster_of, int K,
+                            int32_t *out_sizes, int64_t *out_sab, int64_t *out_sa2, int64_t *out_sb2, double *out_scores,
+                            int32_t *out_first, float *out_kernel_ms);
+
+/* The resident chunk as the chain reads it: n_c x m f32 (the gathered cells, the K mean rows, or the X of mi_annot_score).
+ * MI_EINVAL for a NULL argument, MI_ESTATE when no chunk is resident. */
+int mi_annot_fetch_chunk(mi_annot *h, float *out);
 
 #ifdef __cplusplus
 }

@@ -156,6 +156,10 @@ def _signatures():
         "mi_annot_score": (C.c_int, [vp, f32p, C.c_int, i64p, i64p, i64p, f64p,
                                      i32p, f32p]),
         "mi_annot_fine_tune": (C.c_int, [vp, i32p, f64p, f64p, i32p, f32p]),
+        "mi_annot_score_matrix": (C.c_int, [vp, vp, C.c_int, i32p, C.c_int, C.c_int, i64p, i64p, i64p, f64p, i32p, f32p]),
+        "mi_annot_score_clusters": (C.c_int, [vp, vp, C.c_int, i32p, i32p, C.c_int, i32p, i64p, i64p, i64p, f64p, i32p,
+                                              f32p]),
+        "mi_annot_fetch_chunk": (C.c_int, [vp, f32p]),
     }
     return sig
 

@@ -9,6 +9,11 @@ with R's SingleR is not pinned.
 
 The device work is include/mi_annot.h (csrc/annot_kernels.hip): the reference is uploaded and ranked once into a handle, the
 test cells are densified on the marker genes and scored in chunks of at most ``MAX_CHUNK`` cells.  There is no CPU path.
+
+The cells may also be an open ``preprocess.ExpressionMatrix``: its marker columns are then gathered on the device, chunk by
+chunk, and no n x g matrix crosses the host (``single_r(handle, ...)``, ``handle.annotate(...)``).  ``clusters=`` annotates
+one mean profile per cluster instead of every cell (SingleR's ``clusters =``), the means being one device reduction over
+the handle (:func:`cluster_means`).
 """
 from __future__ import annotations
 
@@ -166,6 +171,13 @@ class Reference:
 
 # ---- the device handle ----------------------------------------------------------------------------------------------------
 
+def _which(which: str) -> int:
+    """0 for the ``"counts"`` of an expression handle, 1 for its ``"normalized"`` matrix"""
+    if which not in ("counts", "normalized"):
+        raise ValueError("which must be 'counts' or 'normalized' (got %r)" % (which,))
+    return int(which == "normalized")
+
+
 class Annotator(_lib.Handle):
     """mi_annot: a reference restricted to m marker genes (``R`` S x m), its label ids in [0, L) and the pair masks,
     resident and ranked on the device.  ``score`` takes a chunk of cells (n_c x m), ``fine_tune`` works on that chunk."""
@@ -193,17 +205,76 @@ class Annotator(_lib.Handle):
         if X.ndim != 2 or X.shape[1] != self.m:
             raise ValueError("X must be (n_c, %d) (got %s)" % (self.m, X.shape))
         n = X.shape[0]
-        scores, first = np.empty((n, self.L), dtype=np.float64), np.empty(n, dtype=np.int32)
+        outs = self._outputs(n, integers)
+        ms = (C.c_float * 3)()
+        self.n_c = 0
+        _lib.call("mi_annot_score", self._handle(), X, n, *outs, ms)
+        self.n_c = n
+        return self._result(outs, {"rank": ms[0], "cross": ms[1], "scores": ms[2]}, integers)
+
+    def _outputs(self, n: int, integers: bool):
+        """the five host outputs of a scoring call on n rows, in the order of the C prototypes (None where not asked for)"""
         sab = np.empty((n, self.S), dtype=np.int64) if integers else None
         sa2 = np.empty(n, dtype=np.int64) if integers else None
         sb2 = np.empty(self.S, dtype=np.int64) if integers else None
-        ms = (C.c_float * 3)()
-        self.n_c = 0
-        _lib.call("mi_annot_score", self._handle(), X, n, sab, sa2, sb2, scores, first, ms)
-        self.n_c = n
-        out = {"scores": scores, "first_labels": first, "kernel_ms": {"rank": float(ms[0]), "cross": float(ms[1]), "scores": float(ms[2])}}
+        return sab, sa2, sb2, np.empty((n, self.L), dtype=np.float64), np.empty(n, dtype=np.int32)
+
+    @staticmethod
+    def _result(outs, ms: dict, integers: bool) -> dict:
+        sab, sa2, sb2, scores, first = outs
+        out = {"scores": scores, "first_labels": first, "kernel_ms": {k: float(v) for k, v in ms.items()}}
         if integers:
             out.update(sab=sab, sa2=sa2, sb2=sb2)
+        return out
+
+    def _cols(self, handle, cols):
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        if cols.shape != (self.m,):
+            raise ValueError("cols must hold the handle's positions of the %d marker genes (got shape %s)" % (self.m, cols.shape))
+        return cols
+
+    def score_matrix(self, handle, cols, i0: int, i1: int, which: str = "normalized", integers: bool = False) -> dict:
+        """:meth:`score` on the cells ``i0 .. i1 - 1`` of an open ``preprocess.ExpressionMatrix`` (dense or sparse),
+        restricted to its genes ``cols`` (m indices, no repeats), gathered on the device: the ``"counts"`` (the uploaded
+        values) or the ``"normalized"`` matrix.  The same dict, bit for bit that of ``score`` on the densified slice;
+        ``kernel_ms`` gains ``gather``.  The handle is not modified."""
+        w = _which(which)
+        cols = self._cols(handle, cols)
+        n = int(i1) - int(i0)
+        outs = self._outputs(max(n, 0), integers)
+        ms = (C.c_float * 4)()
+        self.n_c = 0
+        _lib.call("mi_annot_score_matrix", self._handle(), handle._handle(), w, cols, int(i0), n, *outs, ms)
+        self.n_c = n
+        return self._result(outs, dict(zip(("gather", "rank", "cross", "scores"), ms)), integers)
+
+    def score_clusters(self, handle, cols, cluster_of, K: int, which: str = "normalized", integers: bool = False) -> dict:
+        """:meth:`score` on K rows, row c the mean profile on the genes ``cols`` of the handle's cells with
+        ``cluster_of[i] == c`` (ids in [0, K), every id used): the fp64 sum in ascending cell index, divided by the size,
+        rounded to fp32.  Also returns ``sizes`` (K,); ``kernel_ms`` gains ``means``."""
+        w = _which(which)
+        cols = self._cols(handle, cols)
+        of = np.ascontiguousarray(cluster_of, dtype=np.int32)
+        if of.shape != (handle.n,):
+            raise ValueError("cluster_of must hold one cluster id per cell of the handle (%d; got shape %s)" % (handle.n, of.shape))
+        K = int(K)
+        outs = self._outputs(max(K, 0), integers)
+        sizes = np.empty(max(K, 0), dtype=np.int32)
+        ms = (C.c_float * 4)()
+        self.n_c = 0
+        _lib.call("mi_annot_score_clusters", self._handle(), handle._handle(), w, cols, of, K, sizes, *outs, ms)
+        self.n_c = K
+        out = self._result(outs, dict(zip(("means", "rank", "cross", "scores"), ms)), integers)
+        out["sizes"] = sizes
+        return out
+
+    def fetch_chunk(self) -> np.ndarray:
+        """the resident chunk as the chain reads it, (n_c, m) float32: the cells of the last ``score`` / ``score_matrix``,
+        or the K mean rows of the last ``score_clusters``"""
+        if self.n_c < 1:
+            raise _lib.MiSaError(MI_ESTATE, "no chunk is resident: the last scoring call was refused, or none has run")
+        out = np.empty((self.n_c, self.m), dtype=np.float32)
+        _lib.call("mi_annot_fetch_chunk", self._handle(), out)
         return out
 
     def fine_tune(self) -> dict:
@@ -236,11 +307,12 @@ def _best_two(scores):
     return s[:, -1].copy(), (s[:, -2].copy() if s.shape[1] > 1 else np.full(s.shape[0], -np.inf))
 
 
-def _run(ann: Annotator, rows_of, n: int, chunk: int, fine_tune: bool, integers: bool) -> dict:
-    """every chunk through the handle; rows_of(i0, i1) -> the dense (i1 - i0, m) float32 block of the cells i0 .. i1 - 1"""
+def _run(ann: Annotator, score_of, n: int, chunk: int, fine_tune: bool, integers: bool) -> dict:
+    """every chunk through the handle; score_of(i0, i1) -> the result of one of ``ann``'s scoring calls on the cells
+    i0 .. i1 - 1 (which stay resident for the fine-tuning)"""
     parts, ms = [], {"rank_ref": ann.rank_ref_ms}
     for i0, i1 in _chunks(n, chunk):
-        r = ann.score(rows_of(i0, i1), integers=integers)
+        r = score_of(i0, i1)
         _add_ms(ms, r.pop("kernel_ms"))
         if fine_tune:
             t = ann.fine_tune()
@@ -268,22 +340,12 @@ def score_pass(X, R, labels=None, masks=None, fine_tune: bool = False, device: i
     ids = np.zeros(R.shape[0], dtype=np.int32) if labels is None else np.asarray(labels, dtype=np.int32)
     L = int(ids.max()) + 1 if ids.size else 0
     with Annotator(R, ids, L, masks, device=device) as ann:
-        return _run(ann, lambda i0, i1: X[i0:i1], X.shape[0], chunk, fine_tune, True)
+        return _run(ann, lambda i0, i1: ann.score(X[i0:i1], integers=True), X.shape[0], chunk, fine_tune, True)
 
 
-def single_r(X, gene_names, ref: Reference, fine_tune: bool = True, prune: bool = True, device: int = 0,
-             chunk: int = MAX_CHUNK) -> dict:
-    """Annotate the cells of ``X`` (n cells x g genes: a dense array or a ``scipy.sparse`` matrix of log-normalised values,
-    such as ``preprocess.log_normalize`` returns, with its ``gene_names``) against ``ref``.
-
-    Returns ``labels`` (after fine-tuning), ``first_labels`` (the argmax of the scores) and ``pruned_labels`` (``None``
-    where pruned) as the reference's own label values (object arrays); ``scores`` (n, L) with the columns in the order of
-    ``label_values``; ``tuned_best``, ``tuned_next``, ``iterations``, ``delta``; ``marker_genes`` (the names of M);
-    ``label_ids`` (the final label ids) and ``kernel_ms`` per pass.  A sparse ``X`` is densified on the marker genes chunk
-    by chunk (``chunk`` cells, at most ``MAX_CHUNK``), so memory stays bounded for any n."""
-    names = list(gene_names)
-    if len(X.shape) != 2 or X.shape[1] != len(names):
-        raise ValueError("X must be (n, g) with g gene names (got %s, %d names)" % (tuple(X.shape), len(names)))
+def _marker_setup(names, ref: Reference):
+    """steps 1 and 2 for a test matrix with the gene names ``names`` -> (cols, annotator arguments): the test-side positions
+    of the marker genes M, and ``(R on M, label ids, L, pair masks)``"""
     test_idx, ref_idx = common_genes(names, ref.gene_names)
     pairs, M = ref.markers_on(ref_idx)
     if len(M) < 1:
@@ -291,28 +353,102 @@ def single_r(X, gene_names, ref: Reference, fine_tune: bool = True, prune: bool 
                          % len(test_idx))
     if len(M) > MAX_GENES:
         raise ValueError("%d marker genes exceed %d: lower de_n" % (len(M), MAX_GENES))
-    cols = test_idx[M]
-    n = X.shape[0]
-    sparse = hasattr(X, "tocsr")
-    if sparse:
-        Xm = X.tocsc()[:, cols].tocsr()
-        rows_of = lambda i0, i1: np.ascontiguousarray(Xm[i0:i1].toarray(), dtype=np.float32)
+    return test_idx[M], (ref.R[:, ref_idx[M]], ref.label_ids, ref.L, pair_masks(pairs, M, ref.L))
+
+
+def single_r(X, gene_names, ref: Reference, fine_tune: bool = True, prune: bool = True, device: int = 0,
+             chunk: int = MAX_CHUNK, which: str = "normalized", clusters=None) -> dict:
+    """Annotate the cells of ``X`` (n cells x g genes, with its ``gene_names``) against ``ref``.  ``X`` is a dense array or
+    a ``scipy.sparse`` matrix of log-normalised values, such as ``preprocess.log_normalize`` returns, or an open
+    ``preprocess.ExpressionMatrix`` (dense or sparse; also the ``corrected`` handle of ``sctransform(...,
+    return_corrected=True)``), whose ``which`` matrix (``"normalized"``, the output of ``normalize()`` or the ``data`` slot,
+    or ``"counts"``, the uploaded values) is read where it is: the marker columns are gathered on the device and nothing of
+    the n x g matrix crosses the host.  ``"normalized"`` before ``normalize()`` raises the library's ``MI_ESTATE``.  ``which``
+    is used for a handle only, which is annotated on its own device.
+
+    Returns ``labels`` (after fine-tuning), ``first_labels`` (the argmax of the scores) and ``pruned_labels`` (``None``
+    where pruned) as the reference's own label values (object arrays); ``scores`` (n, L) with the columns in the order of
+    ``label_values``; ``tuned_best``, ``tuned_next``, ``iterations``, ``delta``; ``marker_genes`` (the names of M);
+    ``label_ids`` (the final label ids) and ``kernel_ms`` per pass (with ``gather`` for a handle).  A sparse ``X`` is
+    densified on the marker genes chunk by chunk (``chunk`` cells, at most ``MAX_CHUNK``), so memory stays bounded for any n.
+
+    ``clusters`` (SingleR's ``clusters =``): one cluster label per cell, any hashable values.  The K clusters are annotated
+    instead of the cells, each as the mean profile of its cells on the marker genes (the fp64 sum in cell order, divided by
+    the size, rounded to fp32; one device reduction for every kind of ``X``): every per-row result then has K rows, in the
+    order of ``cluster_values`` (first appearance), and the pruning runs over the K rows, as SingleR's does.  Also returned:
+    ``cluster_values``, ``cluster_sizes`` and ``cell_labels``, each cell's cluster's label (n,), what
+    ``plot_and_save_embedding`` takes.  A host ``X`` is uploaded as it is into a temporary ``ExpressionMatrix`` and read as
+    its ``"counts"``: its values must be non-negative and finite, as ``find_all_markers`` requires of sparse input."""
+    from . import preprocess
+    names = list(gene_names)
+    on_handle = isinstance(X, preprocess.ExpressionMatrix)
+    shape = (X.n, X.g) if on_handle else tuple(X.shape)
+    if len(shape) != 2 or shape[1] != len(names):
+        raise ValueError("X must be (n, g) with g gene names (got %s, %d names)" % (shape, len(names)))
+    _which(which)
+    n = rows = shape[0]
+    if clusters is not None:
+        if len(clusters) != n:
+            raise ValueError("clusters must hold one label per cell: %d labels, %d cells" % (len(clusters), n))
+        cluster_ids, cluster_values = encode_labels(clusters)
+        rows = len(cluster_values)
+        if rows > MAX_CHUNK:
+            raise ValueError("%d clusters exceed %d" % (rows, MAX_CHUNK))
+    cols, ref_args = _marker_setup(names, ref)
+    if on_handle:
+        device = X.device
+    if clusters is not None:
+        handle = X if on_handle else preprocess.ExpressionMatrix(X, device=device)
+        try:
+            with Annotator(*ref_args, device=device) as ann:
+                score_of = lambda i0, i1: ann.score_clusters(handle, cols, cluster_ids, rows, which if on_handle else "counts")
+                out = _run(ann, score_of, rows, MAX_CHUNK, fine_tune, False)
+        finally:
+            if not on_handle:
+                handle.close()
     else:
-        Xd = np.asarray(X)
-        rows_of = lambda i0, i1: np.ascontiguousarray(Xd[i0:i1][:, cols], dtype=np.float32)
-    with Annotator(ref.R[:, ref_idx[M]], ref.label_ids, ref.L, pair_masks(pairs, M, ref.L), device=device) as ann:
-        out = _run(ann, rows_of, n, chunk, fine_tune, False)
+        if on_handle:
+            def score_of(i0, i1):
+                return ann.score_matrix(X, cols, i0, i1, which)
+        elif hasattr(X, "tocsr"):
+            Xm = X.tocsc()[:, cols].tocsr()
+            def score_of(i0, i1):
+                return ann.score(np.ascontiguousarray(Xm[i0:i1].toarray(), dtype=np.float32))
+        else:
+            Xd = np.asarray(X)
+            def score_of(i0, i1):
+                return ann.score(np.ascontiguousarray(Xd[i0:i1][:, cols], dtype=np.float32))
+        with Annotator(*ref_args, device=device) as ann:
+            out = _run(ann, score_of, n, chunk, fine_tune, False)
     if not fine_tune:
         out["labels"] = out["first_labels"].copy()
         out["tuned_best"], out["tuned_next"] = _best_two(out["scores"])
-        out["iterations"] = np.zeros(n, dtype=np.int32)
+        out["iterations"] = np.zeros(rows, dtype=np.int32)
     values = np.empty(ref.L, dtype=object)
     values[:] = ref.label_values
     delta, pruned = prune_scores(out["scores"], out["labels"], out["tuned_best"], out["tuned_next"])
     pruned_labels = values[out["labels"]]
     if prune:
         pruned_labels[pruned] = None
-    return {"labels": values[out["labels"]], "first_labels": values[out["first_labels"]], "pruned_labels": pruned_labels,
-            "label_ids": out["labels"], "label_values": list(ref.label_values), "scores": out["scores"],
-            "tuned_best": out["tuned_best"], "tuned_next": out["tuned_next"], "iterations": out["iterations"], "delta": delta,
-            "marker_genes": [names[j] for j in cols], "kernel_ms": out["kernel_ms"]}
+    res = {"labels": values[out["labels"]], "first_labels": values[out["first_labels"]], "pruned_labels": pruned_labels,
+           "label_ids": out["labels"], "label_values": list(ref.label_values), "scores": out["scores"],
+           "tuned_best": out["tuned_best"], "tuned_next": out["tuned_next"], "iterations": out["iterations"], "delta": delta,
+           "marker_genes": [names[j] for j in cols], "kernel_ms": out["kernel_ms"]}
+    if clusters is not None:
+        res.update(cluster_values=cluster_values, cluster_sizes=out["sizes"], cell_labels=res["labels"][cluster_ids])
+    return res
+
+
+def cluster_means(handle, cols, cluster_of, which: str = "normalized"):
+    """The rows clusters mode ranks, on their own: ``(means (K, m) float32, sizes (K,) int32)`` of the genes ``cols`` of an
+    open ``ExpressionMatrix`` over the cells of each cluster id of ``cluster_of`` (ids in [0, K), K = max + 1, every id
+    used).  ``means[c, s] = float32(fp64 sum of x[i, cols[s]] over the cells i of cluster c in ascending order / size)``;
+    a sparse handle returns the dense handle's bits.  (:meth:`Annotator.score_clusters` on a one-sample reference.)"""
+    cols = np.ascontiguousarray(cols, dtype=np.int32)
+    of = np.asarray(cluster_of)
+    if cols.ndim != 1 or cols.size < 1 or cols.size > MAX_GENES:
+        raise ValueError("cols must hold 1 to %d gene indices (got shape %s)" % (MAX_GENES, cols.shape))
+    K = int(of.max()) + 1 if of.size else 0
+    with Annotator(np.zeros((1, cols.size), dtype=np.float32), np.zeros(1, dtype=np.int32), 1, device=handle.device) as ann:
+        sizes = ann.score_clusters(handle, cols, of, K, which)["sizes"]
+        return ann.fetch_chunk(), sizes

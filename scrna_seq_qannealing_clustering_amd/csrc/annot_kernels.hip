@@ -23,14 +23,26 @@
 //                      ranked over G' by the whole workgroup, one after another; its sorted positions yield sum a b and sum
 //                      b^2 directly (the zero block's share is closed-form), so no rank array of the sample is kept.  At most
 //                      L iterations: `use` strictly shrinks or the loop stops.
-// Sums are integers (any order gives the same value) or fp64 expressions of one thread; integer LDS atomics only; ordinary
-// vector stores.
+// The chunk may come from a resident mi_prep_matrix (mi_annot_score_matrix, mi_annot_score_clusters) with no host traffic:
+//   k_annot_gather_dense  chunk[i][s] = V[(row0 + i) g + cols[s]]: thread = slot, blockIdx.y = cell, 64-bit element indices.
+//   k_annot_gather_csr    one workgroup per cell, as k_prep_csr_select: the row's m value words zeroed in LDS, a barrier, the
+//                         cell's stored entries whose gene has a slot (gmap: g int32, -1 = absent) written over their slot
+//                         (the columns of a row are distinct: no two entries share a slot), a barrier, one coalesced store.
+//   k_annot_means<Src>    one wavefront per (slot, block of 64 clusters), lane = cluster.  The gene's entries (the n cells of
+//                         a dense column; the stored entries of the transpose, rows ascending) are fetched 64 at a time, one
+//                         per lane, then handed round in entry order: every lane adds entry j in fp64 when its cell's label
+//                         is the lane's cluster.  Each (cluster, slot) sum is therefore the sequential fp64 sum in ascending
+//                         cell index of the specification; a skipped zero would add +0.0 to a non-negative sum, so both
+//                         sources give the same bits.  mean = (float)(sum / (double)size).
+// Sums are integers (any order gives the same value) or fp64 expressions of one thread; integer LDS traffic and atomics only
+// in the gather; ordinary vector stores.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "../../include/mi_annot.h"
 #include "mi_midrank.h"
+#include "mi_prep_handle.h"
 #include "mi_sa_device.h"
 
 namespace mi_sa_impl {
@@ -381,6 +393,95 @@ __global__ void __launch_bounds__(kAnnotThreads) k_annot_fine_tune(TuneArgs a)
     }
 }
 
+// ---- the chunk from a resident expression handle ---------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kAnnotThreads) k_annot_gather_dense(const float *__restrict__ V, long long g, int row0,
+                                                                      const int32_t *__restrict__ cols, int n_c, int m,
+                                                                      float *__restrict__ X)
+{
+    const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    for (int i = blockIdx.y; i < n_c; i += gridDim.y)
+        if (s < m) X[(size_t)i * m + s] = V[(size_t)((long long)(row0 + i) * g + cols[s])];
+}
+
+__global__ void __launch_bounds__(kAnnotThreads) k_annot_gather_csr(const int64_t *__restrict__ indptr,
+                                                                    const int32_t *__restrict__ indices,
+                                                                    const float *__restrict__ vals,
+                                                                    const int32_t *__restrict__ gmap, int row0, int n_c, int m,
+                                                                    float *__restrict__ X)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    uint32_t *row = reinterpret_cast<uint32_t *>(lds);                                     // m value words
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int i = blockIdx.x; i < n_c; i += gridDim.x) {
+        for (int s = tid; s < m; s += nt) row[s] = 0u;
+        __syncthreads();
+        const int64_t e1 = indptr[(size_t)row0 + i + 1];
+        for (int64_t e = indptr[(size_t)row0 + i] + tid; e < e1; e += nt) {
+            const int s = gmap[indices[e]];
+            if (s >= 0) row[s] = __float_as_uint(vals[e]);
+        }
+        __syncthreads();
+        for (int s = tid; s < m; s += nt) X[(size_t)i * m + s] = __uint_as_float(row[s]);
+        __syncthreads();
+    }
+}
+
+// the entries of one gene in ascending cell order: entry k of count(col) is the value at(col, k).v of cell at(col, k).cell
+struct ColEntry {
+    float v;
+    int cell;
+};
+
+struct DenseColumn {
+    const float *V = nullptr;
+    int n = 0;
+    long long g = 0;
+    __device__ int count(int) const { return n; }
+    __device__ ColEntry at(int col, int k) const { return ColEntry{V[(size_t)((long long)k * g + col)], k}; }
+};
+
+struct CscColumn {
+    const int64_t *colptr = nullptr;
+    const int32_t *rows = nullptr, *pos = nullptr;
+    const float *V = nullptr;                                                              // in the CSR order: entry pos[e]
+    __device__ int count(int col) const { return (int)(colptr[col + 1] - colptr[col]); }
+    __device__ ColEntry at(int col, int k) const
+    {
+        const int64_t e = colptr[col] + k;
+        return ColEntry{V[pos[e]], rows[e]};
+    }
+};
+
+template <class Src>
+__global__ void __launch_bounds__(kAnnotThreads) k_annot_means(Src src, const int32_t *__restrict__ cols,
+                                                               const int32_t *__restrict__ cluster_of,
+                                                               const int32_t *__restrict__ sizes, int K, int m,
+                                                               float *__restrict__ X)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = (int)blockIdx.x * kAnnotWaves + wave, c = (int)blockIdx.y * 64 + lane;   // (no barrier below: a wavefront may leave)
+    if (s >= m) return;
+    const int col = cols[s], count = src.count(col);
+    double sum = 0.0;
+    for (int k0 = 0; k0 < count; k0 += 64) {
+        float v = 0.0f;
+        int lab = -1;
+        if (k0 + lane < count) {
+            const ColEntry e = src.at(col, k0 + lane);
+            v = e.v;
+            lab = cluster_of[e.cell];
+        }
+        const int left = count - k0 < 64 ? count - k0 : 64;
+        for (int j = 0; j < left; ++j) {
+            const float vj = __shfl(v, j);
+            const int lj = __shfl(lab, j);
+            if (lj == c) sum += (double)vj;
+        }
+    }
+    if (c < K) X[(size_t)c * m + s] = (float)(sum / (double)sizes[c]);
+}
+
 // entries of the LDS sort array for rows of m genes (at least 2: the arrays carved after it stay 16-byte aligned)
 inline int sort_cap(int m) { return m > 2 ? pow2_at_least(m) : 2; }
 
@@ -422,6 +523,95 @@ struct mi_annot {
     DevArray<uint32_t> d_masks;
     DevArray<double> d_scores, d_best, d_next;
 };
+
+namespace {
+
+// the chunk and everything the chain writes per cell, for n_c cells (contents are not kept)
+int reserve_chunk(mi_annot *h, int n_c)
+{
+    HIP_TRY(h->d_X.reserve((size_t)n_c * h->m));
+    HIP_TRY(h->d_chi.reserve((size_t)n_c * h->mpad));
+    HIP_TRY(h->d_clo.reserve((size_t)n_c * h->mpad));
+    HIP_TRY(h->d_sa2.reserve((size_t)n_c));
+    HIP_TRY(h->d_sab.reserve((size_t)n_c * h->S));
+    HIP_TRY(h->d_scores.reserve((size_t)n_c * h->L));
+    HIP_TRY(h->d_first.reserve((size_t)n_c));
+    return MI_OK;
+}
+
+// The chain on the n_c rows of h->d_X (after reserve_chunk): ranking, cross and score kernels, whose times go to
+// out_kernel_ms[0 .. 2] (nullable); the chunk is resident once they have run; then the downloads the caller asked for.
+int score_chunk(mi_annot *h, int n_c, int64_t *out_sab, int64_t *out_sa2, int64_t *out_sb2, double *out_scores,
+                int32_t *out_first, float *out_kernel_ms)
+{
+    const int S = h->S, m = h->m, L = h->L, mpad = h->mpad;
+    {
+        Timer tm;
+        MI_TRY(tm.start(0));
+        MI_TRY(launch_rank(h->d_X, n_c, m, mpad, h->d_chi, h->d_clo, h->d_sa2));
+        MI_TRY(tm.stop(0, out_kernel_ms ? out_kernel_ms + 0 : nullptr));
+    }
+    {
+        CrossArgs a;
+        a.ahi = h->d_chi; a.alo = h->d_clo; a.bhi = h->d_rhi; a.blo = h->d_rlo;
+        a.n = n_c; a.S = S; a.mpad = mpad; a.sab = h->d_sab;
+        const long long tiles = (long long)((n_c + 15) / 16) * ((S + 16 * kCrossCols - 1) / (16 * kCrossCols));
+        const long long need = (tiles + kAnnotWaves - 1) / kAnnotWaves, most = (long long)(h->cus > 0 ? h->cus : 256) * 8;
+        Timer tm;
+        MI_TRY(tm.start(0));
+        hipLaunchKernelGGL(k_annot_cross, dim3((unsigned)(need < most ? need : most)), dim3(kAnnotThreads), 0, 0, a);
+        MI_TRY(tm.stop(0, out_kernel_ms ? out_kernel_ms + 1 : nullptr));
+    }
+    {
+        ScoreArgs a;
+        a.sab = h->d_sab; a.sa2 = h->d_sa2; a.sb2 = h->d_sb2; a.off = h->d_off;
+        a.n = n_c; a.S = S; a.L = L; a.m = m; a.scores = h->d_scores; a.first = h->d_first;
+        const size_t bytes = (size_t)((S + 1) & ~1) * 8 + 3 * 64 * 8;
+        Timer tm;
+        MI_TRY(tm.start(0));
+        hipLaunchKernelGGL(k_annot_scores, dim3((unsigned)n_c), dim3(kAnnotThreads), bytes, 0, a);
+        MI_TRY(tm.stop(0, out_kernel_ms ? out_kernel_ms + 2 : nullptr));
+    }
+    h->n_c = n_c;
+    if (out_sab) {
+        std::vector<long long> g((size_t)n_c * S);
+        HIP_TRY(hipMemcpy(g.data(), h->d_sab, g.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n_c; ++i)
+            for (int p = 0; p < S; ++p) out_sab[(size_t)i * S + h->perm[p]] = g[(size_t)i * S + p];
+    }
+    if (out_sa2) HIP_TRY(hipMemcpy(out_sa2, h->d_sa2, (size_t)n_c * sizeof(long long), hipMemcpyDeviceToHost));
+    if (out_sb2) {
+        std::vector<long long> g((size_t)S);
+        HIP_TRY(hipMemcpy(g.data(), h->d_sb2, g.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        for (int p = 0; p < S; ++p) out_sb2[h->perm[p]] = g[p];
+    }
+    if (out_scores) HIP_TRY(hipMemcpy(out_scores, h->d_scores, (size_t)n_c * L * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_first) HIP_TRY(hipMemcpy(out_first, h->d_first, (size_t)n_c * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+// The checks mi_annot_score_matrix and mi_annot_score_clusters share on (M, which), after the NULL checks: which, the device.
+int check_source(const mi_annot *h, const mi_prep_matrix *M, int which)
+{
+    if (which != MI_PREP_MARKERS_COUNTS && which != MI_PREP_MARKERS_NORMALIZED)
+        return fail(MI_EINVAL, "which must be 0 (counts) or 1 (normalised), got %d", which);
+    if (M->device != h->device) return fail(MI_EINVAL, "the matrix is on device %d, the annotator on device %d", M->device, h->device);
+    return MI_OK;
+}
+
+// cols: m indices in [0, g), no repeats -> gmap (g entries): the slot of every gene, -1 = absent
+int check_cols(const int32_t *cols, int m, int g, std::vector<int32_t> &gmap)
+{
+    gmap.assign((size_t)g, -1);
+    for (int s = 0; s < m; ++s) {
+        if (cols[s] < 0 || cols[s] >= g) return fail(MI_EINVAL, "column %d (slot %d) is not in [0, %d)", cols[s], s, g);
+        if (gmap[cols[s]] >= 0) return fail(MI_EINVAL, "column %d is repeated (slots %d and %d)", cols[s], gmap[cols[s]], s);
+        gmap[cols[s]] = s;
+    }
+    return MI_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -504,62 +694,14 @@ int mi_annot_score(mi_annot *h, const float *X, int n_c, int64_t *out_sab, int64
     if (!X) return fail(MI_EINVAL, "NULL argument");
     if (n_c < 1) return fail(MI_EINVAL, "n_c must be >= 1 (got %d)", n_c);
     if (n_c > MI_ANNOT_MAX_CHUNK) return fail(MI_EUNSUPPORTED, "%d cells exceed a chunk of %d", n_c, MI_ANNOT_MAX_CHUNK);
-    const int S = h->S, m = h->m, L = h->L, mpad = h->mpad;
+    const int m = h->m;
     size_t bad = 0;
     if (!finite_bits(X, (size_t)n_c * m, &bad)) return fail(MI_EINVAL, "X[%zu, %zu] is not finite", bad / m, bad % m);
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(h->d_X.reserve((size_t)n_c * m));
-        HIP_TRY(h->d_chi.reserve((size_t)n_c * mpad));
-        HIP_TRY(h->d_clo.reserve((size_t)n_c * mpad));
-        HIP_TRY(h->d_sa2.reserve((size_t)n_c));
-        HIP_TRY(h->d_sab.reserve((size_t)n_c * S));
-        HIP_TRY(h->d_scores.reserve((size_t)n_c * L));
-        HIP_TRY(h->d_first.reserve((size_t)n_c));
+        MI_TRY(reserve_chunk(h, n_c));
         HIP_TRY(hipMemcpy(h->d_X, X, (size_t)n_c * m * sizeof(float), hipMemcpyHostToDevice));
-        {
-            Timer tm;
-            MI_TRY(tm.start(0));
-            MI_TRY(launch_rank(h->d_X, n_c, m, mpad, h->d_chi, h->d_clo, h->d_sa2));
-            MI_TRY(tm.stop(0, out_kernel_ms ? out_kernel_ms + 0 : nullptr));
-        }
-        {
-            CrossArgs a;
-            a.ahi = h->d_chi; a.alo = h->d_clo; a.bhi = h->d_rhi; a.blo = h->d_rlo;
-            a.n = n_c; a.S = S; a.mpad = mpad; a.sab = h->d_sab;
-            const long long tiles = (long long)((n_c + 15) / 16) * ((S + 16 * kCrossCols - 1) / (16 * kCrossCols));
-            const long long need = (tiles + kAnnotWaves - 1) / kAnnotWaves, most = (long long)(h->cus > 0 ? h->cus : 256) * 8;
-            Timer tm;
-            MI_TRY(tm.start(0));
-            hipLaunchKernelGGL(k_annot_cross, dim3((unsigned)(need < most ? need : most)), dim3(kAnnotThreads), 0, 0, a);
-            MI_TRY(tm.stop(0, out_kernel_ms ? out_kernel_ms + 1 : nullptr));
-        }
-        {
-            ScoreArgs a;
-            a.sab = h->d_sab; a.sa2 = h->d_sa2; a.sb2 = h->d_sb2; a.off = h->d_off;
-            a.n = n_c; a.S = S; a.L = L; a.m = m; a.scores = h->d_scores; a.first = h->d_first;
-            const size_t bytes = (size_t)((S + 1) & ~1) * 8 + 3 * 64 * 8;
-            Timer tm;
-            MI_TRY(tm.start(0));
-            hipLaunchKernelGGL(k_annot_scores, dim3((unsigned)n_c), dim3(kAnnotThreads), bytes, 0, a);
-            MI_TRY(tm.stop(0, out_kernel_ms ? out_kernel_ms + 2 : nullptr));
-        }
-        h->n_c = n_c;
-        if (out_sab) {
-            std::vector<long long> g((size_t)n_c * S);
-            HIP_TRY(hipMemcpy(g.data(), h->d_sab, g.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            for (int i = 0; i < n_c; ++i)
-                for (int p = 0; p < S; ++p) out_sab[(size_t)i * S + h->perm[p]] = g[(size_t)i * S + p];
-        }
-        if (out_sa2) HIP_TRY(hipMemcpy(out_sa2, h->d_sa2, (size_t)n_c * sizeof(long long), hipMemcpyDeviceToHost));
-        if (out_sb2) {
-            std::vector<long long> g((size_t)S);
-            HIP_TRY(hipMemcpy(g.data(), h->d_sb2, g.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            for (int p = 0; p < S; ++p) out_sb2[h->perm[p]] = g[p];
-        }
-        if (out_scores) HIP_TRY(hipMemcpy(out_scores, h->d_scores, (size_t)n_c * L * sizeof(double), hipMemcpyDeviceToHost));
-        if (out_first) HIP_TRY(hipMemcpy(out_first, h->d_first, (size_t)n_c * sizeof(int32_t), hipMemcpyDeviceToHost));
-        return MI_OK;
+        return score_chunk(h, n_c, out_sab, out_sa2, out_sb2, out_scores, out_first, out_kernel_ms);
     });
 }
 
@@ -590,6 +732,111 @@ int mi_annot_fine_tune(mi_annot *h, int32_t *out_labels, double *out_best, doubl
         if (out_best) HIP_TRY(hipMemcpy(out_best, h->d_best, (size_t)n_c * sizeof(double), hipMemcpyDeviceToHost));
         if (out_next) HIP_TRY(hipMemcpy(out_next, h->d_next, (size_t)n_c * sizeof(double), hipMemcpyDeviceToHost));
         if (out_iterations) HIP_TRY(hipMemcpy(out_iterations, h->d_iters, (size_t)n_c * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return MI_OK;
+    });
+}
+
+int mi_annot_score_matrix(mi_annot *h, mi_prep_matrix *M, int which, const int32_t *cols, int row0, int n_c, int64_t *out_sab,
+                          int64_t *out_sa2, int64_t *out_sb2, double *out_scores, int32_t *out_first, float *out_kernel_ms)
+{
+    if (out_kernel_ms) out_kernel_ms[0] = out_kernel_ms[1] = out_kernel_ms[2] = out_kernel_ms[3] = 0.0f;
+    if (!h) return fail(MI_EINVAL, "NULL argument");
+    h->n_c = 0;                                // a refused or failed call leaves no resident chunk
+    return guarded([&]() -> int {
+        if (!M || !cols) return fail(MI_EINVAL, "NULL argument");
+        MI_TRY(check_source(h, M, which));
+        if (row0 < 0 || n_c < 1 || (long long)row0 + n_c > M->n)
+            return fail(MI_EINVAL, "rows [%d, %d + %d) are not a range of the %d cells", row0, row0, n_c, M->n);
+        if (n_c > MI_ANNOT_MAX_CHUNK) return fail(MI_EUNSUPPORTED, "%d cells exceed a chunk of %d", n_c, MI_ANNOT_MAX_CHUNK);
+        const int m = h->m;
+        std::vector<int32_t> gmap;
+        MI_TRY(check_cols(cols, m, M->g, gmap));
+        MI_TRY(check_state(M, which == MI_PREP_MARKERS_NORMALIZED ? NEED_NORMALIZED : 0));
+        // (the handle's values are finite and non-negative by mi_prep_create*'s checks: no scan)
+        HIP_TRY(hipSetDevice(h->device));
+        MI_TRY(reserve_chunk(h, n_c));
+        const float *V = which == MI_PREP_MARKERS_NORMALIZED ? M->d_Y : M->d_X;
+        DevBufs bufs;
+        {
+            Timer tm;
+            if (M->sparse) {
+                int32_t *d_gmap = nullptr;
+                HIP_TRY(bufs.upload(&d_gmap, gmap.data(), gmap.size()));
+                MI_TRY(tm.start(0));
+                hipLaunchKernelGGL(k_annot_gather_csr, dim3((unsigned)n_c), dim3(kAnnotThreads), (size_t)m * sizeof(uint32_t), 0,
+                                   M->d_indptr, M->d_indices, V, d_gmap, row0, n_c, m, h->d_X);
+            } else {
+                int32_t *d_cols = nullptr;
+                HIP_TRY(bufs.upload(&d_cols, cols, (size_t)m));
+                MI_TRY(tm.start(0));
+                hipLaunchKernelGGL(k_annot_gather_dense, dim3((unsigned)((m + kAnnotThreads - 1) / kAnnotThreads), (unsigned)n_c),
+                                   dim3(kAnnotThreads), 0, 0, V, (long long)M->g, row0, d_cols, n_c, m, h->d_X);
+            }
+            MI_TRY(tm.stop(0, out_kernel_ms ? out_kernel_ms + 0 : nullptr));
+        }
+        return score_chunk(h, n_c, out_sab, out_sa2, out_sb2, out_scores, out_first, out_kernel_ms ? out_kernel_ms + 1 : nullptr);
+    });
+}
+
+int mi_annot_score_clusters(mi_annot *h, mi_prep_matrix *M, int which, const int32_t *cols, const int32_t *cluster_of, int K,
+                            int32_t *out_sizes, int64_t *out_sab, int64_t *out_sa2, int64_t *out_sb2, double *out_scores,
+                            int32_t *out_first, float *out_kernel_ms)
+{
+    if (out_kernel_ms) out_kernel_ms[0] = out_kernel_ms[1] = out_kernel_ms[2] = out_kernel_ms[3] = 0.0f;
+    if (!h) return fail(MI_EINVAL, "NULL argument");
+    h->n_c = 0;                                // a refused or failed call leaves no resident chunk
+    return guarded([&]() -> int {
+        if (!M || !cols) return fail(MI_EINVAL, "NULL argument");
+        MI_TRY(check_source(h, M, which));
+        if (!cluster_of) return fail(MI_EINVAL, "NULL argument");
+        if (K < 1) return fail(MI_EINVAL, "K must be >= 1 (got %d)", K);
+        if (K > MI_ANNOT_MAX_CHUNK) return fail(MI_EUNSUPPORTED, "%d clusters exceed a chunk of %d", K, MI_ANNOT_MAX_CHUNK);
+        const int m = h->m, n = M->n;
+        std::vector<int32_t> gmap, sizes((size_t)K, 0);
+        MI_TRY(check_cols(cols, m, M->g, gmap));
+        for (int i = 0; i < n; ++i) {
+            if (cluster_of[i] < 0 || cluster_of[i] >= K)
+                return fail(MI_EINVAL, "cluster %d of cell %d is not in [0, %d)", cluster_of[i], i, K);
+            ++sizes[cluster_of[i]];
+        }
+        for (int c = 0; c < K; ++c)
+            if (sizes[c] == 0) return fail(MI_EINVAL, "cluster %d has no cells", c);
+        MI_TRY(check_state(M, which == MI_PREP_MARKERS_NORMALIZED ? NEED_NORMALIZED : 0));
+        HIP_TRY(hipSetDevice(h->device));
+        MI_TRY(reserve_chunk(h, K));
+        const float *V = which == MI_PREP_MARKERS_NORMALIZED ? M->d_Y : M->d_X;
+        DevBufs bufs;
+        int32_t *d_cols = nullptr, *d_of = nullptr, *d_sizes = nullptr;
+        HIP_TRY(bufs.upload(&d_cols, cols, (size_t)m));
+        HIP_TRY(bufs.upload(&d_of, cluster_of, (size_t)n));
+        HIP_TRY(bufs.upload(&d_sizes, sizes.data(), sizes.size()));
+        {
+            const dim3 grid((unsigned)((m + kAnnotWaves - 1) / kAnnotWaves), (unsigned)((K + 63) / 64));
+            Timer tm;
+            MI_TRY(tm.start(0));
+            if (M->sparse) {
+                CscColumn src;
+                src.colptr = M->d_colptr; src.rows = M->d_rows; src.pos = M->d_pos; src.V = V;
+                hipLaunchKernelGGL(k_annot_means<CscColumn>, grid, dim3(kAnnotThreads), 0, 0, src, d_cols, d_of, d_sizes, K, m, h->d_X);
+            } else {
+                DenseColumn src;
+                src.V = V; src.n = n; src.g = M->g;
+                hipLaunchKernelGGL(k_annot_means<DenseColumn>, grid, dim3(kAnnotThreads), 0, 0, src, d_cols, d_of, d_sizes, K, m, h->d_X);
+            }
+            MI_TRY(tm.stop(0, out_kernel_ms ? out_kernel_ms + 0 : nullptr));
+        }
+        if (out_sizes) std::copy(sizes.begin(), sizes.end(), out_sizes);
+        return score_chunk(h, K, out_sab, out_sa2, out_sb2, out_scores, out_first, out_kernel_ms ? out_kernel_ms + 1 : nullptr);
+    });
+}
+
+int mi_annot_fetch_chunk(mi_annot *h, float *out)
+{
+    if (!h || !out) return fail(MI_EINVAL, "NULL argument");
+    if (h->n_c < 1) return fail(MI_ESTATE, "no chunk is resident");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipMemcpy(out, h->d_X, (size_t)h->n_c * h->m * sizeof(float), hipMemcpyDeviceToHost));
         return MI_OK;
     });
 }

@@ -257,6 +257,12 @@ class ExpressionMatrix(_lib.Handle):
         self.timing["markers_ms"] = ms
         return {"rank2": rank2, "npos": npos, "sum": sums, "tie": tie, "kernel_ms": ms}
 
+    def annotate(self, gene_names, ref, **kw) -> dict:
+        """:func:`annotate.single_r` on this handle, read where it is (``which="normalized"`` by default; ``clusters=``
+        annotates cluster means)."""
+        from . import annotate
+        return annotate.single_r(self, gene_names, ref, **kw)
+
     def select_regressed(self, genes, Q, clip: float = 10.0):
         """:meth:`select` on the residuals of a linear model: with ``y`` the chosen column of the normalised matrix and
         ``Q`` (n, q) an orthonormal basis of the design (:func:`design_basis`), ``r = y - Q (Q^T y)`` and
