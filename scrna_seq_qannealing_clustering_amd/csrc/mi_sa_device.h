@@ -306,30 +306,6 @@ __device__ __forceinline__ ReplicaGroup replica_group(const EllArgs &a, int r)
     return {g, r - g * rg};
 }
 
-// fp64 weighted pair term of the reported energy (chain 2d): c64 / 2 sum_q (W_q^2 - sum_{i in q} w_i^2), returned as this
-// lane's share of a wave sum (lane 0 carries the cluster sums); c64 of resolution group grp.  label(i): the label of position i (every lane of the wave
-// calls it for the same t).
-template <typename LabelF>
-__device__ double node_weight_energy(const EllArgs &a, int lane, int grp, LabelF label)
-{
-    double own = 0.0, tot = 0.0;
-    for (int t = 0; t < a.slots; ++t) {
-        const double w = a.nw64[t * 64 + lane];
-        own -= w * w;
-    }
-    for (int q = 0; q < a.K; ++q) {
-        double s = 0.0;
-        for (int t = 0; t < a.slots; ++t) {
-            const int i = t * 64 + lane;
-            if (label(i) == (uint32_t)q) s += a.nw64[i];        // (0 at holes and past n)
-        }
-        s = wave_sum_f64(s);
-        tot += s * s;
-    }
-    const double c64 = a.gconst ? a.gconst[grp] : (a.ell_val64 ? a.c_pair64 : (double)a.c_pair);
-    return 0.5 * c64 * (own + (lane == 0 ? tot : 0.0));
-}
-
 // The weighted slot of a structured binary model (EllArgs::wslot): a sequential sweep over its lanes -- few variables,
 // the slack bits of a squared constraint, coupled to everything through the pair term only -- with the oracle's expression
 // f = g + (c * (float)w) * (float)(A - w z).  z: the lane's bit; A: sum_j w_j z_j, updated.  Returns the mask of flips.

@@ -20,7 +20,7 @@
 // The rest is k_anneal_potts' fast path made lean: the accept mask of a slot by fixed-point rounds over a DPP prefix
 // sum of packed per-cluster size changes, with only wave-uniform masks alive across the loop; the cluster sizes a lane
 // needs picked out of the scan by one more v_perm_b32 each; cluster sizes in LDS (two atomics per mover).
-#include "mi_sa_device.h"
+#include "mi_sa_chain_ends.h"
 
 namespace mi_sa_impl {
 
@@ -89,7 +89,6 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
     uint16_t *cell = reinterpret_cast<uint16_t *>(lds);
     const uint32_t cnt_base = (uint32_t)slots * 128u;
     int *cnt = reinterpret_cast<int *>(lds + cnt_base);
-    const uint16_t *init = static_cast<const uint16_t *>(a.init);
     // w mod (K-1) without the integer division: q = mulhi(w, floor(2^32 / d)) is floor(w / d) or one less
     const uint32_t dK = (uint32_t)(K - 1);
     const uint32_t magic = dK == 1u ? 0xffffffffu : (uint32_t)(0x100000000ull / dK);
@@ -129,40 +128,8 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
     }
 
     // ---- initial labels (the chain's tag-1 words, or the caller's / the previous launch's states) ----
-    for (int tg = 0; tg * 4 < slots; ++tg) {
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-        if (!init) philox4x32_10((uint32_t)(tg * 64 + lane), 0u, gid, 1u, a.seed_lo, a.seed_hi, w);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int t = 4 * tg + c;
-            if (t >= slots) break;
-            const int i = t * 64 + lane;
-            // (bit 31 of meta: nobody sits here -- past n, or a hole of a padded layout: label 0, in no cluster, never proposed)
-            const bool present = (a.meta[i] >> 31) == 0u;
-            uint32_t v = 0u;
-            if (present) v = init ? (uint32_t)init[(size_t)r * n + i] : (w[c] % (uint32_t)K);
-            cell[i] = (uint16_t)enc_label<KM>(v);
-        }
-    }
-    {
-        int cntv = 0;                                               // lane q: number of variables with label q
-        for (int q = 0; q < K; ++q) {
-            int c = 0;
-            for (int t = 0; t < slots; ++t)
-                c += __popcll(__ballot((a.meta[t * 64 + lane] >> 31) == 0u && dec_label<KM>(cell[t * 64 + lane]) == (uint32_t)q));
-            if (lane == q) cntv = c;
-        }
-        cnt[lane] = cntv;                                           // (64 words reserved)
-    }
-    if constexpr (WT) {
-        // the integer cluster sums (exact: integer atomics in any order; the wave's LDS operations run in order)
-        cnt[lane] = 0;
-        for (int t = 0; t < slots; ++t) {
-            const int i = t * 64 + lane;
-            if ((a.meta[i] >> 31) == 0u)
-                __hip_atomic_fetch_add(&cnt[dec_label<KM>(cell[i])], a.nwq[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        }
-    }
+    potts_initial_labels<WT>(a, r, gid, lane, cnt, [&](int i, uint32_t v) { cell[i] = (uint16_t)enc_label<KM>(v); },
+                             [&](int i) { return dec_label<KM>(cell[i]); });
 
     constexpr int G = D / 4;
     const __amdgpu_buffer_rsrc_t rs_adj = __builtin_amdgcn_make_buffer_rsrc(
@@ -452,32 +419,8 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D == 16 ? 4 : 2))) k
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
-    // ---- epilogue: labels out, exact fp64 energy (the sums of k_anneal_potts) ----
-    uint16_t *dst = static_cast<uint16_t *>(a.states) + (size_t)r * n;
-    double e = 0.0;
-    for (int t = 0; t < slots; ++t) {
-        const int i = t * 64 + lane;
-        if (i >= n) continue;
-        const uint32_t li = dec_label<KM>(cell[i]);
-        dst[i] = (uint16_t)li;
-        for (int k = 0; k < D; ++k) {
-            const size_t at = ((size_t)t * D + k) * 64 + lane;
-            const uint32_t cc = a.ell_col[at];
-            const double vv = a.ell_val64 ? a.ell_val64[at] : (double)a.ell_val[at];
-            if ((int)cc > i && dec_label<KM>(cell[cc]) == li) e += vv;
-        }
-    }
-    if constexpr (WT) {
-        e += node_weight_energy(a, lane, rgp.g, [&](int j) { return dec_label<KM>(cell[j]); });
-    } else {
-        const int cntv = cnt[lane];
-        if (lane < K) e += (a.ell_val64 ? a.c_pair64 : (double)a.c_pair) * 0.5 * (double)cntv * (double)(cntv - 1);
-    }
-    e = wave_sum_f64(e);
-    if (lane == 0) {
-        a.energy[r] = e + (WT && a.gconst ? a.gconst[a.groups + rgp.g] : a.offset);
-        atomicAdd(&a.stats[1], accepted);
-    }
+    // ---- chain out: labels, exact fp64 energy ----
+    potts_chain_out<WT>(a, r, rgp.g, lane, D, cnt, accepted, [&](int i) { return dec_label<KM>(cell[i]); });
 }
 
 }  // namespace

@@ -13,7 +13,7 @@
 // itself with weight +0.0f (adding +0.0f is the identity, so padded and unpadded sums are bit-equal).
 // One wavefront owns one replica; per-replica state that needs random access (cached fields g for K2,
 // labels for K3) lives in LDS.  Chain specification: DESIGN.md / oracle/sa_oracle.c (2b), (2c).
-#include "mi_sa_device.h"
+#include "mi_sa_chain_ends.h"
 
 namespace mi_sa_impl {
 
@@ -419,8 +419,7 @@ __global__ void __launch_bounds__(TW ? 128 : 64, (TW ? 2 : (D <= 32 ? 4 : 2))) k
     }
     e = wave_sum_f64(e);
     if (lane == 0) {
-        const double cp = a.ell_val64 ? a.c_pair64 : (double)a.c_pair;
-        a.energy[r] = e + cp * 0.5 * ((double)cnt * (double)cnt - (double)cnt2) + a.offset;     // (w = 1: cnt (cnt - 1) / 2 pairs)
+        a.energy[r] = binary_chain_finish(a.ell_val64, a.c_pair, a.c_pair64, a.offset, e, cnt, cnt2);
         atomicAdd(&a.stats[1], accepted);
     }
 }
@@ -461,41 +460,10 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
     // LDS per wave: the labels (one byte per variable) and the K cluster sizes (one int each, 64 reserved)
     uint8_t *lab = reinterpret_cast<uint8_t *>(lds) + (size_t)wave * ((size_t)slots * 64 + 256);
     int *cnt = reinterpret_cast<int *>(lab + (size_t)slots * 64);
-    const uint16_t *init = static_cast<const uint16_t *>(a.init);
     const uint2 *rows = a.rows;
 
-    for (int tg = 0; tg * 4 < slots; ++tg) {
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (!init) slot_words(w, tg, lane, 0u, gid, 1u, a.seed_lo, a.seed_hi);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int t = 4 * tg + c;
-            if (t >= slots) break;
-            const int i = t * 64 + lane;
-            uint32_t v = 0;
-            // (bit 31 of meta: no variable sits at this position -- past n, or a hole of a padded layout,
-            // mi_sa_plan_slot_layout / mi_sa_problem_set_absent: label 0, in no cluster, never proposed)
-            const bool present = (a.meta[i] >> 31) == 0u;
-            if (present) v = init ? (uint32_t)init[(size_t)r * n + i] : (w[c] % (uint32_t)K);
-            lab[i] = (uint8_t)v;
-        }
-    }
-    int cntv = 0;                                            // lane q: number of variables with label q
-    for (int q = 0; q < K; ++q) {
-        int c = 0;
-        for (int t = 0; t < slots; ++t)
-            c += __popcll(__ballot((a.meta[t * 64 + lane] >> 31) == 0u && lab[t * 64 + lane] == q));
-        if (lane == q) cntv = c;
-    }
-    cnt[lane] = cntv;
-    if constexpr (WT) {
-        // the integer cluster sums (exact: integer atomics in any order; the wave's LDS operations run in order)
-        cnt[lane] = 0;
-        for (int t = 0; t < slots; ++t) {
-            const int i = t * 64 + lane;
-            if ((a.meta[i] >> 31) == 0u) __hip_atomic_fetch_add(&cnt[lab[i]], a.nwq[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        }
-    }
+    potts_initial_labels<WT>(a, r, gid, lane, cnt, [&](int i, uint32_t v) { lab[i] = (uint8_t)v; },
+                             [&](int i) { return (uint32_t)lab[i]; });
 
     constexpr bool PF = (D == 16);
     constexpr int DR = D ? D : 1;                            // register-resident entries (none for D = 0)
@@ -805,32 +773,8 @@ __global__ void __launch_bounds__(256, (D <= 32 ? 4 : 2)) k_anneal_potts(EllArgs
     }
 #endif
 
-    // ---- epilogue: labels out, exact fp64 energy ----
-    uint16_t *dst = static_cast<uint16_t *>(a.states) + (size_t)r * n;
-    double e = 0.0;
-    for (int t = 0; t < slots; ++t) {
-        const int i = t * 64 + lane;
-        if (i >= n) continue;
-        const int li = lab[i];
-        dst[i] = (uint16_t)li;
-        for (int k = 0; k < W; ++k) {
-            const uint32_t cc = a.ell_col[((size_t)t * W + k) * 64 + lane];
-            const size_t at = ((size_t)t * W + k) * 64 + lane;
-            const double vv = a.ell_val64 ? a.ell_val64[at] : (double)a.ell_val[at];
-            if ((int)cc > i && lab[cc] == li) e += vv;
-        }
-    }
-    if constexpr (WT) {
-        e += node_weight_energy(a, lane, rgp.g, [&](int j) { return (uint32_t)lab[j]; });
-    } else {
-        cntv = cnt[lane];
-        if (lane < K) e += (a.ell_val64 ? a.c_pair64 : (double)a.c_pair) * 0.5 * (double)cntv * (double)(cntv - 1);
-    }
-    e = wave_sum_f64(e);
-    if (lane == 0) {
-        a.energy[r] = e + (WT && a.gconst ? a.gconst[a.groups + rgp.g] : a.offset);
-        atomicAdd(&a.stats[1], accepted);
-    }
+    // ---- chain out: labels, exact fp64 energy ----
+    potts_chain_out<WT>(a, r, rgp.g, lane, W, cnt, accepted, [&](int i) { return (uint32_t)lab[i]; });
 }
 
 }  // namespace

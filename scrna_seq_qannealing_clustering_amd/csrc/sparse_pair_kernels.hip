@@ -12,7 +12,7 @@
 //
 // The chain is K2's (oracle/sa_oracle.c 2b), bit for bit; only models whose every slot is free of internal edges
 // (the slot-independent order) take this kernel -- the others run on k_anneal_csr_rank1.
-#include "mi_sa_device.h"
+#include "mi_sa_chain_ends.h"
 
 namespace mi_sa_impl {
 
@@ -528,10 +528,7 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
             e += (a.lin64 ? a.lin64[i] : (double)a.lin[i]) + 0.5 * acc;
         }
         e = wave_sum_f64(e);
-        if (lane == 0) {
-            const double cp64 = a.ell_val64 ? a.c_pair64 : (double)a.c_pair;
-            a.energy[r] = e + cp64 * 0.5 * ((double)cnt * (double)cnt - (double)cnt2) + a.offset;
-        }
+        if (lane == 0) a.energy[r] = binary_chain_finish(a.ell_val64, a.c_pair, a.c_pair64, a.offset, e, cnt, cnt2);
     }
     if (lane == 0) atomicAdd(&a.stats[1], accepted);
 #ifdef MI_K2P_PROFILE

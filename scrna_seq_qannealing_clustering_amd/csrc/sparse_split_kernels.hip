@@ -24,7 +24,7 @@
 // instead of ten at the head of every fourth slot.  The state is one 32-bit LDS cell per seat (ds_read_b32 gathers cost
 // a lone wavefront two thirds of what ds_read_u16 ones do); NW = 1 is the same step without the exchange: the
 // one-wavefront-per-replica kernel for few replicas on models too small for wider blocks.
-#include "mi_sa_device.h"
+#include "mi_sa_chain_ends.h"
 
 namespace mi_sa_impl {
 
@@ -73,27 +73,14 @@ __global__ void __launch_bounds__(64 * NW, 1) k_anneal_csr_rank1_split(EllArgs a
     const uint32_t gid = a.replica_offset + (uint32_t)r;
     const int n = a.n, slots = a.slots, blocks = slots / NW;        // slots is a multiple of NW (launcher)
     const int comm_at = slots * 256, ring_at = comm_at + kCommBytes;
-    const uint8_t *init = static_cast<const uint8_t *>(a.init);
     int *comm = reinterpret_cast<int *>(lds + comm_at);
     const int gps = (slots + 3) / 4;                                // Philox groups (of four slots) per sweep
 
     // ---- initial state: wave w fills its own slots; S = sum x over the whole replica ----
-    int S = 0;
-    for (int b = 0; b < blocks; ++b) {
-        const int t = b * NW + w, i = t * 64 + lane;
-        bool x;
-        const bool real = i < n && a.lin[i] < INFINITY;            // (+inf linear term = hole of a padded layout: stays 0)
-        if (init) {
-            x = real && init[(size_t)r * n + i] != 0;
-        } else {
-            uint32_t iw[4];
-            philox4x32_10((uint32_t)((t >> 2) * 64 + lane), 0u, gid, 1u, a.seed_lo, a.seed_hi, iw);
-            const int c = t & 3;
-            x = real && ((c == 0 ? iw[0] : (c == 1 ? iw[1] : (c == 2 ? iw[2] : iw[3]))) >> 31);
-        }
+    // (K2s takes no model with pair weights: no weighted slot)
+    int S = binary_initial_state(a, r, gid, lane, w, NW, -1, 0, [&](int i, bool x) {
         reinterpret_cast<uint32_t *>(lds)[i] = x ? 0x3c00u : 0u;
-        S += __popcll(__ballot(x));
-    }
+    });
     if constexpr (NW > 1) {
         if (lane == 0) comm[w] = S;
         __syncthreads();
@@ -382,10 +369,8 @@ __global__ void __launch_bounds__(64 * NW, 1) k_anneal_csr_rank1_split(EllArgs a
         e = 0.0; cnt = 0;
         for (int k = 0; k < NW; ++k) { e += esum[k]; cnt += csum[k]; }
     }
-    if (threadIdx.x == 0) {
-        const double cp64 = a.ell_val64 ? a.c_pair64 : (double)a.c_pair;
-        a.energy[r] = e + cp64 * 0.5 * (double)cnt * (double)(cnt - 1) + a.offset;
-    }
+    // (cnt2 = cnt: K2s takes no model with pair weights -- its prologue and this loop count plain on-variables)
+    if (threadIdx.x == 0) a.energy[r] = binary_chain_finish(a.ell_val64, a.c_pair, a.c_pair64, a.offset, e, cnt, cnt);
     if (lane == 0) atomicAdd(&a.stats[1], accepted);
 }
 
@@ -415,7 +400,6 @@ __global__ void __launch_bounds__(TW ? 128 : 64, 1) k_anneal_csr_rank1_wide(EllA
     const int r = blockIdx.x;
     const uint32_t gid = a.replica_offset + (uint32_t)r;
     const int n = a.n, slots = a.slots, blocks = slots / SPB;       // slots is a multiple of SPB (launcher)
-    const uint8_t *init = static_cast<const uint8_t *>(a.init);
     // TW: the ring behind the cells, two groups of [4 / SPB steps][64 lanes][SPB thresholds] (1 KB each)
     const uint32_t ring_lane = (uint32_t)slots * 256u + (uint32_t)lane * (4u * SPB);
 
@@ -460,22 +444,9 @@ __global__ void __launch_bounds__(TW ? 128 : 64, 1) k_anneal_csr_rank1_wide(EllA
     // than 1 is swept by a serial loop -- weighted_slot_sweep)
     const int wslot = WGT ? a.wslot : -1;
     const int wl = wslot >= 0 ? a.wgt[lane] : 0;
-    int S = 0;
-    for (int t = 0; t < slots; ++t) {
-        const int i = t * 64 + lane;
-        bool x;
-        const bool real = i < n && a.lin[i] < INFINITY;            // (+inf linear term = hole of a padded layout: stays 0)
-        if (init) {
-            x = real && init[(size_t)r * n + i] != 0;
-        } else {
-            uint32_t iw[4];
-            philox4x32_10((uint32_t)((t >> 2) * 64 + lane), 0u, gid, 1u, a.seed_lo, a.seed_hi, iw);
-            const int c = t & 3;
-            x = real && ((c == 0 ? iw[0] : (c == 1 ? iw[1] : (c == 2 ? iw[2] : iw[3]))) >> 31);
-        }
+    int S = binary_initial_state(a, r, gid, lane, 0, 1, wslot, wl, [&](int i, bool x) {
         reinterpret_cast<uint32_t *>(lds)[i] = x ? 0x3c00u : 0u;
-        S += (WGT && t == wslot) ? (int)wave_sum_i64(x ? (long long)wl : 0ll) : __popcll(__ballot(x));
-    }
+    });
 
     constexpr int G = D / 4;
     const __amdgpu_buffer_rsrc_t rs_adj = __builtin_amdgcn_make_buffer_rsrc(
@@ -766,8 +737,7 @@ __global__ void __launch_bounds__(TW ? 128 : 64, 1) k_anneal_csr_rank1_wide(EllA
     }
     e = wave_sum_f64(e);
     if (lane == 0) {
-        const double cp64 = a.ell_val64 ? a.c_pair64 : (double)a.c_pair;
-        a.energy[r] = e + cp64 * 0.5 * ((double)cnt * (double)cnt - (double)cnt2) + a.offset;
+        a.energy[r] = binary_chain_finish(a.ell_val64, a.c_pair, a.c_pair64, a.offset, e, cnt, cnt2);
         atomicAdd(&a.stats[1], accepted);
     }
 }
