@@ -140,6 +140,7 @@ typedef struct mi_prep_matrix mi_prep_matrix;
 #define MI_PREP_MAX_PCS      128            /* p of mi_prep_project */
 #define MI_PREP_ROW_SLICE    256            /* rows per partial sum of the column reductions */
 #define MI_PREP_GRAM_CHUNK   512            /* cells whose products accumulate in f32 before the fp64 sum over chunks */
+#define MI_PREP_GRAM_WORKSPACE (256ll << 20)  /* bytes of f32 chunk tiles in flight in mi_prep_gram: more chunks take more passes */
 #define MI_PREP_MAX_DESIGN_COLS 9           /* q of mi_prep_select_regressed: the intercept + 8 covariates */
 #define MI_PREP_SCT_MAX_FIT_CELLS 8192      /* cells of mi_prep_nb_fit: a gene's counts are 32 KB of LDS */
 

@@ -43,7 +43,7 @@ constexpr int kRowSlice = MI_PREP_ROW_SLICE;
 constexpr int kChunk = MI_PREP_GRAM_CHUNK;
 constexpr int kTile = 128, kKC = 32;
 constexpr int kProjCells = 64, kProjCols = MI_PREP_MAX_PCS;
-constexpr size_t kGramWorkspace = (size_t)256 << 20;                    // bytes of f32 tiles in flight between the two Gram kernels
+constexpr size_t kGramWorkspace = (size_t)MI_PREP_GRAM_WORKSPACE;                // bytes of f32 tiles in flight between the two Gram kernels
 constexpr int kMaxQ = MI_PREP_MAX_DESIGN_COLS;
 
 __global__ void __launch_bounds__(256) k_prep_normalize(const float *__restrict__ X, float *__restrict__ Y, int n, int g,

@@ -53,6 +53,7 @@ from . import _lib
 MAX_FEATURES = 4096        # MI_PREP_MAX_FEATURES (include/mi_prep.h)
 MAX_PCS = 128              # MI_PREP_MAX_PCS
 GRAM_CHUNK = 512           # MI_PREP_GRAM_CHUNK
+GRAM_WORKSPACE = 256 << 20  # MI_PREP_GRAM_WORKSPACE: bytes of f32 chunk tiles (128 x 128) one pass of gram() keeps in flight
 MAX_COVARIATES = 8         # MI_PREP_MAX_DESIGN_COLS - 1 (the intercept)
 
 MAX_NNZ = 2 ** 31 - 1      # MI_PREP_MAX_NNZ
