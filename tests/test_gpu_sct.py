@@ -11,7 +11,8 @@ standard errors, over three permutations of the cells of each of the three input
 sensitivity 2.9e-8 se, so TAU = 2.9e-6 (the condition TAU <= 1e-3 holds with three decades to spare); on an MI355X the
 device's largest deviation from the restatement over all shapes is 2.8e-8 se (m = 257; 2.4e-11 at m = 8192) and the stopping
 number evaluated on the host at the device's parameters at most 1.1e-8 (``test_fit_matches_the_restatement`` prints both;
-DESIGN.md section 5c "SCTransform").
+DESIGN.md section 5c "SCTransform").  Every gene here converges; genes at the round limit, failed fits, the alpha bounds, the
+Poisson rule's edge and counts of 2^24 are tests/test_gpu_sct_edges.py.
 
 Residual moments: variance within the project's RTOL about the device's own mean, mean within 1e-9 sum |r| / n.  Z: stage 1
 within 2^-24 |ref| + 1e-12 (x + mu) / sigma of the fp64 expression; stages 2 - 5 bit for bit the numpy expression of
