@@ -56,12 +56,25 @@ __device__ __forceinline__ float half_hi(uint32_t w) { return (float)__builtin_b
 // slot t + 1 are unpacked under the gathers of slot t, next to the own-cell terms -- measured against N16 = 1 on the TW
 // form: 21.08 against 21.27 ms on the benchmark's model.  The D = 16 form WITHOUT a threshold wavefront keeps the 32-bit
 // packing: there the unpack at the top of the slot cost more than the bytes saved (profiles/r05_k2p_nbr16_ab.txt).
-template <int D, bool TW, bool WGT = false, int RW = D, int N16 = 0>
+// Round 6 takes fixed costs off the sweeping wavefront of the N16 = 2 forms, where every instruction of that wavefront is
+// on the critical path (an LDS instruction costs it 12-19 cycles, a vector one 5):
+// GR ("group-wide reads"): the lane's own cells of a group of four slots (only that lane writes them, each in its own
+// slot) and the group's thresholds are read once after the group's barrier -- two ds_read2st64_b32 (the cells lie 256
+// bytes apart) and two ds_read_b128 on one address each, instead of four ds_read_b32 and four ds_read_b64 on eight; the
+// threshold wavefront writes two ds_write_b128 instead of four ds_write_b64 (ring: [2 halves][64 lanes][16 bytes] per group,
+// the same 2048 bytes).  Slot 0's counted wait proves all four back; slots 1 to 3 wait for nothing but their gathers.
+// CY ("carry"; sweeps of six slots and more -- the launcher's choice): the adjacency prefetch runs on over the end of a
+// sweep into the next one instead of fetching the last slot again for nothing and filling the pipeline anew (one exposed L2
+// round trip and ~25 instructions per sweep).
+// All forms: the fp64 energy epilogue requests a slot's indices and values together (two round trips per slot and
+// replica instead of 2 D dependent ones).  profiles/r06_k2p_fixed_costs_ab.txt.
+template <int D, bool TW, bool WGT = false, int RW = D, int N16 = 0, bool CY = false>
 __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_pair(EllArgs a)
 {
     static_assert(RW > D - 4 && RW <= D, "trimmed rows drop part of the last group of four only");
     static_assert(N16 == 0 || !WGT, "the weighted form keeps the 32-bit packing");
     static_assert(N16 != 2 || (TW && D == 16), "the pipelined unpack lives in the threshold-wavefront form's gather window");
+    static_assert(!CY || N16 == 2, "the carried prefetch is the pipelined form's");
     extern __shared__ __attribute__((aligned(16))) char lds[];      // cell of variable i at byte 4 i
     const int lane = threadIdx.x & 63;
     const int pair = blockIdx.x;                                    // replicas 2 pair, 2 pair + 1
@@ -72,8 +85,17 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
     const int n = a.n, slots = a.slots;
     const uint8_t *init = static_cast<const uint8_t *>(a.init);
     uint32_t *cell = reinterpret_cast<uint32_t *>(lds);
+    // GR ("group-wide reads", round 6; the N16 = 2 forms): what a group of four slots reads of its lane's own cells and
+    // thresholds is read once, after the group's barrier
+    // (`make dbg DBG_FLAGS=-DMI_K2P_NO_GROUPREADS` / `-DMI_K2P_NO_CARRY` / `-DMI_K2P_NO_EPI`: the A/B arms without a part)
+#ifdef MI_K2P_NO_GROUPREADS
+    constexpr bool GR = false;
+#else
+    constexpr bool GR = N16 == 2;
+#endif
     // TW: the ring of thresholds behind the cells: 2 groups x 4 slots x 64 lanes x (thrA, thrB)
-    const uint32_t ring_lane = (uint32_t)slots * 256u + (uint32_t)lane * 8u;
+    // (GR: a group's 2048 bytes are [2 halves][64 lanes][thrA, thrB of slot 4 g + 2 h, then of slot 4 g + 2 h + 1])
+    const uint32_t ring_lane = (uint32_t)slots * 256u + (uint32_t)lane * (GR ? 16u : 8u);
 
     if constexpr (TW) {
         if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 1) {
@@ -98,6 +120,15 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
                     philox4x32_10((uint32_t)((t >> 2) * 64 + lane), sw, gidB, 0u, a.seed_lo, a.seed_hi, wb);
 #endif
                     const uint32_t at = ring_lane + buf;
+                    if constexpr (GR) {
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            const f32x2_t t0 = neglog_u2(wa[2 * h], wb[2 * h]) * f32x2_t{TA, TB};
+                            const f32x2_t t1 = neglog_u2(wa[2 * h + 1], wb[2 * h + 1]) * f32x2_t{TA, TB};
+                            const f32x4 thr = {t0.x, t0.y, t1.x, t1.y};
+                            asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(at), "v"(thr), "n"(h * 1024) : "memory");
+                        }
+                    } else
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const f32x2_t thr = neglog_u2(wa[c], wb[c]) * f32x2_t{TA, TB};
@@ -162,22 +193,26 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
     struct NbrPack { u32x4 w[GC]; };                                // N16: the packed neighbour dwords of a slot
     const int lane16 = lane * 16;
     // N16: block b of a slot's [GC + G][64][4] image (constant parts of the offset fold into the 12-bit immediate)
-    auto fetch_block16 = [&](int t, int b) {
-        const int tt = t < slots ? t : slots - 1;
-        return __builtin_amdgcn_raw_buffer_load_b128(rs_adj, lane16 + (b & 3) * 1024, tt * SLOT_BYTES + (b >> 2) * 4096, 0);
+    // a slot past the last one: clamped (fetched for nothing), or -- `wrap`, the carried prefetch: at most five slots ahead
+    // in sweeps of six slots and more -- the slot of the NEXT sweep it stands for
+    using std::integral_constant;
+    using no_wrap = integral_constant<bool, false>;
+    auto slot_of = [&](int t, auto wrap) { return t < slots ? t : (decltype(wrap)::value ? t - slots : slots - 1); };
+    auto fetch_block16 = [&](int t, int b, auto wrap) {
+        return __builtin_amdgcn_raw_buffer_load_b128(rs_adj, lane16 + (b & 3) * 1024, slot_of(t, wrap) * SLOT_BYTES + (b >> 2) * 4096, 0);
     };
-    auto fetch_nbr16 = [&](int t) {
+    auto fetch_nbr16 = [&](int t, auto wrap) {
         NbrPack q;
 #pragma unroll
-        for (int b = 0; b < GC; ++b) q.w[b] = fetch_block16(t, b);
+        for (int b = 0; b < GC; ++b) q.w[b] = fetch_block16(t, b, wrap);
         return q;
     };
-    auto fetch_val16 = [&](int t) {                                 // (.col stays unset: the pipelined form keeps it in a NbrPack)
+    auto fetch_val16 = [&](int t, auto wrap) {                      // (.col stays unset: the pipelined form keeps it in a NbrPack)
         SlotAdj p;
 #pragma unroll
-        for (int g = 0; g < G; ++g) p.val[g] = fetch_block16(t, GC + g);
+        for (int g = 0; g < G; ++g) p.val[g] = fetch_block16(t, GC + g, wrap);
         if constexpr (RW < D) p.lin = p.val[G - 1][3];
-        else p.lin = __builtin_amdgcn_raw_buffer_load_b32(rs_lin, lane * 4, (t < slots ? t : slots - 1) * 256, 0);
+        else p.lin = __builtin_amdgcn_raw_buffer_load_b32(rs_lin, lane * 4, slot_of(t, wrap) * 256, 0);
         return p;
     };
     uint32_t m16 = 0xffffu;
@@ -195,8 +230,8 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
     auto fetch_adj = [&](int t) {
 #endif
         if constexpr (N16 != 0) {
-            SlotAdj p = fetch_val16(t);
-            const NbrPack q = fetch_nbr16(t);
+            SlotAdj p = fetch_val16(t, no_wrap{});
+            const NbrPack q = fetch_nbr16(t, no_wrap{});
 #pragma unroll
             for (int b = 0; b < GC; ++b) p.col[b] = q.w[b];
             return p;
@@ -259,7 +294,27 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
     // operation the compiler may place before it is waited for as well (scripts/check_asm_lds.py checks the emitted
     // code for a read of such a register ahead of its wait at build time).
     // N16 = 2: `nxt` = the packed neighbour dwords of slot t + 1 (fetched a slot ago); addr[] holds slot t's on entry, slot t + 1's on exit
-    auto slot_body = [&](auto c_in_group, int t, const SlotAdj &cur, NbrPack &nxt, uint32_t wordA, uint32_t wordB) {
+    // GR: the lane's own cells and the thresholds of the group's four slots, read at the top of the group (group_reads) --
+    // a lane's own cell is written by that lane in that cell's slot only, and the threshold wavefront wrote the whole group
+    // before the barrier: four LDS instructions and one address a group instead of eight and eight.  They are inline asm
+    // as the gathers are: slot 0's counted wait names all of them (4 + NK0 reads are in flight there, NK0 <= 15 outstanding
+    // means the four are back), the later slots need no wait for them.
+    // (own[h] = the cells of slots 4 g + 2 h and 4 g + 2 h + 1, in the register pair the read wrote: a copy made before the
+    // wait would read the pair too early)
+    struct GroupPre { u32x2 own[2]; f32x4 thr[2]; };
+    auto group_reads = [&](int t, GroupPre &gp) {
+        const uint32_t rb = ring_lane + ring_buf;
+        asm volatile("ds_read_b128 %0, %1" : "=v"(gp.thr[0]) : "v"(rb));
+        asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(gp.thr[1]) : "v"(rb));
+        // own cells 256 bytes apart: one address.  The last group of a sweep of 4 g + 1 .. 4 g + 3 slots (wave-uniform): the
+        // ring lies behind the cells and is not read as one -- a slot that does not exist reads its neighbour's cell again
+        const uint32_t cb = (uint32_t)(t * 256 + lane * 4);
+        if (t + 1 < slots) asm volatile("ds_read2st64_b32 %0, %1 offset1:1" : "=v"(gp.own[0]) : "v"(cb));
+        else asm volatile("ds_read2st64_b32 %0, %1" : "=v"(gp.own[0]) : "v"(cb));
+        if (t + 3 < slots) asm volatile("ds_read2st64_b32 %0, %1 offset0:2 offset1:3" : "=v"(gp.own[1]) : "v"(cb));
+        else asm volatile("ds_read2st64_b32 %0, %1" : "=v"(gp.own[1]) : "v"((t + 2 < slots ? t + 2 : slots - 1) * 256 + lane * 4));
+    };
+    auto slot_body = [&](auto c_in_group, int t, const SlotAdj &cur, NbrPack &nxt, uint32_t wordA, uint32_t wordB, GroupPre &gp) {
         constexpr int C = decltype(c_in_group)::value;
         const int i = t * 64 + lane;
         uint32_t own;                                               // [x_A | x_B] of this lane's variable
@@ -290,9 +345,9 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
             const int NK = g0 == 0 ? NK0 : (RW - 4 * g0 < 16 ? RW - 4 * g0 : 16);
             uint32_t word[16];                                      // (words past NK are never read nor written)
             // the packed neighbour word IS the LDS byte address of its cell (one wavefront per workgroup, no static LDS)
-            if (g0 == 0) asm volatile("ds_read_b32 %0, %1" : "=v"(own) : "v"(i * 4));
+            if (g0 == 0 && !GR) asm volatile("ds_read_b32 %0, %1" : "=v"(own) : "v"(i * 4));
             // (TW: the ring read second, so that "at most 15 reads outstanding" below means the own cell and the thresholds are back)
-            if (g0 == 0 && TW) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(thr2) : "v"(ring_lane + ring_buf), "n"(C * 512));
+            if (g0 == 0 && TW && !GR) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(thr2) : "v"(ring_lane + ring_buf), "n"(C * 512));
 #pragma unroll
             for (int k = 0; k < 16; ++k)
                 if (k < NK)
@@ -311,7 +366,18 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
                 // width) outstanding the lane's own cell and the thresholds are here -- everything that depends only on
                 // them is computed UNDER the gathers (the second wait names its results, so it cannot sink below it)
                 // (N16 = 2: the next slot's neighbour dwords pass through this wait, so their unpack cannot rise above the gathers)
-                if constexpr (N16 == 2)
+                if constexpr (GR) {
+                    // (slot 0: the group's reads are the oldest in flight.  Slots 1 to 3: nothing to wait for; the empty
+                    // statement keeps the own-cell terms and the unpack below the gathers' issue as the wait does)
+                    if constexpr (C == 0)
+                        asm volatile("s_waitcnt lgkmcnt(%6)"
+                                     : "+v"(gp.own[0]), "+v"(gp.own[1]), "+v"(gp.thr[0]), "+v"(gp.thr[1]), "+v"(nxt.w[0]), "+v"(nxt.w[1])
+                                     : "n"(NK0 < 15 ? NK0 : 15) : "memory");
+                    else
+                        asm volatile("" : "+v"(gp.own[C >> 1]), "+v"(gp.thr[C >> 1]), "+v"(nxt.w[0]), "+v"(nxt.w[1]));
+                    own = gp.own[C >> 1][C & 1];
+                    thr2 = f32x2_t{gp.thr[C >> 1][2 * (C & 1)], gp.thr[C >> 1][2 * (C & 1) + 1]};
+                } else if constexpr (N16 == 2)
                     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(own), "+v"(thr2), "+v"(nxt.w[0]), "+v"(nxt.w[1]) : "n"(NK0 < 15 ? NK0 : 15) : "memory");
                 else
                 asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(own), "+v"(thr2) : "n"(NK0 < 15 ? NK0 : 15) : "memory");
@@ -422,7 +488,50 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
         K2P_TICK(t_rounds);
     };
 
-    using std::integral_constant;
+    // N16 = 2: the values one slot ahead (cP / cQ), the neighbour dwords TWO (cNA / cNB), the unpacked addresses of one slot.
+    // At the top of a group of four at slot t: cP = values of t, cNA = neighbour dwords of t + 1, addr[] = addresses of t.
+    // CY: the prefetch index wraps (slot_of), so a sweep ends with exactly that for slot 0 of the next one and only the first
+    // sweep of a launch fills the pipeline (the last one fetches slots 0 and 1 for nothing) -- a sweep of 4 g + 1 or 4 g + 3
+    // slots ends with it in cQ / cNB and moves it over.  (One loop per kernel: both loops in one cost 40 registers.)
+    SlotAdj cP, cQ;
+    NbrPack cNA, cNB;
+    GroupPre gp;
+    auto sweep16 = [&]() {
+        constexpr bool W = CY;
+        const integral_constant<bool, CY> wrap;
+#pragma unroll 1
+        for (int t = 0; t < slots; t += 4) {
+            K2P_TICK(t_top);
+            __builtin_amdgcn_s_barrier();                           // this group's thresholds are in the ring
+            K2P_TICK(t_barrier);
+            if constexpr (GR) group_reads(t, gp);
+            cQ = fetch_val16(t + 1, wrap);
+            cNB = fetch_nbr16(t + 2, wrap);
+            slot_body(integral_constant<int, 0>{}, t, cP, cNA, wa[0], wb[0], gp);
+            if (t + 1 < slots) {                                    // wave-uniform
+                cP = fetch_val16(t + 2, wrap);
+                cNA = fetch_nbr16(t + 3, wrap);
+                slot_body(integral_constant<int, 1>{}, t + 1, cQ, cNB, wa[1], wb[1], gp);
+                if (t + 2 < slots) {
+                    cQ = fetch_val16(t + 3, wrap);
+                    cNB = fetch_nbr16(t + 4, wrap);
+                    slot_body(integral_constant<int, 2>{}, t + 2, cP, cNA, wa[2], wb[2], gp);
+                    if (!W || t + 3 < slots) {
+                        cP = fetch_val16(t + 4, wrap);
+                        cNA = fetch_nbr16(t + 5, wrap);
+                        if (t + 3 < slots) slot_body(integral_constant<int, 3>{}, t + 3, cQ, cNB, wa[3], wb[3], gp);
+                    } else {
+                        cP = cQ;
+                        cNA = cNB;
+                    }
+                }
+            } else if (W) {
+                cP = cQ;
+                cNA = cNB;
+            }
+            ring_buf ^= 2048u;
+        }
+    };
     for (int s = 0; s < a.num_sweeps; ++s) {
         if constexpr (!TW) {
             if (a.temps_per_replica) {
@@ -434,35 +543,14 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
         }
         const uint32_t sw = (uint32_t)s + a.sweep_offset;
         if constexpr (N16 == 2) {
-            // the values one slot ahead as below, the neighbour dwords TWO (NA / NB), the unpacked addresses of one slot
-            SlotAdj P = fetch_val16(0), Q;
-            NbrPack NA = fetch_nbr16(0), NB;
+            if (!CY || s == 0) {
+                cP = fetch_val16(0, no_wrap{});
+                cNA = fetch_nbr16(0, no_wrap{});
 #pragma unroll
-            for (int k = 0; k < (RW < 16 ? RW : 16); ++k) addr[k] = unpack16(NA.w, k);
-            NA = fetch_nbr16(1);
-#pragma unroll 1
-            for (int t = 0; t < slots; t += 4) {
-                K2P_TICK(t_top);
-                __builtin_amdgcn_s_barrier();                       // this group's thresholds are in the ring
-                K2P_TICK(t_barrier);
-                Q = fetch_val16(t + 1);
-                NB = fetch_nbr16(t + 2);
-                slot_body(integral_constant<int, 0>{}, t, P, NA, wa[0], wb[0]);
-                if (t + 1 < slots) {                                // wave-uniform
-                    P = fetch_val16(t + 2);
-                    NA = fetch_nbr16(t + 3);
-                    slot_body(integral_constant<int, 1>{}, t + 1, Q, NB, wa[1], wb[1]);
-                    if (t + 2 < slots) {
-                        Q = fetch_val16(t + 3);
-                        NB = fetch_nbr16(t + 4);
-                        slot_body(integral_constant<int, 2>{}, t + 2, P, NA, wa[2], wb[2]);
-                        P = fetch_val16(t + 4);
-                        NA = fetch_nbr16(t + 5);
-                        if (t + 3 < slots) slot_body(integral_constant<int, 3>{}, t + 3, Q, NB, wa[3], wb[3]);
-                    }
-                }
-                ring_buf ^= 2048u;
+                for (int k = 0; k < (RW < 16 ? RW : 16); ++k) addr[k] = unpack16(cNA.w, k);
+                cNA = fetch_nbr16(1, no_wrap{});
             }
+            sweep16();
         } else {
             NbrPack none;
             // four slots per trip (one Philox block per replica), the adjacency one slot ahead in two register sets
@@ -478,15 +566,15 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
                     philox4x32_10((uint32_t)((t >> 2) * 64 + lane), sw, gidB, 0u, a.seed_lo, a.seed_hi, wb);
                 }
                 Q = fetch_adj(t + 1);
-                slot_body(integral_constant<int, 0>{}, t, P, none, wa[0], wb[0]);
+                slot_body(integral_constant<int, 0>{}, t, P, none, wa[0], wb[0], gp);
                 if (t + 1 < slots) {                                    // wave-uniform
                     P = fetch_adj(t + 2);
-                    slot_body(integral_constant<int, 1>{}, t + 1, Q, none, wa[1], wb[1]);
+                    slot_body(integral_constant<int, 1>{}, t + 1, Q, none, wa[1], wb[1], gp);
                     if (t + 2 < slots) {
                         Q = fetch_adj(t + 3);
-                        slot_body(integral_constant<int, 2>{}, t + 2, P, none, wa[2], wb[2]);
+                        slot_body(integral_constant<int, 2>{}, t + 2, P, none, wa[2], wb[2], gp);
                         P = fetch_adj(t + 4);
-                        if (t + 3 < slots) slot_body(integral_constant<int, 3>{}, t + 3, Q, none, wa[3], wb[3]);
+                        if (t + 3 < slots) slot_body(integral_constant<int, 3>{}, t + 3, Q, none, wa[3], wb[3], gp);
                     }
                 }
                 if constexpr (TW) ring_buf ^= 2048u;
@@ -497,6 +585,11 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
     }
 
     // ---- epilogue: states out, exact fp64 energies (same sums as k_anneal_csr_rank1) ----
+    // The sums and their order are the specification's; the order of the loads is not: per slot all the neighbour indices
+    // and all the values are requested together, then the cells, then the additions in the order of k -- two round trips
+    // per slot and replica instead of 2 D dependent ones -- and the fp64 / fp32 choice of the values is made per slot, not
+    // per entry (one copy of the loop: two cost the weighted form's sweep loop a register).
+    const bool has64 = a.ell_val64 != nullptr;
 #pragma unroll 1
     for (int rep = 0; rep < 2; ++rep) {
         if (rep == 1 && !liveB) break;
@@ -519,12 +612,34 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
             }
             if (!on) continue;
             double acc = 0.0;
+#ifdef MI_K2P_NO_EPI
             for (int k = 0; k < D; ++k) {
                 const size_t at = ((size_t)t * D + k) * 64 + lane;
                 const uint32_t cc = a.ell_col[at];
                 const double vv = a.ell_val64 ? a.ell_val64[at] : (double)a.ell_val[at];
                 if (((cell[cc] >> sh) & 0xffffu) != 0u) acc += vv;
             }
+#else
+#pragma unroll
+            for (int k0 = 0; k0 < D; k0 += 16) {
+                uint32_t cc[16], cw[16];
+                double vv[16];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) cc[k] = a.ell_col[((size_t)t * D + k0 + k) * 64 + lane];
+                if (has64) {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) vv[k] = a.ell_val64[((size_t)t * D + k0 + k) * 64 + lane];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) vv[k] = (double)a.ell_val[((size_t)t * D + k0 + k) * 64 + lane];
+                }
+#pragma unroll
+                for (int k = 0; k < 16; ++k) cw[k] = cell[cc[k]];
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (((cw[k] >> sh) & 0xffffu) != 0u) acc += vv[k];
+            }
+#endif
             e += (a.lin64 ? a.lin64[i] : (double)a.lin[i]) + 0.5 * acc;
         }
         e = wave_sum_f64(e);
@@ -549,9 +664,17 @@ int mi_launch_csr_rank1_pair(const EllArgs &a, const AnnealPlan &plan, hipStream
     if (plan.nbr16) return fail(MI_EUNSUPPORTED, "the timing builds are arms of the 32-bit packing: set k2_nbr16 = 2");
 #endif
     const int rw = plan.trim_rw ? plan.trim_rw : plan.D;
+    // the pipelined form carries its prefetch over the sweep boundary where a sweep is longer than the prefetch is deep
+#ifdef MI_K2P_NO_CARRY
+    const bool carry = false;
+#else
+    const bool carry = a.slots >= 6;
+#endif
 #define MI_K2P(D_, TW_, WGT_, RW_, N16_) \
-    if (plan.D == D_ && plan.tw == TW_ && plan.weighted == WGT_ && rw == RW_ && (plan.nbr16 ? N16_ != 0 : N16_ == 0)) \
-        return launch_planned(k_anneal_csr_rank1_pair<D_, TW_, WGT_, RW_, N16_>, a, plan, st);
+    if (plan.D == D_ && plan.tw == TW_ && plan.weighted == WGT_ && rw == RW_ && (plan.nbr16 ? N16_ != 0 : N16_ == 0)) { \
+        if (N16_ == 2 && carry) return launch_planned(k_anneal_csr_rank1_pair<D_, TW_, WGT_, RW_, N16_, N16_ == 2>, a, plan, st); \
+        return launch_planned(k_anneal_csr_rank1_pair<D_, TW_, WGT_, RW_, N16_>, a, plan, st); \
+    }
     MI_K2P(16, true, true, 16, 0) MI_K2P(16, false, true, 16, 0)                          // pair-term weights
     MI_K2P(16, true, false, 15, 2) MI_K2P(16, true, false, 14, 2) MI_K2P(16, true, false, 13, 2)   // trimmed rows, 16-bit neighbour words
     MI_K2P(16, true, false, 15, 0) MI_K2P(16, true, false, 14, 0) MI_K2P(16, true, false, 13, 0)   // trimmed rows
