@@ -257,6 +257,29 @@ def clustering_dqm(G, num_of_clusters, gamma, sampler=None, sampler_kwargs: Opti
     return sampleset
 
 
+def _modularity_kwargs(beta_range, merge_interval, stability, consensus, split_disconnected, sampler_kwargs) -> dict:
+    """The sampler keywords of the modularity drivers.  Default schedule: 16000 sweeps over ``beta_range``
+    (modularity_beta_range) -- single-site moves over more labels than communities need the time to merge a community
+    split across two labels; 256 reads as the sampler's default.  The drivers' own options are
+    passed on only when set; ``sampler_kwargs`` overrides all of it."""
+    kw = dict(num_sweeps=16000, beta_range=beta_range)
+    if merge_interval is not None:
+        kw["merge_interval"] = merge_interval
+    for key, on in (("stability", stability), ("consensus", consensus), ("split_disconnected", split_disconnected)):
+        if on:
+            kw[key] = True
+    kw.update(sampler_kwargs or {})
+    return kw
+
+
+def _attach_modularity(sampleset, model):
+    """``info["modularity"]`` = ``-energy / m`` of every record, and ``info["split_modularity"]`` beside ``split_energy``."""
+    m = model.info["m"]
+    sampleset.info["modularity"] = -np.asarray(sampleset.record["energy"], dtype=np.float64) / m
+    if "split_energy" in sampleset.info:
+        sampleset.info["split_modularity"] = -np.asarray(sampleset.info["split_energy"], dtype=np.float64) / m
+
+
 def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sampler=None,
                           sampler_kwargs: Optional[dict] = None, verbose=False, merge_interval: Optional[int] = None,
                           stability: bool = False, consensus: bool = False, split_disconnected: bool = False):
@@ -278,22 +301,10 @@ def clustering_modularity(G, resolution: float = 1.0, max_clusters: int = 16, sa
     communities and can only raise the modularity: ``info["split_modularity"] = -split_energy / m``."""
     from .models import build_modularity_potts, modularity_beta_range
     model = build_modularity_potts(G, resolution, max_clusters)
-    # default schedule: 16000 sweeps over modularity_beta_range -- single-site moves over more labels than communities
-    # need the time to merge a community split across two labels (DESIGN.md section 5); 256 reads as the sampler's default
-    kw = dict(num_sweeps=16000, beta_range=modularity_beta_range(model))
-    if merge_interval is not None:
-        kw["merge_interval"] = merge_interval
-    if stability:
-        kw["stability"] = True
-    if consensus:
-        kw["consensus"] = True
-    if split_disconnected:
-        kw["split_disconnected"] = True
-    kw.update(sampler_kwargs or {})
+    kw = _modularity_kwargs(modularity_beta_range(model), merge_interval, stability, consensus, split_disconnected,
+                            sampler_kwargs)
     sampleset = _sampler(sampler).sample_dqm(model, **kw)
-    sampleset.info["modularity"] = -np.asarray(sampleset.record["energy"], dtype=np.float64) / model.info["m"]
-    if "split_energy" in sampleset.info:
-        sampleset.info["split_modularity"] = -np.asarray(sampleset.info["split_energy"], dtype=np.float64) / model.info["m"]
+    _attach_modularity(sampleset, model)
     if verbose:
         print("Modularity: {}\nSolution: {}".format(float(np.max(sampleset.info["modularity"])), sampleset.first.sample))
     return sampleset
@@ -317,16 +328,8 @@ def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=
     from .models import build_modularity_sweep, check_resolutions, modularity_beta_range
     res = check_resolutions(resolutions)
     models = build_modularity_sweep(G, res, max_clusters)
-    kw = dict(num_sweeps=16000, beta_range=[modularity_beta_range(m) for m in models])
-    if merge_interval is not None:
-        kw["merge_interval"] = merge_interval
-    if stability:
-        kw["stability"] = True
-    if consensus:
-        kw["consensus"] = True
-    if split_disconnected:
-        kw["split_disconnected"] = True
-    kw.update(sampler_kwargs or {})
+    kw = _modularity_kwargs([modularity_beta_range(m) for m in models], merge_interval, stability, consensus,
+                            split_disconnected, sampler_kwargs)
     samplesets = _sampler(sampler).sample_dqm_many(models, **kw)
     if stability:
         from .metrics import label_agreement
@@ -334,9 +337,7 @@ def clustering_modularity_sweep(G, resolutions, max_clusters: int = 16, sampler=
         ari = label_agreement(best[1:], best[:-1])["ari"] if len(best) > 1 else np.zeros((0, 0))
     for g, (gamma, model, ss) in enumerate(zip(res, models, samplesets)):
         ss.info["resolution"] = gamma
-        ss.info["modularity"] = -np.asarray(ss.record["energy"], dtype=np.float64) / model.info["m"]
-        if "split_energy" in ss.info:
-            ss.info["split_modularity"] = -np.asarray(ss.info["split_energy"], dtype=np.float64) / model.info["m"]
+        _attach_modularity(ss, model)
         if stability:
             ss.info["ari_to_previous"] = None if g == 0 else float(ari[g - 1, g - 1])
         if verbose:

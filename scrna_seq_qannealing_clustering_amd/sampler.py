@@ -155,7 +155,7 @@ class MI355XSampler:
         ``dimod.DiscreteQuadraticModel`` whose biases have the Potts shape `clustering_dqm` builds
         (DQM_clustering.py:29-43): case-independent linear biases, equal-case quadratic biases."""
         model = dqm if isinstance(dqm, PottsModel) else dqm_to_potts(dqm)
-        return self._sample_potts(model, kwargs)
+        return self._potts_run([model], self._split_kwargs(dict(kwargs)))[0]
 
     def sample_dqm_many(self, models, **kwargs) -> List[SampleSet]:
         """Several node-weighted Potts models that differ only in their pair coefficient and energy offset -- the
@@ -168,80 +168,8 @@ class MI355XSampler:
         ``beta_range`` and a ``batch`` entry with what the groups share: the kernel time and name, the group count, the
         total proposals and accepted moves."""
         models = list(models)
-        wq, cw, w64, c64, offsets = potts_node_weight_groups(models)
-        G = len(models)
-        kw, ignored = self._split_kwargs(dict(kwargs))
-        _check_split(kw, int(kw.get("min_cluster_size") or 0), models)
-        if kw.get("min_cluster_size"):
-            raise ValueError("node weights (a modularity model) together with min_cluster_size are not supported")
-        merge_interval, merge_proposals = self._merge_kwargs(kw, 0)
-        t0 = time.perf_counter()
-        m0 = models[0]
-        n = m0.num_variables
-        seed = self._seed(kw.get("seed"))
-        num_reads, init = self._initial_states(kw, m0.variables, kw.get("num_reads"), "DISCRETE")
-        if num_reads < 1:
-            raise ValueError("'num_reads' should be a positive integer")
-        _check_consensus(kw, m0.num_cases, num_reads)
-        ranges = kw.get("beta_range")
-        per_model = ranges is not None and np.ndim(ranges) == 2
-        if per_model and np.shape(ranges) != (G, 2):
-            raise ValueError("a per-model beta_range needs shape [%d, 2]" % G)
-        scheds = []
-        for g, model in enumerate(models):
-            kg = dict(kw, beta_range=ranges[g]) if per_model else kw
-            scheds.append(self._schedule(kg, lambda model=model: default_potts_beta_range(model)))
-        betas = np.stack([b for b, _, _ in scheds])
-        prob = Problem.potts_csr(m0.rowptr, m0.col, m0.val.astype(np.float32), float(np.float32(m0.c_pair)), n,
-                                 m0.num_cases, lin_offset=m0.lin_offset, device=self.device, order="padded",
-                                 energy_model=(m0.val, m0.c_pair), node_weights=(wq, cw[0], w64))
-        with prob:
-            prob.set_node_weight_groups(cw, c64, offsets)
-            if merge_interval:
-                prob.set_merge_moves(merge_interval, merge_proposals, potts_merge_coefficients(models))
-            init_arr = init
-            if isinstance(init, tuple):           # partial initial states + random remainder (group 0's random rows)
-                prob.anneal(num_reads * G, betas[0, :0], seed, self.replica_offset)
-                rnd, _, _ = prob.fetch(energies=False)
-                rnd = rnd[:num_reads]
-                rnd[: init[1].shape[0]] = init[1]
-                init_arr = rnd
-            if init_arr is not None:
-                init_arr = np.tile(np.asarray(init_arr, dtype=np.uint16), (G, 1))
-            t1 = time.perf_counter()
-            prob.anneal(num_reads * G, betas, seed, self.replica_offset, init_arr)
-            labels, dev_energy, stats = prob.fetch()
-            kernel_ms = prob.kernel_ms()
-            kernel = prob.kernel_name()
-            merges = prob.merges_accepted() if merge_interval else None
-            agree = prob.label_agreement(G) if kw.get("stability") and num_reads >= 2 else None
-            cons = _consensus_info(prob, G, m0, num_reads) if kw.get("consensus") else None
-            comps = prob.components()[0] if kw.get("split_disconnected") else None    # (all groups in one call)
-            t2 = time.perf_counter()
-        batch = {"groups": G, "kernel_ms": kernel_ms, "kernel_name": kernel, "accepted": stats["accepted"],
-                 "proposals": stats["proposals"], "updates_per_s": (stats["proposals"] / (kernel_ms * 1e-3)) if kernel_ms > 0 else None,
-                 "timing": {"upload_s": t1 - t0, "anneal_s": t2 - t1}}
-        out = []
-        for g, model in enumerate(models):
-            rows = slice(g * num_reads, (g + 1) * num_reads)
-            info = {
-                "beta_range": scheds[g][1], "beta_schedule_type": scheds[g][2], "seed": seed,
-                "num_sweeps": int(betas.shape[1]), "num_reads": int(num_reads), "kernel": "potts_csr",
-                "device": self.device, "batch": batch,
-                "energy_evaluation": "device fp64 (caller's coefficients)",
-                "ignored_kwargs": ignored,
-            }
-            if merge_interval:
-                info["merges_accepted"] = merges                  # (all groups together, like "batch")
-            if kw.get("stability"):
-                info["stability"], info["stability_nmi"] = (
-                    mean_pair_agreement(agree["ari"][g], agree["nmi"][g]) if agree is not None else (None, None))
-            if cons is not None:
-                info.update(cons[g])
-            if comps is not None:
-                info.update(_split_info(model, labels[rows], dev_energy[rows], comps[rows]))
-            out.append(SampleSet(labels[rows].astype(np.int32), dev_energy[rows], model.variables, "DISCRETE", info=info))
-        return out
+        groups = potts_node_weight_groups(models)         # (refuses models that are not one graph's node-weighted ones)
+        return self._potts_run(models, self._split_kwargs(dict(kwargs)), groups)
 
     # ------------------------------------------------------------------------------------------
     # internals
@@ -388,13 +316,7 @@ class MI355XSampler:
             dense64 = model.dense_Qs()
             prob = Problem.dense(_symmetric_f32(dense64), offset=model.offset, device=self.device)
         with prob:
-            init_arr = init
-            if isinstance(init, tuple):           # partial initial states + random remainder
-                have = init[1]
-                prob.anneal(num_reads, betas[:0], seed, self.replica_offset)   # RNG init states only
-                rnd, _, _ = prob.fetch(energies=False)
-                rnd[: have.shape[0]] = have
-                init_arr = rnd
+            init_arr = self._random_remainder(prob, num_reads, num_reads, seed, init[1]) if isinstance(init, tuple) else init
             t1 = time.perf_counter()
             prob.anneal(num_reads, betas, seed, self.replica_offset, init_arr,
                         int(kw.get("resync_interval", 0)))
@@ -409,87 +331,120 @@ class MI355XSampler:
         samples = states.astype(np.int8)
         if vartype == "SPIN":
             samples = 2 * samples - 1
-        info = {
-            "beta_range": beta_range, "beta_schedule_type": stype, "seed": seed,
-            "num_sweeps": int(len(betas)), "num_reads": int(num_reads),
-            "kernel": "csr_rank1" if use_csr else "dense", "device": self.device,
-            "timing": {"upload_s": t1 - t0, "anneal_s": t2 - t1, "kernel_ms": kernel_ms},
-            "updates_per_s": (stats["proposals"] / (kernel_ms * 1e-3)) if kernel_ms > 0 else None,
-            "accepted": stats["accepted"], "proposals": stats["proposals"],
-            "energy_evaluation": "device fp64 (caller's coefficients)",
-            "device_energy_max_abs_diff": float(np.max(np.abs(dev_energy - energies))),
-            "ignored_kwargs": ignored,
-        }
+        info = self._info((betas, beta_range, stype), seed, num_reads, "csr_rank1" if use_csr else "dense", ignored,
+                          self._launch_info(t0, t1, t2, kernel_ms, stats))
+        info["device_energy_max_abs_diff"] = float(np.max(np.abs(dev_energy - energies)))
         if kwargs.get("return_embedding"):
             info["embedding_context"] = {"embedding": {}}    # read at BQM_clustering.py:79
         return SampleSet(samples, energies, model.variables, vartype, info=info)
 
-    def _sample_potts(self, model: PottsModel, kwargs) -> SampleSet:
-        kw, ignored = self._split_kwargs(dict(kwargs))
+    def _random_remainder(self, prob, replicas: int, num_reads: int, seed: int, have: np.ndarray) -> np.ndarray:
+        """Initial states where fewer rows are given than there are reads ("partial", ``_initial_states``): the first
+        ``num_reads`` rows of the device's own random initial states -- a zero-sweep anneal of all ``replicas``, fetched
+        -- with the rows ``have`` written over the first of them."""
+        prob.anneal(replicas, np.zeros(0), seed, self.replica_offset)
+        rnd, _, _ = prob.fetch(energies=False)
+        rnd = rnd[:num_reads]
+        rnd[: have.shape[0]] = have
+        return rnd
+
+    @staticmethod
+    def _launch_info(t0, t1, t2, kernel_ms, stats) -> Dict[str, Any]:
+        """What one launch reports about itself in a sampleset's info: the wall-clock split, the kernel time, the moves."""
+        return {"timing": {"upload_s": t1 - t0, "anneal_s": t2 - t1, "kernel_ms": kernel_ms},
+                "updates_per_s": (stats["proposals"] / (kernel_ms * 1e-3)) if kernel_ms > 0 else None,
+                "accepted": stats["accepted"], "proposals": stats["proposals"]}
+
+    def _info(self, sched, seed, num_reads, kernel: str, ignored, launch: Dict[str, Any]) -> Dict[str, Any]:
+        """The entries every sampleset's info has: the schedule ``sched`` (what ``_schedule`` returns), the run's
+        arguments and ``launch`` -- ``_launch_info`` itself, or its ``batch`` form for the models of one launch."""
+        betas, beta_range, stype = sched
+        return {"beta_range": beta_range, "beta_schedule_type": stype, "seed": seed, "num_sweeps": int(len(betas)),
+                "num_reads": int(num_reads), "kernel": kernel, "device": self.device, **launch,
+                "energy_evaluation": "device fp64 (caller's coefficients)", "ignored_kwargs": ignored}
+
+    def _potts_run(self, models: List[PottsModel], checked, groups=None) -> List[SampleSet]:
+        """The one Potts run behind ``sample_dqm`` and ``sample_dqm_many``: ``models`` in ONE upload and ONE launch, one
+        SampleSet each.  ``checked``: what ``_split_kwargs`` returns.  ``groups``: ``potts_node_weight_groups(models)``
+        for the grouped entry, whose models run as resolution groups (a single one too) and report the launch under
+        ``info["batch"]``; None for the single entry, which alone takes a model without node weights, a minimum cluster
+        size and an empty model.  Every refusal comes before any GPU work."""
+        kw, ignored = checked
+        grouped = groups is not None
+        wq, cw, w64, c64, offsets = groups if grouped else (None,) * 5
+        G, m0 = len(models), models[0]
+        n, K = m0.num_variables, m0.num_cases
         t0 = time.perf_counter()
-        n = model.num_variables
         if n == 0:
-            return SampleSet(np.zeros((0, 0), dtype=np.int32), np.zeros(0), [], "DISCRETE",
-                             info={"ignored_kwargs": ignored})
+            return [SampleSet(np.zeros((0, 0), dtype=np.int32), np.zeros(0), [], "DISCRETE",
+                              info={"ignored_kwargs": ignored})]
         seed = self._seed(kw.get("seed"))
-        num_reads, init = self._initial_states(kw, model.variables, kw.get("num_reads"), "DISCRETE")
-        betas, beta_range, stype = self._schedule(kw, lambda: default_potts_beta_range(model))
-        _check_consensus(kw, model.num_cases, num_reads)
+        num_reads, init = self._initial_states(kw, m0.variables, kw.get("num_reads"), "DISCRETE")
+        if num_reads < 1:
+            raise ValueError("'num_reads' should be a positive integer")
+        ranges = kw.get("beta_range")
+        per_model = grouped and ranges is not None and np.ndim(ranges) == 2
+        if per_model and np.shape(ranges) != (G, 2):
+            raise ValueError("a per-model beta_range needs shape [%d, 2]" % G)
+        scheds = [self._schedule(dict(kw, beta_range=ranges[g]) if per_model else kw,
+                                 lambda model=model: default_potts_beta_range(model)) for g, model in enumerate(models)]
+        betas = np.stack([b for b, _, _ in scheds]) if grouped else scheds[0][0]
+        _check_consensus(kw, K, num_reads)
         # the CQM's "every cluster has at least m members" (CQM_clustering.py:46-48): a hard constraint on moves
-        min_size = int(kw.get("min_cluster_size", model.info.get("min_cluster_size", 0)) or 0)
-        _check_split(kw, min_size, [model])
-        if model.node_weight is not None and min_size > 0:
+        min_size = int(kw.get("min_cluster_size", 0 if grouped else m0.info.get("min_cluster_size", 0)) or 0)
+        _check_split(kw, min_size, models)
+        if m0.node_weight is not None and min_size > 0:
             raise ValueError("node weights (a modularity model) together with min_cluster_size are not supported")
         merge_interval, merge_proposals = self._merge_kwargs(kw, min_size)
-        prob = Problem.potts_csr(model.rowptr, model.col, model.val.astype(np.float32),
-                                 float(np.float32(model.c_pair)), n, model.num_cases,
-                                 lin_offset=model.lin_offset, device=self.device, order="padded",
-                                 energy_model=(model.val, model.c_pair), node_weights=potts_node_weights(model))
-        if min_size * model.num_cases > n:
-            raise ValueError("min_cluster_size %d x %d clusters exceeds the %d variables" % (min_size, model.num_cases, n))
+        if min_size * K > n:
+            raise ValueError("min_cluster_size %d x %d clusters exceeds the %d variables" % (min_size, K, n))
+        prob = Problem.potts_csr(m0.rowptr, m0.col, m0.val.astype(np.float32), float(np.float32(m0.c_pair)), n, K,
+                                 lin_offset=m0.lin_offset, device=self.device, order="padded",
+                                 energy_model=(m0.val, m0.c_pair),
+                                 node_weights=(wq, cw[0], w64) if grouped else potts_node_weights(m0))
         with prob:
+            if grouped:
+                prob.set_node_weight_groups(cw, c64, offsets)
             if merge_interval:
-                prob.set_merge_moves(merge_interval, merge_proposals, potts_merge_coefficients(model))
+                prob.set_merge_moves(merge_interval, merge_proposals, potts_merge_coefficients(models))
             init_arr = init
-            if isinstance(init, tuple) or (min_size > 0 and init is None):
+            if isinstance(init, tuple) or (min_size > 0 and init is None):    # (every group starts from group 0's rows)
                 have = init[1] if isinstance(init, tuple) else np.zeros((0, n), dtype=np.uint16)
-                prob.anneal(num_reads, betas[:0], seed, self.replica_offset)
-                rnd, _, _ = prob.fetch(energies=False)
-                rnd[: have.shape[0]] = have
-                init_arr = rnd
+                init_arr = self._random_remainder(prob, num_reads * G, num_reads, seed, have)
             if min_size > 0:
-                init_arr = _make_feasible(np.array(init_arr, dtype=np.uint16, copy=True), model.num_cases, min_size)
+                init_arr = _make_feasible(np.array(init_arr, dtype=np.uint16, copy=True), K, min_size)
                 prob.set_option("min_cluster_size", min_size)
+            if grouped and init_arr is not None:
+                init_arr = np.tile(np.asarray(init_arr, dtype=np.uint16), (G, 1))
             t1 = time.perf_counter()
-            prob.anneal(num_reads, betas, seed, self.replica_offset, init_arr)
-            labels, dev_energy, stats = prob.fetch()
+            prob.anneal(num_reads * G, betas, seed, self.replica_offset, init_arr)
+            labels, energies, stats = prob.fetch()       # (energies: on the device, in the models' fp64 coefficients)
             kernel_ms = prob.kernel_ms()
+            kernel_name = prob.kernel_name() if grouped else None
             merges = prob.merges_accepted() if merge_interval else None
-            agree = prob.label_agreement(1) if kw.get("stability") and num_reads >= 2 else None
-            cons = _consensus_info(prob, 1, model, num_reads) if kw.get("consensus") else None
-            comps = prob.components()[0] if kw.get("split_disconnected") else None
+            agree = prob.label_agreement(G) if kw.get("stability") and num_reads >= 2 else None
+            cons = _consensus_info(prob, G, m0, num_reads) if kw.get("consensus") else None
+            comps = prob.components()[0] if kw.get("split_disconnected") else None    # (all groups in one call)
             t2 = time.perf_counter()
-        energies = dev_energy                    # evaluated on the device in the model's fp64 coefficients
-        info = {
-            "beta_range": beta_range, "beta_schedule_type": stype, "seed": seed,
-            "num_sweeps": int(len(betas)), "num_reads": int(num_reads), "kernel": "potts_csr",
-            "device": self.device,
-            "timing": {"upload_s": t1 - t0, "anneal_s": t2 - t1, "kernel_ms": kernel_ms},
-            "updates_per_s": (stats["proposals"] / (kernel_ms * 1e-3)) if kernel_ms > 0 else None,
-            "accepted": stats["accepted"], "proposals": stats["proposals"],
-            "energy_evaluation": "device fp64 (caller's coefficients)",
-            "ignored_kwargs": ignored,
-        }
-        if merge_interval:
-            info["merges_accepted"] = merges
-        if kw.get("stability"):
-            info["stability"], info["stability_nmi"] = (
-                mean_pair_agreement(agree["ari"][0], agree["nmi"][0]) if agree is not None else (None, None))
-        if cons is not None:
-            info.update(cons[0])
-        if comps is not None:
-            info.update(_split_info(model, labels, energies, comps))
-        return SampleSet(labels.astype(np.int32), energies, model.variables, "DISCRETE", info=info)
+        launch = self._launch_info(t0, t1, t2, kernel_ms, stats)
+        if grouped:                                       # what the groups share, as ONE object: the launch was one
+            del launch["timing"]["kernel_ms"]
+            launch = {"batch": {"groups": G, "kernel_ms": kernel_ms, "kernel_name": kernel_name, **launch}}
+        out = []
+        for g, model in enumerate(models):
+            rows = slice(g * num_reads, (g + 1) * num_reads)
+            info = self._info(scheds[g], seed, num_reads, "potts_csr", ignored, launch)
+            if merge_interval:
+                info["merges_accepted"] = merges                  # (all groups together, like "batch")
+            if kw.get("stability"):
+                info["stability"], info["stability_nmi"] = (
+                    mean_pair_agreement(agree["ari"][g], agree["nmi"][g]) if agree is not None else (None, None))
+            if cons is not None:
+                info.update(cons[g])
+            if comps is not None:
+                info.update(_split_info(model, labels[rows], energies[rows], comps[rows]))
+            out.append(SampleSet(labels[rows].astype(np.int32), energies[rows], model.variables, "DISCRETE", info=info))
+        return out
 
 
 MAX_CONSENSUS_READS = 8192                 # MI_COASSOC_MAX_READS (include/mi_metrics.h)
