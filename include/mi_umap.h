@@ -86,6 +86,62 @@ int mi_umap_layout_f32(int n, int c, const int64_t *rowptr, const int32_t *col, 
                        float b, float alpha0, int T, int neg, uint64_t seed, int device, float *Y_out,
                        float *out_kernel_ms);
 
+/* ---- chain Q: mapping new points onto a fixed reference (csrc/mapping_kernels.hip) --------------------
+ * Exact kNN of a query set against ANOTHER set, then umap-learn's transform rule on those rows: a weighted neighbour vote
+ * (label transfer), the weighted-mean start and the out-of-sample layout.  A query's results depend on the reference and on
+ * that query alone: never on which other queries are sent with it.
+ *
+ * Kernels:
+ *   Q1 k_knn_cross<DP, KM>: k_knn with the queries and the streamed set apart (one query per thread, the reference through an
+ *      LDS tile every lane reads at the same address, top-KM list in registers, KM in {8, 16, 32, 64} >= k; nothing excluded),
+ *      then k_query_dist.  One wavefront per 64 queries: a small m against a large n leaves most CUs idle.
+ *   Q2 k_query_smooth: one thread per query, sigma (64 bisection steps, rho = 0, all k columns) and the k weights.
+ *   Q3 k_query_init<C>, Q5 k_query_vote: one thread per query, fp64 sums in column order.
+ *   Q4 k_umap_transform<G, C>: ALL T epochs in one launch.  A group of G lanes (16, 32 or 64: the smallest >= k) owns a query;
+ *      lane l holds entry l; neighbour, firing ratio and the query's position stay in registers across the epochs. */
+typedef struct mi_umap_query mi_umap_query;
+
+/* Q1.  R: n x dim (the reference), Q: m x dim (the queries), row-major finite f32; 1 <= dim <= 64, n >= 2, m >= 1,
+ * 2 <= k <= min(64, n).  The k neighbours of a query are ordered by ascending (d2, index); nothing is excluded (a query equal to
+ * a reference point finds it at distance 0).  Metrics, the cosine row normalisation (of both sets) and the distances are
+ * mi_umap_knn_f32's; its coordinate-range rule is applied with the ranges taken over R and Q together.  MI_EUNSUPPORTED for n or
+ * m > MI_UMAP_MAX_POINTS or m * k >= 2^30. */
+int mi_umap_query_knn_f32(const float *R, int n, const float *Q, int m, int dim, int k, int metric, int device,
+                          mi_umap_query **out, float *out_kernel_ms);
+int mi_umap_query_destroy(mi_umap_query *q);
+/* nn: m x k indices into R; dist: m x k f32, ascending in each row.  Each nullable. */
+int mi_umap_query_fetch_knn(mi_umap_query *q, int32_t *nn, float *dist);
+
+/* Q2.  sigma_i by U2's 64 bisection steps to sum_{p < k} (d_ip > 0 ? exp(-d_ip / sigma) : 1) = log2(k) (rho = 0, every column),
+ * floored at 1e-3 * the row's OWN mean distance; v_ip = (d_ip > 0 ? exp(-d_ip / sigma_i) : 1) in fp64, stored as f32. */
+int mi_umap_query_smooth(mi_umap_query *q, float *out_kernel_ms);
+/* sigma: m fp64 entries, w: m x k f32 (each nullable).  MI_ESTATE before mi_umap_query_smooth. */
+int mi_umap_query_fetch_smooth(mi_umap_query *q, double *sigma, float *w);
+
+/* Q5.  labels: n entries, -1 = unlabelled, else in [0, L) (MI_EINVAL otherwise).  weighted 0: every labelled neighbour counts
+ * 1; weighted 1: it counts v_ip (MI_ESTATE before mi_umap_query_smooth).  score(l) = the share of label l in the labelled
+ * neighbours' total, fp64 in column order; label: the largest score, ties to the smaller label; score: the winner's.  A row
+ * whose labelled neighbours weigh nothing in all (none is labelled, or every weight is 0) gets label -1 and score 0.
+ * scores: nullable dense m x L fp64 (zeros included); MI_EUNSUPPORTED for m * L >= 2^31. */
+int mi_umap_query_vote(mi_umap_query *q, const int32_t *labels, int L, int weighted, int32_t *label, double *score,
+                       double *scores, float *out_kernel_ms);
+
+/* Q3.  Yref: n x c f32 (finite), c 2 or 3 (else MI_EUNSUPPORTED); Y0_i = sum_p v_ip Yref[nn_ip] / sum_p v_ip, fp64 in column
+ * order on the stored weights, rounded to f32.  MI_ESTATE before mi_umap_query_smooth. */
+int mi_umap_query_init(mi_umap_query *q, int c, const float *Yref, float *Y0, float *out_kernel_ms);
+
+/* Q4 on plain arrays: m queries of k entries each (nn: m x k indices into Yref's n rows, w: m x k weights), 1 <= k <= 64.  Only
+ * the queries move.  Entry (i, p) fires by U4's test on the ratio w_ip / max_p w_ip (one f32 division by the ROW's largest
+ * weight); a firing entry adds U4's attractive term toward Yref[nn_ip] and `neg` repulsive terms from Yref[j],
+ * j = philox4x32_10(q0 + i, p, t, q; seed)[0] % n, with no index skipped.  alpha_t is U4's.  q0: the index of the first query
+ * (rows a .. b of a larger call are reproduced bit for bit by a call on those rows with q0 = a).  MI_EINVAL for NULL
+ * arguments, m or n < 1, k outside [1, 64], an nn outside [0, n), a weight that is not finite and >= 0, a row without a positive
+ * weight, T / neg outside mi_umap_layout_f32's limits, non-finite Yref / Y0 / a / b / alpha0, q0 < 0 or q0 + m > 2^31 - 1;
+ * MI_EUNSUPPORTED for c not 2 or 3, n or m > MI_UMAP_MAX_POINTS or m * k >= 2^30. */
+int mi_umap_transform_layout_f32(int m, int k, const int32_t *nn, const float *w, int n, int c, const float *Yref,
+                                 const float *Y0, float a, float b, float alpha0, int T, int neg, uint64_t seed, int64_t q0,
+                                 int device, float *Y_out, float *out_kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

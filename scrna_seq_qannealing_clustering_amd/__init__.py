@@ -11,6 +11,8 @@ Public surface:
     clustering_modularity_sweep  the same at several resolutions in one GPU launch
     preprocess               counts -> log-normalised matrix -> variable genes -> scaled matrix -> PCA coordinates (module)
     umap, run_umap           Seurat's RunUMAP: kNN -> fuzzy graph -> deterministic layout (module and its driver)
+    mapping                  held-out cells onto a clustered sample: cross kNN, label transfer, extend_labels (module);
+                             umap.transform places them in a fitted embedding
     annotate                 SingleR-style cell-type annotation against a labelled reference (module: Reference, single_r)
 """
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
@@ -23,7 +25,7 @@ __all__ = [
     "MI355XSampler", "SampleSet", "QuboModel", "PottsModel", "BinaryQuadraticModel",
     "DiscreteQuadraticModel", "build_bqm_qubo", "build_bqm2_qubo", "build_bqm3_cut_qubo",
     "build_dqm_potts", "add_size_window_penalty", "default_beta_range", "make_beta_schedule",
-    "qubo_dict_to_model", "preprocess", "umap", "run_umap", "annotate",
+    "qubo_dict_to_model", "preprocess", "umap", "run_umap", "mapping", "annotate",
 ]
 
 
@@ -37,7 +39,7 @@ def __getattr__(name):
                 "clustering_modularity_sweep"):
         from . import clustering
         return getattr(clustering, name)
-    if name in ("preprocess", "umap", "annotate"):
+    if name in ("preprocess", "umap", "mapping", "annotate"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "run_umap":

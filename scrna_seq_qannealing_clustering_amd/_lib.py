@@ -150,6 +150,16 @@ def _signatures():
         "mi_umap_fetch_graph": (C.c_int, [vp, i64p, i32p, f32p]),
         "mi_umap_layout_f32": (C.c_int, [C.c_int, C.c_int, i64p, i32p, f32p, f32p, C.c_float, C.c_float,
                                          C.c_float, C.c_int, C.c_int, C.c_uint64, C.c_int, f32p, f32p]),
+        "mi_umap_query_knn_f32": (C.c_int, [f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, pp, f32p]),
+        "mi_umap_query_destroy": (C.c_int, [vp]),
+        "mi_umap_query_fetch_knn": (C.c_int, [vp, i32p, f32p]),
+        "mi_umap_query_smooth": (C.c_int, [vp, f32p]),
+        "mi_umap_query_fetch_smooth": (C.c_int, [vp, f64p, f32p]),
+        "mi_umap_query_vote": (C.c_int, [vp, i32p, C.c_int, C.c_int, i32p, f64p, f64p, f32p]),
+        "mi_umap_query_init": (C.c_int, [vp, C.c_int, f32p, f32p, f32p]),
+        "mi_umap_transform_layout_f32": (C.c_int, [C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_float,
+                                                   C.c_float, C.c_float, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int,
+                                                   f32p, f32p]),
         # include/mi_annot.h
         "mi_annot_create": (C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_int, u32p, C.c_int, pp, f32p]),
         "mi_annot_destroy": (C.c_int, [vp]),

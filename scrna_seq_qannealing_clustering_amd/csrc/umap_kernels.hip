@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/mi_umap.h"
-#include "mi_sa_device.h"
+#include "mi_umap_shared.h"
 
 namespace mi_sa_impl {
 namespace {
@@ -171,35 +171,7 @@ __global__ void __launch_bounds__(256) k_umap_union_sort(int n, int k, const int
     if (lane == 0) atomicMax(&stats[1], (unsigned int)(rowptr[i + 1] - out));
 }
 
-// ---- U4: one epoch of the layout ----------------------------------------------------------------------------------------------
-template <int C>
-__device__ __forceinline__ void load_y(const float *__restrict__ Y, int v, float (&y)[C])
-{
-    if constexpr (C == 2) {
-        const f32x2 t = *reinterpret_cast<const f32x2 *>(Y + (size_t)v * 2);
-        y[0] = t.x; y[1] = t.y;
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) y[c] = Y[(size_t)v * C + c];
-    }
-}
-
-__device__ __forceinline__ float clamp4(float x) { return fminf(fmaxf(x, -4.0f), 4.0f); }
-
-// s^b for s > 0 on v_log_f32 / v_exp_f32 with reduced arguments: log2 s = e + log2 m with m in [1/2, 1) (the instruction's error
-// stays one f32 step of a number below 1), the product with b in fp64, and 2^x = 2^rint(x) * v_exp_f32(x - rint(x)).  About one
-// f32 step of error in all, where exp2(b * log2(s)) on the raw arguments loses |b log2 s| of them.
-__device__ __forceinline__ double log2_split(float s)
-{
-    return (double)__builtin_amdgcn_frexp_expf(s) + (double)__builtin_amdgcn_logf(__builtin_amdgcn_frexp_mantf(s));
-}
-
-__device__ __forceinline__ float exp2_split(double x)
-{
-    const double xi = rint(x);
-    return ldexpf(__builtin_amdgcn_exp2f((float)(x - xi)), (int)xi);
-}
-
+// ---- U4: one epoch of the layout (load_y, clamp4, log2_split, exp2_split: mi_umap_shared.h) -------------------------------------
 // A group of G lanes owns vertex v = (global thread) / G; lane l of the group takes entries l, l + G, ... of the row in
 // ascending order, each with its negatives, and the G partial sums meet in a butterfly.  s^b and s^(b-1): exp2_split.
 template <int G, int C>
@@ -329,14 +301,7 @@ int mi_umap_knn_f32(const float *X, int n, int dim, int k, int metric, int devic
         for (size_t e = 0; e < cells; ++e)
             if (!std::isfinite(X[e])) return fail(MI_EINVAL, "X[%lld, %lld] is not finite", (long long)(e / dim), (long long)(e % dim));
         if (metric == MI_UMAP_COSINE) {
-            unit.resize(cells);
-            for (int i = 0; i < n; ++i) {
-                double ss = 0.0;
-                for (int c = 0; c < dim; ++c) ss += (double)X[(size_t)i * dim + c] * (double)X[(size_t)i * dim + c];
-                const double nrm = std::sqrt(ss);
-                for (int c = 0; c < dim; ++c)
-                    unit[(size_t)i * dim + c] = nrm > 0.0 ? (float)((double)X[(size_t)i * dim + c] / nrm) : 0.0f;
-            }
+            unit_rows(X, n, dim, unit);
             src = unit.data();
         }
         return mi_snn_check_points(src, n, dim);

@@ -8,12 +8,19 @@ constants ``a, b`` and the initial coordinates are host fp64.  The chain is spec
 of the layout is a gather from the previous epoch's positions with counter-based negatives, so two calls return
 bit-identical coordinates (umap-learn's and uwot's layouts are racy loops: theirs do not).
 
-Not built: spectral initialisation (``init="pca"`` or an array), ``transform`` of new points, supervised UMAP, metrics
-other than ``"euclidean"`` and ``"cosine"``.
+Not built: spectral initialisation (``init="pca"`` or an array), supervised UMAP, metrics other than ``"euclidean"`` and
+``"cosine"``.
 
     emb = preprocess.embed(counts, nfeatures=2000, npcs=50)
     um = umap.run_umap(emb.coords[:, :15])            # Seurat's RunUMAP(dims = 1:15) defaults
     outputs.plot_and_save_embedding(um.coords, labels, "umap.png")
+
+New points are placed in a fitted embedding by :func:`transform` (chain Q of DESIGN.md section 5d, csrc/mapping_kernels.hip):
+the reference embedding stays fixed, every query runs all its epochs in registers in one launch, and a query's coordinates
+do not depend on which other queries are sent with it.
+
+    um = umap.run_umap(X[kept])
+    rest = umap.transform(X[held_out], X[kept], um)    # .coords: where the held-out cells fall in um.coords' picture
 """
 from __future__ import annotations
 
@@ -304,3 +311,85 @@ def run_umap(X, n_neighbors: int = 30, n_components: int = 2, metric: str = "cos
     timing["total_ms"] = total_ms
     return UmapResult(coords=coords, nn=fg.nn, dist=fg.dist, rho=fg.rho, sigma=fg.sigma, rowptr=fg.rowptr, col=fg.col,
                       weights=fg.weights, a=a32, b=b32, n_epochs=T, timing=timing)
+
+
+# ---- new points in a fitted embedding (chain Q) ---------------------------------------------------------------------------------
+
+def transform_layout(nn, w, Yref, init, a: float, b: float, alpha0: float, n_epochs: int, negative_sample_rate: int = 5,
+                     seed: int = 42, first_index: int = 0, device: int = 0, return_ms: bool = False):
+    """Chain Q4 on plain arrays: ``nn`` (m, k) indices into the rows of ``Yref`` (n, 2 or 3), ``w`` (m, k) weights (finite,
+    >= 0, a positive one in every row), ``init`` the (m, c) start; ``alpha0`` is the initial step itself.  Only the queries
+    move.  Row i draws its negatives as query ``first_index + i``: a slice of a larger call is reproduced bit for bit."""
+    nn, w = np.asarray(nn), np.asarray(w)
+    if nn.ndim != 2 or nn.dtype.kind not in "iu" or not 1 <= nn.shape[1] <= 64 or nn.shape[0] < 1:
+        raise ValueError("nn must be an (m, k) integer array with m >= 1 and 1 <= k <= 64")
+    if w.shape != nn.shape or w.dtype.kind not in "fiu":
+        raise ValueError("w must be a numeric array of nn's shape %s" % (nn.shape,))
+    Yref, Y0 = np.asarray(Yref), np.asarray(init)
+    if Yref.ndim != 2 or Yref.shape[0] < 1 or Yref.shape[1] not in (2, 3) or Yref.dtype.kind not in "fiu":
+        raise ValueError("Yref must be a numeric (n, 2) or (n, 3) array")
+    n, c = Yref.shape
+    if Y0.shape != (nn.shape[0], c) or Y0.dtype.kind not in "fiu":
+        raise ValueError("init must be a numeric array of shape (%d, %d)" % (nn.shape[0], c))
+    if nn.min() < 0 or nn.max() >= n:
+        raise ValueError("nn must index the %d rows of Yref" % n)
+    nn = np.ascontiguousarray(nn, dtype=np.int32)
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    Yref = np.ascontiguousarray(Yref, dtype=np.float32)
+    Y0 = np.ascontiguousarray(Y0, dtype=np.float32)
+    if not (np.isfinite(w).all() and (w >= 0).all() and (w.max(axis=1) > 0).all()):
+        raise ValueError("w must be finite and >= 0 with a positive weight in every row")
+    if not (np.isfinite(Yref).all() and np.isfinite(Y0).all()):
+        raise ValueError("Yref and init must be finite")
+    a, b = float(a), float(b)
+    if not (math.isfinite(a) and math.isfinite(b)):
+        raise ValueError("a and b must be finite")
+    T, alpha0, neg, seed = _check_layout_args(n_epochs, alpha0, negative_sample_rate, seed)
+    q0 = first_index
+    if isinstance(q0, bool) or int(q0) != q0 or q0 < 0 or int(q0) + nn.shape[0] > 2 ** 31 - 1:
+        raise ValueError("first_index must be an integer >= 0 with first_index + m <= 2^31 - 1")
+    out = np.empty_like(Y0)
+    ms = _lib.call_ms("mi_umap_transform_layout_f32", nn.shape[0], nn.shape[1], nn, w, n, c, Yref, Y0, a, b, alpha0, T, neg,
+                      C.c_uint64(seed), C.c_int64(int(q0)), int(device), out)
+    return (out, ms) if return_ms else out
+
+
+def transform(X_new, X_ref, model, n_neighbors: int = 30, metric: str = "cosine", n_epochs=None, learning_rate: float = 1.0,
+              negative_sample_rate: int = 5, seed: int = 42, first_index: int = 0, device: int = 0) -> Result:
+    """Places ``X_new`` in the embedding ``model`` (a :class:`UmapResult`, or anything with ``coords``, ``a``, ``b``,
+    ``n_epochs``) fitted on ``X_ref``, by umap-learn's transform rule: the ``n_neighbors`` nearest reference points of every
+    query, membership weights with rho = 0, the weighted mean of their positions as the start, then ``n_epochs`` epochs
+    (``None``: a third of the fit's, at least 1) at a quarter of ``learning_rate`` in which only the queries move.  Pass the
+    fit's ``n_neighbors`` and ``metric``.  Firing ratios are normalised per row where umap-learn normalises per batch, so
+    ``transform(Q)[a:b]`` equals ``transform(Q[a:b], first_index=a)`` bit for bit.  Returns ``coords``, ``init``, ``nn``,
+    ``dist``, ``sigma``, ``weights``, ``n_epochs``, ``timing``."""
+    from .mapping import QueryGraph, _check_pair
+    t_all = time.perf_counter()
+    Q, R, k = _check_pair(X_new, X_ref, n_neighbors, metric)
+    try:
+        Yref, a, b, fit_epochs = np.asarray(model.coords), float(model.a), float(model.b), model.n_epochs
+    except AttributeError as exc:
+        raise ValueError("model needs coords, a, b and n_epochs (a UmapResult): %s" % exc) from None
+    if Yref.ndim != 2 or Yref.shape[0] != R.shape[0] or Yref.shape[1] not in (2, 3) or Yref.dtype.kind not in "fiu":
+        raise ValueError("model.coords must be (%d, 2) or (%d, 3): one row per row of X_ref" % (R.shape[0], R.shape[0]))
+    if not np.isfinite(Yref).all() or not (math.isfinite(a) and math.isfinite(b)):
+        raise ValueError("model.coords, model.a and model.b must be finite")
+    if n_epochs is None:
+        if isinstance(fit_epochs, bool) or int(fit_epochs) != fit_epochs or fit_epochs < 1:
+            raise ValueError("model.n_epochs must be a positive integer")
+        n_epochs = max(1, int(fit_epochs) // 3)
+    T, lr, neg, seed = _check_layout_args(n_epochs, learning_rate, negative_sample_rate, seed)
+    if isinstance(first_index, bool) or int(first_index) != first_index or first_index < 0 \
+            or int(first_index) + Q.shape[0] > 2 ** 31 - 1:
+        raise ValueError("first_index must be an integer >= 0 with first_index + m <= 2^31 - 1")
+    with QueryGraph(Q, R, k, metric, device) as g:
+        nn, dist = g.fetch_knn()
+        sigma, w = g.smooth().fetch_smooth()
+        Y0 = g.init(Yref)
+        timing = dict(g.timing)
+    coords, ms = transform_layout(nn, w, Yref, Y0, a, b, lr / 4.0, T, neg, seed, first_index, device, return_ms=True)
+    timing["layout_ms"] = ms
+    total_ms = (time.perf_counter() - t_all) * 1e3
+    timing["host_ms"] = total_ms - sum(timing[s] for s in ("knn_ms", "smooth_ms", "init_ms", "layout_ms"))
+    timing["total_ms"] = total_ms
+    return Result(coords=coords, init=Y0, nn=nn, dist=dist, sigma=sigma, weights=w, n_epochs=T, timing=timing)
