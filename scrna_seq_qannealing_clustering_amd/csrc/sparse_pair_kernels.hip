@@ -38,6 +38,8 @@ __device__ __forceinline__ float half_hi(uint32_t w) { return (float)__builtin_b
 // 1.5-2), and a third of the instructions of a slot are these thresholds.  A 128-thread workgroup puts its two
 // wavefronts on different SIMDs and every SIMD ends up with two sweeping and two threshold wavefronts
 // (scripts/probe_placement.hip).  Same chain: the thresholds are the same function of (variable, sweep, replica).
+// Priority: the threshold wavefront stays at 0; the sweeping wavefront runs at 3, and in the pipelined forms (N16 = 2) at 3
+// or 2, set once per sweep by its hardware wave slot, so that the two sweeping wavefronts of a SIMD lead in turn (PR below).
 // WGT: the model carries pair-term weights (mi_sa_problem_set_pair_weights; weighted_slot_sweep): a template switch, so
 // that the other models' code is what it was.
 // RW < D ("trimmed rows", the name's " r<RW>"): the model's longest row is RW < D entries, so entries RW.. D-1 of every
@@ -277,6 +279,38 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
 #ifndef MI_K2P_DBG_NOPRIO
     if constexpr (TW) __builtin_amdgcn_s_setprio(3);
 #endif               // the sweeping wavefront is the critical path of its workgroup
+    // PR ("priority rotation", round 7; the N16 = 2 forms): a SIMD holds two sweeping wavefronts.  Measured with both at 3 for
+    // the whole launch (the -DMI_K2P_DBG_WAVETIMES build on the benchmark's shape): on every one of the 1024 SIMDs the one
+    // that started first is the quicker, by 19 % in the median, and the launch ends with the slower ones.  So each sets its
+    // priority once per sweep to 3 or 2 (the threshold wavefronts stay at 0): bit 1 of its hardware wave slot, flipped
+    // every sweep.  The sweeping wavefronts of a SIMD were found in slots 1 and 3 or 0 and 2, which differ in that bit, so
+    // they take the higher priority in turn; two whose slots agree in bit 1 would change together and keep the order they
+    // had.  With it the median ratio is 9 % -- the older one is still the quicker everywhere, the sharing is more even, not
+    // even.  s counts the sweeps of THIS launch: the chain's own counter (sw) is not involved, and no value any wavefront
+    // computes depends on the priority.
+    // (`make dbg DBG_FLAGS=-DMI_K2P_NO_PRIO_ROTATE`: the fixed priority, for the A/B.  The other policies measured in
+    // round 7 -- the bit moving with the sweep, bit 0, the slot's parity, a lower priority across the field sums, a start
+    // delay -- are in profiles/r07_k2p_simd_sharing.txt)
+#if defined(MI_K2P_NO_PRIO_ROTATE) || defined(MI_K2P_DBG_NOPRIO)
+    constexpr bool PR = false;
+#else
+    constexpr bool PR = N16 == 2;
+#endif
+    // HW_REG_HW_ID (register 4, all 32 bits): the wave slot of the SIMD in bits 3:0
+    const uint32_t wave_slot = PR ? (__builtin_amdgcn_s_getreg(4 | (31 << 11)) & 15u) : 0u;
+    auto sweep_priority = [&](int s) {
+        if constexpr (PR) {
+            if ((((wave_slot >> 1) ^ (uint32_t)s) & 1u) != 0u) __builtin_amdgcn_s_setprio(3);   // (the instruction takes an immediate)
+            else __builtin_amdgcn_s_setprio(2);
+        }
+    };
+#ifdef MI_K2P_DBG_WAVETIMES
+    // TIMING-ONLY build (wrong states): HW_ID, XCC_ID (register 20) and the ticks around the sweeps, written over the
+    // first 24 bytes of the replica-A row of states after the epilogue (scripts/k2p_wave_times.py reads them)
+    const unsigned long long wt_id = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |
+                                     ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);
+    const unsigned long long wt_t0 = __builtin_amdgcn_s_memtime();
+#endif
     unsigned long long accepted = 0;
     uint32_t accA = 0, accB = 0;                                    // accepted moves of the running sweep, per replica
     uint32_t wa[4] = {0u, 0u, 0u, 0u}, wb[4] = {0u, 0u, 0u, 0u};
@@ -542,6 +576,7 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
             }
         }
         const uint32_t sw = (uint32_t)s + a.sweep_offset;
+        sweep_priority(s);
         if constexpr (N16 == 2) {
             if (!CY || s == 0) {
                 cP = fetch_val16(0, no_wrap{});
@@ -583,6 +618,9 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
         accepted += (unsigned long long)accA + (liveB ? (unsigned long long)accB : 0ull);
         accA = accB = 0;
     }
+#ifdef MI_K2P_DBG_WAVETIMES
+    const unsigned long long wt_t1 = __builtin_amdgcn_s_memtime();
+#endif
 
     // ---- epilogue: states out, exact fp64 energies (same sums as k_anneal_csr_rank1) ----
     // The sums and their order are the specification's; the order of the loads is not: per slot all the neighbour indices
@@ -601,6 +639,9 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
         for (int t = 0; t < slots; ++t) {
             const int i = t * 64 + lane;
             const bool on = ((cell[i] >> sh) & 0xffffu) != 0u;
+#ifdef MI_K2P_DBG_WAVETIMES   /* (the record's bytes belong to lane 0's stores below) */
+            if (rep == 0 && i < 24) { } else
+#endif
             if (i < n) dst[i] = (uint8_t)on;
             if (WGT && t == wslot) {
                 cnt += wave_sum_i64(on ? (long long)wl : 0ll);
@@ -646,6 +687,14 @@ __global__ void __launch_bounds__(TW ? 128 : 64, TW ? 1 : 2) k_anneal_csr_rank1_
         if (lane == 0) a.energy[r] = binary_chain_finish(a.ell_val64, a.c_pair, a.c_pair64, a.offset, e, cnt, cnt2);
     }
     if (lane == 0) atomicAdd(&a.stats[1], accepted);
+#ifdef MI_K2P_DBG_WAVETIMES
+    if (lane == 0 && n >= 24 && ((size_t)rA * n) % 4 == 0) {        // (rows of 64 k bytes: the padded layouts)
+        uint32_t *q = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a.states) + (size_t)rA * n);
+        q[0] = (uint32_t)wt_id; q[1] = (uint32_t)(wt_id >> 32);
+        q[2] = (uint32_t)wt_t0; q[3] = (uint32_t)(wt_t0 >> 32);
+        q[4] = (uint32_t)wt_t1; q[5] = (uint32_t)(wt_t1 >> 32);
+    }
+#endif
 #ifdef MI_K2P_PROFILE
     if (lane == 0) {
         atomicAdd(&a.stats[8], t_top); atomicAdd(&a.stats[9], t_gather); atomicAdd(&a.stats[10], t_sum);
