@@ -13,6 +13,8 @@ Public surface:
     umap, run_umap           Seurat's RunUMAP: kNN -> fuzzy graph -> deterministic layout (module and its driver)
     mapping                  held-out cells onto a clustered sample: cross kNN, label transfer, extend_labels (module);
                              umap.transform places them in a fitted embedding
+    tsne, run_tsne           Seurat's RunTSNE: kNN -> perplexity calibration -> joint P -> exact-repulsion layout (module and
+                             its driver)
     annotate                 SingleR-style cell-type annotation against a labelled reference (module: Reference, single_r)
 """
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
@@ -25,7 +27,7 @@ __all__ = [
     "MI355XSampler", "SampleSet", "QuboModel", "PottsModel", "BinaryQuadraticModel",
     "DiscreteQuadraticModel", "build_bqm_qubo", "build_bqm2_qubo", "build_bqm3_cut_qubo",
     "build_dqm_potts", "add_size_window_penalty", "default_beta_range", "make_beta_schedule",
-    "qubo_dict_to_model", "preprocess", "umap", "run_umap", "mapping", "annotate",
+    "qubo_dict_to_model", "preprocess", "umap", "run_umap", "mapping", "annotate", "tsne", "run_tsne",
 ]
 
 
@@ -39,10 +41,13 @@ def __getattr__(name):
                 "clustering_modularity_sweep"):
         from . import clustering
         return getattr(clustering, name)
-    if name in ("preprocess", "umap", "mapping", "annotate"):
+    if name in ("preprocess", "umap", "mapping", "annotate", "tsne"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "run_umap":
         from .umap import run_umap
         return run_umap
+    if name == "run_tsne":
+        from .tsne import run_tsne
+        return run_tsne
     raise AttributeError(name)

@@ -160,6 +160,19 @@ def _signatures():
         "mi_umap_transform_layout_f32": (C.c_int, [C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_float,
                                                    C.c_float, C.c_float, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int,
                                                    f32p, f32p]),
+        # include/mi_tsne.h
+        "mi_tsne_knn_f32": (C.c_int, [f32p, C.c_int, C.c_int, C.c_double, C.c_int, pp, f32p]),
+        "mi_tsne_destroy": (C.c_int, [vp]),
+        "mi_tsne_fetch_knn": (C.c_int, [vp, i32p, f32p]),
+        "mi_tsne_calibrate": (C.c_int, [vp, f32p]),
+        "mi_tsne_fetch_calibration": (C.c_int, [vp, f64p, f32p]),
+        "mi_tsne_symmetrize": (C.c_int, [vp, f32p]),
+        "mi_tsne_info": (C.c_int, [vp, ip, ip, i64p, ip]),
+        "mi_tsne_fetch_graph": (C.c_int, [vp, i64p, i32p, f32p]),
+        "mi_tsne_layout_f32": (C.c_int, [C.c_int, C.c_int, i64p, i32p, f32p, f32p, f32p, f32p, C.c_float, C.c_float, C.c_int,
+                                         C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p,
+                                         f64p, f32p]),
+        "mi_tsne_kl_f32": (C.c_int, [C.c_int, C.c_int, i64p, i32p, f32p, f32p, C.c_int, f64p, f32p]),
         # include/mi_annot.h
         "mi_annot_create": (C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_int, u32p, C.c_int, pp, f32p]),
         "mi_annot_destroy": (C.c_int, [vp]),
