@@ -15,6 +15,8 @@ Public surface:
                              umap.transform places them in a fitted embedding
     tsne, run_tsne           Seurat's RunTSNE: kNN -> perplexity calibration -> joint P -> exact-repulsion layout (module and
                              its driver)
+    anchors                  Seurat's FindTransferAnchors / TransferData / MapQuery: anchor-based label and feature transfer
+                             (module: find_transfer_anchors, transfer_data, map_query)
     annotate                 SingleR-style cell-type annotation against a labelled reference (module: Reference, single_r)
 """
 from .bqm import BinaryQuadraticModel, DiscreteQuadraticModel
@@ -27,7 +29,7 @@ __all__ = [
     "MI355XSampler", "SampleSet", "QuboModel", "PottsModel", "BinaryQuadraticModel",
     "DiscreteQuadraticModel", "build_bqm_qubo", "build_bqm2_qubo", "build_bqm3_cut_qubo",
     "build_dqm_potts", "add_size_window_penalty", "default_beta_range", "make_beta_schedule",
-    "qubo_dict_to_model", "preprocess", "umap", "run_umap", "mapping", "annotate", "tsne", "run_tsne",
+    "qubo_dict_to_model", "preprocess", "umap", "run_umap", "mapping", "anchors", "annotate", "tsne", "run_tsne",
 ]
 
 
@@ -41,7 +43,7 @@ def __getattr__(name):
                 "clustering_modularity_sweep"):
         from . import clustering
         return getattr(clustering, name)
-    if name in ("preprocess", "umap", "mapping", "annotate", "tsne"):
+    if name in ("preprocess", "umap", "mapping", "anchors", "annotate", "tsne"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "run_umap":

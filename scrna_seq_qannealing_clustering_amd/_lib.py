@@ -160,6 +160,16 @@ def _signatures():
         "mi_umap_transform_layout_f32": (C.c_int, [C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_float,
                                                    C.c_float, C.c_float, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int,
                                                    f32p, f32p]),
+        # include/mi_anchors.h
+        "mi_anchors_find_f32": (C.c_int, [f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, pp, f32p]),
+        "mi_anchors_destroy": (C.c_int, [vp]),
+        "mi_anchors_info": (C.c_int, [vp, ip, ip, i64p, i64p, f32p]),
+        "mi_anchors_fetch": (C.c_int, [vp, i32p, i32p, i32p, i32p, i32p, i32p]),
+        "mi_anchors_set_scores": (C.c_int, [vp, f64p]),
+        "mi_anchors_weights": (C.c_int, [vp, C.c_int, C.c_double, f32p]),
+        "mi_anchors_fetch_weights": (C.c_int, [vp, i64p, i32p, f64p, i32p, f32p]),
+        "mi_anchors_predict_labels": (C.c_int, [vp, i32p, C.c_int, i32p, f64p, f64p, f32p]),
+        "mi_anchors_predict_features": (C.c_int, [vp, f32p, C.c_int, f32p, f32p]),
         # include/mi_tsne.h
         "mi_tsne_knn_f32": (C.c_int, [f32p, C.c_int, C.c_int, C.c_double, C.c_int, pp, f32p]),
         "mi_tsne_destroy": (C.c_int, [vp]),

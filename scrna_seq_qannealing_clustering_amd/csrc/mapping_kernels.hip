@@ -300,6 +300,22 @@ int check_finite(const float *X, size_t rows, int cols, const char *what)
 }
 
 }  // namespace
+
+// Q1 on DEVICE pointers (declared in mi_umap_shared.h): mi_umap_query_knn_f32 and chain A (anchor_kernels.hip) both come here
+int mi_query_knn_dev(const float *dR, int n, const float *dQ, int m, int dim, int k, int metric, int32_t *d_nn, float *d_dist)
+{
+    if (dim <= 16) launch_knn_cross<16>(dR, n, dQ, m, dim, k, d_nn);
+    else if (dim <= 32) launch_knn_cross<32>(dR, n, dQ, m, dim, k, d_nn);
+    else launch_knn_cross<64>(dR, n, dQ, m, dim, k, d_nn);
+    if (d_dist) {
+        const long long total = (long long)m * k;
+        const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+        hipLaunchKernelGGL(k_query_dist, dim3(blocks), dim3(256), 0, 0, dR, dQ, m, dim, k, metric, d_nn, d_dist);
+    }
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
 }  // namespace mi_sa_impl
 using namespace mi_sa_impl;
 
@@ -364,12 +380,7 @@ int mi_umap_query_knn_f32(const float *R, int n, const float *Q, int m, int dim,
         HIP_TRY(q->d_dist.resize((size_t)m * k));
         Timer tm;
         MI_TRY(tm.start(0));
-        if (dim <= 16) launch_knn_cross<16>(dR, n, dQ, m, dim, k, q->d_nn);
-        else if (dim <= 32) launch_knn_cross<32>(dR, n, dQ, m, dim, k, q->d_nn);
-        else launch_knn_cross<64>(dR, n, dQ, m, dim, k, q->d_nn);
-        const long long total = (long long)m * k;
-        const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        hipLaunchKernelGGL(k_query_dist, dim3(blocks), dim3(256), 0, 0, dR, dQ, m, dim, k, metric, q->d_nn, q->d_dist);
+        MI_TRY(mi_query_knn_dev(dR, n, dQ, m, dim, k, metric, q->d_nn, q->d_dist));
         MI_TRY(tm.stop(0, out_kernel_ms));
         return MI_OK;
     });

@@ -23,6 +23,11 @@ inline void unit_rows(const float *X, int n, int dim, std::vector<float> &unit)
     }
 }
 
+// mapping_kernels.hip: chain Q1 on DEVICE pointers, for mi_umap_query_knn_f32 and anchor_kernels.hip.  d_nn: m x k indices into
+// R by ascending (d2, index), 1 <= k <= min(n, 64), nothing excluded; d_dist (nullable): the metric's m x k f32 distances
+// (MI_UMAP_EUCLIDEAN: sqrt of the search's d2).  The caller has checked the points (mi_snn_check_points on both sets together).
+int mi_query_knn_dev(const float *dR, int n, const float *dQ, int m, int dim, int k, int metric, int32_t *d_nn, float *d_dist);
+
 template <int C>
 __device__ __forceinline__ void load_y(const float *__restrict__ Y, int v, float (&y)[C])
 {

@@ -8,8 +8,8 @@ Everything numeric past the argument checks runs in libmi_sa.so (csrc/mapping_ke
 chain is specified in DESIGN.md section 5d ("chain Q").  A query's result depends on the reference and on that query alone,
 never on which other queries are sent with it.
 
-Not built: anchor-based integration (``FindTransferAnchors``), the reference-range split of the cross kNN (one wavefront
-serves 64 queries: few queries against a large reference leave most of the device idle).
+Anchor-based transfer (``FindTransferAnchors`` / ``TransferData``) is :mod:`anchors`.  Not built: the reference-range split
+of the cross kNN (one wavefront serves 64 queries: few queries against a large reference leave most of the device idle).
 
     kept = np.flatnonzero([G.nodes[v]["label1"] for v in G.nodes])         # clustering.graph_subsampling
     ext = mapping.extend_labels(emb.coords[:, :15], kept, labels_kept)      # labels for all cells
